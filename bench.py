@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the radiation-search PPO hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--configs 3,4|none]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--configs 3,4|none] [--dump-outputs DIR]
 
 Headline workload (BASELINE.json configs[1]): single-agent RadSearch, 1 source, no obstructions, 4096 envs per
 GPU, 2x64 MLP actor-critic, walls enforced, 480 steps/epoch, 120 steps/episode, synthetic spawns from
@@ -25,6 +25,7 @@ one process per GPU, RCCL) BEFORE touching the GPU and relays rank 0's line; und
 `python -m torch.distributed.run ... bench.py --gpus N` it reads RANK/LOCAL_RANK/WORLD_SIZE as usual.
 """
 import argparse
+import dataclasses
 import json
 import os
 import socket
@@ -512,6 +513,38 @@ def run_config_a2c(dev, iters: int = 2, warmup: int = 1, cpu: bool = True):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_ENVS = 512                # env columns of the rollout buffer kept: the whole buffer is ~140 MB at 4096 envs
+
+
+def dump_outputs(out_dir: str, col, ac, stats, res) -> None:
+    """What one PPO iteration hands its caller, as DIR/<name>.npy (float32, float64 where the library computes in float64):
+        buf_<field>     the rollout buffer after GAE [480, envs, ...] (obs, act, logp, val, rew, last_val, cut, adv, ret,
+                        source_tar), on a fixed sample of DUMP_ENVS env columns (default_rng(0), ascending; all of them when fewer)
+        collect_<key>   the epoch statistics collect() returned
+        update_<field>  the UpdateResult of update()
+        param_<name>    the actor / critic parameters after the update
+    about 20 MB in all.  Under several ranks this is rank 0's shard."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    buf = col.buf
+    envs = np.sort(np.random.default_rng(0).choice(buf.N, size=min(buf.N, DUMP_ENVS), replace=False))
+    idx = torch.from_numpy(envs).to(buf.obs.device)
+    out = {}
+    for k in ("obs", "act", "logp", "val", "rew", "last_val", "cut", "adv", "ret", "source_tar"):
+        t = getattr(buf, k).index_select(1, idx)
+        out["buf_" + k] = t if t.dtype == torch.float64 else t.float()
+    for k, v in stats.items():
+        out["collect_" + k] = torch.as_tensor(v).double()
+    for k, v in dataclasses.asdict(res).items():
+        out["update_" + k] = torch.tensor(float(v), dtype=torch.float64)
+    for k, p in ac.named_parameters():
+        out["param_" + k.replace(".", "_")] = p.detach().float()
+    for k, t in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), t.cpu().numpy())
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -526,7 +559,11 @@ def main():
     ap.add_argument("--configs", default=None, help="comma list of extra BASELINE configs to run at N=1 (default '3,4,a2c': BASELINE configs 3 and 4 and the RAD-A2C row f2; 'none')")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -579,11 +616,12 @@ def main():
 
     phases = {"collect": 0.0, "update": 0.0}
     stop_iters = []
+    last = {}                                   # what the last timed iteration returned (--dump-outputs)
 
     def one_iter(timed: bool):
         if timed:
             torch.cuda.synchronize(); a = time.perf_counter()
-        col.collect()
+        stats = col.collect()
         if timed:
             torch.cuda.synchronize(); b = time.perf_counter()
         res = col.update()
@@ -592,6 +630,7 @@ def main():
             phases["collect"] += b - a
             phases["update"] += c - b
             stop_iters.append(res[0].stop_iteration)
+            last.update(stats=stats, res=res)
 
     for _ in range(args.warmup):
         one_iter(False)
@@ -608,6 +647,8 @@ def main():
     if world > 1:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
     dt = float(dt_t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, col, agents[0].agent, last["stats"], last["res"][0])
 
     env_steps = args.steps * T_EPOCH * N * world
     result = {

@@ -1,10 +1,11 @@
 """the safe reader of the reference's saved test-environment sets (radiation_ppo_amd/testsets.py).
 It must (1) return exactly what joblib's own loader returns for a file of the reference's structure written here,
-(2) execute nothing: a file that smuggles a callable is rejected before anything runs, (3) in this container, parse every
-set the reference ships (1000 environments each, lattice coordinates, obstruction counts as the file name says)."""
-import glob
+(2) execute nothing: a file that smuggles a callable is rejected before anything runs, (3) parse the sets the reference ships
+(a sample of its own files, stored under tests/golden: 1000 environments each, lattice coordinates, obstruction counts as the
+file name says)."""
 import os
 import pickle
+import tarfile
 
 import numpy as np
 import pytest
@@ -65,13 +66,18 @@ def test_reader_executes_nothing(tmp_path):
     assert not marker.exists()
 
 
-REF_SETS = sorted(glob.glob("/root/reference/algos/multiagent/evaluation/test_environments/test_env_dict_obs*_v4"))
+# the reference's own set files: the names of all of them and the bytes of the sample below (tests/golden/make_testset_files.py)
+REF_ARCHIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "testset_files.tar.xz")
 
 
-@pytest.mark.skipif(not REF_SETS, reason="the reference tree exists only in the build container")
-def test_every_reference_set_parses():
-    assert len(REF_SETS) >= 30
-    for f in REF_SETS[::6] + [x for x in REF_SETS if "obs1_none" in x]:      # a sample keeps the CPU suite short; scripts parse all
+def test_every_reference_set_parses(tmp_path):
+    with tarfile.open(REF_ARCHIVE, "r:xz") as tar:
+        ref_sets = tar.extractfile("MANIFEST").read().decode().split()
+        assert len(ref_sets) >= 30
+        sample = ref_sets[::6] + [x for x in ref_sets if "obs1_none" in x]     # a sample keeps the CPU suite short; scripts parse all
+        for name in sample:
+            (tmp_path / name).write_bytes(tar.extractfile(name).read())
+    for f in (str(tmp_path / name) for name in sample):
         d = load_test_environments(f)
         k = int(os.path.basename(f).split("_obs")[1].split("_")[0])
         s = summarize_test_set(d)

@@ -201,6 +201,10 @@ int rs_rollout(rs_handle* h, const rs_mlp_params* actor, const rs_mlp_params* cr
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 
+// one 512-thread workgroup (two waves per SIMD) per CU: the dynamic LDS of both K7 kernels fits the CU's 160 KB
+static_assert(sizeof(float) * rs_grad2_lds_floats(8) <= 160 * 1024 && sizeof(float) * rs_grad2_lds_floats(1) <= 160 * 1024,
+              "K7 workgroup exceeds the CU's LDS");
+
 size_t rs_ppo_grad_workspace_bytes(void) {
     const size_t slabs = RS_GRAD_BLOCKS;
     return slabs * (size_t)(rs_net_params(8) + rs_net_params(1)) * sizeof(float) + 2 * slabs * 5 * sizeof(double) + 1024;

@@ -48,6 +48,13 @@ __host__ __device__ constexpr int rs_grad2_lds_floats(int nout) {
     return ((rs_mlp_lds_floats(nout) + 3) & ~3) + 2 * 2 * 16 * 64 + 2 * 4 * 64 + 8 * RS_G2_WAVE_FLOATS;
 }
 
+// the value lane l ^ 32 holds (__shfl_xor(x, 32) without the LDS crossbar): v_permlane32_swap exchanges the upper half of its
+// first operand with the lower half of its second
+__device__ __forceinline__ float rs_other_half(float x, int h) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(h ? r[0] : r[1]);
+}
+
 __device__ __forceinline__ void rs_stage32(float* T, const f32x16& v, int c, int h) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) T[rs_kappa(r, h) * RS_T2 + c] = v[r];
@@ -127,13 +134,16 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
     // after the dW3 phase), so no HBM latency is exposed and no register is held across the group.
     // Every wave runs the same number of trips; a trip past the last group works on clamped rows with weight 0.
     const int trips = (groups + n_waves - 1) / n_waves;
+    // The rows' transfers are addressed as a wave-uniform base (SGPR pair: the group's first float) plus a 32-bit per-lane byte
+    // offset, the global_load_lds_dword saddr form: no 64-bit per-lane address pair is formed or kept live across the group.
     const long x_last = (long)M * RS_IN - 1;
     auto dma_rows = [&](int g) {
+        const char* gx = reinterpret_cast<const char*>(B.x + (long)g * (32 * RS_IN));
+        const int lim = (int)(x_last - (long)g * (32 * RS_IN));    // tail of the last group / lanes past the 352 floats: stay in bounds
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            long idx = (long)g * (32 * RS_IN) + i * 64 + lane;
-            idx = idx < x_last ? idx : x_last;                  // tail of the last group / lanes past the 352 floats: stay in bounds
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(B.x + idx),
+            const int o = min(i * 64 + lane, lim);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gx + 4u * (unsigned)o),
                                              (__attribute__((address_space(3))) void*)(xraw + i * 64), 4, 0, 0);
         }
     };
@@ -209,7 +219,11 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
 #pragma unroll
         for (int it = 0; it < 2; ++it)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) H2[it][r] = W.b2[32 * it + rs_kappa(r, h)];
+            for (int q = 0; q < 4; ++q) {
+                // units rs_kappa(4q .. 4q+3, h) = 8q + 4h + 0..3 are consecutive: one b128 read
+                const float4 b = *reinterpret_cast<const float4*>(W.b2 + 32 * it + 8 * q + 4 * h);
+                H2[it][4 * q + 0] = b.x; H2[it][4 * q + 1] = b.y; H2[it][4 * q + 2] = b.z; H2[it][4 * q + 3] = b.w;
+            }
         RS_STAMP(2);                                    // tanh 1 + bias loads
         {
             // both output tiles advance together: two independent accumulators per fragment pair
@@ -281,8 +295,8 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
             }
 #pragma unroll
             for (int o = 0; o < NOUT; ++o) {
-                // fixed summation order in both lanes: (half 0) + (half 1)
-                const float q = __shfl_xor(pacc[o], 32);
+                // fixed summation order in both lanes: (half 0) + (half 1); the other half's value by one v_permlane32_swap
+                const float q = rs_other_half(pacc[o], h);
                 out[o] = (h ? (q + pacc[o]) : (pacc[o] + q)) + W.b3[o];
             }
         }
@@ -487,7 +501,7 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
             float rs = 0.0f;
 #pragma unroll
             for (int n = 0; n < 16; ++n) rs += Pt[c * RS_T2 + 16 * h + n];
-            rs += __shfl_xor(rs, 32);
+            rs += rs_other_half(rs, h);
             if (h == 0) dbl[32 * it + c] += rs;
         }
         RS_STAMP(10);                                   // R4 / R5 dW2 + db2

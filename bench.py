@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the radiation-search PPO hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--configs 3,4|none] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full [--configs 3,4,a2c|none]]
 
 Headline workload (BASELINE.json configs[1]): single-agent RadSearch, 1 source, no obstructions, 4096 envs per
 GPU, 2x64 MLP actor-critic, walls enforced, 480 steps/epoch, 120 steps/episode, synthetic spawns from
@@ -12,13 +12,18 @@ the loop (forward, sampling, env step, buffer write, resets), the GAE pass, and 
 (<= 40 Adam steps with KL early stop).  Nothing is skipped inside the timed region.
     value        = env steps/s over the whole job  = K * 480 * (envs per GPU * N) / wall
     ms_per_step  = wall per PPO iteration (PPO iters/s = 1000 / ms_per_step)
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
-    roofline                  the dominant kernel of the iteration (fused PPO loss+gradient pass, MFMA bound)
-    roofline_env_step[_large_n], roofline_gae   the HBM-class kernels (K1 at 4096 and 2^20 envs, K4)
-    cpu_baseline              the oracle (a port of the reference's env) on the host cores
-    configs                   BASELINE configs 3 and 4 at their stated sizes: one or two PPO iterations each with
-                              ms_per_step, phase split and their own roofline figures (N = 1 only)
-all timed in this run with HIP events on the launch stream.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line;
+besides the contract keys it carries what the timed steps measured on their own:
+    phase_ms, update_adam_steps           collect / update split, Adam steps before the KL stop
+    roofline                              the dominant kernel of the iteration (fused PPO loss+gradient pass, MFMA bound)
+    roofline_rollout, roofline_gae        the rollout (K6) and GAE (K4) launches
+all from HIP events on the launch stream around the library launches of the timed steps.  --full adds what takes runs
+of its own after the timed steps:
+    roofline.avg_launch_ms_isolated       the gradient pass re-run back to back
+    roofline_env_step[_large_n]           the env-step kernel (K1) at this size, and at 2^20 envs (N = 1 only)
+    cpu_baseline                          the oracle (a port of the reference's env) on the host cores (N = 1 only)
+    configs                               BASELINE configs 3 and 4 and the RAD-A2C row at their stated sizes: one or two PPO
+                                          iterations each with ms_per_step, phase split and their own roofline figures (N = 1 only)
 
 Multi-GPU: `--gpus N` with no launcher in the environment starts its own N ranks (torch.distributed.run,
 one process per GPU, RCCL) BEFORE touching the GPU and relays rank 0's line; under the driver's own
@@ -556,14 +561,18 @@ def main():
                     help="weak: 4096 envs per GPU (default); strong: 4096 envs in total (SURVEY 8d Metric 2)")
     ap.add_argument("--collector", choices=["fused", "torch"], default="fused")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for functional tests)")
-    ap.add_argument("--configs", default=None, help="comma list of extra BASELINE configs to run at N=1 (default '3,4,a2c': BASELINE configs 3 and 4 and the RAD-A2C row f2; 'none')")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also time the kernels on their own, the CPU baseline and the extra configs (see the module doc)")
+    ap.add_argument("--configs", default=None, help="with --full: comma list of extra BASELINE configs to run at N=1 (default '3,4,a2c': BASELINE configs 3 and 4 and the RAD-A2C row f2; 'none')")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="with --full: seconds of work per core of the CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.configs not in (None, "none") and not args.full:
+        ap.error("--configs runs extra configurations: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -672,7 +681,7 @@ def main():
     if rank == 0:
         pmc = pmc_traffic() if N == ENVS_PER_GPU else None
         if args.collector == "fused":
-            g_iso_ms, g_m = time_grad_pass(col)
+            g_iso_ms, g_m = time_grad_pass(col) if args.full else (None, T_EPOCH * N)      # one launch covers the epoch's batch
             result["roofline"] = grad_roofline(events.get("rs_ppo_grad", []), stop_iters, agents[0].train_pi_iters, g_m,
                                                iso_ms=g_iso_ms, traffic=pmc)
             if events.get("rs_rollout"):
@@ -689,18 +698,19 @@ def main():
                 result["roofline_gae"] = {"bound": "hbm", "kernel": "rs_gae_kernel", "achieved": g_gbs, "peak": HBM_PEAK_GBS,
                                           "unit": "GB/s", "frac": g_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": g_ms,
                                           "bytes_per_launch": GAE_BYTES_PER_SAMPLE * N * T_EPOCH}
-        k1 = time_step_kernel(env)
-        bytes_per_launch = K1_BYTES_PER_AGENT_STEP * N * 1
-        achieved = bytes_per_launch / (k1["avg_ms"] * 1e-3) / 1e9
-        result["roofline_env_step"] = {"bound": "hbm", "kernel": "rs_step_kernel<false>", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                                       "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                                       "traffic": pmc.get("env_step_4096_bytes_per_launch") if pmc else None,
-                                       "traffic_source": pmc.get("source") if pmc else None,
-                                       "bytes_per_launch": bytes_per_launch, "avg_launch_ms": k1["avg_ms"],
-                                       "median_launch_ms": k1["median_ms"], "back_to_back_ms": k1["train_ms"],
-                                       "env_only_steps_per_s": N / (k1["train_ms"] * 1e-3),
-                                       "note": "4096 envs = 0.64 MB per launch: launch-latency bound, see roofline_env_step_large_n"}
-        if world == 1:
+        if args.full:
+            k1 = time_step_kernel(env)
+            bytes_per_launch = K1_BYTES_PER_AGENT_STEP * N * 1
+            achieved = bytes_per_launch / (k1["avg_ms"] * 1e-3) / 1e9
+            result["roofline_env_step"] = {"bound": "hbm", "kernel": "rs_step_kernel<false>", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                                           "traffic": pmc.get("env_step_4096_bytes_per_launch") if pmc else None,
+                                           "traffic_source": pmc.get("source") if pmc else None,
+                                           "bytes_per_launch": bytes_per_launch, "avg_launch_ms": k1["avg_ms"],
+                                           "median_launch_ms": k1["median_ms"], "back_to_back_ms": k1["train_ms"],
+                                           "env_only_steps_per_s": N / (k1["train_ms"] * 1e-3),
+                                           "note": "4096 envs = 0.64 MB per launch: launch-latency bound, see roofline_env_step_large_n"}
+        if args.full and world == 1:
             # the same kernel where it is bandwidth-sized: 2^20 envs
             try:
                 big = RadSearchVec(1 << 20, number_agents=1, obstruction_count=0, enforce_grid_boundaries=True, seed=SEED, device=dev)

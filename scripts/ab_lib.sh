@@ -7,7 +7,7 @@ for sfx in "$@"; do
   lib=$GRAFT_REPO_ROOT/radiation_ppo_amd/lib/librs_hip${sfx}.so
   echo "== variant '${sfx}'" >> $out
   RS_LIB_PATH=$lib python scripts/time_pfgru.py 2>/dev/null >> $out
-  RS_LIB_PATH=$lib python bench.py --steps 3 --warmup 1 --configs a2c --no-cpu-baseline 2>/dev/null | python -c "
+  RS_LIB_PATH=$lib python bench.py --steps 3 --warmup 1 --full --configs a2c --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=[json.loads(l) for l in sys.stdin if l.startswith('{')][-1]; c=d['configs']['row_f2_rada2c']
 print(round(c['value']), round(c['ms_per_step'],1), c['phase_ms'], c['update_split_ms'])" >> $out

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r4_prof
 rm -rf $OUT && mkdir -p $OUT
 cd $R
-rocprofv3 --kernel-trace --stats -d $OUT/head -o p --output-format csv -- python3 bench.py --steps 10 --warmup 2 --configs none --no-cpu-baseline > $OUT/head.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/head -o p --output-format csv -- python3 bench.py --steps 10 --warmup 2 --full --configs none --no-cpu-baseline > $OUT/head.log 2>&1
 python3 scripts/summarize_rocprof.py $(find $OUT/head -name "*kernel_stats.csv" | head -1) $OUT/r04_kernel_stats.csv 40
 rocprofv3 --kernel-trace --stats -d $OUT/c4 -o p --output-format csv -- python3 scripts/prof_c4.py > $OUT/c4.log 2>&1
 python3 scripts/summarize_rocprof.py $(find $OUT/c4 -name "*kernel_stats.csv" | head -1) $OUT/r04_config4_kernel_stats.csv 45

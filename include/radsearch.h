@@ -434,6 +434,28 @@ int rs_cnn_trunk_prepare(int32_t in_channels, const float* w1, const float* b1, 
 int rs_cnn_trunk_infer(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent, int64_t num_samples,
                        const float* wscratch, float* a2, rs_stream_t stream);
 
+/* ---- The same trunk for square maps of any side 8 <= map_side (M) <= 256 (rs_cnn_sized.hip): the maps without enforced walls
+ * (RADTEAM_core.py:1727-1738; 147 x 147 for 120-step episodes).  The contract of rs_cnn_trunk_* with M*M cells per plane and the pooled
+ * side P = M / 2 (floor, as torch's max_pool2d: an odd M drops the last conv1 row and column):
+ *   maps [S][4][M*M]; cells / pcells [S][A] flat cell indices (-1 = empty one-hot); w1 [8][Cin][3][3], b1 [8], w2 [16][8][3][3], b2 [16]
+ *   read in their torch layouts (no prepare step, no weight scratch);
+ *   a2 [S][16*P*P] in torch's Flatten order (c*P*P + y*P + x).  For training (all three non-NULL, or all NULL): p1 [S][P*P][8],
+ *   amax [S][P*P][8] uint8 (0..3, row-major, first maximum), relu_mask [S][P*P] uint16.  rs_cnn_sized_infer = the forward without them.
+ * Backward: da2 [S][16*P*P]; slab [slab_rows][rs_cnn_sized_slab_row(Cin)] with slab_rows >= rs_cnn_sized_slab_rows(S, M, Cin) receives
+ * per-workgroup partial sums {dW1 8*Cin*9 | db1 8 | dW2 1152 | db2 16}; the caller sums the first rs_cnn_sized_slab_rows rows.  No
+ * atomics: the result is bit-identical from one call to the next.
+ * A side outside [8, 256] returns RS_ERR_UNSUPPORTED (the slab functions return 0). */
+int32_t rs_cnn_sized_slab_row(int32_t in_channels);
+int32_t rs_cnn_sized_slab_rows(int64_t num_samples, int32_t map_side, int32_t in_channels);
+int rs_cnn_sized_forward(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,
+                         int64_t num_samples, int32_t map_side, const float* w1, const float* b1, const float* w2, const float* b2,
+                         float* a2, float* p1, uint8_t* amax, uint16_t* relu_mask, rs_stream_t stream);
+int rs_cnn_sized_infer(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent, int64_t num_samples,
+                       int32_t map_side, const float* w1, const float* b1, const float* w2, const float* b2, float* a2, rs_stream_t stream);
+int rs_cnn_sized_backward(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,
+                          int64_t num_samples, int32_t map_side, const float* w2, const float* da2, const uint16_t* relu_mask,
+                          const float* p1, const uint8_t* amax, float* slab, int32_t slab_rows, rs_stream_t stream);
+
 /* The RAD-TEAM heads behind their first Linear layer (CNNBase.select_action, RADTEAM_core.py:1838-1892; Actor :1000-1023, Critic
  * :1250-1271): y1 [N][32] = Linear(2704, 32)(a2), pre-activation -> ReLU -> Linear(32, 16) (w2 [16][32], b2) -> ReLU -> Linear(16, out_dim)
  * (w3 [out_dim][16], b3).  out_dim = 8: the action logits -> log-softmax, inverse-CDF draw on u [n * u_stride] (a = #{j < 7: cdf_j <= u}),

@@ -128,6 +128,12 @@ SYMBOLS = [
     ("rs_actor_loss", C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_double, C.c_void_p]),
     ("rs_cnn_trunk_prepare", C.c_int, [C.c_int32] + [C.c_void_p] * 6),
     ("rs_cnn_trunk_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rs_cnn_sized_slab_row", C.c_int32, [C.c_int32]),
+    ("rs_cnn_sized_slab_rows", C.c_int32, [C.c_int64, C.c_int32, C.c_int32]),
+    ("rs_cnn_sized_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 9),
+    ("rs_cnn_sized_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6),
+    ("rs_cnn_sized_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6
+     + [C.c_int32, C.c_void_p]),
     ("rs_cnn_head", C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                               C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     ("rs_store_rows", C.c_int, [C.c_void_p] * 17 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

@@ -196,6 +196,76 @@ class ConvTrunk(torch.autograd.Function):
                 g[n1 + 8 + 1152:], None)
 
 
+class SizedConvTrunk(torch.autograd.Function):
+    """ConvTrunk for square maps of any side 8 <= M <= 256 (rs_cnn_sized_forward / _backward: tiled, so that the 147 x 147 maps of
+    walls-off runs stay on HIP kernels).  a2 [S, 16 P P] with P = M // 2; same arguments and agent convention as ConvTrunk."""
+
+    @staticmethod
+    def forward(ctx, maps, cells, pcells, agent, w1, b1, w2, b2, grad_mode=True):
+        lib = _lib.load()
+        S, M = maps.shape[0], maps.shape[-1]
+        assert maps.dtype == torch.float32 and maps.is_contiguous() and maps.shape[1:] == (4, M, M)
+        P = M // 2
+        A = 0
+        if agent >= 0:
+            assert cells.dtype == torch.int64 and pcells.dtype == torch.int64 and cells.is_contiguous() and pcells.is_contiguous()
+            assert cells.shape == pcells.shape and cells.shape[0] == S
+            A = cells.shape[1]
+        w1c, b1c, w2c, b2c = (t.detach().contiguous() for t in (w1, b1, w2, b2))
+        assert w1c.shape == (8, 6 if agent >= 0 else 4, 3, 3) and w2c.shape == (16, 8, 3, 3)
+        train = bool(grad_mode) and any(ctx.needs_input_grad[4:8])
+        a2 = torch.empty(S, 16 * P * P, dtype=torch.float32, device=maps.device)
+        p1 = torch.empty(S, P * P, 8, dtype=torch.float32, device=maps.device) if train else None
+        amax = torch.empty(S, P * P, 8, dtype=torch.uint8, device=maps.device) if train else None
+        mask = torch.empty(S, P * P, dtype=torch.int16, device=maps.device) if train else None
+        stream = torch.cuda.current_stream(maps.device).cuda_stream
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with _lib.timed("rs_cnn_sized_forward_train" if train else "rs_cnn_sized_forward"):
+            _lib.check(lib.rs_cnn_sized_forward(maps.data_ptr(), ptr(cells) if agent >= 0 else None, ptr(pcells) if agent >= 0 else None, A,
+                                                agent, S, M, w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), a2.data_ptr(),
+                                                ptr(p1), ptr(amax), ptr(mask), stream), "rs_cnn_sized_forward")
+        if train:
+            ctx.save_for_backward(maps, cells if agent >= 0 else maps, pcells if agent >= 0 else maps, w2c, mask, p1, amax)
+            ctx.agent, ctx.A, ctx.cin = agent, A, (6 if agent >= 0 else 4)
+        return a2
+
+    @staticmethod
+    def backward(ctx, da2):
+        lib = _lib.load()
+        maps, cells, pcells, w2c, mask, p1, amax = ctx.saved_tensors
+        S, M, cin, agent = maps.shape[0], maps.shape[-1], ctx.cin, ctx.agent
+        da2 = da2.contiguous()
+        rows, row = lib.rs_cnn_sized_slab_rows(S, M, cin), lib.rs_cnn_sized_slab_row(cin)
+        slab = torch.empty(rows, row, dtype=torch.float32, device=maps.device)
+        stream = torch.cuda.current_stream(maps.device).cuda_stream
+        with _lib.timed("rs_cnn_sized_backward"):
+            _lib.check(lib.rs_cnn_sized_backward(maps.data_ptr(), cells.data_ptr() if agent >= 0 else None,
+                                                 pcells.data_ptr() if agent >= 0 else None, ctx.A, agent, S, M, w2c.data_ptr(),
+                                                 da2.data_ptr(), mask.data_ptr(), p1.data_ptr(), amax.data_ptr(), slab.data_ptr(), rows,
+                                                 stream), "rs_cnn_sized_backward")
+        g = slab.sum(dim=0)
+        n1 = 8 * cin * 9
+        return (None, None, None, None, g[:n1].view(8, cin, 3, 3), g[n1:n1 + 8], g[n1 + 8:n1 + 8 + 1152].view(16, 8, 3, 3),
+                g[n1 + 8 + 1152:], None)
+
+
+def sized_trunk_sample_bytes(side: int) -> int:
+    """Device bytes one sample of an update chunk takes on the SizedConvTrunk path: a2 and its gradient (16 P P floats each), the
+    saved p1 (8 floats), amax (8 bytes) and ReLU mask (2 bytes) per pooled cell, and the Linear(16 P P, 32) activations."""
+    P = side // 2
+    return 2 * 4 * 16 * P * P + (32 + 8 + 2) * P * P + 4 * 4 * 32
+
+
+def _trunk(maps, cells, pcells, agent, conv1, conv2):
+    """The conv trunk on the resident maps: K9 / K10 at 27 x 27, the tiled kernels at any other square side."""
+    X, Y = maps.shape[-2:]
+    if (X, Y) == (27, 27):
+        return ConvTrunk.apply(maps, cells, pcells, agent, conv1.weight, conv1.bias, conv2.weight, conv2.bias, torch.is_grad_enabled())
+    if X != Y:
+        raise ValueError(f"the HIP CNN trunk takes square heat maps, got {X} x {Y}")
+    return SizedConvTrunk.apply(maps, cells, pcells, agent, conv1.weight, conv1.bias, conv2.weight, conv2.bias, torch.is_grad_enabled())
+
+
 class _LinearTall(torch.autograd.Function):
     """y = x W^T + b for a tall x [S, in] (the Linear layers behind the trunk: in = 2704 / 32 / 16): the weight gradient is reduced
     in two steps (partial products over 1024-row slabs -- 4096 for the wide first layer -- in one batched GEMM, then a sum), because
@@ -256,14 +326,11 @@ class CNNActor(nn.Module):
 
     def logits_from_maps(self, maps, cells, pcells, agent: int):
         """Owner `agent`'s logits for samples described by the resident shared maps [S,4,X,Y] + cell indices [S,A]:
-        HIP trunk (ConvTrunk) + the three Linear layers.  The trunk kernels K9 / K10 hold one 27 x 27 image in LDS (the walls-enforced
-        size every CLI of the reference trains with, main.py:311-316); any other map size -- 147 x 147 without enforced walls,
-        RADTEAM_core.py:1727-1738 -- takes the dense stack through the library convolutions (the same nn.Sequential)."""
-        if tuple(maps.shape[-2:]) != (27, 27):
-            with torch.backends.cudnn.flags(enabled=False):         # the native convolution: no MIOpen solver search for a one-off shape
-                return self.logits(actor_stack_from(maps, cells, pcells, agent))
+        HIP trunk + the three Linear layers.  The trunk kernels K9 / K10 (ConvTrunk) hold one 27 x 27 image in LDS (the walls-enforced
+        size every CLI of the reference trains with, main.py:311-316); any other square size -- 147 x 147 without enforced walls,
+        RADTEAM_core.py:1727-1738 -- takes the tiled kernels (SizedConvTrunk)."""
         a = self.actor
-        x = ConvTrunk.apply(maps, cells, pcells, agent, a[0].weight, a[0].bias, a[3].weight, a[3].bias, torch.is_grad_enabled())
+        x = _trunk(maps, cells, pcells, agent, a[0], a[3])
         for layer in list(a)[6:-1]:
             x = _head(layer, x)
         return x
@@ -288,13 +355,9 @@ class CNNCritic(nn.Module):
         return self.critic(x).squeeze(-1)
 
     def value_from_maps(self, maps):
-        """V for samples given as resident shared maps [S,4,X,Y]: HIP trunk (ConvTrunk) + the Linear layers (27 x 27 maps; other sizes
-        through the library convolutions, see CNNActor.logits_from_maps)."""
-        if tuple(maps.shape[-2:]) != (27, 27):
-            with torch.backends.cudnn.flags(enabled=False):
-                return self.critic(maps).squeeze(-1)
+        """V for samples given as resident shared maps [S,4,X,Y]: HIP trunk + the Linear layers (see CNNActor.logits_from_maps)."""
         c = self.critic
-        x = ConvTrunk.apply(maps, None, None, -1, c[0].weight, c[0].bias, c[3].weight, c[3].bias, torch.is_grad_enabled())
+        x = _trunk(maps, None, None, -1, c[0], c[3])
         for layer in list(c)[6:]:
             x = _head(layer, x)
         return x.squeeze(-1)

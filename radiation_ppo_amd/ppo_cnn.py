@@ -21,7 +21,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .envs import RadSearchVec
-from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from
+from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from, sized_trunk_sample_bytes
 from .pfgru import PredictorBank, hash_bits, hash_uniform
 from .ppo import (EpochStats, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
                   reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
@@ -249,10 +249,10 @@ class CNNCollector:
                 raise ValueError(f"agent {ag.id} was built for {ag.map_dim} maps, the environment produces {(X, Y)} "
                                  "(radiation_ppo_amd.maps.heat_map_geometry gives the size for an env)")
             if (X, Y) != (27, 27):
-                # RADTEAM_core.py:1727-1738: without enforced walls the maps grow to 147 x 147.  K5 handles any size; the trunk goes
-                # through the dense stack and the library convolutions there (maps.CNNActor.logits_from_maps): update chunks sized so
-                # that one dense [chunk, 6, X, Y] stack stays near 1 GB
-                ag.chunk = min(ag.chunk, max(64, (1 << 28) // (6 * X * Y)))
+                # RADTEAM_core.py:1727-1738: without enforced walls the maps grow to 147 x 147.  K5 handles any size, the trunk takes the
+                # tiled kernels (maps.SizedConvTrunk): update chunks sized so that a chunk's trunk activations, their gradient and the
+                # first Linear's stay near 16 GB (the 27 x 27 path's 524 288-sample chunk takes ~15 GB)
+                ag.chunk = min(ag.chunk, max(64, (16 << 30) // sized_trunk_sample_bytes(X)))
         need = self.T * self.N * 4 * X * Y * 4
         if need > 200e9:
             raise MemoryError(f"{X} x {Y} heat maps: the epoch's stored maps would take {need / 1e9:.0f} GB; use fewer envs")
@@ -328,22 +328,25 @@ class CNNCollector:
 
     @property
     def use_heads(self) -> bool:
-        """The select_action round of every agent as trunk (one prepared launch) + BLAS Linear(2704, 32) + rs_cnn_head, buffer rows by
-        rs_store_rows: the walls-enforced 27 x 27 maps only (the trunk kernels' size)."""
-        return self.use_glue and tuple(self.maps.map_dimensions) == (27, 27) and getattr(self, "heads", True)
+        """The select_action round of every agent as trunk (one launch) + BLAS Linear(16 P P, 32) + rs_cnn_head, buffer rows by
+        rs_store_rows; any map size (K9 at 27 x 27, the tiled trunk elsewhere)."""
+        return self.use_glue and getattr(self, "heads", True)
 
     def _prepare_heads(self) -> None:
         """Once per epoch (the networks do not change during collection): every agent's convolution weights in the trunk kernel's
-        layout; the fixed-address buffers of the fused round."""
+        layout (27 x 27; the tiled trunk reads torch's layout); the fixed-address buffers of the fused round."""
         lib, dev, N, A = _lib.load(), self.env.device, self.N, self.A
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         if getattr(self, "_wt", None) is None:
             self._wt = {a: torch.empty(lib.rs_cnn_trunk_scratch_floats(6), dtype=torch.float32, device=dev) for a in self.agents}
             self._wt_c = {a: torch.empty(lib.rs_cnn_trunk_scratch_floats(4), dtype=torch.float32, device=dev) for a in self.agents}
-            self._a2 = torch.empty(N, 2704, dtype=torch.float32, device=dev)
+            P = self.maps.map_dimensions[0] // 2
+            self._a2 = torch.empty(N, 16 * P * P, dtype=torch.float32, device=dev)
             self._k_act = torch.zeros(A, N, dtype=torch.int64, device=dev)
             self._k_f = torch.zeros(A, 3, N, dtype=torch.float32, device=dev)                   # logp, value, bootstrap value
             self._x_buf = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)   # the step's observation (buffer row)
+        if tuple(self.maps.map_dimensions) != (27, 27):
+            return
         for a, ag in self.agents.items():
             m = ag.pi.actor
             _lib.check(lib.rs_cnn_trunk_prepare(6, m[0].weight.data_ptr(), m[0].bias.data_ptr(), m[3].weight.data_ptr(), m[3].bias.data_ptr(),
@@ -363,13 +366,27 @@ class CNNCollector:
             if ag.global_critic and a != first:
                 continue
             c = ag.critic.critic
-            _lib.check(lib.rs_cnn_trunk_infer(critic_maps.data_ptr(), None, None, 0, -1, N, self._wt_c[a].data_ptr(), self._a2.data_ptr(), st),
-                       "rs_cnn_trunk_infer")
+            self._trunk_infer(critic_maps, None, None, -1, c, self._wt_c[a], st)
             y1 = torch.nn.functional.linear(self._a2, c[6].weight, c[6].bias)
             copies = A if ag.global_critic else 1
             _lib.check(lib.rs_cnn_head(y1.data_ptr(), c[8].weight.data_ptr(), c[8].bias.data_ptr(), c[10].weight.data_ptr(), c[10].bias.data_ptr(), 1,
                                        None, 1, None, None, None, 1, self._k_f[0 if ag.global_critic else a, slot].data_ptr(), copies, 3 * N,
                                        None if mask8 is None else mask8.data_ptr(), N, st), "rs_cnn_head")
+
+    def _trunk_infer(self, maps, cells, pcells, agent: int, seq, wt, st) -> None:
+        """self._a2 = the conv trunk of module `seq` (actor / critic nn.Sequential) on the round's maps: K9 with the prepared weights
+        `wt` at 27 x 27, the tiled trunk on the modules' own weights elsewhere."""
+        lib, N = _lib.load(), self.N
+        A = self.A if agent >= 0 else 0
+        cp = lambda t: None if t is None else t.data_ptr()
+        M = self.maps.map_dimensions[0]
+        if tuple(self.maps.map_dimensions) == (27, 27):
+            _lib.check(lib.rs_cnn_trunk_infer(maps.data_ptr(), cp(cells), cp(pcells), A, agent, N, wt.data_ptr(), self._a2.data_ptr(), st),
+                       "rs_cnn_trunk_infer")
+        else:
+            _lib.check(lib.rs_cnn_sized_infer(maps.data_ptr(), cp(cells), cp(pcells), A, agent, N, M, seq[0].weight.data_ptr(),
+                                              seq[0].bias.data_ptr(), seq[3].weight.data_ptr(), seq[3].bias.data_ptr(), self._a2.data_ptr(),
+                                              st), "rs_cnn_sized_infer")
 
     @torch.no_grad()
     def _step_glued(self, epoch_ended: bool) -> None:
@@ -390,8 +407,7 @@ class CNNCollector:
             self._x_buf.copy_(self.obs)
             for a, ag in self.agents.items():
                 m = ag.pi.actor
-                _lib.check(lib.rs_cnn_trunk_infer(critic.data_ptr(), cells.data_ptr(), pcells.data_ptr(), A, a, N, self._wt[a].data_ptr(),
-                                                  self._a2.data_ptr(), st), "rs_cnn_trunk_infer")
+                self._trunk_infer(critic, cells, pcells, a, m, self._wt[a], st)
                 y1 = torch.nn.functional.linear(self._a2, m[6].weight, m[6].bias)
                 _lib.check(lib.rs_cnn_head(y1.data_ptr(), m[8].weight.data_ptr(), m[8].bias.data_ptr(), m[10].weight.data_ptr(), m[10].bias.data_ptr(), 8,
                                            self._u.data_ptr() + 4 * a, A, self._k_act[a].data_ptr(), self._k_f[a, 0].data_ptr(),

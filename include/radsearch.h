@@ -427,6 +427,37 @@ int rs_a2c_heads_loss(const float* weights, const float* hs, const int64_t* act,
                       const float* sample_weight, float* dhs, float* dfac, float* tfac, float* stats, int64_t samples, double clip_ratio,
                       double vf_coef, rs_stream_t stream);
 
+/* ---- RAD-A2C actor-critic at other widths (csrc/rs_rnn_sized.hip) ------------------------------------------------------------
+ * The counterparts of rs_rnn_policy_step_rows, rs_gru_forward / _backward, rs_a2c_heads_loss and rs_gru_h0_reset for a GRU of
+ * hid = 1..64 units and single-hidden-layer heads of pol, val = 2..64 units (11 observations + 2 location inputs, 8 actions).  Widths
+ * outside these ranges return RS_ERR_UNSUPPORTED, NULL pointers or bad counts RS_ERR_INVALID_ARG, both before anything is launched.
+ *   rs_rnn_sized_weight_floats(hid, pol, val): floats of the packed actor-critic (layout: csrc/rs_rnn_sized.hip; packer: rada2c.py),
+ *       0 when unsupported.  rs_gru_sized_weight_floats(hid): floats of the packed W_hh / b_hh that the sequence kernels read;
+ *       rs_gru_sized_gate_floats(hid): floats per (step, episode) of their gates buffer.
+ *   rs_rnn_sized_step: as rs_rnn_policy_step_rows with the widths as arguments and logits [N][8] as one more optional output;
+ *       h / h_out [N][hid] (h_out may alias h).  Rows of a plain [N][.] call have strides 11 / 2 / 1.
+ *   rs_gru_sized_forward : gi [L][E][3 hid], h0 [E][hid] -> hs [L][E][hid], gates [L][E][rs_gru_sized_gate_floats(hid)]
+ *   rs_gru_sized_backward: dhs [L][E][hid], hs, gates, h0 -> dgi [L][E][3 hid], dgh [L][E][3 hid] (the caller forms the weight
+ *       gradients as for rs_gru_backward)
+ *   rs_a2c_sized_heads_loss: as rs_a2c_heads_loss with hs / dhs [S][hid], dfac [S][P8 + V8 + 16] = d pre-tanh policy [P8] | value [V8]
+ *       | d logits [8] | d value | zeros, tfac [S][P8 + V8] (P8, V8: pol, val rounded up to a multiple of 8)
+ *   rs_gru_h0_reset_sized: rs_gru_h0_reset for h [A][N][hid]. */
+int32_t rs_rnn_sized_weight_floats(int32_t hid, int32_t pol, int32_t val);
+int32_t rs_gru_sized_weight_floats(int32_t hid);
+int32_t rs_gru_sized_gate_floats(int32_t hid);
+int rs_rnn_sized_step(const float* weights, int32_t hid, int32_t pol, int32_t val, const float* x, int32_t x_stride, const float* loc,
+                      int32_t loc_stride, const float* h, const float* u, int32_t u_stride, float* h_out, float* logits, float* value,
+                      int64_t* act, float* logp, int8_t* act8, int32_t act8_stride, const uint8_t* mask, int32_t num_envs, rs_stream_t stream);
+int rs_gru_sized_forward(const float* gi, const float* h0, const float* weights, float* hs, float* gates, int32_t hid, int32_t steps,
+                         int32_t episodes, rs_stream_t stream);
+int rs_gru_sized_backward(const float* dhs, const float* hs, const float* gates, const float* h0, const float* weights, float* dgi, float* dgh,
+                          int32_t hid, int32_t steps, int32_t episodes, rs_stream_t stream);
+int rs_a2c_sized_heads_loss(const float* weights, int32_t hid, int32_t pol, int32_t val, const float* hs, const int64_t* act, const float* adv,
+                            const float* ret, const float* logp_old, const float* sample_weight, float* dhs, float* dfac, float* tfac,
+                            float* stats, int64_t samples, double clip_ratio, double vf_coef, rs_stream_t stream);
+int rs_gru_h0_reset_sized(float* h, const int64_t* base_key, const int64_t* episodes_begun, const uint8_t* mask, double scale, int32_t hid,
+                          int32_t num_envs, int32_t num_agents, rs_stream_t stream);
+
 /* The forward trunk as the collectors use it: rs_cnn_trunk_prepare re-arranges a network's convolution weights into wscratch
  * (rs_cnn_trunk_scratch_floats floats) once per epoch, rs_cnn_trunk_infer is then ONE launch per select_action round (a2 only). */
 int rs_cnn_trunk_prepare(int32_t in_channels, const float* w1, const float* b1, const float* w2, const float* b2, float* wscratch,

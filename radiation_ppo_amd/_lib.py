@@ -140,6 +140,16 @@ SYMBOLS = [
     ("rs_gru_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ("rs_gru_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_int32, C.c_void_p]),
+    ("rs_rnn_sized_weight_floats", C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    ("rs_gru_sized_weight_floats", C.c_int32, [C.c_int32]),
+    ("rs_gru_sized_gate_floats", C.c_int32, [C.c_int32]),
+    ("rs_rnn_sized_step", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("rs_gru_sized_forward", C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    ("rs_gru_sized_backward", C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    ("rs_a2c_sized_heads_loss", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10
+     + [C.c_int64, C.c_double, C.c_double, C.c_void_p]),
+    ("rs_gru_h0_reset_sized", C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 ]
 
 _lib = None

@@ -145,8 +145,8 @@ def run_test_environments(agent: VecAgentPPO, env_sets: Dict[str, tuple], montec
         x = obs.clone()
         stat.standardize(obs[..., 0], out=x[..., 0])
         vec.action_uniforms(u)
-        if recurrent and agent.agent.fused_policy and hasattr(agent, "policy_step_hip"):
-            a = torch.empty(N, dtype=torch.int64, device=dev)             # K14: GRU cell + heads + draw in one launch
+        if recurrent and (agent.agent.fused_policy or (agent.agent.sized_policy and dev.type == "cuda")) and hasattr(agent, "policy_step_hip"):
+            a = torch.empty(N, dtype=torch.int64, device=dev)             # K14 (or the sized step): GRU cell + heads + draw in one launch
             agent.policy_step_hip(x[:, 0].contiguous(), bank.predict(x)[:, 0].contiguous(), hid, u=u[:, 0].contiguous(), h_out=hid, act=a)
         elif recurrent:
             logits, _, hid = agent.agent.policy_step(x[:, 0], bank.predict(x)[:, 0], hid)
@@ -202,7 +202,7 @@ def _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruc
     bank.reset()
     gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(agent.agent.hid, dtype=torch.int64, device=dev).view(1, -1)
     hid = agent.agent.gru_h0(hash_uniform(gk)).contiguous()
-    fused = agent.agent.fused_policy and hasattr(agent, "policy_step_hip")
+    fused = (agent.agent.fused_policy or (agent.agent.sized_policy and dev.type == "cuda")) and hasattr(agent, "policy_step_hip")
     run = torch.zeros(E, dtype=torch.int64, device=dev)
     steps = torch.zeros(E, dtype=torch.int32, device=dev)
     ret = torch.zeros(E, dtype=torch.float32, device=dev)

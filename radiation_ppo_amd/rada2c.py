@@ -123,6 +123,11 @@ class RNNModelActorCritic(nn.Module):
         # actions (K12 / K14 / K15) and a 24-unit PFGRU (K11 / K13); any other size runs the same arithmetic composed from library ops
         self.fused_policy = (obs_dim, pad_dim, hid, pol, val, act_dim) == (11, 2, 24, [32], [32], 8)
         self.fused_pfgru = self.rec == 24 and obs_dim == 11
+        # every other GRU width 1..64 with single-layer heads of 2..64 units runs on the sized kernels (csrc/rs_rnn_sized.hip): policy
+        # step, GRU sequence and heads-loss; multi-layer heads and wider layers stay on the library-op composition
+        self.pol, self.val = pol, val
+        self.sized_policy = (not self.fused_policy and (obs_dim, pad_dim, act_dim) == (11, 2, 8) and 1 <= hid <= 64 and len(pol) == 1
+                             and len(val) == 1 and 2 <= pol[0] <= 64 and 2 <= val[0] <= 64)
 
     # ---- batched arithmetic
     def gru_cell(self, x: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
@@ -238,6 +243,87 @@ class GRUSequence(torch.autograd.Function):
                                        dgi.data_ptr(), dgh.data_ptr(), L, E, st), "rs_gru_backward")
         h_prev = torch.cat((h0.unsqueeze(0), hs[:-1]), dim=0)
         gw_ih = torch.bmm(dgi.transpose(1, 2), x).sum(dim=0)               # per-step partial products, then the sum over time
+        gw_hh = torch.bmm(dgh.transpose(1, 2), h_prev).sum(dim=0)
+        return None, None, gw_ih, gw_hh, dgi.sum(dim=(0, 1)), dgh.sum(dim=(0, 1))
+
+
+class HeadsLossSized(torch.autograd.Function):
+    """HeadsLoss on the sized heads-loss kernel (rs_a2c_sized_heads_loss) for single-layer heads of 2..64 units behind a GRU of 1..64:
+    the same outputs, the head weight gradients reduced from the per-sample factors with the same two-step GEMMs."""
+
+    @staticmethod
+    def forward(ctx, hs, w1, b1, w2, b2, v1, vb1, v2, vb2, packed, act, adv, ret, logp_old, wt, clip, vf):
+        S, hid = hs.shape
+        pol, val = w1.shape[0], v1.shape[0]
+        P8, V8 = (pol + 7) // 8 * 8, (val + 7) // 8 * 8
+        FT = P8 + V8
+        dev = hs.device
+        hs = hs.contiguous()
+        dhs = torch.empty(S, hid, dtype=torch.float32, device=dev)
+        dfac = torch.empty(S, FT + 16, dtype=torch.float32, device=dev)
+        tfac = torch.empty(S, FT, dtype=torch.float32, device=dev)
+        stats = torch.empty((S + 63) // 64, 8, dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().rs_a2c_sized_heads_loss(packed.data_ptr(), hid, pol, val, hs.data_ptr(), act.data_ptr(), adv.data_ptr(),
+                                                       ret.data_ptr(), logp_old.data_ptr(), wt.data_ptr(), dhs.data_ptr(), dfac.data_ptr(),
+                                                       tfac.data_ptr(), stats.data_ptr(), S, float(clip), float(vf),
+                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rs_a2c_sized_heads_loss")
+        st = stats.double().sum(dim=0)[:6]
+        g1 = _two_step(dfac[:, :pol], hs)                                 # [pol, hid]: Woms[0]
+        gv1 = _two_step(dfac[:, P8:P8 + val], hs)                         # [val, hid]: Valms[0]
+        g2 = _two_step(dfac[:, FT:FT + 8], tfac[:, :pol])                 # [8, pol]
+        g3 = _two_step(dfac[:, FT + 8:FT + 9], tfac[:, P8:P8 + val])      # [1, val]
+        m = (S // 1024) * 1024
+        gb = dfac[m:].sum(dim=0)
+        if m:
+            gb = gb + dfac[:m].view(m // 1024, 1024, FT + 16).sum(dim=1).sum(dim=0)
+        ctx.save_for_backward(dhs, g1, gv1, g2, g3, gb)
+        ctx.widths = (pol, val, P8, FT)
+        loss = (-(st[4] - vf * st[3])).float()
+        ctx.mark_non_differentiable(st)
+        return loss, st
+
+    @staticmethod
+    def backward(ctx, g, _):
+        dhs, g1, gv1, g2, g3, gb = ctx.saved_tensors
+        pol, val, P8, FT = ctx.widths
+        return (g * dhs, g * g1, g * gb[:pol], g * g2, g * gb[FT:FT + 8], g * gv1, g * gb[P8:P8 + val], g * g3, g * gb[FT + 8:FT + 9],
+                None, None, None, None, None, None, None, None)
+
+
+class GRUSequenceSized(torch.autograd.Function):
+    """GRUSequence for a GRU of 1..64 units on the sized sequence kernels (rs_gru_sized_forward / _backward): the same split -- input
+    projection and weight gradients as library GEMMs, the time loop and its back-propagation in one launch each."""
+
+    @staticmethod
+    def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh):
+        L, E, K = x.shape
+        H = w_hh.shape[1]
+        assert x.is_cuda and w_hh.shape[0] == 3 * H
+        lib = _lib.load()
+        x = x.contiguous(); h0 = h0.contiguous()
+        gi = torch.addmm(b_ih, x.view(L * E, K), w_ih.t()).view(L, E, 3 * H)
+        wg = pack_sized_gru_weights(w_hh.detach(), b_hh.detach())
+        hs = torch.empty(L, E, H, dtype=torch.float32, device=x.device)
+        gates = torch.empty(L, E, lib.rs_gru_sized_gate_floats(H), dtype=torch.float32, device=x.device)
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(lib.rs_gru_sized_forward(gi.data_ptr(), h0.data_ptr(), wg.data_ptr(), hs.data_ptr(), gates.data_ptr(), H, L, E, st),
+                   "rs_gru_sized_forward")
+        ctx.save_for_backward(x, h0, wg, hs, gates)
+        return hs
+
+    @staticmethod
+    def backward(ctx, dhs):
+        x, h0, wg, hs, gates = ctx.saved_tensors
+        L, E, H = hs.shape
+        lib = _lib.load()
+        dgi = torch.empty(L, E, 3 * H, dtype=torch.float32, device=x.device)
+        dgh = torch.empty_like(dgi)
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        dhs = dhs.contiguous()
+        _lib.check(lib.rs_gru_sized_backward(dhs.data_ptr(), hs.data_ptr(), gates.data_ptr(), h0.data_ptr(), wg.data_ptr(), dgi.data_ptr(),
+                                             dgh.data_ptr(), H, L, E, st), "rs_gru_sized_backward")
+        h_prev = torch.cat((h0.unsqueeze(0), hs[:-1]), dim=0)
+        gw_ih = torch.bmm(dgi.transpose(1, 2), x).sum(dim=0)
         gw_hh = torch.bmm(dgh.transpose(1, 2), h_prev).sum(dim=0)
         return None, None, gw_ih, gw_hh, dgi.sum(dim=(0, 1)), dgh.sum(dim=(0, 1))
 
@@ -483,6 +569,62 @@ def pack_policy_weights(ac: "RNNModelActorCritic") -> torch.Tensor:
     return w
 
 
+def _tier(hid: int) -> int:
+    """The GRU width the sized kernels are instantiated for (csrc/rs_rnn_sized.hip): hid rounded up to a multiple of 16."""
+    return (hid + 15) // 16 * 16
+
+
+def _gate_blocks(w: torch.Tensor, hid: int, HT: int) -> torch.Tensor:
+    """[3 hid, K] (gate order r, z, n) -> [HT / 8, 24, K]: unit block b's rows r(8) | z(8) | n(8), padded units zero."""
+    K = w.shape[1]
+    p = torch.zeros(3, HT, K, dtype=torch.float32, device=w.device)
+    p[:, :hid] = w.reshape(3, hid, K)
+    return p.view(3, HT // 8, 8, K).permute(1, 0, 2, 3).reshape(HT // 8, 24, K)
+
+
+def pack_sized_policy_weights(ac: "RNNModelActorCritic") -> torch.Tensor:
+    """GRU + single-layer heads in the layout rs_rnn_sized_step / rs_a2c_sized_heads_loss read (csrc/rs_rnn_sized.hip), for any GRU
+    width 1..64 and head widths 2..64: GRU blocks of 8 units, then 8-unit blocks of each head, then the output biases."""
+    v = ac.pi.logits_net.v_net
+    g = v.seq_model
+    hid, HT = ac.hid, _tier(ac.hid)
+    nb = HT // 8
+    dev = g.weight_ih_l0.device
+    W1, W2, V1 = v.Woms[0].weight, v.Woms[2].weight, v.Valms[0].weight
+    pol, val = W1.shape[0], V1.shape[0]
+    n = _lib.load().rs_rnn_sized_weight_floats(hid, pol, val)
+    assert n > 0 and g.input_size == 13 and W2.shape[0] == 8, "rs_rnn_sized_step: GRU(13, 1..64), single-layer heads of 2..64 units, 8 actions"
+    pad = lambda t, r, c: F.pad(t, (0, c - t.shape[1], 0, r - t.shape[0]))
+    col = lambda t: t.reshape(-1, 1)
+    gih = _gate_blocks(torch.cat([g.weight_ih_l0, col(g.bias_ih_l0)], 1), hid, HT)              # [nb, 24, 14]
+    ghh = _gate_blocks(torch.cat([pad(g.weight_hh_l0, 3 * hid, HT), col(g.bias_hh_l0)], 1), hid, HT)
+    gru = torch.cat([gih[:, :, :13].transpose(1, 2).reshape(nb, -1), gih[:, :, 13], ghh[:, :, :HT].transpose(1, 2).reshape(nb, -1),
+                     ghh[:, :, HT]], 1)
+    P8, V8 = (pol + 7) // 8 * 8, (val + 7) // 8 * 8
+    W1b = pad(W1, P8, HT).view(P8 // 8, 8, HT)
+    W2b = pad(W2, 8, P8).view(8, P8 // 8, 8).permute(1, 0, 2)                                    # [block, action, unit]
+    polb = torch.cat([W1b.transpose(1, 2).reshape(P8 // 8, -1), F.pad(v.Woms[0].bias, (0, P8 - pol)).view(-1, 8),
+                      W2b.transpose(1, 2).reshape(P8 // 8, -1), W1b.reshape(P8 // 8, -1), W2b.reshape(P8 // 8, -1)], 1)
+    V1b = pad(V1, V8, HT).view(V8 // 8, 8, HT)
+    valb = torch.cat([V1b.transpose(1, 2).reshape(V8 // 8, -1), F.pad(v.Valms[0].bias, (0, V8 - val)).view(-1, 8),
+                      F.pad(v.Valms[2].weight.reshape(-1), (0, V8 - val)).view(-1, 8), V1b.reshape(V8 // 8, -1)], 1)
+    tail = F.pad(torch.cat([v.Woms[2].bias.reshape(-1), v.Valms[2].bias.reshape(-1)]), (0, 7))
+    w = torch.cat([gru.reshape(-1), polb.reshape(-1), valb.reshape(-1), tail]).float().contiguous()
+    assert w.numel() == n and w.device == dev
+    return w
+
+
+def pack_sized_gru_weights(w_hh: torch.Tensor, b_hh: torch.Tensor) -> torch.Tensor:
+    """W_hh / b_hh in the layout rs_gru_sized_forward / _backward read: HH [nb][HT][24] | BHH [nb][24] | HHB [nb][24][HT]."""
+    hid = w_hh.shape[1]
+    HT = _tier(hid)
+    nb = HT // 8
+    blk = _gate_blocks(torch.cat([F.pad(w_hh, (0, HT - hid)), b_hh.reshape(-1, 1)], 1), hid, HT)      # [nb, 24, HT + 1]
+    w = torch.cat([blk[:, :, :HT].transpose(1, 2).reshape(-1), blk[:, :, HT].reshape(-1), blk[:, :, :HT].reshape(-1)]).float().contiguous()
+    assert w.numel() == _lib.load().rs_gru_sized_weight_floats(hid)
+    return w
+
+
 def unpack_train_grads(cell, g: torch.Tensor) -> Dict[str, torch.Tensor]:
     """A summed gradient slab [PF_TRAIN_GRAD_FLOATS] -> gradients by parameter name (PFGRUCell.named_parameters)."""
     zr = g[:48 * 28].view(48, 28)
@@ -557,7 +699,7 @@ class RNNAgentPPO:
         ver = tuple(p._version for p in self.agent.pi.parameters())
         if getattr(self, "_polw_ver", None) != ver:
             with torch.no_grad():
-                w = pack_policy_weights(self.agent)
+                w = pack_policy_weights(self.agent) if self.agent.fused_policy else pack_sized_policy_weights(self.agent)
                 if getattr(self, "_polw", None) is None:
                     self._polw = w
                 else:
@@ -571,6 +713,14 @@ class RNNAgentPPO:
         ptr = lambda t: None if t is None else t.data_ptr()
         for t in (x, loc, h, u, h_out, logits, value, act, logp):
             assert t is None or (t.is_cuda and t.is_contiguous())
+        ac = self.agent
+        if not ac.fused_policy:                                          # the sized step (rs_rnn_sized_step), packed rows
+            assert ac.sized_policy
+            _lib.check(_lib.load().rs_rnn_sized_step(w.data_ptr(), ac.hid, ac.pol[0], ac.val[0], x.data_ptr(), _lib.RS_OBS_DIM, loc.data_ptr(), 2,
+                                                     h.data_ptr(), ptr(u), 1, ptr(h_out), ptr(logits), ptr(value), ptr(act), ptr(logp), None, 1,
+                                                     None, x.shape[0], C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+                       "rs_rnn_sized_step")
+            return
         _lib.check(_lib.load().rs_rnn_policy_step(w.data_ptr(), x.data_ptr(), loc.data_ptr(), h.data_ptr(), ptr(u), ptr(h_out), ptr(logits),
                                                   ptr(value), ptr(act), ptr(logp), x.shape[0],
                                                   C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "rs_rnn_policy_step")
@@ -582,6 +732,16 @@ class RNNAgentPPO:
         N, A = x.shape[0], x.shape[1]
         w = self.policy_weights()
         fl = lambda t, k: None if t is None else t.data_ptr() + 4 * a * k
+        ac = self.agent
+        if not ac.fused_policy:                                          # the sized step on the same rows
+            assert ac.sized_policy
+            _lib.check(_lib.load().rs_rnn_sized_step(w.data_ptr(), ac.hid, ac.pol[0], ac.val[0], fl(x, _lib.RS_OBS_DIM), A * _lib.RS_OBS_DIM,
+                                                     fl(loc, 2), 2 * A, h.data_ptr(), fl(u, 1), A, None if u is None else h.data_ptr(), None,
+                                                     value.data_ptr(), None if act is None else act.data_ptr(),
+                                                     None if logp is None else logp.data_ptr(), None if act8 is None else act8.data_ptr() + a, A,
+                                                     None if mask8 is None else mask8.data_ptr(), N,
+                                                     C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "rs_rnn_sized_step")
+            return
         _lib.check(_lib.load().rs_rnn_policy_step_rows(w.data_ptr(), fl(x, _lib.RS_OBS_DIM), A * _lib.RS_OBS_DIM, fl(loc, 2), 2 * A, h.data_ptr(),
                                                        fl(u, 1), A, None if u is None else h.data_ptr(), value.data_ptr(),
                                                        None if act is None else act.data_ptr(), None if logp is None else logp.data_ptr(),
@@ -863,17 +1023,21 @@ class RNNAgentPPO:
         # the GRU over the whole (padded) episode batch in one sequence call, as grad_step does (:564): states past an episode's
         # end are computed and never used (weight 0)
         g = ac.pi.logits_net.v_net.seq_model
+        sized = X.is_cuda and ac.sized_policy and getattr(self, "use_sized", True)
         if X.is_cuda and ac.hid == 24 and g.input_size == 13 and getattr(self, "use_k12", True):
             # K12: the recurrence and its back-propagation through time in one launch each
             hs = GRUSequence.apply(torch.cat((X, loc), dim=2), h, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)
+        elif sized:                                            # the same split at any other GRU width 1..64 (rs_gru_sized_*)
+            hs = GRUSequenceSized.apply(torch.cat((X, loc), dim=2), h, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)
         else:
             with torch.backends.cudnn.flags(enabled=False):    # (the library path; on the GPU MIOpen's RNN backward is slower than native)
                 hs, _ = g(torch.cat((X, loc), dim=2), h.unsqueeze(0).contiguous())
-        if X.is_cuda and ac.fused_policy and getattr(self, "use_k15", True):
-            # K15: heads + per-sample loss + their back-propagation in one launch
+        fused_heads = X.is_cuda and ac.fused_policy and getattr(self, "use_k15", True)
+        if fused_heads or sized:
+            # K15 (or its sized counterpart): heads + per-sample loss + their back-propagation in one launch
             v = ac.pi.logits_net.v_net
             flat = lambda t: t.reshape(L * E).contiguous()
-            loss_g, st = HeadsLoss.apply(hs.reshape(L * E, -1), v.Woms[0].weight, v.Woms[0].bias, v.Woms[2].weight, v.Woms[2].bias,
+            loss_g, st = (HeadsLoss if fused_heads else HeadsLossSized).apply(hs.reshape(L * E, -1), v.Woms[0].weight, v.Woms[0].bias, v.Woms[2].weight, v.Woms[2].bias,
                                          v.Valms[0].weight, v.Valms[0].bias, v.Valms[2].weight, v.Valms[2].bias, self.policy_weights(),
                                          flat(B.act[:, sl]), flat(B.adv[:, sl]), flat(B.ret[:, sl]), flat(B.logp[:, sl]), flat(w),
                                          self.clip_ratio, 0.01)
@@ -1013,14 +1177,21 @@ class RNNCollector:
         self._src = torch.zeros(self.N, 2, dtype=torch.float32, device=dev)
         # K14 (rs_rnn_policy_step): GRU cell + heads + draw in one launch instead of ~35 library kernels per call
         self.use_k14 = torch.device(dev).type == "cuda" and all(ag.agent.fused_policy for ag in agents.values())
+        # the sized step (rs_rnn_sized_step) in K14's place for the other widths it serves (RNNModelActorCritic.sized_policy)
+        self.use_sized = torch.device(dev).type == "cuda" and not self.use_k14 and all(ag.agent.sized_policy for ag in agents.values())
         self._k_act = torch.zeros(self.A, self.N, dtype=torch.int64, device=dev)
         self._k_f = torch.zeros(self.A, 3, self.N, dtype=torch.float32, device=dev)          # logp, value, bootstrap value
         self.obs = None
         self.started = False
         self.epoch = 0
         # the lock-step's element-wise bookkeeping as three launches (rs_collect_*; ~30 torch launches before): needs K14 and the fused bank
-        self.use_glue = self.use_k14 and fused_pf
+        self.use_glue = (self.use_k14 or self.use_sized) and fused_pf
         self._cs = None
+
+    @property
+    def _kstep(self) -> bool:
+        """The policy step runs as one launch (K14 or the sized step) and the buffer rows are written by rs_store_rows."""
+        return self.use_k14 or self.use_sized
 
     def _glue_state(self) -> "_lib.RsCollectState":
         """rs_collect_state over the collector's (fixed-address) buffers, built once the first observation exists."""
@@ -1081,8 +1252,13 @@ class RNNCollector:
         _lib.check(lib.rs_collect_post_reset(C.byref(cs), 0 if epoch_ended else 1, st), "rs_collect_post_reset")
         if not epoch_ended:                                                                    # train.py:505-518 (reset_hidden)
             self.bank.reset_kernel(cut)
-            _lib.check(lib.rs_gru_h0_reset(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(), cut.data_ptr(),
-                                           1.0 / math.sqrt(self.agents[0].agent.hid), N, A, st), "rs_gru_h0_reset")
+            hid = self.agents[0].agent.hid
+            if self.use_k14:
+                _lib.check(lib.rs_gru_h0_reset(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(), cut.data_ptr(),
+                                               1.0 / math.sqrt(hid), N, A, st), "rs_gru_h0_reset")
+            else:
+                _lib.check(lib.rs_gru_h0_reset_sized(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(), cut.data_ptr(),
+                                                     1.0 / math.sqrt(hid), hid, N, A, st), "rs_gru_h0_reset_sized")
 
     def _x(self, obs: torch.Tensor) -> torch.Tensor:
         x = obs.clone()
@@ -1099,6 +1275,13 @@ class RNNCollector:
             _lib.check(_lib.load().rs_gru_h0_reset(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(), m8.data_ptr(),
                                                    1.0 / math.sqrt(self.agents[0].agent.hid), self.N, self.A,
                                                    C.c_void_p(torch.cuda.current_stream(self.h.device).cuda_stream)), "rs_gru_h0_reset")
+            return
+        if self.use_sized:                                                     # the same at the agent's GRU width
+            m8 = m.view(torch.uint8)
+            hid = self.agents[0].agent.hid
+            _lib.check(_lib.load().rs_gru_h0_reset_sized(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(),
+                                                         m8.data_ptr(), 1.0 / math.sqrt(hid), hid, self.N, self.A,
+                                                         C.c_void_p(torch.cuda.current_stream(self.h.device).cuda_stream)), "rs_gru_h0_reset_sized")
             return
         key = (self.bank._base * 1000003) ^ ((self.episodes_begun.view(1, -1) * 8 + 5) * _s64(0xA24BAED4963EE407))      # [A, N]
         u = hash_uniform(key.unsqueeze(-1) * 1048583 + self._gidx.view(1, 1, -1))
@@ -1123,7 +1306,7 @@ class RNNCollector:
         env.action_uniforms(self._u)
         loc = self.bank.predict(x)                                            # PFGRU (K11), carried particle sets
         for a, ag in self.agents.items():
-            if self.use_k14:
+            if self._kstep:
                 act = self._k_act[a]
                 ag.policy_step_hip(x[:, a].contiguous(), loc[:, a].contiguous(), self.h[a], u=self._u[:, a].contiguous(), h_out=self.h[a],
                                    value=self._k_f[a, 1], act=act, logp=self._k_f[a, 0])
@@ -1138,7 +1321,7 @@ class RNNCollector:
             self._row_f[0, :, a] = logp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1)
             self._row_f[1, :, a] = v
             self._act8[:, a] = act.to(torch.int8)
-        fast = self.use_k14                                                   # one store kernel per lock-step instead of ~19 launches
+        fast = self._kstep                                                    # one store kernel per lock-step instead of ~19 launches
         if not fast:
             put(buf.act, self._row_act); put(buf.logp, self._row_f[0]); put(buf.val, self._row_f[1])
             put(buf.obs, x)
@@ -1163,7 +1346,7 @@ class RNNCollector:
         xb = self._x(self.obs)
         locb = self.bank.predict(xb, mask=boot)
         for a, ag in self.agents.items():
-            if self.use_k14:
+            if self._kstep:
                 ag.policy_step_hip(xb[:, a].contiguous(), locb[:, a].contiguous(), self.h[a], value=self._k_f[a, 2])
                 continue
             _, vb, _ = ag.agent.policy_step(xb[:, a], locb[:, a], self.h[a])
@@ -1200,7 +1383,7 @@ class RNNCollector:
         self._acc.zero_()
         self._t.zero_()
         self._reset_hidden(None)                                              # train.py:322-329: every epoch starts fresh
-        if self.use_k14:
+        if self._kstep:
             for ag in self.agents.values():
                 ag.policy_weights()                                           # re-packed in place after an update
         if self.bank.impl == "hip":

@@ -347,6 +347,26 @@ int rs_pfgru_step_recorded(const float* weights, const float* obs, float* h, flo
 int rs_pfgru_reset(float* h, float* p, const int64_t* base_key, const int64_t* episode, const int64_t* calls, const uint8_t* mask,
                    int32_t num_envs, int32_t num_agents, rs_stream_t stream);
 
+/* ---- The PFGRU location predictor at hidden widths H = 8, 16, .., 64 (csrc/rs_pfgru_sized.hip) --------------------------------
+ * rs_pfgru_step / _pass / _step_recorded / _reset with the width as the last argument before the stream: 40 particles, 3 inputs,
+ * alpha, tanh and the hid_obs head Linear(H, 24)-ReLU-Linear(24, 2)-ReLU as the reference fixes them, the same draw hash, the particle
+ * sets quad-major [A][N][H / 4][40][4], eps [A][N][40][H].  rs_pfgru_sized_weight_floats(H): floats per owner of the packed weights
+ * (layout: csrc/rs_pfgru_sized.hip; packer: pfgru.py: pack_sized_weights), 0 when unsupported.  A width that is not a multiple of 8 in
+ * 8..64 returns RS_ERR_UNSUPPORTED, NULL pointers or bad counts (N < 1, A outside 1..RS_MAX_AGENTS, steps < 1, alive[] not a
+ * descending prefix count) RS_ERR_INVALID_ARG, both before anything is launched.  rs_pfgru_sized_pass takes up to 8 steps per launch. */
+int32_t rs_pfgru_sized_weight_floats(int32_t hidden);
+int rs_pfgru_sized_step(const float* weights, const float* obs, float* h, float* p, const int64_t* base_key, const int64_t* episode,
+                        const int64_t* calls, const uint8_t* mask, int32_t carry_hidden, double alpha, float* pred, int32_t num_envs,
+                        int32_t num_agents, int32_t hidden, rs_stream_t stream);
+int rs_pfgru_sized_pass(const float* weights, const float* obs, float* h, float* p, const int64_t* base_key, const int64_t* episode,
+                        const int64_t* calls, double alpha, float* pred, const int32_t* alive, int32_t steps, int32_t episodes, int32_t hidden,
+                        rs_stream_t stream);
+int rs_pfgru_sized_step_recorded(const float* weights, const float* obs, float* h, float* p, const float* eps, const int32_t* idx,
+                                 const uint8_t* mask, int32_t carry_hidden, double alpha, float* pred, int32_t num_envs, int32_t num_agents,
+                                 int32_t hidden, rs_stream_t stream);
+int rs_pfgru_sized_reset(float* h, float* p, const int64_t* base_key, const int64_t* episode, const int64_t* calls, const uint8_t* mask,
+                         int32_t num_envs, int32_t num_agents, int32_t hidden, rs_stream_t stream);
+
 /* All draws of one PFGRU training pass over an episode-major batch (the counter hash of rada2c.HashDraws: keys [E] int64):
  * h0 [E][40][24] initial particles (uniforms), eps [L][E][40][24] reparameterisation noise (standard normals), u [L][E][40]
  * resampling uniforms (float64).  Replaces torch.rand / FloatTensor.normal_ / torch.multinomial's generator in update_model

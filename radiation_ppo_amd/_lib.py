@@ -110,6 +110,12 @@ SYMBOLS = [
     ("rs_pfgru_pass", C.c_int, [C.c_void_p] * 7 + [C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ("rs_pfgru_reset", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p]),
+    ("rs_pfgru_sized_weight_floats", C.c_int32, [C.c_int32]),
+    ("rs_pfgru_sized_step", C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    ("rs_pfgru_sized_pass", C.c_int, [C.c_void_p] * 7 + [C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    ("rs_pfgru_sized_step_recorded", C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                                    C.c_void_p]),
+    ("rs_pfgru_sized_reset", C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("rs_pfgru_draws", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rs_pfgru_train", C.c_int, [C.c_void_p] * 15 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     ("rs_pfgru_train_keyed", C.c_int, [C.c_void_p] * 14 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

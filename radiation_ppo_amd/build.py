@@ -15,7 +15,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "librs_hip.so")
 
 SOURCES = ["rs_env.hip", "rs_ppo.hip", "rs_maps.hip", "rs_cnn.hip", "rs_cnn_sized.hip", "rs_pfgru.hip", "rs_gru.hip", "rs_pfgru_train.hip", "rs_rnn_policy.hip", "rs_welford.hip", "rs_cnn_loss.hip",
-           "rs_rnn_sized.hip"]
+           "rs_rnn_sized.hip", "rs_pfgru_sized.hip"]
 # -ffp-contract=off: float64 env arithmetic must round like the reference's Python floats (no FMA fusing)
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
           "-Wno-unused-function"]
@@ -23,7 +23,8 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # which costs more issue slots than it saves next to f32 MFMAs (measured: scripts/micro/mfma_valu_coissue.hip)
 # rs_rnn_sized.hip: the 64-unit tier's unrolled block loops exceed the default full-unroll budget; left rolled, the register arrays they
 # index go to scratch (528 bytes per lane at 64 units)
-EXTRA_CFLAGS = {"rs_ppo.hip": ["-fno-slp-vectorize"], "rs_rnn_sized.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"]}
+EXTRA_CFLAGS = {"rs_ppo.hip": ["-fno-slp-vectorize"], "rs_rnn_sized.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
+                "rs_pfgru_sized.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"]}
 
 
 def hipcc() -> str:
@@ -63,8 +64,17 @@ def build(force: bool = False, verbose: bool = True, defines=(), suffix: str = "
             subprocess.run(cmd, check=True)
         return obj
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-        objs = list(ex.map(compile_one, SOURCES))
+    # as many compilers at once as there are CPUs to run them (MAX_JOBS caps it where set), the two slowest translation units first
+    # (~70 and ~45 s; the others 2-15 s): one compiler per source at once needs ~2.5 GB on a small build machine for no gain in time
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    jobs = max(1, min(len(SOURCES), cpus, int(os.environ.get("MAX_JOBS") or cpus)))
+    order = sorted(SOURCES, key=lambda f: f not in ("rs_rnn_sized.hip", "rs_pfgru_sized.hip"))
+    with ThreadPoolExecutor(max_workers=jobs) as ex:
+        done = dict(zip(order, ex.map(compile_one, order)))
+    objs = [done[f] for f in SOURCES]
     cmd = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", lib]
     if verbose:
         print("[radiation_ppo_amd.build]", " ".join(cmd), flush=True)

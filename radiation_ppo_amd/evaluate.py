@@ -136,7 +136,7 @@ def run_test_environments(agent: VecAgentPPO, env_sets: Dict[str, tuple], montec
     if recurrent:
         from .pfgru import PredictorBank, hash_uniform
         bank = PredictorBank(N, 1, hidden_size=agent.agent.rec, seed=seed, carry_hidden=True, device=dev,
-                             impl="hip" if agent.agent.fused_pfgru else "torch")
+                             impl="hip" if (agent.agent.fused_pfgru or (agent.agent.sized_pfgru and dev.type == "cuda")) else "torch")
         bank.cells[0] = agent.agent.model
         bank.reset()
         gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(agent.agent.hid, dtype=torch.int64, device=dev).view(1, -1)
@@ -197,7 +197,7 @@ def _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruc
     stat = DeviceWelford((E, 1), dev)
     stat.update(obs[..., 0])
     bank = PredictorBank(E, 1, hidden_size=agent.agent.rec, seed=seed, carry_hidden=True, device=dev,
-                         impl="hip" if agent.agent.fused_pfgru else "torch")
+                         impl="hip" if (agent.agent.fused_pfgru or (agent.agent.sized_pfgru and dev.type == "cuda")) else "torch")
     bank.cells[0] = agent.agent.model
     bank.reset()
     gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(agent.agent.hid, dtype=torch.int64, device=dev).view(1, -1)

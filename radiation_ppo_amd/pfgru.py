@@ -100,6 +100,59 @@ def pack_weights(cells) -> torch.Tensor:
     return torch.stack(rows).contiguous()
 
 
+# the widths csrc/rs_pfgru_sized.hip serves (a multiple of 8 from 8 to 64); PredictorBank(impl="hip") keeps K11 at 24
+SIZED_WIDTHS = (8, 16, 24, 32, 40, 48, 56, 64)
+
+
+def _r16(v: int) -> int:
+    return (v + 15) // 16 * 16
+
+
+def sized_layout(H: int) -> dict:
+    """Offsets (floats) of csrc/rs_pfgru_sized.hip's packed per-owner weights at width H, and the owner stride."""
+    K, nb = H + 3, H // 8
+    L = dict(R=0)
+    L["RB"] = _r16(K * H)
+    L["ZN"] = _r16(L["RB"] + H)
+    L["ZNB"] = _r16(L["ZN"] + nb * K * 24)
+    L["O"] = _r16(L["ZNB"] + nb * 24)
+    L["OB"] = L["O"] + K
+    L["H0"] = _r16(L["OB"] + 1)
+    L["H0B"] = L["H0"] + H * 24
+    L["H2"] = L["H0B"] + 24
+    L["H2B"] = L["H2"] + 48
+    L["stride"] = _r16(L["H2B"] + 2)
+    return L
+
+
+def pack_sized_weights(cells) -> torch.Tensor:
+    """[A, stride] float32 for rs_pfgru_sized_*: R [K][H] (fc_r, k-major) | RB | H / 8 blocks [K][24] of [fc_z | mu | var] for units
+    8b .. 8b+7 | their biases [H / 8][24] | O [K] | OB | H0 [H][24] | H0B | H2 [2][24] | H2B (layout: csrc/rs_pfgru_sized.hip)."""
+    H = cells[0].h_dim
+    L = sized_layout(H)
+    K, nb = H + 3, H // 8
+    rows = []
+    for c in cells:
+        assert c.h_dim == H and H in SIZED_WIDTHS and c.num_particles == 40 and c.input_size == 3, "rs_pfgru_sized: 40 particles x 8..64 units"
+        w = torch.zeros(L["stride"], dtype=torch.float32, device=c.fc_z.weight.device)
+        w[L["R"]:L["R"] + K * H] = c.fc_r.weight.t().reshape(-1)
+        w[L["RB"]:L["RB"] + H] = c.fc_r.bias
+        fz, fn, bz, bn = c.fc_z.weight, c.fc_n.weight, c.fc_z.bias, c.fc_n.bias
+        for b in range(nb):
+            u = slice(8 * b, 8 * b + 8)
+            v = slice(H + 8 * b, H + 8 * b + 8)
+            w[L["ZN"] + b * K * 24:L["ZN"] + (b + 1) * K * 24] = torch.cat([fz[u], fn[u], fn[v]], 0).t().reshape(-1)
+            w[L["ZNB"] + b * 24:L["ZNB"] + (b + 1) * 24] = torch.cat([bz[u], bn[u], bn[v]])
+        w[L["O"]:L["OB"]] = c.fc_obs.weight.reshape(-1)
+        w[L["OB"]] = c.fc_obs.bias[0]
+        w[L["H0"]:L["H0B"]] = c.hid_obs[0].weight.t().reshape(-1)
+        w[L["H0B"]:L["H2"]] = c.hid_obs[0].bias
+        w[L["H2"]:L["H2B"]] = c.hid_obs[2].weight.reshape(-1)
+        w[L["H2B"]:L["H2B"] + 2] = c.hid_obs[2].bias
+        rows.append(w)
+    return torch.stack(rows).contiguous()
+
+
 class _Linear3D(torch.autograd.Function):
     """y = x W^T + b for x [B, P, K] with a weight gradient that is reduced in two steps: per-b partial products [B, K, O] (one
     batched GEMM) and a sum over b.  autograd's own dW = x.reshape(B * P, K)^T @ g.reshape(B * P, O) is a tall-skinny GEMM with a
@@ -188,21 +241,26 @@ class PredictorBank:
     """One PFGRUCell per owner, evaluated for all envs at once; what feeds heat-map channel 0 (`rs_maps_update`'s pred)."""
 
     def __init__(self, num_envs: int, number_agents: int, hidden_size: int = 24, seed: int = 0, env_id_base: int = 0,
-                 carry_hidden: bool = False, device="cuda:0", impl: str = "hip"):
-        """impl: "hip" = the fused step / reset kernels (csrc/rs_pfgru.hip through the C ABI; the product path, cuda only);
-        "torch" = the same arithmetic composed from torch ops (what the kernel is tested against; also runs on the CPU)."""
+                 carry_hidden: bool = False, device="cuda:0", impl: str = "hip", sized: Optional[bool] = None):
+        """impl: "hip" = the fused step / reset kernels (csrc/rs_pfgru.hip at 24 hidden units, csrc/rs_pfgru_sized.hip at the other
+        SIZED_WIDTHS, through the C ABI; the product path, cuda only); "torch" = the same arithmetic composed from torch ops (what the
+        kernels are tested against; also runs on the CPU).  sized: force the sized kernels (True, e.g. at 24 units to hold them to K11)
+        or K11 (False); None = K11 at 24 units, the sized kernels otherwise."""
         assert impl in ("hip", "torch")
         self.N, self.A, self.dev = num_envs, number_agents, torch.device(device)
         self.impl = impl
         if impl == "hip":
             if self.dev.type != "cuda":
                 raise RuntimeError("PredictorBank(impl='hip') needs a cuda device; there is no CPU fallback for the product path")
-            if hidden_size != 24:
-                raise NotImplementedError("rs_pfgru_step is built for the reference's 24 hidden units (RADTEAM_core.py:1790-1795)")
+            if hidden_size not in SIZED_WIDTHS:
+                raise NotImplementedError("the PFGRU kernels serve 8, 16, .., 64 hidden units (rs_pfgru_step: 24, rs_pfgru_sized_step: "
+                                          f"the other multiples of 8), not {hidden_size}")
             self._lib = _lib.load()
             self._pred = torch.zeros(num_envs, number_agents, 2, dtype=torch.float32, device=self.dev)
         self.cells = [PFGRUCell(hidden_size=hidden_size).to(self.dev) for _ in range(number_agents)]
         self.carry_hidden = carry_hidden
+        self.sized = impl == "hip" and (hidden_size != 24 if sized is None else bool(sized))
+        assert self.sized or impl != "hip" or hidden_size == 24
         P, H = self.cells[0].num_particles, hidden_size
         self.P, self.H = P, H
         env = torch.arange(num_envs, dtype=torch.int64, device=self.dev) + int(env_id_base)
@@ -257,11 +315,7 @@ class PredictorBank:
         self.episode.add_(m1.long())                      # counters change in place: a captured collector step refers to them
         self.calls.masked_fill_(m1, 0)
         if self.impl == "hip":
-            m8 = None if mask is None else m1.to(torch.uint8)
-            with _lib.timed("rs_pfgru_reset"):
-                _lib.check(self._lib.rs_pfgru_reset(self._hq.data_ptr(), self.p.data_ptr(), self._base.data_ptr(), self.episode.data_ptr(),
-                                                    self.calls.data_ptr(), None if m8 is None else m8.data_ptr(), self.N, self.A,
-                                                    self._stream()), "rs_pfgru_reset")
+            self.reset_kernel(None if mask is None else m1.to(torch.uint8))
             return
         k = self._key(0)
         u = hash_uniform(k.view(self.A, self.N, 1, 1) * 1048583 + self._pu.view(1, 1, self.P, self.H)).float()
@@ -276,26 +330,33 @@ class PredictorBank:
     # `episode` / `calls` are NOT touched here, `mask8` is a uint8 tensor or None, the prediction comes back as the bank's own buffer
     def predict_kernel(self, obs: torch.Tensor, mask8: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert self.impl == "hip" and obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape == (self.N, self.A, _lib.RS_OBS_DIM)
-        with _lib.timed("rs_pfgru_step"):
-            _lib.check(self._lib.rs_pfgru_step(self._packed().data_ptr(), obs.data_ptr(), self._hq.data_ptr(), self.p.data_ptr(),
-                                               self._base.data_ptr(), self.episode.data_ptr(), self.calls.data_ptr(),
-                                               None if mask8 is None else mask8.data_ptr(), 1 if self.carry_hidden else 0,
-                                               float(self.cells[0].resamp_alpha), self._pred.data_ptr(), self.N, self.A, self._stream()),
-                       "rs_pfgru_step")
+        args = (self._packed().data_ptr(), obs.data_ptr(), self._hq.data_ptr(), self.p.data_ptr(), self._base.data_ptr(),
+                self.episode.data_ptr(), self.calls.data_ptr(), None if mask8 is None else mask8.data_ptr(), 1 if self.carry_hidden else 0,
+                float(self.cells[0].resamp_alpha), self._pred.data_ptr(), self.N, self.A)
+        if self.sized:
+            with _lib.timed("rs_pfgru_sized_step"):
+                _lib.check(self._lib.rs_pfgru_sized_step(*args, self.H, self._stream()), "rs_pfgru_sized_step")
+        else:
+            with _lib.timed("rs_pfgru_step"):
+                _lib.check(self._lib.rs_pfgru_step(*args, self._stream()), "rs_pfgru_step")
         return self._pred
 
     def reset_kernel(self, mask8: Optional[torch.Tensor] = None) -> None:
         assert self.impl == "hip"
-        with _lib.timed("rs_pfgru_reset"):
-            _lib.check(self._lib.rs_pfgru_reset(self._hq.data_ptr(), self.p.data_ptr(), self._base.data_ptr(), self.episode.data_ptr(),
-                                                self.calls.data_ptr(), None if mask8 is None else mask8.data_ptr(), self.N, self.A,
-                                                self._stream()), "rs_pfgru_reset")
+        args = (self._hq.data_ptr(), self.p.data_ptr(), self._base.data_ptr(), self.episode.data_ptr(), self.calls.data_ptr(),
+                None if mask8 is None else mask8.data_ptr(), self.N, self.A)
+        if self.sized:
+            with _lib.timed("rs_pfgru_sized_reset"):
+                _lib.check(self._lib.rs_pfgru_sized_reset(*args, self.H, self._stream()), "rs_pfgru_sized_reset")
+        else:
+            with _lib.timed("rs_pfgru_reset"):
+                _lib.check(self._lib.rs_pfgru_reset(*args, self._stream()), "rs_pfgru_reset")
 
     def _packed(self) -> torch.Tensor:
         ver = tuple(p._version for c in self.cells for p in c.parameters())
         if getattr(self, "_pack_ver", None) != ver:
             with torch.no_grad():
-                w = pack_weights(self.cells)
+                w = pack_sized_weights(self.cells) if self.sized else pack_weights(self.cells)
                 if getattr(self, "_wpack", None) is None:
                     self._wpack = w
                 else:
@@ -327,13 +388,7 @@ class PredictorBank:
         A, N, P, H = self.A, self.N, self.P, self.H
         if self.impl == "hip":
             assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape == (N, A, _lib.RS_OBS_DIM)
-            m8 = None if mask is None else mask.to(torch.uint8)
-            with _lib.timed("rs_pfgru_step"):
-                _lib.check(self._lib.rs_pfgru_step(self._packed().data_ptr(), obs.data_ptr(), self._hq.data_ptr(), self.p.data_ptr(),
-                                                   self._base.data_ptr(), self.episode.data_ptr(), self.calls.data_ptr(),
-                                                   None if m8 is None else m8.data_ptr(), 1 if self.carry_hidden else 0,
-                                                   float(self.cells[0].resamp_alpha), self._pred.data_ptr(), N, A, self._stream()),
-                           "rs_pfgru_step")
+            self.predict_kernel(obs, None if mask is None else mask.to(torch.uint8))
             self.calls.add_(1 if mask is None else mask.long())
             return self._pred.clone()
         W = self._stacked()

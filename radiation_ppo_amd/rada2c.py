@@ -42,7 +42,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .envs import RadSearchVec
-from .pfgru import PFGRUCell, PredictorBank, _s64, hash_normal, hash_uniform
+from .pfgru import SIZED_WIDTHS, PFGRUCell, PredictorBank, _s64, hash_normal, hash_uniform
 from .ppo import (DeviceWelford, EpochStats, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
                   reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
 
@@ -123,6 +123,9 @@ class RNNModelActorCritic(nn.Module):
         # actions (K12 / K14 / K15) and a 24-unit PFGRU (K11 / K13); any other size runs the same arithmetic composed from library ops
         self.fused_policy = (obs_dim, pad_dim, hid, pol, val, act_dim) == (11, 2, 24, [32], [32], 8)
         self.fused_pfgru = self.rec == 24 and obs_dim == 11
+        # the PFGRU's no-grad passes and the collectors' steps at the other widths rs_pfgru_sized serves (a multiple of 8 up to 64); its
+        # training pass (update_model) stays on library ops there: K13 is built for 24 units only
+        self.sized_pfgru = obs_dim == 11 and self.rec != 24 and self.rec in SIZED_WIDTHS
         # every other GRU width 1..64 with single-layer heads of 2..64 units runs on the sized kernels (csrc/rs_rnn_sized.hip): policy
         # step, GRU sequence and heads-loss; multi-layer heads and wider layers stay on the library-op composition
         self.pol, self.val = pol, val
@@ -775,19 +778,21 @@ class RNNAgentPPO:
         return torch.stack(locs), (torch.stack(parts) if want_particles else None)
 
     def _pfgru_pass_hip(self, X: torch.Tensor, draws: "HashDraws", lens_host: Optional[List[int]] = None) -> torch.Tensor:
-        """The no-grad PFGRU pass of grad_step (:555-558) on K11: X [L, E, 11] -> loc [L, E, 2].  Particle sets start from the
-        reset kernel's hash draws and are carried; the draw keys are the chunk's episode keys."""
-        from .pfgru import pack_weights
+        """The no-grad PFGRU pass of grad_step (:555-558) on K11 (rs_pfgru_sized_pass for sized_pfgru): X [L, E, 11] -> loc [L, E, 2].
+        Particle sets start from the reset kernel's hash draws and are carried; the draw keys are the chunk's episode keys."""
+        from .pfgru import pack_sized_weights, pack_weights
         lib = _lib.load()
         L, E = X.shape[0], X.shape[1]
         dev = X.device
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        h = torch.empty(1, E, 40, 24, dtype=torch.float32, device=dev)
+        sized = self.agent.sized_pfgru
+        H = self.agent.rec if sized else 24
+        h = torch.empty(1, E, 40, H, dtype=torch.float32, device=dev)
         p = torch.empty(1, E, 40, dtype=torch.float32, device=dev)
         base = draws.k.contiguous().view(1, E)
         episode = torch.ones(E, dtype=torch.int64, device=dev)
         calls = torch.arange(L, dtype=torch.int64, device=dev).view(L, 1).expand(L, E).contiguous()   # the step counter of every launch
-        wts = pack_weights([self.agent.model])
+        wts = pack_sized_weights([self.agent.model]) if sized else pack_weights([self.agent.model])
         loc = torch.zeros(L, E, 2, dtype=torch.float32, device=dev)
         # episodes sorted by descending length: the ones still running at step t are a prefix, the launch covers only those
         alive = [E] * L
@@ -799,9 +804,14 @@ class RNNAgentPPO:
         Xc = X.contiguous()
         alive_h = (C.c_int32 * L)(*alive)
         self.k11_particle_steps.append(40 * (int(sum(lens_host)) if lens_host is not None else L * E))
-        with _lib.timed("rs_pfgru_pass"):
-            _lib.check(lib.rs_pfgru_pass(wts.data_ptr(), Xc.data_ptr(), h.data_ptr(), p.data_ptr(), base.data_ptr(), episode.data_ptr(), calls.data_ptr(),
-                                         float(self.agent.model.resamp_alpha), loc.data_ptr(), alive_h, L, E, st), "rs_pfgru_pass")
+        args = (wts.data_ptr(), Xc.data_ptr(), h.data_ptr(), p.data_ptr(), base.data_ptr(), episode.data_ptr(), calls.data_ptr(),
+                float(self.agent.model.resamp_alpha), loc.data_ptr(), alive_h, L, E)
+        if sized:
+            with _lib.timed("rs_pfgru_sized_pass"):
+                _lib.check(lib.rs_pfgru_sized_pass(*args, H, st), "rs_pfgru_sized_pass")
+        else:
+            with _lib.timed("rs_pfgru_pass"):
+                _lib.check(lib.rs_pfgru_pass(*args, st), "rs_pfgru_pass")
         return loc
 
     def _pfgru_pass_hip_recorded(self, X: torch.Tensor, draws: "RecordedKernelDraws") -> torch.Tensor:
@@ -982,7 +992,7 @@ class RNNAgentPPO:
             for lo in range(0, E, self.episode_chunk):
                 Bc = B.chunk(slice(lo, min(lo + self.episode_chunk, E)))
                 if K == 1:
-                    loc = self._pfgru_pass_hip(Bc.X, HashDraws(Bc.key * 64 + 17 + its[0]), Bc.lens_host)      # (fused_pfgru only: see update_agent)
+                    loc = self._pfgru_pass_hip(Bc.X, HashDraws(Bc.key * 64 + 17 + its[0]), Bc.lens_host)      # (fused_pfgru or sized_pfgru: see update_agent)
                     loc.record_stream(main)
                     out[its[0]].append(loc)
                     continue
@@ -1015,7 +1025,7 @@ class RNNAgentPPO:
                 pass
             elif isinstance(draws, RecordedKernelDraws) and X.is_cuda:
                 loc = self._pfgru_pass_hip_recorded(X, draws)
-            elif isinstance(draws, HashDraws) and X.is_cuda and ac.fused_pfgru:
+            elif isinstance(draws, HashDraws) and X.is_cuda and (ac.fused_pfgru or ac.sized_pfgru):
                 loc = self._pfgru_pass_hip(X, draws, B.lens_host)          # K11 with carried particle sets: one launch per step
             else:
                 loc, _ = self._pfgru_pass(X[..., :3], draws, False)
@@ -1091,7 +1101,7 @@ class RNNAgentPPO:
         model_loss = self.update_model(B)
         self.pi_optimizer.zero_grad(set_to_none=True)
         kk, term, s = 0, False, None
-        ahead = self.device.type == "cuda" and self.agent.fused_pfgru and getattr(self, "use_prefetch", True)
+        ahead = self.device.type == "cuda" and (self.agent.fused_pfgru or self.agent.sized_pfgru) and getattr(self, "use_prefetch", True)
         # the passes are prefetched one group ahead: iteration 0 alone (its chain starts at once), then `pass_batch` iterations per pass
         K = max(1, int(getattr(self, "pass_batch", 2)))        # A/B on one box, ms per iteration: 2: 1201, 3: 1205, 4: 1195-1203, 5: 1202, 8: 1221 (1: 1223)
         groups = [[0]] + [list(range(i, min(i + K, self.train_pi_iters))) for i in range(1, self.train_pi_iters, K)]
@@ -1160,7 +1170,9 @@ class RNNCollector:
         self._u = torch.empty(self.N, self.A, dtype=torch.float32, device=dev)
         self._act8 = torch.empty(self.N, self.A, dtype=torch.int8, device=dev)
         self.h = torch.zeros(self.A, self.N, hid, dtype=torch.float32, device=dev)                 # GRU states
-        fused_pf = torch.device(dev).type == "cuda" and all(ag.agent.fused_pfgru for ag in agents.values())
+        # the bank on the PFGRU kernels: K11 at 24 units, rs_pfgru_sized at the other widths it serves (one width for all agents)
+        fused_pf = (torch.device(dev).type == "cuda" and all(ag.agent.fused_pfgru or ag.agent.sized_pfgru for ag in agents.values())
+                    and len({ag.agent.rec for ag in agents.values()}) == 1)
         self.bank = PredictorBank(self.N, self.A, hidden_size=agents[0].agent.rec, seed=int(env.cfg.seed),
                                   env_id_base=int(env.cfg.env_id_base), carry_hidden=True, device=dev, impl="hip" if fused_pf else "torch")
         for a, ag in agents.items():                                         # the bank evaluates the agents' own PFGRU modules
@@ -1397,7 +1409,8 @@ class RNNCollector:
                 x = self._x(self.obs)
                 for a, ag in self.agents.items():
                     ag.agent.policy_step(x[:, a], torch.zeros(self.N, 2, device=x.device), self.h[a])
-                self.bank._packed()
+                if self.bank.impl == "hip":                                   # (the library-op bank has no packed weights)
+                    self.bank._packed()
             torch.cuda.current_stream(self.env.device).wait_stream(side)
             torch.cuda.synchronize(self.env.device)
             self._graph = torch.cuda.CUDAGraph()

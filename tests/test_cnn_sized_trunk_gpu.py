@@ -111,6 +111,14 @@ def test_sized_trunk_matches_float64(M, S):
     _check_trunk(critic.critic, maps, None, None, -1, maps.double().cpu(), f"critic M={M} S={S}")
 
 
+@pytest.mark.parametrize("M,S", [(8, 1), (8, 67), (9, 3), (34, 3), (34, 67), (35, 1), (35, 67), (256, 1), (256, 3)])
+def test_sized_trunk_at_the_ends_of_its_range_matches_float64(M, S):
+    """test_sized_trunk_matches_float64 at the ends of the accepted sides (8: one 4 x 4 tile, 9: the odd row / column dropped by the
+    pool; 256: 8 x 8 tiles of 16) and at M = 34 / 35, where P = 17 = 16 + 1: the second tile column and row are one pooled cell wide
+    and their halo lies mostly outside the map.  At 256, S <= 3 keeps the float64 CPU reference within seconds."""
+    test_sized_trunk_matches_float64(M, S)
+
+
 def test_sized_trunk_on_walls_off_maps():
     """K5's own maps at 147 x 147: a walls-off env with 2 owners and obstacles after 30 lock-steps (detectors leave the search area)."""
     import numpy as np

@@ -1,0 +1,133 @@
+"""The float64 references of the sized-kernel tests (tests/_f64_ref.py) held to the project's own float32 paths on the CPU: the
+hand-written heads loss against the library branch of RNNAgentPPO.a2c_losses, the float64 draw against the collector's float32
+inverse-CDF composition, the ratio targets, the PFGRU step with its kink mask against PFGRUCell in float32, and the quad layout of
+the particle sets.  A wrong reference fails here, before a GPU test relies on it."""
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(__file__))
+import _f64_ref as R  # noqa: E402
+
+
+def test_head_grid_meets_every_head_pair_at_every_tier():
+    grid = R.head_grid()
+    assert sorted(grid) == sorted(R.HIDS) and all(len(v) == 3 for v in grid.values())
+    for t in (16, 32, 48, 64):
+        met = {pair for h in R.HIDS if R.tier(h) == t for pair in grid[h]}
+        assert met == set(R.HEADS), (t, set(R.HEADS) - met)
+    edges = {w for pair in R.HEADS for w in pair}
+    assert {2, 4, 63, 64} <= edges and {9, 17, 33, 41, 57} <= edges
+
+
+def test_target_ratios_hit_every_branch_with_a_margin():
+    r = R.target_ratios(20000, torch.Generator().manual_seed(1), clip=0.2, margin=0.02)
+    assert float(r.min()) >= 0.6 and float(r.max()) <= 1.6
+    assert float(((r - 0.8).abs().min())) >= 0.02 - 1e-12 and float(((r - 1.2).abs().min())) >= 0.02 - 1e-12
+    for part in (r < 0.8, (r > 0.8) & (r < 1.2), r > 1.2):
+        assert 0.3 < float(part.double().mean()) < 0.37
+
+
+@pytest.mark.parametrize("hid,pol,val", [(9, 64, 2), (40, 9, 57)])
+def test_heads_loss_f64_equals_the_library_branch_of_a2c_losses(hid, pol, val):
+    """The float64 twin (nn.GRU + R.heads_loss_f64) against a2c_losses on the CPU, whose library branch is the float32 torch path:
+    the statistics (the branch's loss statistic is -(surrogate - 0.01 value loss + alpha entropy)) and every pi gradient.  Float32
+    torch against float64: statistics rtol 2e-5, atol 1e-7, gradients rtol 1e-4, atol 1e-5 of each tensor's scale."""
+    from radiation_ppo_amd.rada2c import RNNAgentPPO
+    torch.manual_seed(hid)
+    ag = RNNAgentPPO(id=0, seed=1, actor_critic_args=R.rnn_args(hid, pol, val), device="cpu")
+    with torch.no_grad():
+        for p in ag.agent.pi.parameters():
+            p.mul_(1.7)
+    ag.agent.train()
+    ac64 = R.f64(ag.agent)
+    B = R.make_batch(5 + hid, T=40, N=60, device="cpu")
+    L, E = B.X.shape[0], B.X.shape[1]
+    g = torch.Generator().manual_seed(2)
+    loc = torch.rand(L, E, 2, generator=g)
+    h0 = (torch.rand(E, hid, generator=g) * 2 - 1) / hid ** 0.5
+    lp64 = R.chain_logp_f64(ac64, B.X.double(), loc.double(), h0.double(), B.act)
+    B.logp = (lp64 - torch.log(R.target_ratios(L * E, g).view(L, E))).float()
+    loss, st = ag.a2c_losses(B, slice(0, E), R.GruH0(h0), loc=loc)
+    loss.backward()
+    B64 = R.batch_to(B, "cpu", torch.float64)
+    gru = ac64.pi.logits_net.v_net.seq_model
+    hs, _ = gru(torch.cat((B64.X, loc.double()), dim=2), h0.double().unsqueeze(0))
+    flat = lambda t: t.reshape(L * E)
+    loss64, st64, _ = R.heads_loss_f64(ac64, hs.reshape(L * E, hid), flat(B.act), flat(B64.adv), flat(B64.ret), flat(B64.logp), flat(B64.w),
+                                       ag.clip_ratio, 0.01)
+    loss64.backward()
+    assert float(st64[2]) > 0.05 * float(st64[5])
+    want = [st64[0], st64[1], st64[2], st64[3], -(st64[4] - 0.01 * st64[3] + ag.alpha * st64[1]), st64[5]]
+    for q, (k, b) in enumerate(zip((0, 1, 2, 3, 4, 6), want)):
+        R.close(st[k].reshape(1), b.reshape(1), f"stat {q}", rtol=2e-5, noise=0.0, tiny=1e-7)
+    p64 = dict(ac64.pi.named_parameters())
+    for k, p in ag.agent.pi.named_parameters():
+        R.close(p.grad, p64[k].grad, f"grad {k}", rtol=1e-4, noise=1e-5)
+
+
+def test_draw_f64_equals_the_float32_composition():
+    """R.draw_f64 against the collector's float32 inverse-CDF draw (test_rnn_sized_gpu._torch_step): the same action except where
+    the uniform is within 1e-5 of a CDF step, and R.check_draw accepts the float32 draw."""
+    from radiation_ppo_amd.rada2c import RNNModelActorCritic
+    torch.manual_seed(0)
+    ac = RNNModelActorCritic(**R.rnn_args(17, 9, 57))
+    N = 5000
+    g = torch.Generator().manual_seed(4)
+    x, loc, h, u = torch.randn(N, 11, generator=g), torch.rand(N, 2, generator=g), torch.rand(N, 17, generator=g) - 0.5, torch.rand(N, generator=g)
+    with torch.no_grad():
+        lg32, _, _ = ac.policy_step(x, loc, h)
+        lp32 = torch.log_softmax(lg32, dim=-1)
+        act32 = (torch.cumsum(lp32.exp(), dim=-1)[:, :-1] <= u.unsqueeze(-1)).sum(dim=-1)
+        lg64, _, _ = R.f64(ac).policy_step(x.double(), loc.double(), h.double())
+    act64, lp64, cdf64 = R.draw_f64(lg64, u)
+    assert float((cdf64[:, -1] - 1).abs().max()) < 1e-12 and int(act64.min()) >= 0 and int(act64.max()) <= 7
+    assert len(set(act64.tolist())) == 8
+    R.check_draw(act32, lp32.gather(-1, act32.unsqueeze(-1)).squeeze(-1), act64, lp64, cdf64, u, "float32 torch")
+
+
+@pytest.mark.parametrize("H", [8, 64])
+def test_pfgru_step_f64_and_its_kink_mask_against_the_float32_cell(H):
+    """R.pfgru_step_f64 against PFGRUCell.forward in float32 with the same indices and noise: h, p within float32 rounding, mean_hid
+    is the mean the prediction is formed from, and on the outputs R.hid_obs_fragile keeps, the float32 prediction agrees."""
+    from radiation_ppo_amd.pfgru import PFGRUCell
+    torch.manual_seed(H)
+    cell = PFGRUCell(hidden_size=H)
+    with torch.no_grad():
+        for p in cell.parameters():
+            p.mul_(2.0)
+    c64 = R.f64(cell)
+    B, P = 300, 40
+    g = torch.Generator().manual_seed(3)
+    obs = torch.rand(B, 3, generator=g)
+    obs[:, 0] = obs[:, 0] * 40 - 10
+    h0, p0 = torch.rand(B, P, H, generator=g), torch.log_softmax(torch.randn(B, P, generator=g), dim=-1)
+    eps, idx = torch.randn(B, P, H, generator=g), torch.randint(0, P, (B, P), generator=g)
+    with torch.no_grad():
+        pr32, (h32, p32) = cell(obs, (h0, p0), eps, resample_idx=idx)
+    pr64, h64, p64, mean = R.pfgru_step_f64(c64, obs.double(), h0.double(), p0.double(), eps.double(), idx)
+    assert torch.equal(c64.hid_obs(mean), pr64)
+    R.close(h32, h64, "h", rtol=2e-5, noise=1e-5)
+    R.close(p32, p64, "p", rtol=2e-5, noise=1e-5)
+    keep = ~R.hid_obs_fragile(c64, mean, 1e-4)
+    assert float(keep.float().mean()) > 0.5
+    R.close(pr32[keep], pr64[keep], "pred", rtol=1e-4, noise=1e-5, tiny=2e-6)
+    # the mask is what it says: kept outputs have no hidden or output pre-activation within 1e-4 of 0
+    z0 = torch.nn.functional.linear(mean, c64.hid_obs[0].weight, c64.hid_obs[0].bias)
+    z2 = torch.nn.functional.linear(torch.relu(z0), c64.hid_obs[2].weight, c64.hid_obs[2].bias)
+    assert bool((z2[keep].abs() >= 1e-4).all()) and bool((z0.abs().amin(dim=1, keepdim=True).expand(B, 2)[keep] >= 1e-4).all())
+
+
+def test_quad_layout_round_trip():
+    """PredictorBank.to_quads puts particle q's unit u at [u // 4, q, u % 4] (include/radsearch.h's quad-major sets), from_quads
+    inverts it."""
+    from radiation_ppo_amd.pfgru import PredictorBank
+    A, N, P, H = 2, 3, 40, 16
+    h = torch.arange(A * N * P * H, dtype=torch.float64).view(A, N, P, H)
+    q = PredictorBank.to_quads(h)
+    assert q.shape == (A, N, H // 4, P, 4) and q.is_contiguous()
+    for (a, n, p, u) in [(0, 0, 0, 0), (1, 2, 39, 15), (0, 1, 7, 5), (1, 0, 20, 12)]:
+        assert q[a, n, u // 4, p, u % 4] == h[a, n, p, u]
+    assert torch.equal(PredictorBank.from_quads(q), h)

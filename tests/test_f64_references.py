@@ -1,7 +1,9 @@
 """The float64 references of the sized-kernel tests (tests/_f64_ref.py) held to the project's own float32 paths on the CPU: the
 hand-written heads loss against the library branch of RNNAgentPPO.a2c_losses, the float64 draw against the collector's float32
 inverse-CDF composition, the ratio targets, the PFGRU step with its kink mask against PFGRUCell in float32, and the quad layout of
-the particle sets.  A wrong reference fails here, before a GPU test relies on it."""
+the particle sets; and those of the default-width tests (test_rnn_default_f64_gpu.py, test_pfgru_default_f64_gpu.py): the PFGRU training
+loss written out in float64 (model_loss_f64) against RNNAgentPPO.model_loss + autograd in float32, held to a tenth of K13's bound, and
+its kink counter against a brute-force count.  A wrong reference fails here, before a GPU test relies on it."""
 import os
 import sys
 
@@ -88,7 +90,7 @@ def test_draw_f64_equals_the_float32_composition():
     R.check_draw(act32, lp32.gather(-1, act32.unsqueeze(-1)).squeeze(-1), act64, lp64, cdf64, u, "float32 torch")
 
 
-@pytest.mark.parametrize("H", [8, 64])
+@pytest.mark.parametrize("H", [8, 24, 64])
 def test_pfgru_step_f64_and_its_kink_mask_against_the_float32_cell(H):
     """R.pfgru_step_f64 against PFGRUCell.forward in float32 with the same indices and noise: h, p within float32 rounding, mean_hid
     is the mean the prediction is formed from, and on the outputs R.hid_obs_fragile keeps, the float32 prediction agrees."""
@@ -131,3 +133,78 @@ def test_quad_layout_round_trip():
     for (a, n, p, u) in [(0, 0, 0, 0), (1, 2, 39, 15), (0, 1, 7, 5), (1, 0, 20, 12)]:
         assert q[a, n, u // 4, p, u % 4] == h[a, n, p, u]
     assert torch.equal(PredictorBank.from_quads(q), h)
+
+
+def _k13_case(c, shrink=True):
+    """The case's batch, agent (CPU, float32), loss weights and draws; shrink: the 65 episodes of 120 steps become 8."""
+    from radiation_ppo_amd.rada2c import BpArgs, RNNAgentPPO
+    T, N, ragged, srt, (l2, l1, elbo), seed = c
+    B = R.k13_batch(T, 8 if (shrink and N == 65) else N, seed, ragged, srt)
+    bpa = BpArgs(l2_weight=l2, l1_weight=l1, elbo_weight=elbo, area_scale=2500.0)
+    torch.manual_seed(5)
+    ag = RNNAgentPPO(id=0, seed=1, bp_args=bpa, device="cpu")
+    R.k13_cell(ag.agent.model, seed)
+    return B, ag, bpa, R.k13_draws(B.X.shape[0], B.X.shape[1], 100 + seed)
+
+
+@pytest.mark.parametrize("case", R.K13_CASES, ids=R.k13_case_id)
+def test_model_loss_f64_against_the_float32_library_path(case):
+    """R.model_loss_f64 + float64 autograd against RNNAgentPPO.model_loss + autograd in float32 on the CPU, the same recorded draws, on
+    every case of the K13 test: the loss within a TENTH of K13's bound (5e-7 of the sum of its absolute per-(step, episode) terms) and
+    every gradient block within a tenth of K13's (R.check_k13_grads, scale 0.1).  The library path has the same ReLU / |.| kinks as
+    the kernel and no allowance for them is made here either.  Also the conditions the GPU test relies on: fewer than 20 % of the
+    float64 location outputs on valid steps are clamped by hid_obs's final ReLU, a ragged case holds a one-step episode next to a
+    full-length one, and fc_obs.bias's float64 gradient is below the floor."""
+    from radiation_ppo_amd.rada2c import RecordedDraws
+    B, ag, bpa, (pf, eps, idx) = _k13_case(case)
+    L, E = B.X.shape[0], B.X.shape[1]
+    cell = ag.agent.model
+    res, g64, _ = R.k13_reference(cell, B, bpa, pf, eps, idx)
+    assert res.clamped < 0.2, res.clamped
+    if case[2]:
+        lens = B.lens.tolist()
+        assert 1 in lens and case[0] in lens
+        assert (lens == sorted(lens, reverse=True)) == case[3]
+    cell.train()
+    loss32 = ag.model_loss(B, slice(0, E), RecordedDraws(pf, None, eps, idx))
+    loss32.backward()
+    err = abs(float(loss32.detach()) - float(res.loss.detach()))
+    assert err <= 0.1 * 5e-6 * float(res.mags), (err, float(res.mags))
+    worst = R.check_k13_grads({k: p.grad for k, p in cell.named_parameters()}, g64, L, E, R.k13_case_id(case), scale=0.1)
+    gmax = max(float(v.abs().max()) for v in g64.values())
+    assert float(g64["fc_obs.bias"].abs().max()) <= 1e-12 * gmax
+    print(f"{R.k13_case_id(case)}: loss {err / (5e-6 * float(res.mags)):.4f} of K13's bound, worst block {0.1 * worst:.4f} of K13's bound, "
+          f"kinks {res.kinks} of {res.samples}")
+
+
+def test_model_loss_f64_steps_the_cell_and_its_kink_counter_counts():
+    """model_loss_f64's hand-written step is PFGRUCell.forward with resample_idx plus cell.particle_predictions (float64, to 1e-13), its
+    loss is RNNAgentPPO.model_loss on a float64 twin fed float64 inputs (which pins float32 only where the inputs are float32 already)
+    to 1e-6, and R.kink_count equals a brute-force count over every evaluation -- on tensors with planted near-kink values."""
+    import math
+    case = R.K13_CASES[7]
+    B, ag, bpa, (pf, eps, idx) = _k13_case(case)
+    L, E = B.X.shape[0], B.X.shape[1]
+    c64 = R.f64(ag.agent.model)
+    tar32, bp32 = R.k13_inputs(B, bpa)
+    res = R.model_loss_f64(c64, B.X, tar32, bp32, B.valid, B.lens, B.w_ep, bpa, pf, eps, idx)
+    with torch.no_grad():
+        h, p = pf.double(), torch.full((E, 40), math.log(1 / 40), dtype=torch.float64)
+        for t in range(L):
+            loc, (h, p) = c64(B.X[t, :, :3].double(), (h, p), eps[t].double(), resample_idx=idx[t])
+            assert float((loc - res.loc[t]).abs().max()) < 1e-13, t
+    g = torch.Generator().manual_seed(0)
+    z0, z2, d = torch.randn(5, 4, 41, 24, generator=g).double(), torch.randn(5, 4, 41, 2, generator=g).double(), torch.randn(5, 4, 41, 2, generator=g).double()
+    z0[0, 0, 0, 3] = 5e-6; z0[4, 3, 40, 23] = -9e-6; z0[1, 1, 1, 1] = 2e-5            # the last one is outside the window
+    z2[2, 2, 7, 1] = -1e-6; z2[0, 0, 0, 0] = 1e-7                                       # (0, 0, 0) is flagged twice, counted once
+    d[3, 1, 40, 0] = 3e-6; d[4, 0, 5, 1] = 4e-6                                         # step 4 of episode 0 is padding
+    valid = torch.ones(5, 4, dtype=torch.bool); valid[4, 0] = False
+    for l1_on in (True, False):
+        brute = 0
+        for t in range(5):
+            for e in range(4):
+                for q in range(41):
+                    near = bool((z0[t, e, q].abs() < R.KINK_EPS).any()) or bool((z2[t, e, q].abs() < R.KINK_EPS).any()) \
+                        or (l1_on and bool((d[t, e, q].abs() < R.KINK_EPS).any()))
+                    brute += int(near and bool(valid[t, e]))
+        assert R.kink_count(z0, z2, d, valid, l1_on=l1_on) == brute == (4 if l1_on else 3)

@@ -257,6 +257,14 @@ typedef struct rs_update_state {
 int rs_adam_step(const rs_mlp_params* actor, const rs_mlp_params* critic, const float* grads, float* m, float* v,
                  const double* stats, rs_update_state* state, float lr, float kl_threshold, rs_stream_t stream);
 
+/* rs_ppo_grad (with stop_flag = &state->stopped) followed by rs_adam_step (with its stats), for ONE rank: the slab reduction, the
+ * Adam step and the state update run as one launch behind the two gradient kernels instead of three.  Every output -- grads
+ * (with the (hi, lo) tail), stats, the parameters, m, v, *state -- is bitwise what the two calls leave.  Under data parallelism
+ * an all-reduce of `grads` belongs between the two calls: use them. */
+int rs_ppo_update_step(const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_ppo_batch* batch, float* grads,
+                       double* stats, void* workspace, float* m, float* v, rs_update_state* state, float lr, float kl_threshold,
+                       rs_stream_t stream);
+
 /* ---- RAD-TEAM heat maps (MapsBuffer, NeuralNetworkCores/RADTEAM_core.py:395-932) ------------------------
  * Per env the maps every agent's MapsBuffer would hold are kept ONCE (all owners see the same observations, so
  * readings / visit counts / obstacles / combined-locations maps and the estimator state are identical across

@@ -182,6 +182,96 @@ __global__ void rs_adam_commit_kernel(const double* __restrict__ stats, const fl
     if (st->last_stats[0] < (double)thr) st->adam_step += 1; else st->stopped = 1;
 }
 
+// Single-GPU tail of one Adam step: what rs_ppo_reduce_kernel, rs_adam_apply_kernel and rs_adam_commit_kernel do, in one launch and
+// with their arithmetic in their order (bitwise the same results).  A workgroup reduces its 64 parameters over the slabs (16 chunks,
+// then the 16 partial sums in order), recomputes the five statistics sums in the order block 0 of the reduce kernel uses -- every
+// workgroup then knows the KL -- and takes the Adam step on its own 64 parameters.  Workgroup 0 alone writes stats, the (hi, lo) tail
+// of the gradient bucket and the update state.  The step count and the stop flag are read from `snap`, the copy K7's critic launch made
+// of them before this kernel started: no workgroup reads a word another one writes, and none waits for another.
+__global__ void __launch_bounds__(1024) rs_ppo_tail_kernel(const float* __restrict__ pa, const float* __restrict__ pc,
+                                                           const double* __restrict__ sa, const double* __restrict__ sc, int n_waves,
+                                                           float* __restrict__ grads, double* __restrict__ stats, float alpha, float vf,
+                                                           RsParamSeg S, float* __restrict__ m, float* __restrict__ v,
+                                                           rs_update_state* __restrict__ st, const int* __restrict__ snap, float lr, float thr) {
+    __shared__ float part[16][64];
+    __shared__ double spart[5][64];
+    __shared__ double stot[5];
+    constexpr int NA = rs_net_params(8), NC = rs_net_params(1);
+    const int col = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    const int p = blockIdx.x * 64 + col;
+    const int adam_step = snap[0];
+    if (snap[1]) {
+        // early stop already hit: the gradient kernels were no-ops, the state stays as it is; gradients and statistics read zero
+        if (grp == 0 && p < NA + NC + RS_PPO_STATS_TAIL) grads[p] = 0.0f;
+        if (blockIdx.x == 0 && threadIdx.x < 5) stats[threadIdx.x] = 0.0;
+        return;
+    }
+    float acc = 0.0f;
+    if (p < NA + NC) {
+        const float* src = (p < NA) ? pa + p : pc + (p - NA);
+        const int stride = (p < NA) ? NA : NC;
+        const int per = (n_waves + 15) / 16;
+        const int w0 = grp * per, w1 = min(w0 + per, n_waves);
+        for (int w = w0; w < w1; ++w) acc += src[(size_t)w * stride];
+    }
+    part[grp][col] = acc;
+    if (threadIdx.x < 64) {
+        double t[5] = {0, 0, 0, 0, 0};
+        for (int w = threadIdx.x; w < n_waves; w += 64) {
+            t[0] += sa[w * 5 + 0]; t[1] += sa[w * 5 + 1]; t[2] += sa[w * 5 + 2]; t[4] += sa[w * 5 + 4];
+            t[3] += sc[w * 5 + 3];
+        }
+        for (int q = 0; q < 5; ++q) spart[q][threadIdx.x] = t[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {                             // one thread per statistic: the 64 partial sums in index order
+        double t = 0;
+        for (int i = 0; i < 64; ++i) t += spart[threadIdx.x][i];
+        stot[threadIdx.x] = t;
+    }
+    float g = 0.0f;
+    if (grp == 0 && p < NA + NC) {
+        g = part[0][col];
+        for (int g2 = 1; g2 < 16; ++g2) g += part[g2][col];
+        grads[p] = g;
+    }
+    __syncthreads();
+    if (grp != 0) return;
+    double t[5];
+    for (int q = 0; q < 5; ++q) t[q] = stot[q];
+    t[4] = -(t[4] - (double)vf * t[3] + (double)alpha * t[1]);           // ppo.py:1221-1225
+    const bool take = t[0] < (double)thr;                                 // kl >= 1.5 * target_kl: no step (ppo.py:1252-1261)
+    if (take && p < NA + NC) {
+        const int i = p;
+        int seg = 0;
+#pragma unroll
+        for (int k = 1; k < 12; ++k) seg += (i >= S.off[k]) ? 1 : 0;
+        float* pp = S.p[seg] + (i - S.off[seg]);
+        const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+        const int step = adam_step + 1;
+        const float mi = m[i] + (g - m[i]) * (1.0f - b1);            // exp_avg.lerp_(grad, 1 - beta1)
+        const float vi = b2 * v[i] + (1.0f - b2) * g * g;            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+        m[i] = mi; v[i] = vi;
+        const float bc1 = 1.0f - powf(b1, (float)step), bc2 = 1.0f - powf(b2, (float)step);
+        const float step_size = lr / bc1;
+        const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+        *pp = *pp - step_size * (mi / denom);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        // the statistics also ride at the end of the gradient bucket as float32 (hi, lo) pairs, as rs_ppo_reduce_kernel leaves them
+        for (int q = 0; q < 5; ++q) {
+            stats[q] = t[q];
+            const float hi = (float)t[q];
+            grads[NA + NC + 2 * q] = hi;
+            grads[NA + NC + 2 * q + 1] = (float)(t[q] - (double)hi);
+            st->last_stats[q] = t[q];
+        }
+        for (int q = 10; q < RS_PPO_STATS_TAIL; ++q) grads[NA + NC + q] = 0.0f;
+        st->iters += 1;
+        if (take) st->adam_step = adam_step + 1; else st->stopped = 1;
+    }
+}
+
 extern "C" {
 
 int rs_rollout(rs_handle* h, const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_rollout_args* args,
@@ -210,9 +300,7 @@ size_t rs_ppo_grad_workspace_bytes(void) {
     return slabs * (size_t)(rs_net_params(8) + rs_net_params(1)) * sizeof(float) + 2 * slabs * 5 * sizeof(double) + 1024;
 }
 
-int rs_adam_step(const rs_mlp_params* actor, const rs_mlp_params* critic, const float* grads, float* m, float* v,
-                 const double* stats, rs_update_state* state, float lr, float kl_threshold, rs_stream_t stream) {
-    if (!actor || !critic || !grads || !m || !v || !state) return RS_ERR_INVALID_ARG;
+static RsParamSeg rs_param_seg(const rs_mlp_params* actor, const rs_mlp_params* critic) {
     RsParamSeg S;
     const float* ptrs[12] = {actor->w1, actor->b1, actor->w2, actor->b2, actor->w3, actor->b3,
                              critic->w1, critic->b1, critic->w2, critic->b2, critic->w3, critic->b3};
@@ -220,22 +308,37 @@ int rs_adam_step(const rs_mlp_params* actor, const rs_mlp_params* critic, const 
     int o = 0;
     for (int k = 0; k < 12; ++k) { S.p[k] = const_cast<float*>(ptrs[k]); S.off[k] = o; o += sizes[k]; }
     S.off[12] = o;
+    return S;
+}
+
+int rs_adam_step(const rs_mlp_params* actor, const rs_mlp_params* critic, const float* grads, float* m, float* v,
+                 const double* stats, rs_update_state* state, float lr, float kl_threshold, rs_stream_t stream) {
+    if (!actor || !critic || !grads || !m || !v || !state) return RS_ERR_INVALID_ARG;
+    const RsParamSeg S = rs_param_seg(actor, critic);
+    const int o = S.off[12];
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(rs_adam_apply_kernel, dim3((o + 255) / 256), dim3(256), 0, s, S, grads, m, v, stats, state, lr, kl_threshold);
     hipLaunchKernelGGL(rs_adam_commit_kernel, dim3(1), dim3(1), 0, s, stats, grads + o, state, kl_threshold);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 
-int rs_ppo_grad(const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_ppo_batch* batch, float* grads,
-                double* stats, void* workspace, const int32_t* stop_flag, rs_stream_t stream) {
-    if (!actor || !critic || !batch || !grads || !stats || !workspace || batch->M < 1) return RS_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return RS_ERR_WORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// the slab workspace of one gradient pass: actor slabs, critic slabs, their float64 statistics, the state copy of the fused tail
+struct RsGradWs { float *pa, *pc; double *sa, *sc; int* snap; };
+
+static RsGradWs rs_grad_ws(void* workspace) {
     const int slabs = RS_GRAD_BLOCKS;                                // the 8 waves of a workgroup reduce in LDS: one slab per workgroup
-    float* pa = static_cast<float*>(workspace);
-    float* pc = pa + (size_t)slabs * rs_net_params(8);
-    double* sa = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(pc + (size_t)slabs * rs_net_params(1)) + 255) & ~uintptr_t(255));
-    double* sc = sa + (size_t)slabs * 5;
+    RsGradWs w;
+    w.pa = static_cast<float*>(workspace);
+    w.pc = w.pa + (size_t)slabs * rs_net_params(8);
+    w.sa = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(w.pc + (size_t)slabs * rs_net_params(1)) + 255) & ~uintptr_t(255));
+    w.sc = w.sa + (size_t)slabs * 5;
+    w.snap = reinterpret_cast<int*>(w.sc + (size_t)slabs * 5);       // inside the 1024 spare bytes of rs_ppo_grad_workspace_bytes()
+    return w;
+}
+
+// the two K7 launches; ust != nullptr: the critic launch also leaves the copy of the update state the fused tail reads
+static int rs_launch_k7(const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_ppo_batch* batch, const RsGradWs& w,
+                        const int32_t* stop_flag, const rs_update_state* ust, hipStream_t s) {
     const size_t lds_a = sizeof(float) * (size_t)rs_grad2_lds_floats(8);
     const size_t lds_c = sizeof(float) * (size_t)rs_grad2_lds_floats(1);
     // > 64 KB of dynamic LDS needs the attribute on every device the library is used on: set it per call (cheap, no sync)
@@ -248,11 +351,37 @@ int rs_ppo_grad(const rs_mlp_params* actor, const rs_mlp_params* critic, const r
     // per-phase cycle counts are those of a wave that has its SIMD to itself)
     if (const char* e = getenv("RS_K7_THREADS")) threads = atoi(e) == 256 ? 256 : 512;
 #endif
-    hipLaunchKernelGGL(rs_ppo_grad2_kernel<8>, dim3(RS_GRAD_BLOCKS), dim3(threads), lds_a, s, to_dev(actor), *batch, pa, sa, stop_flag);
-    hipLaunchKernelGGL(rs_ppo_grad2_kernel<1>, dim3(RS_GRAD_BLOCKS), dim3(threads), lds_c, s, to_dev(critic), *batch, pc, sc, stop_flag);
+    hipLaunchKernelGGL(rs_ppo_grad2_kernel<8>, dim3(RS_GRAD_BLOCKS), dim3(threads), lds_a, s, to_dev(actor), *batch, w.pa, w.sa, stop_flag,
+                       (const rs_update_state*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(rs_ppo_grad2_kernel<1>, dim3(RS_GRAD_BLOCKS), dim3(threads), lds_c, s, to_dev(critic), *batch, w.pc, w.sc, stop_flag,
+                       ust, ust ? w.snap : (int*)nullptr);
+    return RS_OK;
+}
+
+int rs_ppo_grad(const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_ppo_batch* batch, float* grads,
+                double* stats, void* workspace, const int32_t* stop_flag, rs_stream_t stream) {
+    if (!actor || !critic || !batch || !grads || !stats || !workspace || batch->M < 1) return RS_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return RS_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const RsGradWs w = rs_grad_ws(workspace);
+    if (const int rc = rs_launch_k7(actor, critic, batch, w, stop_flag, nullptr, s)) return rc;
     const int np = rs_net_params(8) + rs_net_params(1);
-    hipLaunchKernelGGL(rs_ppo_reduce_kernel, dim3((np + 63) / 64), dim3(1024), 0, s, pa, pc, sa, sc, slabs, grads, stats,
+    hipLaunchKernelGGL(rs_ppo_reduce_kernel, dim3((np + 63) / 64), dim3(1024), 0, s, w.pa, w.pc, w.sa, w.sc, RS_GRAD_BLOCKS, grads, stats,
                        batch->alpha, batch->vf_coef, stop_flag);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_ppo_update_step(const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_ppo_batch* batch, float* grads,
+                       double* stats, void* workspace, float* m, float* v, rs_update_state* state, float lr, float kl_threshold,
+                       rs_stream_t stream) {
+    if (!actor || !critic || !batch || !grads || !stats || !workspace || !m || !v || !state || batch->M < 1) return RS_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return RS_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const RsGradWs w = rs_grad_ws(workspace);
+    if (const int rc = rs_launch_k7(actor, critic, batch, w, &state->stopped, state, s)) return rc;
+    const int np = rs_net_params(8) + rs_net_params(1);
+    hipLaunchKernelGGL(rs_ppo_tail_kernel, dim3((np + 63) / 64), dim3(1024), 0, s, w.pa, w.pc, w.sa, w.sc, RS_GRAD_BLOCKS, grads, stats,
+                       batch->alpha, batch->vf_coef, rs_param_seg(actor, critic), m, v, state, w.snap, lr, kl_threshold);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

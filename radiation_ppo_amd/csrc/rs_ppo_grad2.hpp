@@ -16,12 +16,16 @@
 #define RS_T2 33                                   // row stride of the 32-sample LDS tiles (floats)
 
 // Diagnostic build only (-DRS_K7_STAMPS, scripts/k7_stamps.py): s_memtime stamps at the phase boundaries of the sample-group
-// loop, summed per wave in scalar registers and added to a table no other code reads.  The product build contains none of it.
+// loop, summed per wave in scalar registers and added to a table no other code reads; slot 12 is the prologue (kernel entry to
+// the first trip), slot 13 the epilogue (last trip to the end of the kernel).  The product build contains none of it.
 #ifdef RS_K7_STAMPS
 #define RS_K7_NPH 16
 __device__ unsigned long long rs_k7_stamp_table[2][RS_K7_NPH];
-#define RS_STAMP_DECL unsigned long long st_acc[RS_K7_NPH] = {0}; const unsigned long long st_rt0 = __builtin_amdgcn_s_memrealtime(); \
-                      unsigned long long st_last = rs_k7_now();
+#define RS_STAMP_ENTRY const unsigned long long st_rt0 = __builtin_amdgcn_s_memrealtime(); const unsigned long long st_t0 = rs_k7_now();
+#define RS_STAMP_DECL unsigned long long st_acc[RS_K7_NPH] = {0}; unsigned long long st_last = rs_k7_now(); st_acc[12] = st_last - st_t0;
+// end of the kernel: the epilogue's cycles, the 100 MHz ticks of the whole kernel (in-kernel clock = cycles / ticks * 100 MHz)
+#define RS_STAMP_EXIT(net) do { RS_STAMP(13); if ((threadIdx.x & 63) == 0) { st_acc[14] = __builtin_amdgcn_s_memrealtime() - st_rt0; \
+                           for (int q = 0; q < RS_K7_NPH; ++q) atomicAdd(&rs_k7_stamp_table[net][q], st_acc[q]); } } while (0)
 #define RS_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("; RS_STAMP_MARK " #i); const unsigned long long t_ = rs_k7_now(); st_acc[i] += t_ - st_last; st_last = t_; \
                          __builtin_amdgcn_sched_barrier(0); } while (0)
 __device__ __forceinline__ unsigned long long rs_k7_now() {
@@ -30,7 +34,9 @@ __device__ __forceinline__ unsigned long long rs_k7_now() {
     return t;
 }
 #else
+#define RS_STAMP_ENTRY
 #define RS_STAMP_DECL
+#define RS_STAMP_EXIT(net)
 // product build: a phase boundary is a scheduling fence only (A/B switch RS_K7_NO_PHASE_FENCE: hipcc is then free to move LDS
 // reads, staging writes and VALU work across the phases)
 #ifdef RS_K7_NO_PHASE_FENCE
@@ -62,9 +68,14 @@ __device__ __forceinline__ void rs_stage32(float* T, const f32x16& v, int c, int
 
 template <int NOUT>
 __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, rs_ppo_batch B, float* __restrict__ partial,
-                                                              double* __restrict__ stat_partial, const int* __restrict__ stop) {
+                                                              double* __restrict__ stat_partial, const int* __restrict__ stop,
+                                                              const rs_update_state* __restrict__ ust, int* __restrict__ snap) {
     extern __shared__ __align__(16) float smem_f[];
+    // snap (fused single-GPU tail only): a copy of the update state's step count and stop flag for rs_ppo_tail_kernel, all of whose
+    // workgroups read them while one of them writes the state -- the copy is what makes that free of a race without any waiting
+    if (snap && blockIdx.x == 0 && threadIdx.x == 0) { snap[0] = ust->adam_step; snap[1] = ust->stopped; }
     if (stop && *stop) return;
+    RS_STAMP_ENTRY
     RsMlpLds<NOUT> W;
     W.carve(smem_f);
     float* w2tf = smem_f + ((rs_mlp_lds_floats(NOUT) + 3) & ~3);   // 16-byte aligned; [2 it][2 kt][4 r4][64 lanes][4]: W2[32kt + kappa(r, l>>5)][32it + (l&31)]
@@ -78,33 +89,36 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
     float* xraw = Pt + 32 * RS_T2;                             // [32][11]  the group's sample rows as they lie in HBM (LDS-DMA target)
     float* xsc = xraw + RS_XRAW;                               // [192]     the group's per-sample scalars (LDS-DMA target)
     float* dbl = xsc + RS_XSC;                                 // [64]      db2 accumulators of this wave
-    W.fill(prm);
+    // Fragment fill, one pass per array and ONE barrier.  Not RsMlpLds::fill (the forward kernel's): K7 wants W2 in the b128 form
+    // below, the layer-1 bias inside w1f, and never reads W.b1.
+    // layer-1 fragments with the bias in the padded input column k = 11 (k-step 5, upper lane half)
+    float* w1b = W.w1f;
+    for (int i = threadIdx.x; i < 2 * 6 * 64; i += blockDim.x) {
+        const int l = i & 63, s = (i >> 6) % 6, it = i / (6 * 64);
+        const int row = 32 * it + (l & 31), k = 2 * s + (l >> 5);
+        w1b[i] = RS_TANH_PRESCALE * ((k < RS_IN) ? prm.w1[row * RS_IN + k] : prm.b1[row]);
+    }
     // W2 fragments for the matrix pipe, four consecutive k-steps per lane contiguous ([it][kt][r / 4][lane][r % 4]): one
-    // ds_read_b128 feeds four MFMAs (an LDS read instruction costs the wave ~13 issue cycles whatever its width).  The forward
-    // copy (W.w2f, filled by W.fill in the layout rs_policy_forward uses) is rewritten in the same form below.
+    // ds_read_b128 feeds four MFMAs (an LDS read instruction costs the wave ~13 issue cycles whatever its width).  w2tf is
+    // the transpose (dh1 = W2^T dpre2), W.w2f the forward copy with the tanh prescale.
     for (int i = threadIdx.x; i < 2 * 2 * 16 * 64; i += blockDim.x) {
         const int ri = i & 3, l = (i >> 2) & 63, r4 = (i >> 8) & 3, kt = (i >> 10) & 1, it = i >> 11;
         const int r = 4 * r4 + ri;
         w2tf[i] = prm.w2[(32 * kt + rs_kappa(r, l >> 5)) * RS_HID + 32 * it + (l & 31)];
+        W.w2f[i] = RS_TANH_PRESCALE * prm.w2[(32 * it + (l & 31)) * RS_HID + 32 * kt + rs_kappa(r, l >> 5)];
     }
     for (int i = threadIdx.x; i < 2 * 4 * 64; i += blockDim.x) {
         int l = i & 63, sq = (i >> 6) & 3, it = i >> 8;
         int o = 2 * sq + (l >> 5);
         w3tf[i] = (o < NOUT) ? prm.w3[o * RS_HID + 32 * it + (l & 31)] : 0.0f;
     }
+    for (int i = threadIdx.x; i < 2 * NOUT * 32; i += blockDim.x) {
+        const int q = i & 31, o = (i >> 5) % NOUT, hh = i / (32 * NOUT);
+        W.w3h[i] = prm.w3[o * RS_HID + 32 * (q >> 4) + rs_kappa(q & 15, hh)];
+    }
+    for (int i = threadIdx.x; i < 64; i += blockDim.x) W.b2[i] = RS_TANH_PRESCALE * prm.b2[i];
+    for (int i = threadIdx.x; i < NOUT; i += blockDim.x) W.b3[i] = prm.b3[i];
     dbl[lane] = 0.0f;
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * 2 * 16 * 64; i += blockDim.x) {
-        const int ri = i & 3, l = (i >> 2) & 63, r4 = (i >> 8) & 3, kt = (i >> 10) & 1, it = i >> 11;
-        const int r = 4 * r4 + ri;
-        W.w2f[i] = RS_TANH_PRESCALE * prm.w2[(32 * it + (l & 31)) * RS_HID + 32 * kt + rs_kappa(r, l >> 5)];
-    }
-    // layer-1 fragments with the bias in the padded input column k = 11 (k-step 5, upper lane half)
-    float* w1b = W.w1f;
-    for (int i = threadIdx.x; i < 2 * 32; i += blockDim.x) {
-        const int it = i >> 5, row = i & 31;
-        w1b[(it * 6 + 5) * 64 + 32 + row] = W.b1[32 * it + row];
-    }
     __syncthreads();
 
     const int M = B.M;
@@ -527,20 +541,41 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
         rs_wave_sync();
         RS_STAMP(11);                                   // R6 dW1
     }
-#ifdef RS_K7_STAMPS
-    if (lane == 0) {
-        st_acc[14] = __builtin_amdgcn_s_memrealtime() - st_rt0;     // 100 MHz ticks over the same span: in-kernel clock = cycles / ticks * 100 MHz
-        for (int q = 0; q < RS_K7_NPH; ++q) atomicAdd(&rs_k7_stamp_table[NOUT == 8 ? 0 : 1][q], st_acc[q]);
+    // ---- one partial slab per WORKGROUP, parameter order {w1, b1, w2, b2, w3, b3}.  Every wave writes its accumulators to a
+    // slab of its own in LDS, then all 512 threads add the eight slabs in wave order, (((0 + w0) + w1) + ...) + w7 (fixed order ->
+    // reproducible), and write the sums straight to the workgroup's slab in HBM.  Eight private slabs do not fit the LDS at
+    // once; the weight fragments are dead by now, so the whole allocation is reused in two rounds: dW2 (8 x 4096 floats), then
+    // everything else (8 x RS_REST floats) and the float64 statistics.
+    constexpr int RS_REST = rs_net_params(NOUT) - 64 * 64;          // w1, b1, b2, w3, b3
+    static_assert(8 * 64 * 64 <= rs_grad2_lds_floats(NOUT) && 8 * ((RS_REST + 1) & ~1) + 2 * 8 * 5 <= rs_grad2_lds_floats(NOUT),
+                  "the epilogue's slabs must fit K7's LDS");
+    // thread and lane indices afresh, opaque to the compiler: derived from the ones above, the epilogue's addresses and loop bounds
+    // are computed in front of the trip loop and held across it, in a kernel that has no register to spare (they went to scratch)
+    int tid_e = threadIdx.x;
+    asm volatile("" : "+v"(tid_e));
+    const int lane_e = tid_e & 63, h_e = lane_e >> 5, c_e = lane_e & 31, l15_e = lane_e & 15, l4_e = lane_e >> 4;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last trip's look-ahead DMA has landed: nothing writes LDS behind our back
+    const float db2v = dbl[lane_e];                     // (dbl lives in the region being overwritten: read it first)
+    __syncthreads();                                  // every wave is done with its staging tiles and the fragments
+    float* outp = partial + (size_t)blockIdx.x * rs_net_params(NOUT);
+    {
+        float* g_w2 = smem_f + wid * (64 * 64);
+#pragma unroll
+        for (int it = 0; it < 2; ++it)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = 32 * it + rs_kappa(r, h_e);
+                g_w2[row * 64 + c_e] = acc2[it][0][r];
+                g_w2[row * 64 + 32 + c_e] = acc2[it][1][r];
+            }
     }
-#endif
-
-    // ---- one partial slab per WORKGROUP, parameter order {w1, b1, w2, b2, w3, b3}: the eight waves add their
-    // accumulators into one LDS slab in wave order (fixed order -> reproducible), then the block streams it out.
-    __syncthreads();                                  // every wave is done with its staging tiles
-    float* red = w3tf + 2 * 4 * 64;                   // reuse the staging region: rs_net_params(NOUT) floats
-    double* sred = reinterpret_cast<double*>(red + ((rs_net_params(NOUT) + 1) & ~1));
-    float* g_w1 = red, *g_b1 = g_w1 + 64 * 11, *g_w2 = g_b1 + 64, *g_b2 = g_w2 + 64 * 64, *g_w3 = g_b2 + 64, *g_b3 = g_w3 + NOUT * 64;
-    const float db2v = dbl[lane];                     // (dbl lives in the region being overwritten: read it first)
+    __syncthreads();
+    for (int i = tid_e; i < 64 * 64; i += blockDim.x) {
+        float v = 0.0f + smem_f[i];
+#pragma unroll
+        for (int wv = 1; wv < 8; ++wv) v += smem_f[wv * (64 * 64) + i];
+        outp[64 * RS_IN + 64 + i] = v;
+    }
     // accs (16x16 D layout: row 4*(lane>>4) + q, every column identical): rows 0..NOUT-1 = db3, rows 8..11 = statistics sums
     // of this wave; bring them to lane 0 (row r lives in lanes with lane>>4 == r/4, register r%4)
     float db3r[NOUT];
@@ -552,39 +587,41 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
         if (NOUT == 8) { sv[0] = (double)t0; sv[1] = (double)t1; sv[2] = (double)t2; sv[3] = 0.0; sv[4] = (double)t3; }
         else { sv[0] = 0.0; sv[1] = 0.0; sv[2] = 0.0; sv[3] = (double)t0; sv[4] = 0.0; }
     }
-    __syncthreads();                                  // all dbl reads done before the slab is written
-    for (int wv = 0; wv < 8; ++wv) {
-        if (wid == wv) {
-            const bool first = wv == 0;
+    constexpr int RS_RSTR = (RS_REST + 1) & ~1;       // slab stride of round two (even: the doubles behind the slabs stay aligned)
+    double* sred = reinterpret_cast<double*>(smem_f + 8 * RS_RSTR);     // [8 waves][5]
+    __syncthreads();                                  // round one has been read
+    {
+        float* g_w1 = smem_f + wid * RS_RSTR, *g_b1 = g_w1 + 64 * RS_IN, *g_b2 = g_b1 + 64, *g_w3 = g_b2 + 64, *g_b3 = g_w3 + NOUT * 64;
+        g_b2[lane_e] = db2v;
 #pragma unroll
-            for (int it = 0; it < 2; ++it)
+        for (int u = 0; u < 4; ++u)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = 32 * it + rs_kappa(r, h);
-                    g_w2[row * 64 + c] = (first ? 0.0f : g_w2[row * 64 + c]) + acc2[it][0][r];
-                    g_w2[row * 64 + 32 + c] = (first ? 0.0f : g_w2[row * 64 + 32 + c]) + acc2[it][1][r];
-                }
-            g_b2[lane] = (first ? 0.0f : g_b2[lane]) + db2v;
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int row = 16 * u + 4 * l4 + q;
-                    if (l15 < RS_IN) g_w1[row * RS_IN + l15] = (first ? 0.0f : g_w1[row * RS_IN + l15]) + acc1[u][q];
-                    if (l15 == RS_IN) g_b1[row] = (first ? 0.0f : g_b1[row]) + acc1[u][q];
-                    const int o = 4 * l4 + q;
-                    if (o < NOUT) g_w3[o * 64 + 16 * u + l15] = (first ? 0.0f : g_w3[o * 64 + 16 * u + l15]) + acc3[u][q];
-                }
-            if (lane == 0) {
-#pragma unroll
-                for (int o = 0; o < NOUT; ++o) g_b3[o] = (first ? 0.0f : g_b3[o]) + db3r[o];
-#pragma unroll
-                for (int q = 0; q < 5; ++q) sred[q] = (first ? 0.0 : sred[q]) + sv[q];
+            for (int q = 0; q < 4; ++q) {
+                const int row = 16 * u + 4 * l4_e + q;
+                if (l15_e < RS_IN) g_w1[row * RS_IN + l15_e] = acc1[u][q];
+                if (l15_e == RS_IN) g_b1[row] = acc1[u][q];
+                const int o = 4 * l4_e + q;
+                if (o < NOUT) g_w3[o * 64 + 16 * u + l15_e] = acc3[u][q];
             }
+        if (lane_e == 0) {
+#pragma unroll
+            for (int o = 0; o < NOUT; ++o) g_b3[o] = db3r[o];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) sred[wid * 5 + q] = sv[q];
         }
-        __syncthreads();
     }
-    float* outp = partial + (size_t)blockIdx.x * rs_net_params(NOUT);
-    for (int i = threadIdx.x; i < rs_net_params(NOUT); i += blockDim.x) outp[i] = red[i];
-    if (threadIdx.x < 5) stat_partial[(size_t)blockIdx.x * 5 + threadIdx.x] = sred[threadIdx.x];
+    __syncthreads();
+    for (int i = tid_e; i < RS_REST; i += blockDim.x) {
+        float v = 0.0f + smem_f[i];
+#pragma unroll
+        for (int wv = 1; wv < 8; ++wv) v += smem_f[wv * RS_RSTR + i];
+        outp[i < 64 * RS_IN + 64 ? i : i + 64 * 64] = v;          // {w1, b1} lie in front of w2 in the slab, {b2, w3, b3} behind it
+    }
+    if (tid_e < 5) {
+        double v = 0.0 + sred[tid_e];
+#pragma unroll
+        for (int wv = 1; wv < 8; ++wv) v += sred[wv * 5 + tid_e];
+        stat_partial[(size_t)blockIdx.x * 5 + tid_e] = v;
+    }
+    RS_STAMP_EXIT(NOUT == 8 ? 0 : 1);
 }

@@ -12,6 +12,7 @@ Mirrors (paths relative to the reference root):
                          (gradient = mean over ranks of each rank's mean over its episodes).
 """
 import ctypes as C
+import os
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
 
@@ -145,6 +146,25 @@ class FusedPPOGrad:
             _lib.check(self.lib.rs_ppo_grad(C.byref(pa), C.byref(pc), C.byref(b), self.bucket.data_ptr(), self.stats.data_ptr(),
                                             self._ws_ptr, (self.state.data_ptr() + 4) if use_stop_flag else None,
                                             torch.cuda.current_stream(X.device).cuda_stream), "rs_ppo_grad")
+        return self.stats, self.grads
+
+    def step(self, X, act, adv, ret, logp_old, w, clip_ratio: float, alpha: float, vf_coef: float = 0.01, *, lr: float,
+             kl_threshold: float):
+        """One iteration of the early-stopped loop on ONE rank: __call__(use_stop_flag=True) + adam_step() as rs_ppo_update_step,
+        where the slab reduction, the Adam step and the state update are one launch behind the two gradient kernels (bitwise the
+        same results).  With more ranks the all-reduce sits between the two, so they stay separate calls."""
+        for t in (X, adv, ret, logp_old, w):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert act.dtype == torch.int64 and act.is_contiguous()
+        self.stats_from_bucket = False
+        b = _lib.RsPpoBatch(X.data_ptr(), act.data_ptr(), adv.data_ptr(), ret.data_ptr(), logp_old.data_ptr(), w.data_ptr(),
+                            X.shape[0], clip_ratio, alpha, vf_coef)
+        pa, pc = mlp_params(self.ac.actor), mlp_params(self.ac.critic)
+        # the bracket bench.py reads: the two gradient kernels and the launch behind them, as around rs_ppo_grad
+        with _lib.timed("rs_ppo_grad"):
+            _lib.check(self.lib.rs_ppo_update_step(C.byref(pa), C.byref(pc), C.byref(b), self.bucket.data_ptr(), self.stats.data_ptr(),
+                                                   self._ws_ptr, self.m.data_ptr(), self.v.data_ptr(), self.state.data_ptr(), lr,
+                                                   kl_threshold, torch.cuda.current_stream(X.device).cuda_stream), "rs_ppo_update_step")
         return self.stats, self.grads
 
     def allreduce(self) -> None:
@@ -483,14 +503,20 @@ class VecAgentPPO:
     def _update_agent_fused(self, X, act, adv, ret, logp_old, w) -> UpdateResult:
         """update_agent / update_rada2c control flow (ppo.py:789-796,1250-1261) with no host round trip inside
         the loop: rs_ppo_grad computes statistics + gradients, rs_adam_step takes the KL early-stop decision and
-        the Adam step on the device; iterations after the stop are no-ops.  One sync at the end."""
+        the Adam step on the device (one rank: both as rs_ppo_update_step); iterations after the stop are no-ops.  One sync at
+        the end."""
         if self._fused is None:
             self._fused = FusedPPOGrad(self.agent)
         f = self._fused
         lr = self.actor_learning_rate * (0.99 ** (self.epochs_done // 100))   # StepLR(100, 0.99) (ppo.py:205-207)
         thr = 1.5 * self.target_kl
         f.begin_update()
+        # one rank: the fused tail (rs_ppo_update_step).  RS_PPO_SPLIT_TAIL=1 keeps the separate calls for A/B timing.
+        one_rank = _world() == 1 and not os.environ.get("RS_PPO_SPLIT_TAIL")
         for _ in range(self.train_pi_iters):
+            if one_rank:
+                f.step(X, act, adv, ret, logp_old, w, self.clip_ratio, self.alpha, lr=lr, kl_threshold=thr)
+                continue
             stats, grads = f(X, act, adv, ret, logp_old, w, self.clip_ratio, self.alpha, use_stop_flag=True)
             if _world() > 1:
                 f.allreduce()

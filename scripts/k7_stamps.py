@@ -7,14 +7,14 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ["RS_LIB_PATH"] = os.path.join(ROOT, "radiation_ppo_amd", "lib", "librs_hip_stamps.so")
+os.environ["RS_LIB_PATH"] = os.environ.get("RS_STAMPS_LIB") or os.path.join(ROOT, "radiation_ppo_amd", "lib", "librs_hip_stamps.so")
 import torch  # noqa: E402
 
 from radiation_ppo_amd import _lib  # noqa: E402
 from radiation_ppo_amd.ppo import FFActorCritic, FusedPPOGrad  # noqa: E402
 
 PH = ["top: wait DMA, operand reads", "L1 mfma", "tanh1 + b2", "L2 mfma + stage h1^T", "tanh2", "out layer (VALU)", "loss",
-      "dW3 (+ row sums)", "dh2 -> dpre2, DMA issue", "R3 dh1 mfma, dpre1", "R4/5 dW2 + db2", "R6 dW1", "-", "-", "-", "loop"]
+      "dW3 (+ row sums)", "dh2 -> dpre2, DMA issue", "R3 dh1 mfma, dpre1", "R4/5 dW2 + db2", "R6 dW1", "prologue", "epilogue", "-", "loop"]
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 4096 * 480
 torch.manual_seed(0)
 ac = FFActorCritic().cuda()
@@ -52,3 +52,8 @@ for net, name in ((0, "actor"), (1, "critic")):
     for q, c in enumerate(cyc):
         if c:
             print(f"   {PH[q]:30s} {c / groups:8.0f} cyc  {100.0 * c / tot:5.1f} %")
+    # prologue and epilogue are paid once per wave and launch, not per group: 256 workgroups x 8 waves
+    waves = 256 * (4 if os.environ.get('RS_K7_THREADS') == '256' else 8) * R
+    mhz = tot / max(rt, 1) * 100
+    for q in (12, 13):
+        print(f"   {PH[q]:30s} {cyc[q] / waves:8.0f} cyc per wave and launch = {cyc[q] / waves / mhz:6.2f} us")

@@ -410,6 +410,31 @@ int rs_pfgru_train_keyed(const float* weights, const float* obs, const float* ta
                          const int64_t* keys, float* h0, float* hs, float* ps, float* gates, int32_t* idx, float* loss, float* grads, int32_t steps,
                          int32_t episodes, double alpha, double l2_weight, double l1_weight, double elbo_weight, rs_stream_t stream);
 
+/* ---- The PFGRU training pass at hidden widths H = 8, 16, .., 64 (csrc/rs_pfgru_sized_train.hip) -------------------------------
+ * rs_pfgru_draws and rs_pfgru_train with the width as an argument: 40 particles, 3 inputs, tanh, hid_obs Linear(H, 24)-ReLU-
+ * Linear(24, 2)-ReLU, the same loss, the same draw hash (key particle * 4096 + unit), resampling indices constant in the backward pass.
+ *   rs_pfgru_sized_train_weight_floats(H) / _grad_floats(H): floats of the packed weights / of one episode's gradient slab (layouts:
+ *   csrc/rs_pfgru_sized_train.hip; packer / unpacker: rada2c.py: pack_sized_train_weights / unpack_sized_train_grads); 0 for a width
+ *   that is not a multiple of 8 in 8..64.
+ *   rs_pfgru_sized_draws: h0 [E][40][H], eps [L][E][40][H], u [L][E][40] (float64).
+ *   rs_pfgru_sized_train: obs [L][E][11], target [L][E][2], bp [L][E], lens [E] (1..L; steps beyond are never touched), w_ep [E] (an
+ *   episode with w_ep == 0 gets an exactly zero slab row and loss), h0 / eps / u as above; u may be NULL: idx[] is then INPUT and left
+ *   untouched.  Scratch: hs [L][E][40][H] (the resampled particle set after every step), ps [L][E][2][40] (log weights before / after
+ *   the step's resampling), gates [L][E][4][40][H] (z | r | n | eps * softplus'(var)); idx [L][E][40] (output when u is given);
+ *   loss [E] = w_ep[e] * total_e; grads [E][rs_pfgru_sized_train_grad_floats(H)], the caller sums the rows:
+ *   d[fc_z | fc_r] [2H][H + 4] (column H + 3 = bias) | d fc_n [2H][H + 4] | d hid_obs[0] [24][H + 1] | d hid_obs[2] [2][25] |
+ *   d fc_obs [H + 4] | padding to a multiple of 16 (zero).
+ * Both entries return RS_ERR_INVALID_ARG before anything is launched for an unsupported width, a NULL required pointer, steps < 1 or
+ * episodes < 0; episodes == 0 is a successful no-op. */
+int32_t rs_pfgru_sized_train_weight_floats(int32_t hidden);
+int32_t rs_pfgru_sized_train_grad_floats(int32_t hidden);
+int rs_pfgru_sized_draws(const int64_t* keys, int32_t episodes, int32_t steps, int32_t hidden, float* h0, float* eps, double* u,
+                         rs_stream_t stream);
+int rs_pfgru_sized_train(const float* weights, const float* obs, const float* target, const float* bp, const int64_t* lens, const float* w_ep,
+                         const float* h0, const float* eps, const double* u, float* hs, float* ps, float* gates, int32_t* idx, float* loss,
+                         float* grads, int32_t steps, int32_t episodes, double alpha, double l2_weight, double l1_weight, double elbo_weight,
+                         int32_t hidden, rs_stream_t stream);
+
 /* ---- RAD-A2C GRU recurrence -----------------------------------------------------------------
  * The time loop of torch.nn.GRU(13, 24, 1) as SeqPt.forward / grad_step run it over whole episodes
  * (NeuralNetworkCores/RADA2C_core.py:377-381, :550-566) and of its back-propagation through time, for an episode-major batch

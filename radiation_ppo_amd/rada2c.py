@@ -123,8 +123,8 @@ class RNNModelActorCritic(nn.Module):
         # actions (K12 / K14 / K15) and a 24-unit PFGRU (K11 / K13); any other size runs the same arithmetic composed from library ops
         self.fused_policy = (obs_dim, pad_dim, hid, pol, val, act_dim) == (11, 2, 24, [32], [32], 8)
         self.fused_pfgru = self.rec == 24 and obs_dim == 11
-        # the PFGRU's no-grad passes and the collectors' steps at the other widths rs_pfgru_sized serves (a multiple of 8 up to 64); its
-        # training pass (update_model) stays on library ops there: K13 is built for 24 units only
+        # the PFGRU at the other widths the sized kernels serve (a multiple of 8 up to 64): rs_pfgru_sized for the no-grad passes and the
+        # collectors' steps, rs_pfgru_sized_train for the training pass (update_model); K13 itself is built for 24 units only
         self.sized_pfgru = obs_dim == 11 and self.rec != 24 and self.rec in SIZED_WIDTHS
         # every other GRU width 1..64 with single-layer heads of 2..64 units runs on the sized kernels (csrc/rs_rnn_sized.hip): policy
         # step, GRU sequence and heads-loss; multi-layer heads and wider layers stay on the library-op composition
@@ -385,19 +385,24 @@ class KernelDraws:
     step; same keys, same hash, same values (the normals to float32 rounding of the library log / cos).  scratch: where the draws go
     (Scratch; the previous pass's draws are overwritten, stream ordered) -- None: fresh tensors."""
 
-    def __init__(self, keys: torch.Tensor, L: int, scratch: Optional[Scratch] = None, tag: str = ""):
+    def __init__(self, keys: torch.Tensor, L: int, scratch: Optional[Scratch] = None, tag: str = "", H: int = 24):
         self.k = keys.contiguous()
         E, dev = keys.shape[0], keys.device
         if scratch is None:
-            self._pf = torch.empty(E, 40, 24, dtype=torch.float32, device=dev)
-            self._eps = torch.empty(L, E, 40, 24, dtype=torch.float32, device=dev)
+            self._pf = torch.empty(E, 40, H, dtype=torch.float32, device=dev)
+            self._eps = torch.empty(L, E, 40, H, dtype=torch.float32, device=dev)
             self._u = torch.empty(L, E, 40, dtype=torch.float64, device=dev)
         else:
-            self._pf = scratch.get("draws_pf" + tag, (E, 40, 24), torch.float32, dev)
-            self._eps = scratch.get("draws_eps" + tag, (L, E, 40, 24), torch.float32, dev)
+            self._pf = scratch.get("draws_pf" + tag, (E, 40, H), torch.float32, dev)
+            self._eps = scratch.get("draws_eps" + tag, (L, E, 40, H), torch.float32, dev)
             self._u = scratch.get("draws_u" + tag, (L, E, 40), torch.float64, dev)
-        _lib.check(_lib.load().rs_pfgru_draws(self.k.data_ptr(), E, L, self._pf.data_ptr(), self._eps.data_ptr(), self._u.data_ptr(),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rs_pfgru_draws")
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if H == 24:
+            _lib.check(_lib.load().rs_pfgru_draws(self.k.data_ptr(), E, L, self._pf.data_ptr(), self._eps.data_ptr(), self._u.data_ptr(), st),
+                       "rs_pfgru_draws")
+        else:                                                                # the same hash at width H (csrc/rs_pfgru_sized_train.hip)
+            _lib.check(_lib.load().rs_pfgru_sized_draws(self.k.data_ptr(), E, L, H, self._pf.data_ptr(), self._eps.data_ptr(),
+                                                        self._u.data_ptr(), st), "rs_pfgru_sized_draws")
 
     def pf_h0(self):
         return self._pf
@@ -441,8 +446,9 @@ class RecordedDraws:
 
 
 class RecordedKernelDraws(RecordedDraws):
-    """RecordedDraws in the buffers the kernels read (K11: rs_pfgru_step_recorded, K13: rs_pfgru_train with u = NULL): the
-    reference's own h0 / noise / resampling indices go straight into the HIP kernels (tests/test_rows_f_golden_gpu.py)."""
+    """RecordedDraws in the buffers the kernels read (K11: rs_pfgru_step_recorded, K13: rs_pfgru_train with u = NULL, at any width of
+    the sized kernels rs_pfgru_sized_train with u = NULL): the reference's own h0 / noise / resampling indices go straight into the HIP
+    kernels (tests/test_rows_f_golden_gpu.py)."""
 
     def __init__(self, pf_h0, gru_h0, eps, idx):
         super().__init__(pf_h0.contiguous(), gru_h0, eps.contiguous(), idx)
@@ -552,6 +558,50 @@ def pack_train_weights(cell) -> torch.Tensor:
     put(torch.cat([cell.hid_obs[2].weight.reshape(-1), cell.hid_obs[2].bias.reshape(-1)]), 64)
     assert o == PF_TRAIN_WEIGHT_FLOATS
     return w
+
+
+def sized_train_floats(H: int):
+    """(packed weight floats, gradient slab floats) of rs_pfgru_sized_train at width H: rs_pfgru_sized_train_weight_floats / _grad_floats."""
+    K, R = H + 3, 2 * H
+    r16 = lambda v: (v + 15) // 16 * 16
+    return r16(4 * K * R + 2 * R + K + 1 + 48 * H + 24 + 48 + 2), r16(2 * R * (H + 4) + 24 * (H + 1) + 50 + H + 4)
+
+
+def pack_sized_train_weights(cell) -> torch.Tensor:
+    """The PFGRU's parameters in the layout rs_pfgru_sized_train reads (csrc/rs_pfgru_sized_train.hip): the gate matrices k-major for
+    the forward products and in their own [out][in] layout for the transposed products of the backward walk."""
+    H = cell.h_dim
+    assert H in SIZED_WIDTHS and cell.num_particles == 40 and cell.input_size == 3, "rs_pfgru_sized_train: 40 particles x 8..64 units"
+    zr = torch.cat([cell.fc_z.weight, cell.fc_r.weight], 0)                       # [2H, H + 3]
+    parts = [zr.t(), cell.fc_z.bias, cell.fc_r.bias, cell.fc_n.weight.t(), cell.fc_n.bias, zr, cell.fc_n.weight, cell.fc_obs.weight,
+             cell.fc_obs.bias, cell.hid_obs[0].weight.t(), cell.hid_obs[0].bias, cell.hid_obs[0].weight, cell.hid_obs[2].weight,
+             cell.hid_obs[2].bias]
+    w = torch.cat([p.detach().reshape(-1) for p in parts]).float()
+    n = sized_train_floats(H)[0]
+    assert 0 <= n - w.numel() < 16
+    return F.pad(w, (0, n - w.numel())).contiguous()
+
+
+def sized_train_grad_ranges(H: int) -> Dict[str, Any]:
+    """{parameter name: (first float, rows, columns, row stride)} of a gradient slab of rs_pfgru_sized_train at width H."""
+    R, Cw = 2 * H, H + 4
+    n0 = R * Cw
+    h0 = 2 * n0
+    h2 = h0 + 24 * (H + 1)
+    fo = h2 + 50
+    return {"fc_z.weight": (0, H, H + 3, Cw), "fc_z.bias": (H + 3, H, 1, Cw), "fc_r.weight": (H * Cw, H, H + 3, Cw),
+            "fc_r.bias": (H * Cw + H + 3, H, 1, Cw), "fc_n.weight": (n0, R, H + 3, Cw), "fc_n.bias": (n0 + H + 3, R, 1, Cw),
+            "hid_obs.0.weight": (h0, 24, H, H + 1), "hid_obs.0.bias": (h0 + H, 24, 1, H + 1), "hid_obs.2.weight": (h2, 2, 24, 25),
+            "hid_obs.2.bias": (h2 + 24, 2, 1, 25), "fc_obs.weight": (fo, 1, H + 3, Cw), "fc_obs.bias": (fo + H + 3, 1, 1, Cw)}
+
+
+def unpack_sized_train_grads(cell, g: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """A summed gradient slab [rs_pfgru_sized_train_grad_floats(H)] -> gradients by parameter name (PFGRUCell.named_parameters)."""
+    out = {}
+    for name, (o, rows, cols, stride) in sized_train_grad_ranges(cell.h_dim).items():
+        v = torch.as_strided(g, (rows, cols), (stride, 1), g.storage_offset() + o)
+        out[name] = v.reshape(rows) if name.endswith(".bias") else v
+    return out
 
 
 PF_POLICY_WEIGHT_FLOATS = 5296                                       # include/radsearch.h: RS_RNN_POLICY_WEIGHT_FLOATS
@@ -877,6 +927,8 @@ class RNNAgentPPO:
                          int(sum(Bc.lens_host)) * 40)
         X, tar, bp, lens, w_ep, particle_steps = cache[ck]
         L, E = X.shape[0], X.shape[1]
+        if self.agent.sized_pfgru:
+            return self._model_pass_sized(X, tar, bp, lens, w_ep, particle_steps, d)
         # the walk's scratch (particle sets, log weights, indices, gates: 2.4 MB per full-length episode) is ONE set of buffers shared by
         # all chunks and iterations -- launches are stream ordered, and a chunk's pass is done with them when the next one starts
         sc = self.scratch
@@ -911,9 +963,54 @@ class RNNAgentPPO:
                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "rs_pfgru_train")
         return loss.double().sum(), slab.sum(dim=0), idx
 
+    def _model_pass_sized(self, X, tar, bp, lens, w_ep, particle_steps, d):
+        """model_pass_hip at the widths of the sized kernels: rs_pfgru_sized_train (csrc/rs_pfgru_sized_train.hip), draws in buffers
+        (KernelDraws(H=...) or RecordedKernelDraws).  Every buffer's size is checked against the shapes include/radsearch.h documents
+        before the call: the kernels index them by those shapes alone."""
+        a, dev, sc = self.bp_args, self.device, self.scratch
+        H = self.agent.rec
+        L, E = X.shape[0], X.shape[1]
+        lib = _lib.load()
+        nw, ng = lib.rs_pfgru_sized_train_weight_floats(H), lib.rs_pfgru_sized_train_grad_floats(H)
+        hs = sc.get(f"k13s{H}_hs", (L, E, 40, H), torch.float32, dev)
+        ps = sc.get(f"k13s{H}_ps", (L, E, 2, 40), torch.float32, dev)
+        idx = sc.get(f"k13s{H}_idx", (L, E, 40), torch.int32, dev)
+        gates = sc.get(f"k13s{H}_gates", (L, E, 4, 40, H), torch.float32, dev)
+        loss = torch.empty(E, dtype=torch.float32, device=dev)
+        slab = torch.empty(E, ng, dtype=torch.float32, device=dev)
+        w = pack_sized_train_weights(self.agent.model)
+        self.k13_particle_steps.append(particle_steps)
+        if d._u is None:                                                           # recorded draws: idx is the kernel's INPUT
+            idx.copy_(d._idx32)
+        else:
+            idx.zero_()                                                            # steps beyond an episode's end are never written
+        want = ((w, nw), (X, L * E * 11), (tar, L * E * 2), (bp, L * E), (lens, E), (w_ep, E), (d._pf, E * 40 * H), (d._eps, L * E * 40 * H),
+                (hs, L * E * 40 * H), (ps, L * E * 80), (gates, L * E * 160 * H), (idx, L * E * 40), (loss, E), (slab, E * ng))
+        for k, (t, n) in enumerate(want):
+            assert t.numel() == n and t.is_contiguous() and t.device.type == "cuda", (k, tuple(t.shape), n)
+        assert d._u is None or (d._u.numel() == L * E * 40 and d._u.dtype == torch.float64 and d._u.is_contiguous())
+        assert lens.dtype == torch.int64 and all(t.dtype == torch.float32 for t in (w, X, tar, bp, w_ep, d._pf, d._eps))
+        with _lib.timed("rs_pfgru_sized_train"):
+            _lib.check(lib.rs_pfgru_sized_train(w.data_ptr(), X.data_ptr(), tar.data_ptr(), bp.data_ptr(), lens.data_ptr(), w_ep.data_ptr(),
+                                                d._pf.data_ptr(), d._eps.data_ptr(), None if d._u is None else d._u.data_ptr(), hs.data_ptr(),
+                                                ps.data_ptr(), gates.data_ptr(), idx.data_ptr(), loss.data_ptr(), slab.data_ptr(), L, E,
+                                                float(self.agent.model.resamp_alpha), float(a.l2_weight), float(a.l1_weight),
+                                                float(a.elbo_weight), H, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                       "rs_pfgru_sized_train")
+        return loss.double().sum(), slab.sum(dim=0), idx
+
     # K13's scratch per episode of L steps, bytes: gates 40 x 96, particle sets 40 x 24 floats, log weights + indices 2 x 40 words per step
     # (+ Scratch's 1/8 headroom); the noise and the resampling uniforms are hashed in the kernel (KeyDraws)
     _K13_BYTES_PER_EPISODE_STEP = (40 * 96 + 40 * 24) * 4 + 2 * 40 * 4
+
+    def _k13_bytes(self, L: int) -> int:
+        """Scratch bytes of one episode of L steps in a training pass on the HIP path."""
+        if not self.agent.sized_pfgru:
+            return L * self._K13_BYTES_PER_EPISODE_STEP
+        # rs_pfgru_sized_train: gates 4 x 40 x H, particle sets 40 x H, the noise 40 x H floats, 2 x 40 log weights, 40 indices and 40
+        # float64 uniforms per step; per episode the slab row and the initial particles
+        H = self.agent.rec
+        return L * ((6 * 40 * H + 2 * 40 + 40) * 4 + 40 * 8) + (sized_train_floats(H)[1] + 40 * H) * 4
 
     def _k13_chunk(self, L: int, E: int) -> int:
         """Episodes per K13 pass: `episode_chunk`, clamped so that the pass's scratch fits the memory that is free NOW (plus what the
@@ -922,9 +1019,9 @@ class RNNAgentPPO:
         chunk = min(self.episode_chunk, max(E, 1))
         if self.device.type != "cuda":
             return chunk
-        held = sum(b.numel() * b.element_size() for k, b in self.scratch.bufs.items() if k[0].startswith(("k13_", "draws_")))
+        held = sum(b.numel() * b.element_size() for k, b in self.scratch.bufs.items() if k[0].startswith(("k13_", "k13s", "draws_")))
         free = torch.cuda.mem_get_info(self.device)[0] + held
-        per_ep = L * self._K13_BYTES_PER_EPISODE_STEP * 9 // 8
+        per_ep = self._k13_bytes(L) * 9 // 8
         fit = int(0.85 * free) // max(per_ep, 1)
         if fit < 1:
             raise MemoryError(f"K13 needs {per_ep / 1e6:.1f} MB of scratch per episode; {free / 1e9:.2f} GB are free")
@@ -952,12 +1049,15 @@ class RNNAgentPPO:
                     d = KeyDraws(B.key[sl] * 64 + 1 + it)                           # hashed inside K13's forward walk
                 elif self.device.type == "cuda" and self.agent.fused_pfgru:
                     d = KernelDraws(B.key[sl] * 64 + 1 + it, B.chunk(sl).X.shape[0], scratch=self.scratch)
+                elif self.device.type == "cuda" and self.agent.sized_pfgru and getattr(self, "use_k13", True):
+                    d = KernelDraws(B.key[sl] * 64 + 1 + it, B.chunk(sl).X.shape[0], scratch=self.scratch, tag=f"_{self.agent.rec}",
+                                    H=self.agent.rec)                               # rs_pfgru_sized_draws: the same keys at width H
                 else:
                     d = HashDraws(B.key[sl] * 64 + 1 + it, H=self.agent.rec, hid=self.agent.hid)
                 if isinstance(d, (KeyDraws, KernelDraws, RecordedKernelDraws)) and getattr(self, "use_k13", True):
                     # K13: the episode loop, the loss and its back-propagation through time in one call (two launches)
                     loss, g, _ = self.model_pass_hip(B, sl, d)
-                    by_name = unpack_train_grads(cell, g)
+                    by_name = unpack_sized_train_grads(cell, g) if self.agent.sized_pfgru else unpack_train_grads(cell, g)
                     for name, p in cell.named_parameters():
                         p.grad = by_name[name].clone() if p.grad is None else p.grad.add_(by_name[name])
                     tot += loss

@@ -3,8 +3,9 @@
      against PredictorBank(impl="torch") for each --widths entry, and the sized kernels forced at 24 units against K11; A and B
      alternated rep by rep in one process, HIP events, with the algorithmic work 2 (H + 3) 2H + (H + 3) multiply-adds per particle-step;
   2. the no-grad pass (rs_pfgru_sized_pass) over --episodes episodes of --steps-per-episode steps at 64 units;
-  3. RAD-A2C iterations at rec 64 (default policy widths, --iter-envs envs): the sized PFGRU path against the library-op path,
-     alternated, run 0 (graph capture, warm-up) not reported;
+  3. RAD-A2C iterations at rec 64 (default policy widths, --iter-envs envs): the sized PFGRU path, the same with the PFGRU training pass
+     on library ops (use_k13 = False) and the library-op path, alternated, run 0 (graph capture, warm-up) not reported; the sized path
+     also reports the training pass on its own (rs_pfgru_sized_train, HIP events); --iteration-rec 64,16 runs this leg alone at those widths;
   4. a short RAD-TEAM iteration (collect + update, --iter-envs envs, 2 agents) with a 64-unit predictor, against 24 units (K11).
 One JSON object per line on stdout.  Kernel times in a run of their own: rocprofv3 --kernel-trace --stats -- python
 scripts/time_pfgru_sized.py --skip-iteration."""
@@ -81,28 +82,42 @@ def pass_time(H, E, L, reps):
                           tflops=round(2 * macs(H) * 40 * E * L / t / 1e12, 2))), flush=True)
 
 
-def rada2c_iterations(N, T, L, runs):
+def rada2c_iterations(N, T, L, runs, rec=64):
+    """Whole RAD-A2C iterations at PFGRU width rec, alternated: every kernel sized ("sized"), the sized kernels with the PFGRU training
+    pass on library ops (use_k13 = False: what ran before rs_pfgru_sized_train existed), and library ops throughout.  The sized path also
+    reports the training pass on its own (HIP events around rs_pfgru_sized_train) per particle-step."""
+    from radiation_ppo_amd import _lib
     from radiation_ppo_amd.envs import RadSearchVec
     from radiation_ppo_amd.rada2c import RNNAgentPPO, RNNCollector
 
-    def make(sized):
+    def make(sized, hip_train):
         torch.manual_seed(0)
         env = RadSearchVec(N, number_agents=1, obstruction_count=1, enforce_grid_boundaries=True, seed=5)
-        agents = {0: RNNAgentPPO(id=0, steps_per_epoch=T, steps_per_episode=L, seed=3, actor_critic_args=dict(hidden_sizes_rec=(64,)))}
+        agents = {0: RNNAgentPPO(id=0, steps_per_epoch=T, steps_per_episode=L, seed=3, actor_critic_args=dict(hidden_sizes_rec=(rec,)))}
         agents[0].agent.sized_pfgru = sized
-        return RNNCollector(env, agents, T, L)
-    cols = {"sized": make(True), "library": make(False)}
+        agents[0].use_k13 = hip_train
+        return RNNCollector(env, agents, T, L), agents[0]
+    cols = {"sized": make(True, True), "sized_library_training_pass": make(True, False), "library": make(False, False)}
     for r in range(runs + 1):
-        for path, col in cols.items():
+        for path, (col, ag) in cols.items():
             torch.cuda.synchronize(); t0 = time.perf_counter()
             col.collect()
             torch.cuda.synchronize(); t1 = time.perf_counter()
+            if path == "sized":
+                _lib.EVENTS = {}
             col.update()
             torch.cuda.synchronize(); t2 = time.perf_counter()
+            extra = {}
+            if path == "sized":
+                ev, _lib.EVENTS = _lib.EVENTS, None
+                ms = sum(a.elapsed_time(b) for a, b in ev.get("rs_pfgru_sized_train", []))
+                ps = sum(ag.k13_particle_steps)
+                extra = dict(train_pass_calls=len(ev.get("rs_pfgru_sized_train", [])), train_pass_ms=round(ms, 2), particle_steps=ps,
+                             ns_per_particle_step=round(1e6 * ms / max(ps, 1), 3))
             if r:
-                print(json.dumps(dict(what="rada2c_iteration", rec=64, path=path, bank=col.bank.impl, use_glue=col.use_glue, run=r, envs=N,
+                print(json.dumps(dict(what="rada2c_iteration", rec=rec, path=path, bank=col.bank.impl, use_glue=col.use_glue, run=r, envs=N,
                                       steps_per_epoch=T, collect_s=round(t1 - t0, 3), update_s=round(t2 - t1, 3),
-                                      env_steps_per_s=round(T * N / (t2 - t0), 1))), flush=True)
+                                      env_steps_per_s=round(T * N / (t2 - t0), 1), **extra)), flush=True)
     del cols
     torch.cuda.empty_cache()
 
@@ -144,8 +159,13 @@ def main():
     ap.add_argument("--steps-per-epoch", type=int, default=240)
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--skip-iteration", action="store_true")
+    ap.add_argument("--iteration-rec", default="", help="only the RAD-A2C iterations, at these PFGRU widths (e.g. 64,16)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "time_pfgru_sized.py measures the MI355X"
+    if a.iteration_rec:
+        for rec in (int(v) for v in a.iteration_rec.split(",")):
+            rada2c_iterations(a.iter_envs, a.steps_per_epoch, a.steps_per_episode, a.runs, rec)
+        return
     with torch.no_grad():
         for H in (int(v) for v in a.widths.split(",")):
             step_pair(H, a.envs, a.agents, a.reps, "torch")

@@ -147,6 +147,19 @@ int rs_error_flags(rs_handle* h, rs_stream_t stream, uint32_t* flags_out);
 int rs_gae(const float* rew, const float* val, const uint8_t* cut, const float* last_val, float* adv, float* ret,
            int32_t T, int32_t M, double gamma, double lam, rs_stream_t stream);
 
+/* What one rank's PPO update takes from the finished buffer of a single-agent collector, time-major [T, N], in three launches:
+ *   w[t,n]     = (1 / (episodes of column n * length of the episode step t lies in)) * float32(1 / n_total), float32 operations in
+ *                that order (RolloutBuffer.episode_weights() / n_total, where the tensor library divides by a Python number through
+ *                its reciprocal; cut[t,n] != 0 ends an episode, the last step always ends one);
+ *   mean_std   = { float32(sum(adv) / (T*N)), float32(sqrt(sum(float32((adv - mean)^2)) / (T*N))) }, both sums float64
+ *                (PPOBuffer.get's normalisation, ppo.py:445-446, population std, no epsilon);
+ *   adv_n[t,n] = (adv[t,n] - mean) / std.  adv itself is left as it is.
+ * The sums run in a fixed order without atomics: the same buffer gives the same bits.  workspace: rs_ppo_prepare_workspace_bytes(N)
+ * bytes, 8-byte aligned, device. */
+size_t rs_ppo_prepare_workspace_bytes(int32_t N);
+int rs_ppo_prepare(const uint8_t* cut, const float* adv, float* w, float* adv_n, float* mean_std, void* workspace, int32_t T, int32_t N,
+                   int32_t n_total, rs_stream_t stream);
+
 /* ---- policy (FF_core.ActorCritic, NeuralNetworkCores/FF_core.py:42-129) ---------------------- */
 /* One 2x64 tanh MLP in torch layout: w1 [64,11], b1 [64], w2 [64,64], b2 [64], w3 [out,64], b3 [out]
  * (row-major [out][in] float32, i.e. nn.Linear.weight / .bias of actor.0/.2/.4 or critic.0/.2/.4). */
@@ -258,7 +271,8 @@ int rs_adam_step(const rs_mlp_params* actor, const rs_mlp_params* critic, const 
                  const double* stats, rs_update_state* state, float lr, float kl_threshold, rs_stream_t stream);
 
 /* rs_ppo_grad (with stop_flag = &state->stopped) followed by rs_adam_step (with its stats), for ONE rank: the slab reduction, the
- * Adam step and the state update run as one launch behind the two gradient kernels instead of three.  Every output -- grads
+ * Adam step and the state update run as one launch instead of three, behind ONE launch that runs the gradient passes of both networks
+ * (environment RS_PPO_SPLIT_GRAD=1: one launch per network as in rs_ppo_grad, for A/B timing; same bits).  Every output -- grads
  * (with the (hi, lo) tail), stats, the parameters, m, v, *state -- is bitwise what the two calls leave.  Under data parallelism
  * an all-reduce of `grads` belongs between the two calls: use them. */
 int rs_ppo_update_step(const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_ppo_batch* batch, float* grads,

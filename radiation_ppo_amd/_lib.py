@@ -106,6 +106,8 @@ SYMBOLS = [
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rs_gae", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                          C.c_int32, C.c_double, C.c_double, C.c_void_p]),
+    ("rs_ppo_prepare_workspace_bytes", C.c_size_t, [C.c_int32]),
+    ("rs_ppo_prepare", C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("rs_pfgru_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ("rs_pfgru_step_recorded", C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),

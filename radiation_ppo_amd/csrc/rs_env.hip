@@ -284,6 +284,126 @@ __global__ void __launch_bounds__(64) rs_gae_kernel(const float* __restrict__ re
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// rs_ppo_prepare: what the PPO update needs of the finished buffer besides the buffer itself -- the per-sample episode weights
+// (RolloutBuffer.episode_weights() / n_total) and the normalised advantages (normalize_advantages) -- in three launches.  All sums
+// are float64 in a fixed order (per lane in index order, then per workgroup and over the workgroups in index order; no atomics):
+// two launches on the same buffer give the same bits.
+//
+// Columns: one env column per lane, like K4.  A forward walk numbers every step inside its episode (parked in w), counts the
+// column's episodes (a cut at the last step closes the last episode, it does not open another) and sums the column's advantages;
+// a backward walk knows the steps left to the episode's end, so the episode's length is position + left + 1, and writes
+// w = (1 / (n_ep * len)) * (1 / n_total) with the float32 operations of the tensor expression in their order.  Sixteen rows are
+// loaded before they are used, so a column pays one HBM latency per sixteen steps.
+#define RS_PREP_U 16
+#define RS_PREP_BLOCKS 256
+#define RS_PREP_THREADS 256
+
+__global__ void __launch_bounds__(64) rs_ppo_prepare_cols_kernel(const uint8_t* __restrict__ cut, const float* __restrict__ adv,
+                                                                 float* __restrict__ w, double* __restrict__ col_sums, int T, int N,
+                                                                 float inv_n_total) {
+    __shared__ double lane_sum[64];
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    const bool live = n < N;
+    const int nn = live ? n : N - 1;                                // lanes past the last column read it and write nothing
+    int pos = 0, n_ep = 1;
+    double s = 0.0;
+    for (int tb = 0; tb < T; tb += RS_PREP_U) {
+        uint8_t c[RS_PREP_U];
+        float a[RS_PREP_U];
+#pragma unroll
+        for (int u = 0; u < RS_PREP_U; ++u) {
+            const size_t i = (size_t)min(tb + u, T - 1) * N + nn;
+            c[u] = cut[i]; a[u] = adv[i];
+        }
+#pragma unroll
+        for (int u = 0; u < RS_PREP_U; ++u) {
+            const int t = tb + u;
+            if (t < T) {
+                s += (double)a[u];
+                if (live) w[(size_t)t * N + n] = __int_as_float(pos);
+                if (c[u]) { pos = 0; n_ep += (t < T - 1) ? 1 : 0; } else ++pos;
+            }
+        }
+    }
+    const float n_ep_f = (float)n_ep;
+    int left = 0;
+    for (int tb = T - 1; tb >= 0; tb -= RS_PREP_U) {
+        uint8_t c[RS_PREP_U];
+        int ps[RS_PREP_U];
+#pragma unroll
+        for (int u = 0; u < RS_PREP_U; ++u) {
+            const size_t i = (size_t)max(tb - u, 0) * N + nn;
+            c[u] = cut[i]; ps[u] = __float_as_int(w[i]);              // this lane's own stores of the forward walk
+        }
+#pragma unroll
+        for (int u = 0; u < RS_PREP_U; ++u) {
+            const int t = tb - u;
+            if (t >= 0) {
+                left = (c[u] || t == T - 1) ? 0 : left + 1;
+                const float len = (float)(ps[u] + left + 1);
+                if (live) w[(size_t)t * N + n] = (1.0f / (n_ep_f * len)) * inv_n_total;
+            }
+        }
+    }
+    lane_sum[threadIdx.x] = live ? s : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double v = 0.0;
+        for (int i = 0; i < 64; ++i) v += lane_sum[i];
+        col_sums[blockIdx.x] = v;
+    }
+}
+
+// p[0] + p[1] + ... + p[n-1] for a whole workgroup of RS_PREP_THREADS: thread k sums p[k], p[k + 256], ... in that order, thread 0
+// adds the 256 sums in index order; every thread gets the result.  The order depends on n alone.
+__device__ __forceinline__ double rs_prep_sum(const double* __restrict__ p, int n, double* red) {
+    double v = 0.0;
+    for (int i = threadIdx.x; i < n; i += RS_PREP_THREADS) v += p[i];
+    __syncthreads();                                               // red may still be read from the sum before this one
+    red[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < RS_PREP_THREADS; ++i) t += red[i];
+        red[RS_PREP_THREADS] = t;
+    }
+    __syncthreads();
+    return red[RS_PREP_THREADS];
+}
+
+// mean = float32(sum / n); every workgroup then sums float64((adv - mean)^2), the square taken in float32, over its own samples
+__global__ void __launch_bounds__(RS_PREP_THREADS) rs_ppo_prepare_sq_kernel(const float* __restrict__ adv, const double* __restrict__ col_sums,
+                                                                            int n_col_sums, double* __restrict__ sq_sums, size_t n) {
+    __shared__ double red[RS_PREP_THREADS + 1];
+    const float mean = (float)(rs_prep_sum(col_sums, n_col_sums, red) / (double)n);
+    double v = 0.0;
+    for (size_t i = (size_t)blockIdx.x * RS_PREP_THREADS + threadIdx.x; i < n; i += (size_t)RS_PREP_BLOCKS * RS_PREP_THREADS) {
+        const float d = adv[i] - mean;
+        v += (double)(d * d);
+    }
+    __syncthreads();
+    red[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < RS_PREP_THREADS; ++i) t += red[i];
+        sq_sums[blockIdx.x] = t;
+    }
+}
+
+// std = float32(sqrt(sq / n)) (population std, no epsilon); adv_n = (adv - mean) / std, IEEE float32 division
+__global__ void __launch_bounds__(RS_PREP_THREADS) rs_ppo_prepare_norm_kernel(const float* __restrict__ adv, const double* __restrict__ col_sums,
+                                                                              int n_col_sums, const double* __restrict__ sq_sums,
+                                                                              float* __restrict__ adv_n, float* __restrict__ mean_std, size_t n) {
+    __shared__ double red[RS_PREP_THREADS + 1];
+    const float mean = (float)(rs_prep_sum(col_sums, n_col_sums, red) / (double)n);
+    const float sd = (float)sqrt(rs_prep_sum(sq_sums, RS_PREP_BLOCKS, red) / (double)n);
+    for (size_t i = (size_t)blockIdx.x * RS_PREP_THREADS + threadIdx.x; i < n; i += (size_t)RS_PREP_BLOCKS * RS_PREP_THREADS)
+        adv_n[i] = (adv[i] - mean) / sd;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { mean_std[0] = mean; mean_std[1] = sd; }
+}
+
 // ================================================================================================
 // Host side of the C ABI
 // ================================================================================================
@@ -509,6 +629,29 @@ int rs_gae(const float* rew, const float* val, const uint8_t* cut, const float* 
     chunks = (T + chunk - 1) / chunk;
     hipLaunchKernelGGL(rs_gae_kernel, dim3(col_waves, chunks), dim3(64), 0, s, rew, val, cut, last_val, adv, ret, T, M,
                        gamma, gamma * lam, chunk);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+size_t rs_ppo_prepare_workspace_bytes(int32_t N) {
+    if (N < 1) return 0;
+    return sizeof(double) * ((size_t)(N + 63) / 64 + RS_PREP_BLOCKS);
+}
+
+int rs_ppo_prepare(const uint8_t* cut, const float* adv, float* w, float* adv_n, float* mean_std, void* workspace, int32_t T, int32_t N,
+                   int32_t n_total, rs_stream_t stream) {
+    if (!cut || !adv || !w || !adv_n || !mean_std || !workspace || T < 1 || N < 1 || n_total < 1) return RS_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return RS_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int col_groups = (N + 63) / 64;
+    double* col_sums = static_cast<double*>(workspace);
+    double* sq_sums = col_sums + col_groups;
+    const size_t n = (size_t)T * (size_t)N;
+    // a tensor divided by a Python number is a multiplication by float32(1 / number) in the tensor library; so it is here
+    const float inv_n_total = (float)(1.0 / (double)n_total);
+    hipLaunchKernelGGL(rs_ppo_prepare_cols_kernel, dim3(col_groups), dim3(64), 0, s, cut, adv, w, col_sums, T, N, inv_n_total);
+    hipLaunchKernelGGL(rs_ppo_prepare_sq_kernel, dim3(RS_PREP_BLOCKS), dim3(RS_PREP_THREADS), 0, s, adv, col_sums, col_groups, sq_sums, n);
+    hipLaunchKernelGGL(rs_ppo_prepare_norm_kernel, dim3(RS_PREP_BLOCKS), dim3(RS_PREP_THREADS), 0, s, adv, col_sums, col_groups, sq_sums, adv_n,
+                       mean_std, n);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -336,14 +336,19 @@ static RsGradWs rs_grad_ws(void* workspace) {
     return w;
 }
 
-// the two K7 launches; ust != nullptr: the critic launch also leaves the copy of the update state the fused tail reads
+// the K7 launches; ust != nullptr: the critic's workgroups also leave the copy of the update state the fused tail reads.
+// pair: both networks in one grid of 2 x RS_GRAD_BLOCKS workgroups (rs_ppo_grad2_pair_kernel) instead of one launch each.
 static int rs_launch_k7(const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_ppo_batch* batch, const RsGradWs& w,
-                        const int32_t* stop_flag, const rs_update_state* ust, hipStream_t s) {
+                        const int32_t* stop_flag, const rs_update_state* ust, hipStream_t s, bool pair = false) {
     const size_t lds_a = sizeof(float) * (size_t)rs_grad2_lds_floats(8);
     const size_t lds_c = sizeof(float) * (size_t)rs_grad2_lds_floats(1);
+    const size_t lds_p = lds_a > lds_c ? lds_a : lds_c;
     // > 64 KB of dynamic LDS needs the attribute on every device the library is used on: set it per call (cheap, no sync)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rs_ppo_grad2_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(rs_ppo_grad2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess)
+    if (pair) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(rs_ppo_grad2_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p) != hipSuccess)
+            return RS_ERR_HIP;
+    } else if (hipFuncSetAttribute(reinterpret_cast<const void*>(rs_ppo_grad2_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess ||
+               hipFuncSetAttribute(reinterpret_cast<const void*>(rs_ppo_grad2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess)
         return RS_ERR_HIP;
     int threads = 512;
 #ifdef RS_K7_STAMPS
@@ -351,6 +356,11 @@ static int rs_launch_k7(const rs_mlp_params* actor, const rs_mlp_params* critic,
     // per-phase cycle counts are those of a wave that has its SIMD to itself)
     if (const char* e = getenv("RS_K7_THREADS")) threads = atoi(e) == 256 ? 256 : 512;
 #endif
+    if (pair) {
+        hipLaunchKernelGGL(rs_ppo_grad2_pair_kernel, dim3(2 * RS_GRAD_BLOCKS), dim3(threads), lds_p, s, to_dev(actor), to_dev(critic), *batch,
+                           w.pa, w.pc, w.sa, w.sc, stop_flag, ust, ust ? w.snap : (int*)nullptr);
+        return RS_OK;
+    }
     hipLaunchKernelGGL(rs_ppo_grad2_kernel<8>, dim3(RS_GRAD_BLOCKS), dim3(threads), lds_a, s, to_dev(actor), *batch, w.pa, w.sa, stop_flag,
                        (const rs_update_state*)nullptr, (int*)nullptr);
     hipLaunchKernelGGL(rs_ppo_grad2_kernel<1>, dim3(RS_GRAD_BLOCKS), dim3(threads), lds_c, s, to_dev(critic), *batch, w.pc, w.sc, stop_flag,
@@ -378,7 +388,9 @@ int rs_ppo_update_step(const rs_mlp_params* actor, const rs_mlp_params* critic, 
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return RS_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const RsGradWs w = rs_grad_ws(workspace);
-    if (const int rc = rs_launch_k7(actor, critic, batch, w, &state->stopped, state, s)) return rc;
+    // one launch for both networks; RS_PPO_SPLIT_GRAD=1 keeps one launch per network for A/B timing (read per call: a test flips it)
+    const char* split = getenv("RS_PPO_SPLIT_GRAD");
+    if (const int rc = rs_launch_k7(actor, critic, batch, w, &state->stopped, state, s, !(split && *split && *split != '0'))) return rc;
     const int np = rs_net_params(8) + rs_net_params(1);
     hipLaunchKernelGGL(rs_ppo_tail_kernel, dim3((np + 63) / 64), dim3(1024), 0, s, w.pa, w.pc, w.sa, w.sc, RS_GRAD_BLOCKS, grads, stats,
                        batch->alpha, batch->vf_coef, rs_param_seg(actor, critic), m, v, state, w.snap, lr, kl_threshold);

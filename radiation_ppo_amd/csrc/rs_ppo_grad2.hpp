@@ -66,14 +66,20 @@ __device__ __forceinline__ void rs_stage32(float* T, const f32x16& v, int c, int
     for (int r = 0; r < 16; ++r) T[rs_kappa(r, h) * RS_T2 + c] = v[r];
 }
 
+// The whole pass of one network as ONE workgroup sees it: workgroup `bid` of `nblocks`.  rs_ppo_grad2_kernel passes its launch's own
+// index and grid size; rs_ppo_grad2_pair_kernel runs both networks' workgroups in one grid and hands each its index in its own half.
+// No __restrict__ here: the kernels' own parameters carry it.  Repeated on this inlined function it becomes alias scopes on every
+// access of the group loop, and hipcc then waits for the LDS reads in bulk (s_waitcnt lgkmcnt(0)) where it counted them down one
+// MFMA operand at a time: + 1.7 % on the pass (measured, profiles/r07_update_launches_ab.txt).
 template <int NOUT>
-__global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, rs_ppo_batch B, float* __restrict__ partial,
-                                                              double* __restrict__ stat_partial, const int* __restrict__ stop,
-                                                              const rs_update_state* __restrict__ ust, int* __restrict__ snap) {
+__device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const rs_ppo_batch B, float* partial,
+                                                  double* stat_partial, const int* stop,
+                                                  const rs_update_state* ust, int* snap,
+                                                  const int bid, const int nblocks) {
     extern __shared__ __align__(16) float smem_f[];
     // snap (fused single-GPU tail only): a copy of the update state's step count and stop flag for rs_ppo_tail_kernel, all of whose
     // workgroups read them while one of them writes the state -- the copy is what makes that free of a race without any waiting
-    if (snap && blockIdx.x == 0 && threadIdx.x == 0) { snap[0] = ust->adam_step; snap[1] = ust->stopped; }
+    if (snap && bid == 0 && threadIdx.x == 0) { snap[0] = ust->adam_step; snap[1] = ust->stopped; }
     if (stop && *stop) return;
     RS_STAMP_ENTRY
     RsMlpLds<NOUT> W;
@@ -123,7 +129,7 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
 
     const int M = B.M;
     const int groups = (M + 31) / 32;
-    const int wave_g = blockIdx.x * 8 + wid, n_waves = gridDim.x * 8;
+    const int wave_g = bid * 8 + wid, n_waves = nblocks * 8;
 
     f32x16 acc2[2][2];
     f32x4 acc1[4], acc3[4];
@@ -557,7 +563,7 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last trip's look-ahead DMA has landed: nothing writes LDS behind our back
     const float db2v = dbl[lane_e];                     // (dbl lives in the region being overwritten: read it first)
     __syncthreads();                                  // every wave is done with its staging tiles and the fragments
-    float* outp = partial + (size_t)blockIdx.x * rs_net_params(NOUT);
+    float* outp = partial + (size_t)bid * rs_net_params(NOUT);
     {
         float* g_w2 = smem_f + wid * (64 * 64);
 #pragma unroll
@@ -621,7 +627,27 @@ __global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, r
         double v = 0.0 + sred[tid_e];
 #pragma unroll
         for (int wv = 1; wv < 8; ++wv) v += sred[wv * 5 + tid_e];
-        stat_partial[(size_t)blockIdx.x * 5 + tid_e] = v;
+        stat_partial[(size_t)bid * 5 + tid_e] = v;
     }
     RS_STAMP_EXIT(NOUT == 8 ? 0 : 1);
+}
+
+template <int NOUT>
+__global__ void __launch_bounds__(512, 2) rs_ppo_grad2_kernel(RsMlpParams prm, rs_ppo_batch B, float* __restrict__ partial,
+                                                              double* __restrict__ stat_partial, const int* __restrict__ stop,
+                                                              const rs_update_state* __restrict__ ust, int* __restrict__ snap) {
+    rs_ppo_grad2_body<NOUT>(prm, B, partial, stat_partial, stop, ust, snap, blockIdx.x, gridDim.x);
+}
+
+// Both passes of one Adam step in ONE grid of 2G workgroups: 0..G-1 are the actor launch's workgroups, G..2G-1 the critic launch's
+// (slab, statistics row, snap copy and early exit exactly as in the two launches, so every bit is the same).  Workgroups are handed
+// out in index order and one fits a CU, so a critic workgroup starts on a CU as soon as an actor workgroup retires there: no launch
+// gap between the networks, no drain behind the slowest actor workgroup, and the critic's prologue runs next to the actor's tail.
+__global__ void __launch_bounds__(512, 2) rs_ppo_grad2_pair_kernel(RsMlpParams pa, RsMlpParams pc, rs_ppo_batch B, float* __restrict__ partial_a,
+                                                                   float* __restrict__ partial_c, double* __restrict__ stat_a,
+                                                                   double* __restrict__ stat_c, const int* __restrict__ stop,
+                                                                   const rs_update_state* __restrict__ ust, int* __restrict__ snap) {
+    const int G = gridDim.x >> 1;
+    if ((int)blockIdx.x < G) rs_ppo_grad2_body<8>(pa, B, partial_a, stat_a, stop, nullptr, nullptr, blockIdx.x, G);
+    else rs_ppo_grad2_body<1>(pc, B, partial_c, stat_c, stop, ust, snap, blockIdx.x - G, G);
 }

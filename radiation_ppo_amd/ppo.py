@@ -148,24 +148,38 @@ class FusedPPOGrad:
                                             torch.cuda.current_stream(X.device).cuda_stream), "rs_ppo_grad")
         return self.stats, self.grads
 
-    def step(self, X, act, adv, ret, logp_old, w, clip_ratio: float, alpha: float, vf_coef: float = 0.01, *, lr: float,
-             kl_threshold: float):
-        """One iteration of the early-stopped loop on ONE rank: __call__(use_stop_flag=True) + adam_step() as rs_ppo_update_step,
-        where the slab reduction, the Adam step and the state update are one launch behind the two gradient kernels (bitwise the
-        same results).  With more ranks the all-reduce sits between the two, so they stay separate calls."""
+    def bind(self, X, act, adv, ret, logp_old, w, clip_ratio: float, alpha: float, vf_coef: float = 0.01) -> None:
+        """The argument blocks of rs_ppo_update_step for one update: the batch and the parameter tensors stay where they are over
+        its Adam steps (Adam writes the parameters in place), so the blocks are built once and step_bound() reuses them."""
+        import ctypes as C
         for t in (X, adv, ret, logp_old, w):
             assert t.dtype == torch.float32 and t.is_contiguous()
         assert act.dtype == torch.int64 and act.is_contiguous()
-        self.stats_from_bucket = False
         b = _lib.RsPpoBatch(X.data_ptr(), act.data_ptr(), adv.data_ptr(), ret.data_ptr(), logp_old.data_ptr(), w.data_ptr(),
                             X.shape[0], clip_ratio, alpha, vf_coef)
         pa, pc = mlp_params(self.ac.actor), mlp_params(self.ac.critic)
-        # the bracket bench.py reads: the two gradient kernels and the launch behind them, as around rs_ppo_grad
+        self._bound = (b, pa, pc, (X, act, adv, ret, logp_old, w))            # the tensors: kept alive as long as their addresses are
+        self._bound_args = (C.byref(pa), C.byref(pc), C.byref(b), self.bucket.data_ptr(), self.stats.data_ptr(), self._ws_ptr,
+                            self.m.data_ptr(), self.v.data_ptr(), self.state.data_ptr())
+        self._bound_dev = X.device
+
+    def step_bound(self, lr: float, kl_threshold: float):
+        """One iteration of the early-stopped loop on ONE rank, on the batch bind() was given: __call__(use_stop_flag=True) +
+        adam_step() as rs_ppo_update_step, where both gradient passes are one launch and the slab reduction, the Adam step and the
+        state update are one launch behind it (bitwise the same results).  With more ranks the all-reduce sits between the two,
+        so they stay separate calls."""
+        self.stats_from_bucket = False
+        # the bracket bench.py reads: the gradient pass and the launch behind it, as around rs_ppo_grad
         with _lib.timed("rs_ppo_grad"):
-            _lib.check(self.lib.rs_ppo_update_step(C.byref(pa), C.byref(pc), C.byref(b), self.bucket.data_ptr(), self.stats.data_ptr(),
-                                                   self._ws_ptr, self.m.data_ptr(), self.v.data_ptr(), self.state.data_ptr(), lr,
-                                                   kl_threshold, torch.cuda.current_stream(X.device).cuda_stream), "rs_ppo_update_step")
+            _lib.check(self.lib.rs_ppo_update_step(*self._bound_args, lr, kl_threshold,
+                                                   torch.cuda.current_stream(self._bound_dev).cuda_stream), "rs_ppo_update_step")
         return self.stats, self.grads
+
+    def step(self, X, act, adv, ret, logp_old, w, clip_ratio: float, alpha: float, vf_coef: float = 0.01, *, lr: float,
+             kl_threshold: float):
+        """bind() + step_bound(): one iteration on a batch given with the call."""
+        self.bind(X, act, adv, ret, logp_old, w, clip_ratio, alpha, vf_coef)
+        return self.step_bound(lr, kl_threshold)
 
     def allreduce(self) -> None:
         """mpi_avg_grads (ppo.py:1256) + mpi_avg(kl) (:1250) as ONE RCCL all-reduce per Adam step: the bucket holds the
@@ -513,9 +527,11 @@ class VecAgentPPO:
         f.begin_update()
         # one rank: the fused tail (rs_ppo_update_step).  RS_PPO_SPLIT_TAIL=1 keeps the separate calls for A/B timing.
         one_rank = _world() == 1 and not os.environ.get("RS_PPO_SPLIT_TAIL")
+        if one_rank:
+            f.bind(X, act, adv, ret, logp_old, w, self.clip_ratio, self.alpha)
         for _ in range(self.train_pi_iters):
             if one_rank:
-                f.step(X, act, adv, ret, logp_old, w, self.clip_ratio, self.alpha, lr=lr, kl_threshold=thr)
+                f.step_bound(lr, thr)
                 continue
             stats, grads = f(X, act, adv, ret, logp_old, w, self.clip_ratio, self.alpha, use_stop_flag=True)
             if _world() > 1:
@@ -828,12 +844,37 @@ class FusedCollector:
             getattr(self, k).copy_(st[k])                          # in place: rs_rollout's argument block holds their addresses
 
 
+def prepare_update_hip(col):
+    """(w, adv_n) of ppo_update_from_buffer for one rank and one agent as rs_ppo_prepare computes them: episode_weights() / n_total and
+    normalize_advantages(buf.adv), bit for bit, in three launches.  The outputs and the workspace belong to the collector and are
+    allocated once; buf.adv stays unnormalised."""
+    buf = col.buf
+    lib = _lib.load()
+    p = getattr(col, "_prep", None)
+    if p is None:
+        dev = buf.adv.device
+        p = col._prep = dict(w=torch.empty(buf.T * buf.N, dtype=torch.float32, device=dev),
+                             adv_n=torch.empty(buf.T * buf.N, dtype=torch.float32, device=dev),
+                             mean_std=torch.empty(2, dtype=torch.float32, device=dev),
+                             ws=torch.empty((lib.rs_ppo_prepare_workspace_bytes(buf.N) + 7) // 8, dtype=torch.float64, device=dev))
+    _lib.check(lib.rs_ppo_prepare(buf.cut.data_ptr(), buf.adv.data_ptr(), p["w"].data_ptr(), p["adv_n"].data_ptr(), p["mean_std"].data_ptr(),
+                                  p["ws"].data_ptr(), buf.T, buf.N, col.N, torch.cuda.current_stream(buf.adv.device).cuda_stream),
+               "rs_ppo_prepare")
+    return p["w"], p["adv_n"]
+
+
 def ppo_update_from_buffer(col) -> Dict[int, UpdateResult]:
     """train.py:569-599: PPO update of every agent from the finished buffer of a collector."""
     buf = col.buf
     n_total = col.N * _world()
-    w = (buf.episode_weights() / n_total).reshape(-1)
     out = {}
+    if _world() == 1 and buf.adv.is_cuda and buf.A == 1 and len(col.agents) == 1 and buf.N == col.N:
+        w, adv = prepare_update_hip(col)
+        (a, ag), = col.agents.items()
+        X = buf.obs[:, :, a].reshape(-1, buf.obs.shape[-1])
+        out[a] = ag.update_agent(X, buf.act[:, :, a].reshape(-1), adv, buf.ret[:, :, a].reshape(-1), buf.logp[:, :, a].reshape(-1), w)
+        return out
+    w = (buf.episode_weights() / n_total).reshape(-1)
     for a, ag in col.agents.items():
         adv = normalize_advantages(buf.adv[:, :, a]).reshape(-1)
         X = buf.obs[:, :, a].reshape(-1, buf.obs.shape[-1])

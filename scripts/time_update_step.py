@@ -4,7 +4,8 @@ Times, with HIP events on the launch stream, (a) the gradient pass alone (rs_ppo
 step as VecAgentPPO runs it (gradient pass + Adam + KL commit) at M, M/2 and M/4 samples, three runs of five rounds of 20 steps
 each, medians.  Time per step is a straight line in M: the intercept of the least-squares line is what a step pays whatever the
 batch (prologue and epilogue of the two K7 kernels, the launches behind them, the gaps in between).
-RS_LIB_PATH selects another build; RS_PPO_SPLIT_TAIL=1 keeps the three-kernel tail in a build that has the fused one."""
+RS_LIB_PATH selects another build; RS_PPO_SPLIT_TAIL=1 keeps the three-kernel tail in a build that has the fused one,
+RS_PPO_SPLIT_GRAD=1 one gradient launch per network in a build that has the pair launch (whole step only)."""
 import os
 import sys
 
@@ -53,7 +54,7 @@ torch.manual_seed(0)
 ac = FFActorCritic().cuda()
 f = FusedPPOGrad(ac)
 fused = hasattr(f, "step") and not os.environ.get("RS_PPO_SPLIT_TAIL")
-print(f"lib={os.environ.get('RS_LIB_PATH', 'default')}  tail={'fused (one launch)' if fused else 'reduce + apply + commit (three launches)'}")
+print(f"lib={os.environ.get('RS_LIB_PATH', 'default')}  grad={'one launch per network' if os.environ.get('RS_PPO_SPLIT_GRAD') else 'default'}  tail={'fused (one launch)' if fused else 'reduce + apply + commit (three launches)'}")
 data = {M: batch(M) for M in (M0, M0 // 2, M0 // 4)}
 
 

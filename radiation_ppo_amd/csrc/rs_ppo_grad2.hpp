@@ -47,6 +47,7 @@ __device__ __forceinline__ unsigned long long rs_k7_now() {
 #endif
 #define RS_XRAW 400                                // per-wave landing zone of the group's 32 x 11 sample rows (352 floats, LDS-DMA);
                                                    // between layer 1 and the next DMA it holds the [12][33] dz^T / statistics tile
+                                                   // (actor) or the tail of the stride-36 h2^T tile, the dz / loss rows and a row of ones (critic)
 #define RS_XSC 192                                 // per-wave landing zone of the per-sample scalars: act (32 x int64), adv, logp_old, w, ret
 #define RS_G2_WAVE_FLOATS ((64 + 32) * RS_T2 + RS_XRAW + RS_XSC + 64)
 
@@ -168,16 +169,17 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         }
     };
     auto dma_scal = [&](int g) {
-        // three wave-instructions: [act: 64 dwords = 32 int64] [adv | logp_old] [w | ret]; sample index clamped like the rows
+        // three wave-instructions: [act: 64 dwords = 32 int64] [adv | logp_old] [w | ret]; sample index clamped like the rows.
+        // The critic reads neither the action nor adv / logp_old: it issues the third only.
         const int m0 = g * 32;
         const int ms = min(m0 + c, M - 1);
-        {
+        if constexpr (NOUT == 8) {
             const int mi = min(m0 + (lane >> 1), M - 1);
             const int* src = reinterpret_cast<const int*>(B.act) + 2 * (size_t)mi + (lane & 1);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(xsc), 4, 0, 0);
         }
-        {
+        if constexpr (NOUT == 8) {
             const float* src = (h ? B.logp_old : B.adv) + ms;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(xsc + 64), 4, 0, 0);
@@ -192,6 +194,18 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         const int g0 = wave_g < groups ? wave_g : groups - 1;
         dma_rows(g0);
         dma_scal(g0);
+    }
+    // ---- critic only (NOUT == 1): its sample-group loop differs from the actor's in the sections marked `if constexpr (NOUT == 1)`.
+    // w3v: the 32 output weights of the units this lane holds, W3[0][32 kt + kappa(r, h)] at [16 kt + r], read once as eight b128 and
+    // kept across the trips (output layer and dh2 = W3^T dz both use them).  db2r: the db2 sums of units 32 it + c, in every lane.
+    float w3v[NOUT == 1 ? 32 : 1], db2r[2] = {0.0f, 0.0f};
+    if constexpr (NOUT == 1) {
+        const float4* wrow = reinterpret_cast<const float4*>(W.w3h + h * 32);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const float4 t = wrow[b];
+            w3v[4 * b + 0] = t.x; w3v[4 * b + 1] = t.y; w3v[4 * b + 2] = t.z; w3v[4 * b + 3] = t.w;
+        }
     }
     RS_STAMP_DECL
     for (int trip = 0; trip < trips; ++trip) {
@@ -285,7 +299,14 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         // lane pairs.  Weights are broadcast float4 reads; they are fetched one batch (8 outputs x 4 units) ahead of the FMAs
         // that use them so that the LDS latency is paid once, not per output (summation order per output unchanged: ascending unit)
         float out[NOUT];
-        {
+        if constexpr (NOUT == 1) {
+            // one output: a single ascending-unit fmaf chain over the register-held weights, no prefetch rotation
+            float pacc = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 32; ++q) pacc = fmaf(w3v[q], H2[q >> 4][q & 15], pacc);
+            const float q = rs_other_half(pacc, h);
+            out[0] = (h ? (q + pacc) : (pacc + q)) + W.b3[0];
+        } else {
             float pacc[NOUT];
 #pragma unroll
             for (int o = 0; o < NOUT; ++o) pacc[o] = 0.0f;
@@ -366,8 +387,46 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
 
         // ---------------- backward ----------------
         // dz^T borrows the row landing zone (its rows were consumed by layer 1; the next group's DMA is issued after dW3):
-        // rows 0..NOUT-1 = dz, rows 8..11 = the statistics terms (rows NOUT..7 of the critic's tile are never read)
+        // rows 0..NOUT-1 = dz, rows 8..11 = the statistics terms.  The critic lays the zone out differently, see its section
         float* Dz = xraw;                                // [12][33]
+        if constexpr (NOUT == 1) {
+            // One output row: dW3[unit] += sum_n dz[n] h2[unit][n], db3 += sum_n dz[n] and the value-loss sum as 2 x 32
+            // v_mfma_f32_4x4x1_16b_f32 (K = 1: one instruction per sample, so instruction order is the chain order n = 0..31 the
+            // 16x16x4 tiles had).  Block b of an instruction is the outer product of A lanes 4b..4b+3 and B lanes 4b..4b+3, D[i][j] in
+            // register i of lane 4b + j.  A: even lanes dz[n], odd lanes the loss term; B: lane l < 32 h2[unit 32 hf + l][n], lanes
+            // 32..63 the constant 1.  Register 0 of lane l < 32 is then dW3 of unit 32 hf + l, registers 0 / 1 of the upper lanes are
+            // db3 / the loss sum (first half only; what the other registers and the second half's upper lanes collect is never read).
+            // h2^T is staged with a row stride of 36 floats so that a lane's 32 samples are eight aligned b128 reads; the tile's last
+            // 96 floats, the two A rows and the row of ones lie in the row landing zone, which is free until the DMA issue below.
+            constexpr int T4 = 36;
+            float* zrow = xraw + 96;                     // [2][32]: dz, loss terms
+            float* ones = xraw + 160;                    // [32]
+            zrow[32 * h + c] = h ? sq[0] : dz[0];
+            ones[c] = 1.0f;
+            float4 av[8];
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                rs_wave_sync();                          // the previous readers of Pt are done
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Pt[rs_kappa(r, h) * T4 + c] = H2[hf][r];
+                rs_wave_sync();
+                if (hf == 0) {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) av[q] = *reinterpret_cast<const float4*>(zrow + 32 * (lane & 1) + 4 * q);
+                }
+                const float* brow = (hf == 0 && h) ? ones : Pt + c * T4;
+                float4 bv[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) bv[q] = *reinterpret_cast<const float4*>(brow + 4 * q);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    acc3[hf] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].x, bv[q].x, acc3[hf], 0, 0, 0);
+                    acc3[hf] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].y, bv[q].y, acc3[hf], 0, 0, 0);
+                    acc3[hf] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].z, bv[q].z, acc3[hf], 0, 0, 0);
+                    acc3[hf] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].w, bv[q].w, acc3[hf], 0, 0, 0);
+                }
+            }
+        } else {
         if (h == 0) {
 #pragma unroll
             for (int o = 0; o < NOUT; ++o) Dz[o * RS_T2 + c] = dz[o];
@@ -404,6 +463,7 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
                 for (int u = 0; u < 2; ++u) b_c[u] = b_n[u];
             }
         }
+        }
         RS_STAMP(7);                                    // dW3
         // dh2 = W3^T dz, dpre2 = dh2 * (1 - h2^2) in place of H2
         if (NOUT == 8) {
@@ -426,7 +486,7 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float hv = H2[kt][r];
-                    const float d = W.w3h[h * 32 + kt * 16 + r] * dz[0];
+                    const float d = w3v[kt * 16 + r] * dz[0];
                     H2[kt][r] = fmaf(-(d * hv), hv, d);
                 }
         }
@@ -522,7 +582,8 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
 #pragma unroll
             for (int n = 0; n < 16; ++n) rs += Pt[c * RS_T2 + 16 * h + n];
             rs += rs_other_half(rs, h);
-            if (h == 0) dbl[32 * it + c] += rs;
+            if constexpr (NOUT == 1) db2r[it] += rs;    // same adds in the same order, handed to the epilogue in registers
+            else if (h == 0) dbl[32 * it + c] += rs;
         }
         RS_STAMP(10);                                   // R4 / R5 dW2 + db2
         // R6: dW1[unit][input] += sum_n dpre1[unit][n] x[input][n]  (16x16x4, 8 k-steps per half)
@@ -561,7 +622,8 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
     asm volatile("" : "+v"(tid_e));
     const int lane_e = tid_e & 63, h_e = lane_e >> 5, c_e = lane_e & 31, l15_e = lane_e & 15, l4_e = lane_e >> 4;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last trip's look-ahead DMA has landed: nothing writes LDS behind our back
-    const float db2v = dbl[lane_e];                     // (dbl lives in the region being overwritten: read it first)
+    // (dbl lives in the region being overwritten: read it first); the critic's sums are in registers, unit 32 it + c in lane (c, it)
+    const float db2v = NOUT == 1 ? (h_e ? db2r[1] : db2r[0]) : dbl[lane_e];
     __syncthreads();                                  // every wave is done with its staging tiles and the fragments
     float* outp = partial + (size_t)bid * rs_net_params(NOUT);
     {
@@ -584,14 +646,18 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
     }
     // accs (16x16 D layout: row 4*(lane>>4) + q, every column identical): rows 0..NOUT-1 = db3, rows 8..11 = statistics sums
     // of this wave; bring them to lane 0 (row r lives in lanes with lane>>4 == r/4, register r%4)
+    // The critic's 4x4x1 accumulators: acc3[hf][0] of lane l < 32 = dW3 of unit 32 hf + l, acc3[0][0] / acc3[0][1] of the upper lanes
+    // = db3 / the value-loss sum.
     float db3r[NOUT];
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) db3r[o] = __shfl(accs[o & 3], 16 * (o >> 2));
     double sv[5];
-    {
+    if constexpr (NOUT == 1) {
+        db3r[0] = __shfl(acc3[0][0], 32);
+        sv[0] = 0.0; sv[1] = 0.0; sv[2] = 0.0; sv[3] = (double)__shfl(acc3[0][1], 32); sv[4] = 0.0;
+    } else {
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o) db3r[o] = __shfl(accs[o & 3], 16 * (o >> 2));
         const float t0 = __shfl(accs[0], 32), t1 = __shfl(accs[1], 32), t2 = __shfl(accs[2], 32), t3 = __shfl(accs[3], 32);
-        if (NOUT == 8) { sv[0] = (double)t0; sv[1] = (double)t1; sv[2] = (double)t2; sv[3] = 0.0; sv[4] = (double)t3; }
-        else { sv[0] = 0.0; sv[1] = 0.0; sv[2] = 0.0; sv[3] = (double)t0; sv[4] = 0.0; }
+        sv[0] = (double)t0; sv[1] = (double)t1; sv[2] = (double)t2; sv[3] = 0.0; sv[4] = (double)t3;
     }
     constexpr int RS_RSTR = (RS_REST + 1) & ~1;       // slab stride of round two (even: the doubles behind the slabs stay aligned)
     double* sred = reinterpret_cast<double*>(smem_f + 8 * RS_RSTR);     // [8 waves][5]
@@ -607,8 +673,9 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
                 if (l15_e < RS_IN) g_w1[row * RS_IN + l15_e] = acc1[u][q];
                 if (l15_e == RS_IN) g_b1[row] = acc1[u][q];
                 const int o = 4 * l4_e + q;
-                if (o < NOUT) g_w3[o * 64 + 16 * u + l15_e] = acc3[u][q];
+                if (NOUT == 8 && o < NOUT) g_w3[o * 64 + 16 * u + l15_e] = acc3[u][q];
             }
+        if (NOUT == 1 && lane_e < 32) { g_w3[lane_e] = acc3[0][0]; g_w3[32 + lane_e] = acc3[1][0]; }
         if (lane_e == 0) {
 #pragma unroll
             for (int o = 0; o < NOUT; ++o) g_b3[o] = db3r[o];

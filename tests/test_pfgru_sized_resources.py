@@ -2,58 +2,31 @@
 spills, VGPRs and LDS within the occupancy DESIGN.md section 3 states for every width; the C ABI's argument checks, which return
 before anything is launched; the packed-weight size against the packer."""
 import os
-import re
-import subprocess
-import tempfile
+import sys
 
 import pytest
 
 from radiation_ppo_amd import build
 
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-LDS_PER_CU = 160 * 1024
+sys.path.insert(0, os.path.dirname(__file__))
+import _kernel_meta as M  # noqa: E402
 
-# waves per SIMD DESIGN.md section 3 states by width (one 256-thread workgroup = one wave per SIMD); 512 VGPRs per SIMD lane, granule 8
+# waves per SIMD DESIGN.md section 3 states by width (one 256-thread workgroup = one wave per SIMD)
 WAVES = {8: 4, 16: 4, 24: 3, 32: 3, 40: 2, 48: 2, 56: 2, 64: 1}
-
-
-@pytest.fixture(scope="module")
-def sized_pfgru_kernels():
-    if not os.path.exists(READELF):
-        pytest.skip("llvm-readelf not available")
-    from test_rnn_sized_resources import _code_objects
-    lib = build.build(verbose=False)
-    out = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        for n, co in enumerate(_code_objects(open(lib, "rb").read())):
-            path = os.path.join(tmp, f"co{n}.elf")
-            with open(path, "wb") as f:
-                f.write(co)
-            notes = subprocess.run([READELF, "--notes", path], capture_output=True, text=True, check=True).stdout
-            for block in notes.split("- .agpr_count:")[1:]:
-                name = re.search(r"\.name:\s+(\S+)", block).group(1)
-                if "rs_pfgru_sized_" not in name:
-                    continue
-                val = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", block).group(1))
-                out[name] = dict(vgpr=val("vgpr_count"), scratch=val("private_segment_fixed_size"), vgpr_spill=val("vgpr_spill_count"),
-                                 lds=val("group_segment_fixed_size"))
-    return out
 
 
 @pytest.mark.parametrize("rec", [0, 1])
 @pytest.mark.parametrize("H", sorted(WAVES))
-def test_sized_pfgru_kernels_fit_their_occupancy(sized_pfgru_kernels, H, rec):
-    hits = [k for k in sized_pfgru_kernels if f"rs_pfgru_sized_kernelILi{H}ELb{rec}E" in k]
-    assert len(hits) == 1, (H, rec, sorted(sized_pfgru_kernels))
-    k = sized_pfgru_kernels[hits[0]]
-    assert k["scratch"] == 0 and k["vgpr_spill"] == 0, (hits[0], k)
-    assert k["vgpr"] <= (512 // WAVES[H]) // 8 * 8, (hits[0], k)
-    assert LDS_PER_CU // k["lds"] >= WAVES[H], (hits[0], k)              # LDS does not cut the occupancy below the stated one
+def test_sized_pfgru_kernels_fit_their_occupancy(H, rec):
+    k = M.one(M.library_kernels(), f"rs_pfgru_sized_kernelILi{H}ELb{rec}E")
+    assert k["scratch"] == 0 and k["vgpr_spill"] == 0, k
+    assert M.waves_by_vgpr(k["vgpr"]) >= WAVES[H], k
+    assert M.workgroups_by_lds(k["lds"]) >= WAVES[H], k                  # LDS does not cut the occupancy below the stated one
 
 
-def test_sized_pfgru_reset_has_no_scratch(sized_pfgru_kernels):
-    hits = [k for k in sized_pfgru_kernels if "rs_pfgru_sized_reset_kernel" in k]
-    assert len(hits) == 1 and sized_pfgru_kernels[hits[0]]["scratch"] == 0
+def test_sized_pfgru_reset_has_no_scratch():
+    k = M.one(M.library_kernels(), "rs_pfgru_sized_reset_kernel")
+    assert k["scratch"] == 0, k
 
 
 def test_sized_pfgru_entry_points_check_their_arguments():

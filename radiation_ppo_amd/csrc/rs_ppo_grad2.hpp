@@ -119,8 +119,13 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         int o = 2 * sq + (l >> 5);
         w3tf[i] = (o < NOUT) ? prm.w3[o * RS_HID + 32 * it + (l & 31)] : 0.0f;
     }
+    // The output layer's weights.  Critic: [2 h][32 q] as in RsMlpLds.  Actor: the same values chunk-major, [8 b][2 h][8 o][4 j] with
+    // q = 4 b + j, because there every lane reads the row of an output of its own (A operand of the 4x4x1 chains): the 16 lanes a
+    // ds_read_b128 serves together read four different rows, which lie in four neighbouring 16-byte slots here (no bank conflict;
+    // 128-byte rows would put them two to a bank).
     for (int i = threadIdx.x; i < 2 * NOUT * 32; i += blockDim.x) {
-        const int q = i & 31, o = (i >> 5) % NOUT, hh = i / (32 * NOUT);
+        int q = i & 31, o = (i >> 5) % NOUT, hh = i / (32 * NOUT);
+        if constexpr (NOUT == 8) { q = 4 * (i >> 6) + (i & 3); o = (i >> 2) & 7; hh = (i >> 5) & 1; }
         W.w3h[i] = prm.w3[o * RS_HID + 32 * (q >> 4) + rs_kappa(q & 15, hh)];
     }
     for (int i = threadIdx.x; i < 64; i += blockDim.x) W.b2[i] = RS_TANH_PRESCALE * prm.b2[i];
@@ -295,9 +300,8 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
 #pragma unroll
             for (int r = 0; r < 16; ++r) H2[it][r] = rs_tanh_scaled(H2[it][r]);
         RS_STAMP(4);                                    // tanh 2
-        // output layer on the VALU: out[o] = sum over the 32 units this lane holds of W3[o][unit] * h2[unit], halves added across
-        // lane pairs.  Weights are broadcast float4 reads; they are fetched one batch (8 outputs x 4 units) ahead of the FMAs
-        // that use them so that the LDS latency is paid once, not per output (summation order per output unchanged: ascending unit)
+        // output layer: out[o] = sum over the 32 units this lane holds of W3[o][unit] * h2[unit] (one fmaf chain per output, ascending
+        // unit, from 0.0f), halves added across lane pairs.  Critic: on the VALU.  Actor: the same chains on the matrix pipe.
         float out[NOUT];
         if constexpr (NOUT == 1) {
             // one output: a single ascending-unit fmaf chain over the register-held weights, no prefetch rotation
@@ -307,41 +311,40 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
             const float q = rs_other_half(pacc, h);
             out[0] = (h ? (q + pacc) : (pacc + q)) + W.b3[0];
         } else {
-            float pacc[NOUT];
+            // Eight outputs: two chains of 32 v_mfma_f32_4x4x1_16b_f32, outputs 0..3 and 4..7.  K = 1, so a chain onto one accumulator
+            // is the ascending-unit fmaf chain from 0.0f in instruction order, subnormals kept.  Block b of an instruction is the outer
+            // product of A lanes 4b..4b+3 and B lanes 4b..4b+3, D[i][j] in register i of lane 4b + j; blocks 0..7 are the h = 0 lanes,
+            // 8..15 the h = 1 lanes.  B: the lane's own H2[kt][r]; A: lane l supplies W3[4 set + (l & 3)][32 kt + kappa(r, l >> 5)].
+            // Register i of chain `set` is then the partial logit of output 4 set + i over this lane's half of its own sample.
+            // The two chains alternate, each filling the other's wait states.
+            f32x4 pacc[2];
 #pragma unroll
-            for (int o = 0; o < NOUT; ++o) pacc[o] = 0.0f;
-            const float4* wrow = reinterpret_cast<const float4*>(W.w3h + h * NOUT * 32);      // [o][8 float4], 16-byte aligned rows
-            float4 wb[NOUT];
+            for (int r = 0; r < 4; ++r) { pacc[0][r] = 0.0f; pacc[1][r] = 0.0f; }
+            const float4* wrow = reinterpret_cast<const float4*>(W.w3h) + 8 * h + (lane & 3);     // [8 b][2 h][8 o] float4
+            float4 wv[8][2];
 #pragma unroll
-            for (int o = 0; o < NOUT; ++o) wb[o] = wrow[o * 8];
+            for (int b = 0; b < 8; ++b) { wv[b][0] = wrow[16 * b]; wv[b][1] = wrow[16 * b + 4]; }
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
                 const int kt = b >> 2, r4 = b & 3;
-                float4 wn[NOUT];
-#pragma unroll
-                for (int o = 0; o < NOUT; ++o) wn[o] = (b + 1 < 8) ? wrow[o * 8 + b + 1] : wb[o];
-#pragma unroll
-                for (int o = 0; o < NOUT; ++o) {
-                    pacc[o] = fmaf(wb[o].x, H2[kt][4 * r4 + 0], pacc[o]);
-                    pacc[o] = fmaf(wb[o].y, H2[kt][4 * r4 + 1], pacc[o]);
-                    pacc[o] = fmaf(wb[o].z, H2[kt][4 * r4 + 2], pacc[o]);
-                    pacc[o] = fmaf(wb[o].w, H2[kt][4 * r4 + 3], pacc[o]);
-                }
-                if (b + 1 < 8) {
-                    __builtin_amdgcn_sched_group_barrier(0x100, NOUT, 0);        // next batch's weight reads first ...
-                    __builtin_amdgcn_sched_group_barrier(0x002, 4 * NOUT, 0);    // ... then this batch's FMAs
-                }
-#pragma unroll
-                for (int o = 0; o < NOUT; ++o) wb[o] = wn[o];
+                pacc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[b][0].x, H2[kt][4 * r4 + 0], pacc[0], 0, 0, 0);
+                pacc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[b][1].x, H2[kt][4 * r4 + 0], pacc[1], 0, 0, 0);
+                pacc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[b][0].y, H2[kt][4 * r4 + 1], pacc[0], 0, 0, 0);
+                pacc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[b][1].y, H2[kt][4 * r4 + 1], pacc[1], 0, 0, 0);
+                pacc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[b][0].z, H2[kt][4 * r4 + 2], pacc[0], 0, 0, 0);
+                pacc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[b][1].z, H2[kt][4 * r4 + 2], pacc[1], 0, 0, 0);
+                pacc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[b][0].w, H2[kt][4 * r4 + 3], pacc[0], 0, 0, 0);
+                pacc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[b][1].w, H2[kt][4 * r4 + 3], pacc[1], 0, 0, 0);
             }
 #pragma unroll
             for (int o = 0; o < NOUT; ++o) {
                 // fixed summation order in both lanes: (half 0) + (half 1); the other half's value by one v_permlane32_swap
-                const float q = rs_other_half(pacc[o], h);
-                out[o] = (h ? (q + pacc[o]) : (pacc[o] + q)) + W.b3[o];
+                const float p = pacc[o >> 2][o & 3];
+                const float q = rs_other_half(p, h);
+                out[o] = (h ? (q + p) : (p + q)) + W.b3[o];
             }
         }
-        RS_STAMP(5);                                    // output layer (VALU)
+        RS_STAMP(5);                                    // output layer (critic: VALU, actor: 2 x 32 4x4x1 MFMAs)
         // ---------------- per-sample loss derivative (identical in both lanes of a sample) ----------------
         float dz[NOUT], sq[4];
         if (NOUT == 8) {

@@ -587,6 +587,152 @@ __device__ __forceinline__ unsigned long long rs_es_now() {
 #define RS_ESTAMP(i) do {} while (0)
 #endif
 
+// The state one lock-step reads and writes, as values: what the env arrays hold for env n (RsEnvRegs) and for one of its agents
+// (RsAgentRegs).  rs_env_step_lane loads them, runs the core and stores them; K6 (rs_rollout16.hpp, single agent) keeps them in
+// registers from one lock-step to the next and touches the arrays only around a reset and at the end of the launch.
+struct RsEnvRegs {
+    int sx, sy, intensity, bkg, iter_count;
+    uint32_t episode, tstep, err;      // episode: the id the draws of this episode are keyed by (the array holds the NEXT id); err: flags not yet OR-ed into P.err
+    bool done;
+    __device__ __forceinline__ void load(const RsParams& P, int n) {
+        sx = P.src_x[n]; sy = P.src_y[n];
+        intensity = P.intensity[n]; bkg = P.bkg[n];
+        iter_count = P.iter_count[n];
+        episode = P.episode[n] - 1u; tstep = P.tstep[n];
+        err = 0;
+        done = P.done[n] != 0;
+    }
+    // what a step changes (the per-episode constants are written by the reset alone)
+    __device__ __forceinline__ void store(const RsParams& P, int n) {
+        P.done[n] = done ? 1 : 0;
+        P.iter_count[n] = iter_count;
+        P.tstep[n] = tstep;
+        if (err) P.err[n] |= err;
+        err = 0;
+    }
+};
+struct RsAgentRegs {
+    int x, y, oobc;
+    double sp, prev;
+    uint8_t fl;
+    __device__ __forceinline__ void load(const RsParams& P, size_t ia) {
+        x = P.ax[ia]; y = P.ay[ia]; sp = P.sp[ia]; prev = P.prev[ia]; oobc = P.oobc[ia]; fl = P.aflags[ia];
+    }
+    __device__ __forceinline__ void store(const RsParams& P, size_t ia) const {
+        P.ax[ia] = x; P.ay[ia] = y; P.sp[ia] = sp; P.prev[ia] = prev; P.oobc[ia] = oobc; P.aflags[ia] = fl;
+    }
+};
+
+#ifdef RS_STEP_STAMPS
+#define RS_ESTAMP_PARAM , unsigned long long& es_last
+#define RS_ESTAMP_ARG , es_last
+#else
+#define RS_ESTAMP_PARAM
+#define RS_ESTAMP_ARG
+#endif
+
+// Agent a's part of RadSearch.step on values: take_action, distances, measurement, reward, observation row and the lock-step's
+// outputs.  E is read (done is also set); S is the agent's state before and after.  No env array is touched.
+// CN > 1: the cooperative form (see rs_grp_any): lanes cj = 0..CN-1 of a group call this with the same arguments.
+template <bool HAS_OBS, int CN = 1>
+__device__ __forceinline__ void rs_agent_step_core(const RsParams& P, const RsGeo& g, int n, int a, int act, bool collided, RsEnvRegs& E,
+                                                   RsAgentRegs& S, const RsOut& O, double& max_reward, bool& have_max, int cj RS_ESTAMP_PARAM) {
+    const int N = P.N, A = P.A;
+    const int sx = E.sx, sy = E.sy, intensity = E.intensity, bkg = E.bkg;
+    const uint32_t episode = E.episode, t = E.tstep;
+    const uint32_t k0 = P.seed, k1 = P.env_id_base + (uint32_t)n;
+    uint32_t err = 0;
+    bool done = E.done;
+    if (act < 0) act = RS_IDLE;                             // -1 == idle (:620-623)
+    if (act > RS_ACT_NONE) { err |= RS_ENVERR_BAD_ACTION; act = RS_IDLE; }
+    int x = S.x, y = S.y;
+    double sp = S.sp, prev = S.prev;
+    int oobc = S.oobc;
+    uint8_t fl = S.fl & (RS_AF_BLOCKED | RS_AF_INTERSECT);   // oob/collision reset each step (:479-480)
+    bool moved = false;
+    int px = x, py = y;                                      // agent.detector after take_action
+    // ---- take_action :876-946
+    if (act != RS_ACT_NONE) {
+        if (collided) {
+            fl |= RS_AF_COLLISION;
+        } else {
+            int dx, dy; rs_action_step(act, dx, dy);
+            int tx = x + dx, ty = y + dy;
+            bool roll_back = false;
+            if (P.enforce) {
+                if ((tx < P.bx0 || ty < P.by0) || (P.bx1 <= tx || P.by1 <= ty)) { fl |= RS_AF_OOB; oobc += 1; roll_back = true; }
+            } else {
+                bool lower_b = x < P.sa_x0 || y < P.sa_y0, upper_b = P.sa_x1 < x || P.sa_y1 < y;
+                if (lower_b || upper_b) { fl |= RS_AF_OOB; oobc += 1; }
+            }
+            if (HAS_OBS && g.n > 0 && rs_in_obstruction(g, tx, ty)) { roll_back = true; fl |= RS_AF_BLOCKED; }
+            if (!roll_back) { x = tx; y = ty; px = tx; py = ty; moved = true; }
+        }
+    }
+    RS_ESTAMP(1);                                            // take_action, in_obstruction
+    // ---- distances, line of sight, measurement, reward :486-567
+    double euc = rs_dist_i(x, y, sx, sy);                   // == the stale euc_dist when stalled (position unchanged)
+    double reward;
+#if defined(RS_ABL) && RS_ABL == 3
+    if (moved) sp = euc;
+#else
+    if (moved) sp = (HAS_OBS && g.n > 0) ? rs_shortest_path<CN>(g, P.dsrc, N, n, sx, sy, x, y, cj) : euc;
+#endif
+    if (HAS_OBS && !(sp < INFINITY)) err |= RS_ENVERR_NO_PATH;
+    RS_ESTAMP(2);                                            // shortest path
+#if defined(RS_ABL) && RS_ABL == 2
+    bool inter = false;
+#else
+    bool inter = (HAS_OBS && g.n > 0) ? rs_is_intersect<CN>(g, px, py, sx, sy, euc, sp, cj) : false;
+#endif
+    fl = (uint8_t)((fl & ~RS_AF_INTERSECT) | (inter ? RS_AF_INTERSECT : 0));
+    RS_ESTAMP(3);                                            // is_intersect
+    double lam;
+    if (inter) lam = (double)bkg;
+    else {
+        double r = euc;
+        if (r == 0.0) { err |= RS_ENVERR_ZERO_DIST; r = 1.0; }
+        lam = (P.falloff ? ((double)intensity / (r * r)) : ((double)intensity / r)) + (double)bkg;
+    }
+    int64_t meas = rs_poisson(lam, t, episode, RS_STREAM_STEP + (uint32_t)a, k0, k1);
+    RS_ESTAMP(4);                                            // Poisson measurement
+    if (moved) {
+        if (sp < 110.0) { reward = 0.1; done = true; }
+        else if (sp < prev) { reward = 0.1; prev = sp; }
+        else reward = ((act == RS_IDLE) ? -1.0 : -0.5) * sp / P.max_dist;
+    } else {
+        if (act == RS_IDLE && !(fl & RS_AF_COLLISION)) err |= RS_ENVERR_IDLE_STALL;
+        reward = -0.5 * sp / P.max_dist;
+    }
+    reward = rs_round2(reward);
+    // ---- observation :570-593
+    float* row = O.obs_row + a * RS_OBS_DIM;
+    row[0] = (float)(double)meas;
+    double nx = 0.0, ny = 0.0;
+    if (P.coord_noise) { const RsNoise2 nz = rs_coord_noise(t, episode, (uint32_t)a, k0, k1); nx = nz.x; ny = nz.y; }
+    row[1] = (float)(((double)x + nx) * P.scale);
+    row[2] = (float)(((double)y + ny) * P.scale);
+    RS_ESTAMP(5);                                            // reward, observation head
+    if ((HAS_OBS && g.n > 0) || P.enforce) rs_sensors<HAS_OBS, CN>(P, g, px, py, row + 3, err, cj);
+    else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) row[3 + i] = 0.0f;
+    }
+    RS_ESTAMP(6);                                            // obstruction sensors
+    // ---- team reward with the falsy-reset quirk :662-665
+    if (!have_max || max_reward == 0.0) { max_reward = reward; have_max = true; }
+    else if (max_reward < reward) max_reward = reward;
+    S.x = x; S.y = y; S.sp = sp; S.prev = prev; S.oobc = oobc; S.fl = fl;
+    E.done = done; E.err |= err;
+    const size_t oa = (size_t)n * A + a;
+    if (O.reward) O.reward[oa] = (float)reward;
+    if (O.done) O.done[oa] = done ? 1 : 0;
+    if (O.oob) O.oob[oa] = (fl & RS_AF_OOB) ? 1 : 0;
+    if (O.oobc) O.oobc[oa] = oobc;
+    if (O.blocked) O.blocked[oa] = (fl & RS_AF_BLOCKED) ? 1 : 0;
+    if (O.collision) O.collision[oa] = (fl & RS_AF_COLLISION) ? 1 : 0;
+}
+
 // CN > 1: the cooperative form (see rs_grp_any): lanes cj = 0..CN-1 of a group call this with the same n, g, actions and O.
 // Every lane of the group stores the (identical) results: duplicate addresses inside one store instruction cost nothing,
 // and each lane's later loads of the env state are then ordered after its OWN stores, which the language guarantees.
@@ -595,13 +741,8 @@ __device__ __forceinline__ void rs_env_step_lane(const RsParams& P, const RsGeo&
                                                  bool no_collision_rule = false, int cj = 0) {
     const int N = P.N, A = P.A;
     RS_ESTAMP_DECL
-    const int sx = P.src_x[n], sy = P.src_y[n];
-    const int intensity = P.intensity[n], bkg = P.bkg[n];
-    int iter_count = P.iter_count[n];
-    const uint32_t episode = P.episode[n] - 1u, t = P.tstep[n];   // episode[] holds the NEXT episode id
-    uint32_t err = 0;
-    bool done = P.done[n] != 0;
-    const uint32_t k0 = P.seed, k1 = P.env_id_base + (uint32_t)n;
+    RsEnvRegs E;
+    E.load(P, n);
 
     // collision rule (:908-910): an agent stalls when >1 agents propose its tentative cell.  Proposals
     // are functions of the pre-step positions only, so they are evaluated up front.
@@ -626,101 +767,15 @@ __device__ __forceinline__ void rs_env_step_lane(const RsParams& P, const RsGeo&
     RS_ESTAMP(0);                                            // state loads, collision proposals
     for (int a = 0; a < A; ++a) {
         const size_t ia = (size_t)a * N + n;
-        int act = act_of(a);
-        if (act < 0) act = RS_IDLE;                         // -1 == idle (:620-623)
-        if (act > RS_ACT_NONE) { err |= RS_ENVERR_BAD_ACTION; act = RS_IDLE; }
-        int x = P.ax[ia], y = P.ay[ia];
-        double sp = P.sp[ia], prev = P.prev[ia];
-        int oobc = P.oobc[ia];
-        uint8_t fl = P.aflags[ia] & (RS_AF_BLOCKED | RS_AF_INTERSECT);   // oob/collision reset each step (:479-480)
-        bool moved = false;
-        int px = x, py = y;                                  // agent.detector after take_action
-        // ---- take_action :876-946
-        if (act != RS_ACT_NONE) {
-            if (coll_mask >> a & 1u) {
-                fl |= RS_AF_COLLISION;
-            } else {
-                int dx, dy; rs_action_step(act, dx, dy);
-                int tx = x + dx, ty = y + dy;
-                bool roll_back = false;
-                if (P.enforce) {
-                    if ((tx < P.bx0 || ty < P.by0) || (P.bx1 <= tx || P.by1 <= ty)) { fl |= RS_AF_OOB; oobc += 1; roll_back = true; }
-                } else {
-                    bool lower_b = x < P.sa_x0 || y < P.sa_y0, upper_b = P.sa_x1 < x || P.sa_y1 < y;
-                    if (lower_b || upper_b) { fl |= RS_AF_OOB; oobc += 1; }
-                }
-                if (HAS_OBS && g.n > 0 && rs_in_obstruction(g, tx, ty)) { roll_back = true; fl |= RS_AF_BLOCKED; }
-                if (!roll_back) { x = tx; y = ty; px = tx; py = ty; moved = true; }
-            }
-        }
-        RS_ESTAMP(1);                                        // take_action, in_obstruction
-        // ---- distances, line of sight, measurement, reward :486-567
-        double euc = rs_dist_i(x, y, sx, sy);               // == the stale euc_dist when stalled (position unchanged)
-        double reward;
-#if defined(RS_ABL) && RS_ABL == 3
-        if (moved) sp = euc;
-#else
-        if (moved) sp = (HAS_OBS && g.n > 0) ? rs_shortest_path<CN>(g, P.dsrc, N, n, sx, sy, x, y, cj) : euc;
-#endif
-        if (HAS_OBS && !(sp < INFINITY)) err |= RS_ENVERR_NO_PATH;
-        RS_ESTAMP(2);                                        // shortest path
-#if defined(RS_ABL) && RS_ABL == 2
-        bool inter = false;
-#else
-        bool inter = (HAS_OBS && g.n > 0) ? rs_is_intersect<CN>(g, px, py, sx, sy, euc, sp, cj) : false;
-#endif
-        fl = (uint8_t)((fl & ~RS_AF_INTERSECT) | (inter ? RS_AF_INTERSECT : 0));
-        RS_ESTAMP(3);                                        // is_intersect
-        double lam;
-        if (inter) lam = (double)bkg;
-        else {
-            double r = euc;
-            if (r == 0.0) { err |= RS_ENVERR_ZERO_DIST; r = 1.0; }
-            lam = (P.falloff ? ((double)intensity / (r * r)) : ((double)intensity / r)) + (double)bkg;
-        }
-        int64_t meas = rs_poisson(lam, t, episode, RS_STREAM_STEP + (uint32_t)a, k0, k1);
-        RS_ESTAMP(4);                                        // Poisson measurement
-        if (moved) {
-            if (sp < 110.0) { reward = 0.1; done = true; }
-            else if (sp < prev) { reward = 0.1; prev = sp; }
-            else reward = ((act == RS_IDLE) ? -1.0 : -0.5) * sp / P.max_dist;
-        } else {
-            if (act == RS_IDLE && !(fl & RS_AF_COLLISION)) err |= RS_ENVERR_IDLE_STALL;
-            reward = -0.5 * sp / P.max_dist;
-        }
-        reward = rs_round2(reward);
-        // ---- observation :570-593
-        float* row = O.obs_row + a * RS_OBS_DIM;
-        row[0] = (float)(double)meas;
-        double nx = 0.0, ny = 0.0;
-        if (P.coord_noise) { const RsNoise2 nz = rs_coord_noise(t, episode, (uint32_t)a, k0, k1); nx = nz.x; ny = nz.y; }
-        row[1] = (float)(((double)x + nx) * P.scale);
-        row[2] = (float)(((double)y + ny) * P.scale);
-        RS_ESTAMP(5);                                        // reward, observation head
-        if ((HAS_OBS && g.n > 0) || P.enforce) rs_sensors<HAS_OBS, CN>(P, g, px, py, row + 3, err, cj);
-        else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) row[3 + i] = 0.0f;
-        }
-        RS_ESTAMP(6);                                        // obstruction sensors
-        // ---- team reward with the falsy-reset quirk :662-665
-        if (!have_max || max_reward == 0.0) { max_reward = reward; have_max = true; }
-        else if (max_reward < reward) max_reward = reward;
-        // ---- write back
-        P.ax[ia] = x; P.ay[ia] = y; P.sp[ia] = sp; P.prev[ia] = prev; P.oobc[ia] = oobc; P.aflags[ia] = fl;
-        const size_t oa = (size_t)n * A + a;
-        if (O.reward) O.reward[oa] = (float)reward;
-        if (O.done) O.done[oa] = done ? 1 : 0;
-        if (O.oob) O.oob[oa] = (fl & RS_AF_OOB) ? 1 : 0;
-        if (O.oobc) O.oobc[oa] = oobc;
-        if (O.blocked) O.blocked[oa] = (fl & RS_AF_BLOCKED) ? 1 : 0;
-        if (O.collision) O.collision[oa] = (fl & RS_AF_COLLISION) ? 1 : 0;
+        RsAgentRegs S;
+        S.load(P, ia);
+        rs_agent_step_core<HAS_OBS, CN>(P, g, n, a, act_of(a), (coll_mask >> a & 1u) != 0, E, S, O, max_reward, have_max, cj RS_ESTAMP_ARG);
+        S.store(P, ia);
     }
     if (O.team) O.team[n] = (float)max_reward;
-    P.done[n] = done ? 1 : 0;
-    P.iter_count[n] = iter_count + 1;
-    P.tstep[n] = t + 1;
-    if (err) P.err[n] |= err;
+    E.iter_count += 1;
+    E.tstep += 1;
+    E.store(P, n);
     RS_ESTAMP(7);                                            // write back
 }
 

@@ -410,6 +410,19 @@ int rs_debug_k7_stamps(unsigned long long* out, int clear) {
 }
 #endif
 
+#ifdef RS_K6_STAMPS
+// diagnostic build only: read (and optionally clear) the phase-cycle table of rs_rollout16_kernel; out[2][16], row 1 = obstacle template
+int rs_debug_k6_stamps(unsigned long long* out, int clear) {
+    if (hipDeviceSynchronize() != hipSuccess) return RS_ERR_HIP;
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(rs_k6_stamp_table), sizeof(unsigned long long) * 2 * RS_K6_NPH) != hipSuccess) return RS_ERR_HIP;
+    if (clear) {
+        unsigned long long z[2 * RS_K6_NPH] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(rs_k6_stamp_table), z, sizeof(z)) != hipSuccess) return RS_ERR_HIP;
+    }
+    return RS_OK;
+}
+#endif
+
 int rs_policy_forward(const rs_mlp_params* actor, const rs_mlp_params* critic, const float* x, int32_t M,
                       float* logits, float* value, rs_stream_t stream) {
     if (!actor || !critic || !x || M < 1) return RS_ERR_INVALID_ARG;

@@ -18,6 +18,12 @@
 // before) evaluates the critic on the observations wave 0 leaves in an LDS mailbox -- the pre-reset one for the bootstrap value, the
 // post-reset one for the envs that were cut -- and writes val / last_val itself.  One workgroup barrier per lock-step, mailbox double
 // buffered (wave 0 runs a step ahead).  With the critic skipped outright the lock-step took 7.6 instead of 9.6 us: that is the bound.
+//
+// Wave 0's chain itself (round 10): what is constant for the launch or only changes in the wave's own registers does not go through
+// memory in every lock-step.  The actor's MFMA operands are read from LDS once (RsMlp16::Regs; the template without obstacles, which
+// has the registers), its output layer runs as two 4x4x1 MFMA chains like K7's, and the env state stays in registers between the
+// lock-steps (RsEnvRegs / RsAgentRegs, rs_agent_step_core); the env arrays are written and re-read around a reset only.  Buffers,
+// env arrays and carried state keep their bits (tests/test_k6_chain_bits_gpu.py).
 #pragma once
 #include "rs_mlp.hpp"
 
@@ -52,20 +58,58 @@ struct RsMlp16 {
         }
         for (int i = tid; i < NOUT; i += nt) b3[i] = p.b3[i];
     }
-    // forward for the wave's 16 samples; xs[k] = input k of sample (lane&15), already broadcast to the 4 lanes
-    __device__ __forceinline__ void forward(const float (&xs)[RS_IN_PAD], float (&out)[NOUT]) const {
+    // The operands of forward() that belong to this lane, read once: they are constant for a launch.  K6's wave 0 keeps the actor's
+    // in registers for all its lock-steps (walls-off / no-obstacle template: 124 of the 512 registers a lone wave of a SIMD may use)
+    // instead of reading them from LDS in every lock-step, where each read and its wait is an issue slot of the serial chain.
+    struct Regs {
+        float w1[4 * 3], w2[4 * 16], b2[4 * 4];
+        float w3[2][16];      // NOUT == 8: A operands of the output layer's two 4x4x1 chains, W3[4 set + (l & 3)][16 ut + 4 g + q] at [set][4 ut + q]
+    };
+    __device__ __forceinline__ void load_w3(float (&w3)[2][16]) const {
         const int lane = threadIdx.x & 63, g = lane >> 4;
-        f32x4 H1[4], H2[4];
+#pragma unroll
+        for (int set = 0; set < 2; ++set) {
+            const float4* w = reinterpret_cast<const float4*>(w3g + (g * NOUT + 4 * set + (lane & 3)) * 16);
+#pragma unroll
+            for (int ut = 0; ut < 4; ++ut) {
+                const float4 wv = w[ut];
+                w3[set][4 * ut + 0] = wv.x; w3[set][4 * ut + 1] = wv.y; w3[set][4 * ut + 2] = wv.z; w3[set][4 * ut + 3] = wv.w;
+            }
+        }
+    }
+    // The MFMA A operands are parked in accumulation registers, which the matrix instructions read directly: left to itself the
+    // register allocator keeps them among the 256 architectural VGPRs, where the env step's float64 chains need the room.
+    static __device__ __forceinline__ float park(float v) { float a; asm("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v)); return a; }
+    __device__ __forceinline__ void load(Regs& r) const {
+        const int lane = threadIdx.x & 63, g = lane >> 4;
+#pragma unroll
+        for (int i = 0; i < 4 * 3; ++i) r.w1[i] = park(w1f[i * 64 + lane]);
+#pragma unroll
+        for (int i = 0; i < 4 * 16; ++i) r.w2[i] = park(w2f[i * 64 + lane]);
+#pragma unroll
+        for (int i = 0; i < 4 * 4; ++i) r.b2[i] = b2[16 * (i >> 2) + 4 * g + (i & 3)];
+        if constexpr (NOUT == 8) {
+            load_w3(r.w3);
+#pragma unroll
+            for (int i = 0; i < 32; ++i) r.w3[i >> 4][i & 15] = park(r.w3[i >> 4][i & 15]);
+        }
+    }
+    // the two hidden layers for the wave's 16 samples; xs[k] = input k of sample (lane&15), already broadcast to the 4 lanes.
+    // REG: operands from r (see Regs), else from LDS.
+    template <bool REG>
+    __device__ __forceinline__ void hidden(const float (&xs)[RS_IN_PAD], f32x4 (&H2)[4], const Regs& r) const {
+        const int lane = threadIdx.x & 63, g = lane >> 4;
+        f32x4 H1[4];
 #pragma unroll
         for (int it = 0; it < 4; ++it)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { H1[it][q] = 0.0f; H2[it][q] = b2[16 * it + 4 * g + q]; }
+            for (int q = 0; q < 4; ++q) { H1[it][q] = 0.0f; H2[it][q] = REG ? r.b2[4 * it + q] : b2[16 * it + 4 * g + q]; }
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
             const float b = (g == 0) ? xs[4 * s] : (g == 1) ? xs[4 * s + 1] : (g == 2) ? xs[4 * s + 2] : xs[4 * s + 3];
 #pragma unroll
             for (int it = 0; it < 4; ++it)
-                H1[it] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1f[(it * 3 + s) * 64 + lane], b, H1[it], 0, 0, 0);
+                H1[it] = __builtin_amdgcn_mfma_f32_16x16x4f32(REG ? r.w1[it * 3 + s] : w1f[(it * 3 + s) * 64 + lane], b, H1[it], 0, 0, 0);
         }
 #pragma unroll
         for (int it = 0; it < 4; ++it)
@@ -76,12 +120,25 @@ struct RsMlp16 {
             const float b = H1[ks >> 2][ks & 3];
 #pragma unroll
             for (int it = 0; it < 4; ++it)
-                H2[it] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2f[(it * 16 + ks) * 64 + lane], b, H2[it], 0, 0, 0);
+                H2[it] = __builtin_amdgcn_mfma_f32_16x16x4f32(REG ? r.w2[it * 16 + ks] : w2f[(it * 16 + ks) * 64 + lane], b, H2[it], 0, 0, 0);
         }
 #pragma unroll
         for (int it = 0; it < 4; ++it)
 #pragma unroll
             for (int q = 0; q < 4; ++q) H2[it][q] = rs_tanh_scaled(H2[it][q]);
+    }
+    // fixed-order tree over the four lanes of the sample: (g0 + g1) + (g2 + g3) in every lane, then the bias
+    __device__ __forceinline__ float combine(float p, int o) const {
+        const int g = (threadIdx.x & 63) >> 4;
+        const float q1 = __shfl_xor(p, 16);
+        const float s01 = (g & 1) ? (q1 + p) : (p + q1);
+        const float q2 = __shfl_xor(s01, 32);
+        return ((g & 2) ? (q2 + s01) : (s01 + q2)) + b3[o];
+    }
+    // output layer: out[o] = tree over g of the lane's partial sum p = sum over (ut, q) of W3[o][16 ut + 4 g + q] * H2[ut][q], one
+    // fmaf chain per output in the order ut = 0..3, q = 0..3 from 0.0f
+    __device__ __forceinline__ void output(const f32x4 (&H2)[4], float (&out)[NOUT]) const {
+        const int g = (threadIdx.x & 63) >> 4;
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) {
             const float4* w = reinterpret_cast<const float4*>(w3g + (g * NOUT + o) * 16);
@@ -92,12 +149,35 @@ struct RsMlp16 {
                 p = fmaf(wv.x, H2[ut][0], p); p = fmaf(wv.y, H2[ut][1], p);
                 p = fmaf(wv.z, H2[ut][2], p); p = fmaf(wv.w, H2[ut][3], p);
             }
-            // fixed-order tree over the four lanes of the sample: (g0 + g1) + (g2 + g3) in every lane
-            const float q1 = __shfl_xor(p, 16);
-            const float s01 = (g & 1) ? (q1 + p) : (p + q1);
-            const float q2 = __shfl_xor(s01, 32);
-            out[o] = ((g & 2) ? (q2 + s01) : (s01 + q2)) + b3[o];
+            out[o] = combine(p, o);
         }
+    }
+    // The same chains on the matrix pipe (NOUT == 8), as in K7's actor pass (rs_ppo_grad2.hpp): two alternating chains of 16
+    // v_mfma_f32_4x4x1_16b_f32, outputs 0..3 and 4..7.  K = 1, so a chain onto one accumulator is the fmaf chain above in
+    // instruction order (scripts/micro/mfma4_chain_bits.hip: the same words, subnormals, NaN and -0 included).  Block b of an
+    // instruction is the outer product of A lanes 4b..4b+3 and B lanes 4b..4b+3, D[i][j] in register i of lane 4b + j; the four lanes
+    // of a block share g.  B: the lane's own H2[ut][q]; A: lane l supplies W3[4 set + (l & 3)][16 ut + 4 g + q] (w3[set][4 ut + q]).
+    // Register i of chain `set` is then p of output 4 set + i for this lane's sample.
+    __device__ __forceinline__ void output_mfma(const f32x4 (&H2)[4], float (&out)[NOUT], const float (&w3)[2][16]) const {
+        static_assert(NOUT == 8, "two chains of four outputs");
+        f32x4 pacc[2];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { pacc[0][i] = 0.0f; pacc[1][i] = 0.0f; }
+#pragma unroll
+        for (int ut = 0; ut < 4; ++ut)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                pacc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(w3[0][4 * ut + q], H2[ut][q], pacc[0], 0, 0, 0);
+                pacc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(w3[1][4 * ut + q], H2[ut][q], pacc[1], 0, 0, 0);
+            }
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o) out[o] = combine(pacc[o >> 2][o & 3], o);
+    }
+    __device__ __forceinline__ void forward(const float (&xs)[RS_IN_PAD], float (&out)[NOUT]) const {
+        f32x4 H2[4];
+        Regs none;
+        hidden<false>(xs, H2, none);
+        output(H2, out);
     }
 };
 
@@ -110,6 +190,42 @@ __device__ __forceinline__ void rs_bcast_x16(const float (&xo)[RS_IN_PAD], float
 
 constexpr int RS_MB_PRE = 0, RS_MB_POST = 16 * RS_IN_PAD, RS_MB_FLAGS = 2 * 16 * RS_IN_PAD, RS_MB_SLOT = 2 * 16 * RS_IN_PAD + 16;   // words
 __host__ __device__ constexpr int rs_rollout16_mailbox_bytes() { return 2 * RS_MB_SLOT * 4; }
+
+// What wave 0 keeps out of its lock-step chain (RS_K6_PARENT_CHAIN: A/B switch, the chain as it was before).  The obstacle template
+// sits at the register limit already; it takes what adds no spill.
+#ifdef RS_K6_PARENT_CHAIN
+constexpr bool RS_K6_SHORT = false;
+#else
+constexpr bool RS_K6_SHORT = true;
+#endif
+template <bool HAS_OBS> struct RsK6Cfg {
+    static constexpr bool reg_weights = RS_K6_SHORT && !HAS_OBS;     // actor operands in registers for the launch (RsMlp16::Regs)
+    static constexpr bool mfma_out = RS_K6_SHORT;                    // actor output layer on 4x4x1 MFMA chains
+    static constexpr bool reg_state = RS_K6_SHORT;                   // env state in registers across the lock-steps (RsEnvRegs / RsAgentRegs)
+};
+
+// Diagnostic build only (-DRS_K6_STAMPS, scripts/k6_stamps.py): s_memtime stamps at the phase boundaries of wave 0's lock-step,
+// summed per wave in scalar registers and added (lane 0, plain vector atomics) to a table no other code reads.  Slot 14 holds the
+// launch's 100 MHz ticks, slot 15 the lock-steps counted.  The product build contains none of it.
+#ifdef RS_K6_STAMPS
+#define RS_K6_NPH 16
+__device__ unsigned long long rs_k6_stamp_table[2][RS_K6_NPH];
+__device__ __forceinline__ unsigned long long rs_k6_now() {
+    unsigned long long t;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    return t;
+}
+#define RS_K6STAMP_DECL unsigned long long k6_acc[RS_K6_NPH] = {0}; const unsigned long long k6_rt0 = __builtin_amdgcn_s_memrealtime(); \
+                        unsigned long long k6_last = rs_k6_now();
+#define RS_K6STAMP(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = rs_k6_now(); k6_acc[i] += t_ - k6_last; k6_last = t_; \
+                           __builtin_amdgcn_sched_barrier(0); } while (0)
+#define RS_K6STAMP_EXIT(tmpl, steps) do { if ((threadIdx.x & 63) == 0) { k6_acc[14] = __builtin_amdgcn_s_memrealtime() - k6_rt0; k6_acc[15] = (steps); \
+                           for (int q = 0; q < RS_K6_NPH; ++q) atomicAdd(&rs_k6_stamp_table[tmpl][q], k6_acc[q]); } } while (0)
+#else
+#define RS_K6STAMP_DECL
+#define RS_K6STAMP(i) do {} while (0)
+#define RS_K6STAMP_EXIT(tmpl, steps) do {} while (0)
+#endif
 
 template <bool HAS_OBS>
 __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpParams pa, RsMlpParams pc, rs_rollout_args R) {
@@ -184,10 +300,18 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
     double ep_ret_sum = 0.0, ep_len_sum = 0.0, ep_ret_sq = 0.0;
     float ep_ret_max = -INFINITY, ep_ret_min = INFINITY;
     const uint32_t k0 = P.seed, k1 = P.env_id_base + (uint32_t)n;
-    // per-episode constants and the step counter the sampler's Philox counter needs are mirrored in registers (re-read after a
-    // reset only): a global load per lock-step is a full memory latency for the lone wave of a SIMD
-    uint32_t ep_key = P.episode[n] - 1u, t_key = P.tstep[n];
-    float srcx = (float)P.src_x[n], srcy = (float)P.src_y[n];
+    // The env's state lives in registers for the whole launch (every lane of wave 0 holds the copy of env slot j; the lanes that
+    // step it compute identical results): a global load per lock-step is a full memory latency for the lone wave of a SIMD.  The
+    // env arrays are written before a reset, which works on them, re-read after it, and written at the end of the launch.
+    // Without Cfg::reg_state the step goes through the arrays (rs_env_step_lane) and E only mirrors what the sampler's Philox
+    // counter and the source target need.
+    using Cfg = RsK6Cfg<HAS_OBS>;
+    RsEnvRegs E;
+    RsAgentRegs S;
+    E.load(P, n);
+    S.load(P, (size_t)n);                                         // single agent: row 0
+    RsMlp16<8>::Regs AR;
+    if constexpr (Cfg::reg_weights) ACT.load(AR);
 
     float xo[RS_IN_PAD], xs[RS_IN_PAD];
 #pragma unroll
@@ -213,11 +337,20 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
     O.oob = lds_oob + j - (size_t)n;
     O.oobc = nullptr; O.blocked = nullptr; O.collision = nullptr;
 
+    RS_K6STAMP_DECL
     for (int t = 0; t < T; ++t) {
         const size_t row = (size_t)t * N + n;
         float* M = mbox + (t & 1) * RS_MB_SLOT;
         float lg[8];
-        ACT.forward(xs, lg);
+        {
+            f32x4 H2[4];
+            ACT.template hidden<Cfg::reg_weights>(xs, H2, AR);
+            RS_K6STAMP(0);                                       // hidden layers
+            if constexpr (!Cfg::mfma_out) ACT.output(H2, lg);
+            else if constexpr (Cfg::reg_weights) ACT.output_mfma(H2, lg, AR.w3);
+            else { float w3[2][16]; ACT.load_w3(w3); ACT.output_mfma(H2, lg, w3); }
+            RS_K6STAMP(1);                                       // output layer
+        }
         int a = 0;
         float logp = 0.0f;
         if (own) {
@@ -228,7 +361,7 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
 #pragma unroll
             for (int q = 0; q < 8; ++q) se += __expf(lg[q] - mx);
             const float lse = __logf(se);
-            const uint32_t episode = ep_key, tenv = t_key;
+            const uint32_t episode = E.episode, tenv = E.tstep;
             u32x4 ph = philox4x32_10(0u, tenv, episode, RS_STREAM_ACT, k0, k1);
             const float u = (float)(ph.x >> 8) * (1.0f / 16777216.0f);
             float cdf = 0.0f;
@@ -244,6 +377,7 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
             for (int k = 0; k < RS_OBS_DIM; ++k) tile[lane * RS_OBS_DIM + k] = xo[k];
         }
         __builtin_amdgcn_wave_barrier();                         // (one wave: its LDS operations are ordered; this only pins the compiler)
+        RS_K6STAMP(2);                                           // softmax + draw
         {
             float* dst = R.obs + ((size_t)t * N + (size_t)blockIdx.x * 16) * RS_OBS_DIM;
             for (int i = lane; i < 16 * RS_OBS_DIM; i += RS_WAVE) dst[i] = tile[i];
@@ -254,15 +388,26 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
         if (own) {
             R.act[row] = (int64_t)a;
             R.logp[row] = logp;
-            R.source_tar[row * 2 + 0] = srcx;
-            R.source_tar[row * 2 + 1] = srcy;
+            R.source_tar[row * 2 + 0] = (float)E.sx;
+            R.source_tar[row * 2 + 1] = (float)E.sy;
         }
-        if (HAS_OBS) {
-            const int a_env = __shfl(a, j);
-            rs_env_step_lane<true, 4>(P, g, n, [&](int) -> int { return a_env; }, O, false, cj);
-        } else if (own) {
-            rs_env_step_lane<false>(P, g, n, [&](int) -> int { return a; }, O);
+        RS_K6STAMP(3);                                           // buffer stores
+        if (HAS_OBS || own) {
+            const int a_env = HAS_OBS ? __shfl(a, j) : a;
+            if constexpr (Cfg::reg_state) {
+                double max_reward = 0.0;
+                bool have_max = false;
+#ifdef RS_STEP_STAMPS
+                RS_ESTAMP_DECL
+#endif
+                rs_agent_step_core<HAS_OBS, HAS_OBS ? 4 : 1>(P, g, n, 0, a_env, false, E, S, O, max_reward, have_max, cj RS_ESTAMP_ARG);
+            } else {
+                rs_env_step_lane<HAS_OBS, HAS_OBS ? 4 : 1>(P, g, n, [&](int) -> int { return a_env; }, O, false, cj);
+            }
+            E.iter_count += 1;
+            E.tstep += 1;                                        // the env advanced its step counter
         }
+        RS_K6STAMP(4);                                           // env step
         if (own) {
             const float r = lds_rew[lane];
             const bool terminal = lds_done[lane] != 0;
@@ -270,7 +415,6 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
             R.rew[row] = r;
             ep_ret += r;
             steps += 1;
-            t_key += 1u;                                         // the env advanced its step counter (rs_env_step_lane)
             done_count += terminal ? 1 : 0;
             const bool timeout = steps == L;
             over = terminal || timeout;
@@ -293,14 +437,14 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
                 ep_ret_max = fmaxf(ep_ret_max, ep_ret); ep_ret_min = fminf(ep_ret_min, ep_ret);
             }
         }
-        if (HAS_OBS) {
-            if (__shfl((int)cut, j) != 0) {                      // the env's four lanes reset it together
-                if (ended) P.epoch_end[n] = 1;
-                rs_env_reset_lane<true, 4>(P, g, n, lds_geo, lds_adj, lds_d, tile + j * RS_OBS_DIM, O, j, cj);
-            }
-        } else if (cut) {
+        RS_K6STAMP(5);                                           // Welford + mailbox message
+        if (HAS_OBS ? (__shfl((int)cut, j) != 0) : cut) {        // obstacles: the env's four lanes reset it together
             if (ended) P.epoch_end[n] = 1;
-            rs_env_reset_lane<false>(P, g, n, lds_geo, lds_adj, lds_d, tile + lane * RS_OBS_DIM, O);
+            if constexpr (Cfg::reg_state) { S.store(P, (size_t)n); E.store(P, n); }
+            if constexpr (HAS_OBS) rs_env_reset_lane<true, 4>(P, g, n, lds_geo, lds_adj, lds_d, tile + j * RS_OBS_DIM, O, j, cj);
+            else rs_env_reset_lane<false>(P, g, n, lds_geo, lds_adj, lds_d, tile + lane * RS_OBS_DIM, O);
+            E.load(P, n);                                        // new episode: new source, new Philox counters
+            if constexpr (Cfg::reg_state) S.load(P, (size_t)n);
         }
         if (own) {
             if (cut) {
@@ -313,14 +457,18 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
                 xo[0] = W.standardize(oraw[0]);
                 steps = 0;
                 ep_ret = 0.0f;
-                ep_key = P.episode[n] - 1u; t_key = P.tstep[n];  // new episode: new source, new Philox counters
-                srcx = (float)P.src_x[n]; srcy = (float)P.src_y[n];
 #pragma unroll
                 for (int k = 0; k < RS_IN_PAD; ++k) M[RS_MB_POST + j * RS_IN_PAD + k] = xo[k];
             }
         }
+        RS_K6STAMP(6);                                           // reset
         rs_bcast_x16(xo, xs);
         __syncthreads();                                          // message t is complete; wave 1 takes it from here
+        RS_K6STAMP(7);                                           // broadcast + barrier
+    }
+    RS_K6STAMP_EXIT(HAS_OBS ? 1 : 0, (unsigned long long)T);
+    if constexpr (Cfg::reg_state) {
+        if (HAS_OBS || own) { S.store(P, (size_t)n); E.store(P, n); }
     }
     if (own) {
 #pragma unroll

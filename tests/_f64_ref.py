@@ -401,3 +401,336 @@ def k13_reference(cell, B, bp_args, pf_h0, eps, idx):
     res = model_loss_f64(c64, Bc.X, tar32, bp32, Bc.valid, Bc.lens, Bc.w_ep, bp_args, pf_h0.cpu(), eps.cpu(), idx.cpu())
     res.loss.backward()
     return res, {k: p.grad for k, p in c64.named_parameters()}, c64
+
+
+# ------------------------------------------------------------------------------------------------ feed-forward PPO (K7, rs_policy_forward, K6)
+FF_BLOCKS = (("a.w1", 704), ("a.b1", 64), ("a.w2", 4096), ("a.b2", 64), ("a.w3", 512), ("a.b3", 8),
+             ("c.w1", 704), ("c.b1", 64), ("c.w2", 4096), ("c.b2", 64), ("c.w3", 64), ("c.b3", 1))     # FusedPPOGrad's order
+FF_STATS = ("kl", "entropy", "clipfrac", "value_loss", "loss")
+FF_WAVES = 2048                      # K7: 256 workgroups x 8 waves, one group of 32 samples per wave and trip
+FF_SIZES = (1, 31, 32, 33, 63, 65, 65536, 65537, 65536 + 32 * 1024 + 5, 3 * 65536 + 32 * 7 + 1)
+FF_SCALES = {"base": 0.25, "x3": 0.75}            # parameters = randn x scale
+FF_CASES = [(M, "base") for M in FF_SIZES] + [(33, "x3"), (65537, "x3")]
+FWD_SIZES = (1, 63, 64, 65, 131072, 131073, 131072 + 64 * 1000 + 1)
+FF_CLIP, FF_ALPHA, FF_VF = 0.2, 0.1, 0.01
+
+
+def ff_case_id(c):
+    return f"M{c[0]}-{c[1]}"
+
+
+def ff_trips(M):
+    groups = (M + 31) // 32
+    return (groups + FF_WAVES - 1) // FF_WAVES
+
+
+def ff_tail_start(M):
+    """First sample of the tail: the last trip's samples where K7 takes more than one trip, the last (full or partial) group otherwise."""
+    t = ff_trips(M)
+    return (t - 1) * FF_WAVES * 32 if t > 1 else ((M + 31) // 32 - 1) * 32
+
+
+def ff_weights(M, g):
+    """float32 weights, sum 1 (to float32 rounding): half on the tail, half on the samples before it, each spread as uniform(0.25, 1.75).
+    A tail of more than one group that ends in a partial group gives half of its own half to that partial group, so that the few
+    samples behind the last full group weigh a quarter of the batch.  M <= 32: the tail is the whole batch."""
+    def spread(n, total):
+        u = 0.25 + 1.5 * torch.rand(n, generator=g, dtype=torch.float64)
+        return u * (total / u.sum())
+    s = ff_tail_start(M)
+    w = torch.empty(M, dtype=torch.float64)
+    if s == 0:
+        w[:] = spread(M, 1.0)
+        return w.float()
+    w[:s] = spread(s, 0.5)
+    last = (M - 1) // 32 * 32
+    if M % 32 and last > s:
+        w[s:last] = spread(last - s, 0.25)
+        w[last:] = spread(M - last, 0.25)
+    else:
+        w[s:] = spread(M - s, 0.5)
+    return w.float()
+
+
+def ff_params(ac):
+    """The twelve parameters in FusedPPOGrad's order."""
+    return [ac.actor[0].weight, ac.actor[0].bias, ac.actor[2].weight, ac.actor[2].bias, ac.actor[4].weight, ac.actor[4].bias,
+            ac.critic[0].weight, ac.critic[0].bias, ac.critic[2].weight, ac.critic[2].bias, ac.critic[4].weight, ac.critic[4].bias]
+
+
+def ff_agent(pset, seed=0):
+    """FFActorCritic on the CPU with parameters randn x FF_SCALES[pset]; "x3" is the same draw as "base" times 3."""
+    from radiation_ppo_amd.ppo import FFActorCritic
+    g = torch.Generator().manual_seed(1000 + seed)
+    ac = FFActorCritic()
+    with torch.no_grad():
+        for p in ff_params(ac):
+            p.copy_(torch.randn(p.shape, generator=g) * FF_SCALES[pset])
+    return ac
+
+
+def ff_forward_f64(ac64, X):
+    """(logits [M, 8], value [M]) of the float64 twin on float32 rows widened."""
+    with torch.no_grad():
+        x = X.double().cpu()
+        return ac64.logits(x), ac64.critic(x).squeeze(-1)
+
+
+class FFLoss64:
+    """What ff_loss_f64 returns.  stats [5]: kl, entropy, clip fraction, value loss, loss; stat_mags [5]: the sums of the absolute
+    per-sample terms they are rounded against; grads / mags: twelve tensors each in FusedPPOGrad's order, mags[k][e] the sum over samples
+    of the absolute per-sample term of gradient element e; bp_mags: the same sums with the back-propagated error delta replaced by its
+    bound without cancellation, |W2|^T (|W3|^T |dz| (1 - h2^2)) (1 - h1^2) (zero for the output layer, which has no dot product behind
+    it): the scale the rounding of W3^T dz and W2^T dpre2 is relative to; ratio [M]: the float64 PPO ratios."""
+    stats = stat_mags = grads = mags = bp_mags = ratio = None
+
+    def flat(self):
+        return torch.cat([g.reshape(-1) for g in self.grads]), torch.cat([m.reshape(-1) for m in self.mags])
+
+    def flat_bp(self):
+        return torch.cat([m.reshape(-1) for m in self.bp_mags])
+
+
+def _ff_backward(seq, x, h1, h2, dz):
+    """Gradients and their per-element magnitudes of one 11-64-64-NOUT tanh MLP from the error dz [M, NOUT] at its output: for a
+    weight, dW = delta^T a and |delta|^T |a| (|delta_i a_j| = |delta_i| |a_j|: no per-sample gradient is formed); for a bias, the
+    column sums of delta and of |delta|."""
+    W2, W3 = seq[2].weight, seq[4].weight
+    d2 = (dz @ W3) * (1 - h2 * h2)
+    d1 = (d2 @ W2) * (1 - h1 * h1)
+    # the same chain without cancellation in the two transposed dot products: what their rounding errors are relative to
+    u2 = (dz.abs() @ W3.abs()) * (1 - h2 * h2)
+    u1 = (u2 @ W2.abs()) * (1 - h1 * h1)
+    grads, mags, bps = [], [], []
+    for d, u, a in ((d1, u1, x), (d2, u2, h1), (dz, None, h2)):
+        grads += [d.t() @ a, d.sum(0)]
+        mags += [d.abs().t() @ a.abs(), d.abs().sum(0)]
+        bps += [torch.zeros_like(mags[-2]), torch.zeros_like(mags[-1])] if u is None else [u.t() @ a.abs(), u.sum(0)]
+    return grads, mags, bps
+
+
+def ff_loss_f64(ac64, X, act, adv, ret, logp_old, w, clip, alpha, vf):
+    """The loss of VecAgentPPO.update_agent's unfused branch (ppo.py; test_ppo_gpu._torch_loss_and_grads writes the same):
+    -(sum w min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv) - vf sum w (v - ret)^2 + alpha sum w entropy), the entropy term detached,
+    on the float64 twin ac64 with the float32 inputs widened (their rounding is charged to neither side), forward and backward written
+    out by hand so that the magnitudes come with the gradients (test_f64_references.py holds the gradients to float64 autograd).
+    Magnitudes of the statistics: kl sum w (|logp_old| + |logp|); entropy sum w sum_j p_j (1 + |lp_j|) (the error of lp_j is absolute);
+    clip fraction itself; value loss sum w (d^2 + 2 |d| (1 + |v| + |ret|)), d = v - ret; loss: sum w |surr| (1 + |logp|) + vf x the
+    value loss's + alpha x the entropy's."""
+    res = FFLoss64()
+    with torch.no_grad():
+        x, adv, ret, lpo, w = (t.detach().double().cpu() for t in (X, adv, ret, logp_old, w))
+        act = act.detach().cpu().long()
+        M = x.shape[0]
+        a1 = torch.tanh(torch.nn.functional.linear(x, ac64.actor[0].weight, ac64.actor[0].bias))
+        a2 = torch.tanh(torch.nn.functional.linear(a1, ac64.actor[2].weight, ac64.actor[2].bias))
+        lp_all = torch.log_softmax(torch.nn.functional.linear(a2, ac64.actor[4].weight, ac64.actor[4].bias), dim=-1)
+        c1 = torch.tanh(torch.nn.functional.linear(x, ac64.critic[0].weight, ac64.critic[0].bias))
+        c2 = torch.tanh(torch.nn.functional.linear(c1, ac64.critic[2].weight, ac64.critic[2].bias))
+        v = torch.nn.functional.linear(c2, ac64.critic[4].weight, ac64.critic[4].bias).squeeze(-1)
+        p = lp_all.exp()
+        logp = lp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1)
+        ratio = torch.exp(logp - lpo)
+        lo, hi = 1 - clip, 1 + clip
+        s1, s2 = ratio * adv, torch.clamp(ratio, lo, hi) * adv
+        surr = torch.minimum(s1, s2)
+        live = ((ratio >= lo) & (ratio <= hi)) | (s1 < s2)                 # where the minimum is the unclipped term: d surr / d ratio = adv
+        g_lp = -w * torch.where(live, adv, torch.zeros_like(adv)) * ratio    # d loss / d logp
+        onehot = torch.zeros(M, 8, dtype=torch.float64).scatter_(1, act.unsqueeze(-1), 1.0)
+        dz_a = g_lp.unsqueeze(-1) * (onehot - p)
+        d = v - ret
+        dz_c = (2 * vf * w * d).unsqueeze(-1)
+        ga, ma, ba = _ff_backward(ac64.actor, x, a1, a2, dz_a)
+        gc, mc, bc = _ff_backward(ac64.critic, x, c1, c2, dz_c)
+        res.grads, res.mags, res.bp_mags = ga + gc, ma + mc, ba + bc
+        ent_s = -(p * lp_all).sum(-1)
+        kl, ent, cf, vl, sur = (w * (lpo - logp)).sum(), (w * ent_s).sum(), (w * ((ratio > hi) | (ratio < lo)).double()).sum(), \
+            (w * d * d).sum(), (w * surr).sum()
+        res.stats = torch.stack([kl, ent, cf, vl, -(sur - vf * vl + alpha * ent)])
+        m_ent = (w * (p * (1 + lp_all.abs())).sum(-1)).sum()
+        m_vl = (w * (d * d + 2 * d.abs() * (1 + v.abs() + ret.abs()))).sum()
+        m_sur = (w * surr.abs() * (1 + logp.abs())).sum()
+        res.stat_mags = torch.stack([(w * (lpo.abs() + logp.abs())).sum(), m_ent, cf, m_vl, m_sur + vf * m_vl + alpha * m_ent])
+        res.ratio = ratio
+    return res
+
+
+def _ff_forward_terms(s1, s2, s3):
+    """(E_h1, E_h2, E_out) of ff_error_model, in U and before SAFETY, for layers whose parameters have rms s1, s2, s3."""
+    S1 = 12 * s1 * 0.8                                 # sum |w1 x| + |b1|: depth 11 + 1
+    E_h1 = (12 ** 0.5 + 1) * S1 + 4                    # layer 1 dot (11 + 1 deep, MFMA k-chain) + tanh
+    S2 = 65 * s2                                       # sum |w2 h1| + |b2| <= 65 s: depth 64 (+ bias)
+    E_h2 = 8 * s2 * E_h1 + (8 + 1) * S2 + 4            # h1's error through W2, layer 2 dot, tanh
+    S3 = 65 * s3
+    E_out = 8 * s3 * E_h2 + (8 + 1) * S3 + 1           # h2's error through W3, the 2 x 32 fmaf chains + pair add + bias (depth 64)
+    return E_h1, E_h2, E_out
+
+
+def _ff_lp_term(E_out):
+    # log-probabilities: (out - mx) - lse with lse = __logf(sum of eight __expf): two logits' errors, the two subtractions (2), the
+    # eight-term sum (sqrt(8) + 1 on terms <= 1), __expf 1 + its argument's scaling (terms near 1: <= 1), __logf 1 + 1
+    return 2 * E_out + 2 + 3.8 + 2 + 2
+
+
+def ff_error_model(pset):
+    """The float32 error model of the feed-forward kernels, in units of U, for parameters randn x s (s = FF_SCALES[pset]) and
+    standard-normal inputs (E|x| = 0.8, |tanh| <= 1), term by term after the module docstring: a dot product of depth n carries
+    sqrt(n) U of the sum of its absolute terms in expectation, plus 1 U of that sum for the rounding of the 2 log2(e) prescale folded
+    into W1 / b1 / W2 / b2; rs_tanh_scaled adds 4 U absolute (v_exp_f32 1, the scaling of its argument <= 0.5: |x| sech^2 x <= 0.45,
+    1 + e 0.5, v_rcp_f32 1, fma 0.5, rounded up) and passes the pre-activation's error on with tanh' <= 1; an error e of the inputs of a
+    dot product of depth n with weights of rms s comes out as sqrt(n) s e (independent signs).  E|tanh'| over the units (gain) is 0.5
+    at s = 0.25 (pre-activations of std ~1.2) and 0.15 at s = 0.75 (std ~5: most units saturated); 1 / gain is what the relative error
+    of 1 - h^2 costs per unit of the error of h, summed over samples.  SAFETY multiplies everything: the model is an expectation.
+
+    Returns E_logit (absolute error of a logit or of the value, in U), and k, the multiple of U mag every gradient element and every
+    statistic is allowed (see test_ppo_ff_f64_gpu.py's docstring for the backward terms)."""
+    s = FF_SCALES[pset]
+    gain = {"base": 0.5, "x3": 0.15}[pset]
+    SAFETY = 2.0
+    E_h1, E_h2, E_out = _ff_forward_terms(s, s, s)
+    E_lp = _ff_lp_term(E_out)
+    # p_j = __expf(lp_j): relative E_lp + 1 + |lp_j| (argument scaling at lp ~ -20: 20; such p_j are 2e-9 and weigh nothing: kept)
+    E_p = E_lp + 21
+    # ratio = __expf(logp - lpo): E_lp + subtraction 1 + __expf 1 + |logp - lpo| < 1;  g_lp = -w dr ratio: 2 products
+    E_glp = E_lp + 3 + 2
+    E_dz = E_glp + E_p + 1                             # dz_j = g_lp (1[a = j] - p_j)
+    # dpre2 = (W3^T dz) (1 - h2^2): h2's error in 1 - h2^2 (2 E_h2 / gain), the fma pair (3);  dW2's term dpre2 h1 adds h1's error
+    # (relative to E|h1| ~ 0.5).  dpre1 = (W2^T dpre2) (1 - h1^2): 2 E_h1 / gain, 3;  dW1's term dpre1 x: x is exact.
+    # The rounding of the two transposed dot products themselves (depth 8 and 64) is relative to the sum of their ABSOLUTE terms, not to
+    # their result: over many samples the two differ by ~sqrt(depth), but at a lone sample (M = 1, or a tail of one sample that holds
+    # half of the weight) the unit whose 64 terms cancel best decides a whole row of dW1.  It is therefore charged to bp_mag, the
+    # magnitude without cancellation, at FF_K_BP = SAFETY (sqrt(64) + 1), and not to k.
+    E_d2 = E_dz + 2 * E_h2 / gain + 3
+    E_d1 = E_d2 + 2 * E_h1 / gain + 3
+    # sums over samples: a wave's MFMA accumulators over trips x 32 <= 128 samples (sqrt(128) = 11.3), the 8-wave LDS sum (2.8), the
+    # 256 slabs as 16 chunks of 16 (4 + 4);  float32 torch on the CPU sums M <= 2e5 samples in its GEMM's blocks: its sqrt(M) <= 444
+    # sits inside what SAFETY adds to the forward terms (>= 2000 U at either parameter set)
+    E_sum = 11.3 + 2.8 + 8
+    k = SAFETY * (E_d1 + 2 * E_h2 + E_sum)             # + h2's / h1's relative error in the dW3 / dW2 term (E_h / 0.5)
+    return dict(E_h1=E_h1, E_h2=E_h2, E_logit=SAFETY * E_out, E_lp=SAFETY * E_lp, k=k)
+
+
+FF_K_BP = 2.0 * (64 ** 0.5 + 1)      # see ff_error_model: the transposed dot products' own rounding, on bp_mags
+FF_RTOL = 4 * U                      # the roundings that are relative to the result itself: the last add of the slab sum and the bucket store
+FF_TINY = 1e-30                      # 2^-126 x 1e8: products of w ~ 1e-6 and small factors may pass through float32's subnormal range
+
+
+def ff_ratios(got_stats, got_grads, ref, pset):
+    """[(block, worst |got - ref| / allowed)] over the five statistics and the twelve gradient blocks, allowed = FF_RTOL |ref| +
+    k U mag + FF_TINY with k = ff_error_model(pset)['k'], where a gradient's k U mag is U (k mag + FF_K_BP bp_mag).  got_grads: flat [10441] or the twelve tensors."""
+    k = ff_error_model(pset)["k"]
+    out = []
+    gs = torch.as_tensor(got_stats).detach().double().cpu().reshape(5)
+    for q, name in enumerate(FF_STATS):
+        allowed = FF_RTOL * abs(float(ref.stats[q])) + k * U * float(ref.stat_mags[q]) + FF_TINY
+        err = abs(float(gs[q]) - float(ref.stats[q]))
+        out.append((name, err / allowed if err == err else float("inf")))
+    if not torch.is_tensor(got_grads):
+        got_grads = torch.cat([g.reshape(-1) for g in got_grads])
+    gg = got_grads.detach().double().cpu().reshape(-1)
+    rg, rm = ref.flat()
+    assert gg.shape == rg.shape, (gg.shape, rg.shape)
+    ratio = (gg - rg).abs() / (FF_RTOL * rg.abs() + U * (k * rm + FF_K_BP * ref.flat_bp()) + FF_TINY)
+    ratio = torch.where(torch.isfinite(gg), ratio, torch.full_like(ratio, float("inf")))
+    o = 0
+    for name, n in FF_BLOCKS:
+        out.append((name, float(ratio[o:o + n].max())))
+        o += n
+    return out
+
+
+def check_ff(got_stats, got_grads, ref, pset, name, report=None):
+    """Every statistic and gradient block within the rule (ff_ratios); every block over its allowance is named.  report: a list that
+    receives a line `name | block ratio ...`."""
+    ratios = ff_ratios(got_stats, got_grads, ref, pset)
+    if report is not None:
+        report.append(f"{name} | " + " ".join(f"{b} {r:.4f}" for b, r in ratios))
+    bad = [(b, round(r, 3)) for b, r in ratios if not r <= 1.0]
+    assert not bad, (name, bad)
+    return ratios
+
+
+class FFCase:
+    pass
+
+
+_FF_CACHE = {}
+
+
+def ff_case(M, pset, zero_rows=0):
+    """One case of the K7 tests, built once on the CPU and shared: the float32 agent `ac`, its float64 twin, the float32 batch
+    (X, act, adv, ret, lpo, w) and the float64 reference `ref`.  adv / ret are randn; logp_old = logp64(act) - log(target ratio), rounded
+    to float32, targets from target_ratios (a third below, inside, above the clip range, 0.02 off its edges); asserted: no sample's
+    float64 ratio from the ROUNDED logp_old lies within 0.01 of 1 +- clip (a condition, not an allowance: zero samples are excused).
+    zero_rows: that many scattered rows get w = 0, X x 1e3 and adv x 1e6 (all finite), the other weights are renormalised; the
+    reference is computed with those rows deleted."""
+    key = (M, pset, zero_rows)
+    if key in _FF_CACHE:
+        return _FF_CACHE[key]
+    c = FFCase()
+    g = torch.Generator().manual_seed(7 * M + len(pset) + zero_rows)
+    c.M, c.pset = M, pset
+    c.ac = ff_agent(pset)
+    c.ac64 = f64(c.ac)
+    c.X = torch.randn(M, 11, generator=g)
+    c.act = torch.randint(0, 8, (M,), generator=g)
+    c.adv, c.ret = torch.randn(M, generator=g), torch.randn(M, generator=g)
+    c.w = ff_weights(M, g)
+    keep = torch.ones(M, dtype=torch.bool)
+    if zero_rows:
+        dead = torch.randperm(M, generator=g)[:zero_rows]
+        keep[dead] = False
+        c.X[dead] *= 1e3
+        c.adv[dead] *= 1e6
+        c.w[dead] = 0.0
+        c.w = (c.w.double() / c.w.double().sum()).float()
+    lg, _ = ff_forward_f64(c.ac64, c.X)
+    lp64 = torch.log_softmax(lg, dim=-1).gather(-1, c.act.unsqueeze(-1)).squeeze(-1)
+    c.lpo = (lp64 - torch.log(target_ratios(M, g, FF_CLIP))).float()
+    c.keep = keep
+    c.batch = (c.X, c.act, c.adv, c.ret, c.lpo, c.w)
+    c.ref = ff_loss_f64(c.ac64, *(t[keep] for t in c.batch), FF_CLIP, FF_ALPHA, FF_VF)
+    r = torch.exp(lp64 - c.lpo.double())
+    assert float(torch.minimum((r - (1 - FF_CLIP)).abs(), (r - (1 + FF_CLIP)).abs()).min()) >= 0.01, "a ratio within 0.01 of a clip edge"
+    assert bool(torch.isfinite(c.X).all()) and bool(torch.isfinite(c.adv).all()) and bool(torch.isfinite(c.lpo).all())
+    _FF_CACHE[key] = c
+    return c
+
+
+def ff_torch32(c, rows=None):
+    """The project's float32 torch path on the CPU for case c (FFActorCritic.evaluate + the loss, autograd): (stats [5], flat gradients).
+    rows: a boolean mask of the samples to keep (c.keep where the case has zero-weight rows, which the reference is computed without)."""
+    ac = copy.deepcopy(c.ac)
+    X, act, adv, ret, lpo, w = c.batch if rows is None else (t[rows] for t in c.batch)
+    logp, v, ent = ac.evaluate(X, act)
+    ratio = torch.exp(logp - lpo)
+    surr = torch.min(ratio * adv, torch.clamp(ratio, 1 - FF_CLIP, 1 + FF_CLIP) * adv)
+    vl = (w * (v - ret) ** 2).sum()
+    loss = -((w * surr).sum() - FF_VF * vl + FF_ALPHA * (w * ent).sum().detach())
+    loss.backward()
+    clipped = (ratio > 1 + FF_CLIP) | (ratio < 1 - FF_CLIP)
+    stats = torch.stack([(w * (lpo - logp)).sum(), (w * ent).sum(), (w * clipped.float()).sum(), vl, loss]).detach()
+    return stats, torch.cat([p.grad.reshape(-1) for p in ff_params(ac)])
+
+
+# nn.Linear's default initialisation, uniform(+-1 / sqrt(fan_in)), has rms 1 / sqrt(3 fan_in); the collector test multiplies it by 3
+K6_INIT_SCALES = (3 / 33 ** 0.5, 3 / 192 ** 0.5, 3 / 192 ** 0.5)       # 0.52 for the 11-input layer, 0.22 for the two 64-input layers
+
+
+def fwd_tolerance(pset):
+    """close()'s constants for a logit, a value, a log-probability from the forward half of the model: rtol 4 U (the output's own
+    roundings), no noise term, tiny = the absolute error E_logit U (E_lp U for a log-probability).  pset: a parameter set's name, or
+    the three layers' rms scales (the same terms and the same SAFETY = 2, with each layer's own scale)."""
+    if isinstance(pset, str):
+        m = ff_error_model(pset)
+    else:
+        E_out = _ff_forward_terms(*pset)[2]
+        m = dict(E_logit=2.0 * E_out, E_lp=2.0 * _ff_lp_term(E_out))
+    return dict(rtol=4 * U, noise=0.0, tiny=m["E_logit"] * U), dict(rtol=4 * U, noise=0.0, tiny=m["E_lp"] * U)
+
+
+def close_ratio(got, ref, rtol, noise, tiny):
+    """close()'s worst error / allowance, as a number (for the results file)."""
+    a, b = got.detach().double().cpu(), ref.detach().double().cpu()
+    scale = float(b.abs().max()) if b.numel() else 0.0
+    return float(((a - b).abs() / (rtol * b.abs() + noise * scale + tiny)).max()) if b.numel() else 0.0

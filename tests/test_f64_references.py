@@ -208,3 +208,83 @@ def test_model_loss_f64_steps_the_cell_and_its_kink_counter_counts():
                         or (l1_on and bool((d[t, e, q].abs() < R.KINK_EPS).any()))
                     brute += int(near and bool(valid[t, e]))
         assert R.kink_count(z0, z2, d, valid, l1_on=l1_on) == brute == (4 if l1_on else 3)
+
+
+# ------------------------------------------------------------------------------------------------ feed-forward PPO (tests/test_ppo_ff_f64_gpu.py)
+FF_ALL = R.FF_CASES + [(1000, "base")]
+
+
+def test_ff_loss_f64_equals_float64_autograd_and_its_magnitudes_bound_it():
+    """The hand-written backward of R.ff_loss_f64 against float64 autograd of the loss as ppo.py writes it (1e-12 of each element's
+    magnitude), |gradient| <= magnitude elementwise, a magnitude equals the brute-force sum of |per-sample gradient| on a few samples,
+    and the weights put half of their sum on the tail."""
+    c = R.ff_case(65, "base")
+    X, act, adv, ret, lpo, w = (t.double() if t.is_floating_point() else t for t in c.batch)
+    ac = R.f64(c.ac)
+    logp, v, ent = ac.evaluate(X, act)
+    ratio = torch.exp(logp - lpo)
+    surr = torch.min(ratio * adv, torch.clamp(ratio, 0.8, 1.2) * adv)
+    vl = (w * (v - ret) ** 2).sum()
+    loss = -((w * surr).sum() - R.FF_VF * vl + R.FF_ALPHA * (w * ent).sum().detach())
+    loss.backward()
+    g_auto = torch.cat([p.grad.reshape(-1) for p in R.ff_params(ac)])
+    g, m = c.ref.flat()
+    assert float(((g - g_auto).abs() / (1e-12 * m + 1e-300)).max()) <= 1.0
+    assert bool((g.abs() <= m * (1 + 1e-12)).all())
+    assert abs(float(c.ref.stats[4]) - float(loss.detach())) <= 1e-12 * float(c.ref.stat_mags[4])
+    brute = torch.zeros_like(m)
+    for n in range(65):
+        one = R.ff_loss_f64(c.ac64, *(t[n:n + 1] for t in c.batch), R.FF_CLIP, R.FF_ALPHA, R.FF_VF)
+        brute += one.flat()[0].abs()
+    assert float(((brute - m).abs() / m).max()) < 1e-10
+    for M in R.FF_SIZES:
+        wt = R.ff_weights(M, torch.Generator().manual_seed(M)).double()
+        s = R.ff_tail_start(M)
+        assert abs(float(wt.sum()) - 1) < 1e-5 and float(wt.min()) > 0
+        assert s == 0 or abs(float(wt[s:].sum()) - 0.5) < 1e-5, M
+    assert [R.ff_trips(M) for M in R.FF_SIZES] == [1, 1, 1, 1, 1, 1, 1, 2, 2, 4]
+
+
+@pytest.mark.parametrize("case", FF_ALL, ids=R.ff_case_id)
+def test_ff_loss_f64_against_the_float32_torch_path(case):
+    """R.ff_loss_f64 against the project's float32 torch path on the CPU (FFActorCritic.evaluate + the loss, autograd) under the rule
+    the GPU test holds K7 to (R.check_ff: rtol |ref| + k U mag + tiny, k from R.ff_error_model), at every case of that test: float32
+    torch sums in another order than K7 with the same unit roundoff, so it must pass the same rule."""
+    M, pset = case
+    c = R.ff_case(M, pset, zero_rows=100 if M == 1000 else 0)
+    stats, g = R.ff_torch32(c, rows=c.keep)                  # the zero-weight rows of M = 1000 are left out, as in the reference
+    rep = []
+    R.check_ff(stats, g, c.ref, pset, "torch32 " + R.ff_case_id(case), report=rep)
+    print(rep[0])
+
+
+@pytest.mark.parametrize("case", R.FF_CASES, ids=R.ff_case_id)
+def test_ff_rule_sees_a_lost_or_repeated_tail(case):
+    """The reference recomputed with the tail samples removed (the last trip's, or the last group's), and with them counted twice,
+    must fail the rule at some gradient block by a ratio of at least 100: half of the weight lies on the tail."""
+    M, pset = case
+    c = R.ff_case(M, pset)
+    s = R.ff_tail_start(M)
+    for what, idx in (("removed", torch.arange(0, s)), ("twice", torch.cat((torch.arange(M), torch.arange(s, M))))):
+        r = R.ff_loss_f64(c.ac64, *(t[idx] for t in c.batch), R.FF_CLIP, R.FF_ALPHA, R.FF_VF)
+        ratios = R.ff_ratios(r.stats, r.grads, c.ref, pset)
+        worst = max(x for _, x in ratios[5:])
+        print(f"{R.ff_case_id(case)} tail {what}: worst gradient block {worst:.0f} x the allowance")
+        assert worst >= 100.0, (what, ratios)
+
+
+@pytest.mark.parametrize("pset", sorted(R.FF_SCALES))
+def test_ff_forward_f64_against_the_float32_torch_path(pset):
+    """Logits, value and log-probability of the float64 twin against the float32 module on the CPU within the forward constants
+    (R.fwd_tolerance) the GPU tests of rs_policy_forward and of K6's stored outputs use."""
+    ac = R.ff_agent(pset)
+    X = torch.randn(5000, 11, generator=torch.Generator().manual_seed(3))
+    lg64, v64 = R.ff_forward_f64(R.f64(ac), X)
+    with torch.no_grad():
+        lg, v = ac.logits(X), ac.critic(X).squeeze(-1)
+    t_out, t_lp = R.fwd_tolerance(pset)
+    R.close(lg, lg64, "logits", **t_out)
+    R.close(v, v64, "value", **t_out)
+    R.close(torch.log_softmax(lg, -1), torch.log_softmax(lg64, -1), "logp", **t_lp)
+    print(f"torch32 forward {pset}: logits {R.close_ratio(lg, lg64, **t_out):.4f} value {R.close_ratio(v, v64, **t_out):.4f} "
+          f"logp {R.close_ratio(torch.log_softmax(lg, -1), torch.log_softmax(lg64, -1), **t_lp):.4f}")

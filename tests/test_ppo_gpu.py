@@ -202,12 +202,16 @@ def _replay_check(col, agents, N, T, L, obst, stride=3):
     """Drive oracle/train_loop_oracle.train_loop_trace (RAD-A2C branch; pinned to the reference's own train() by
     tests/test_train_loop_golden.py) with the actions / values the device stored, env by env, and require the
     device buffer to hold what the trace passes to store(): standardised observation (float64 Welford, within 1 ulp
-    of float32), reward, source target, terminal flag -- and a zero bootstrap exactly on terminal trajectories."""
+    of float32), reward, source target, terminal flag -- and a zero bootstrap exactly on terminal trajectories.
+    Returns [(t, n, x)]: for every bootstrap call of the trace (a trajectory cut by the time limit or the epoch's end at
+    stored step t of env n), the standardised pre-reset observation x [11] the trace hands to the critic; the buffer
+    does not hold it, because the env is reset before the next row is stored."""
     from oracle.train_loop_oracle import train_loop_trace
     buf = col.buf
     obs, act, rew, cut, val, logp = (t.cpu().numpy() for t in (buf.obs, buf.act, buf.rew, buf.cut, buf.val, buf.logp))
     lastv = buf.last_val.cpu().numpy()
     src = buf.source_tar.cpu().numpy()
+    boot = []
     for n in range(0, N, stride):
         ref = RadSearchOracle(PhiloxDraws(SEED, n), number_agents=1, obstruction_count=obst, enforce_grid_boundaries=True)
         st = {"t": 0, "after_step": False, "first": True}
@@ -233,6 +237,7 @@ def _replay_check(col, agents, N, T, L, obst, stride=3):
 
         def agent_step(i, observations):
             if st["after_step"] and cut[st["t"] - 1, n, 0]:          # bootstrap call (train.py:476-480)
+                boot.append((st["t"] - 1, n, np.asarray(observations[i], dtype=np.float64)))
                 return 0, float(lastv[st["t"] - 1, n, 0]), 0.0
             t = st["t"]
             return int(act[t, n, 0]), float(val[t, n, 0]), float(logp[t, n, 0])
@@ -252,6 +257,7 @@ def _replay_check(col, agents, N, T, L, obst, stride=3):
         for t, e in zip(cuts_t, gae):
             assert float(lastv[t, n, 0]) == e[2], (n, t)             # 0.0 where the trace ended on a terminal
         assert ref.err == 0
+    return boot
 
 
 @pytest.mark.parametrize("obst", [0, 3])
@@ -262,6 +268,7 @@ def test_fused_collector_replays_through_oracle(obst):
     a second epoch continues from the carried state."""
     from radiation_ppo_amd.envs import RadSearchVec
     from radiation_ppo_amd.ppo import FusedCollector, VecAgentPPO
+    _fused_collector_small(obst)
     N, T, L = 128, 40, 12
     torch.manual_seed(1)
     env = RadSearchVec(N, number_agents=1, obstruction_count=obst, enforce_grid_boundaries=True, seed=SEED)
@@ -271,7 +278,7 @@ def test_fused_collector_replays_through_oracle(obst):
             p.mul_(3.0)                              # make the policy visibly non-uniform
     col = FusedCollector(env, agents, T, L)
     stats = col.collect()
-    _replay_check(col, agents, N, T, L, obst)
+    boot = _replay_check(col, agents, N, T, L, obst)
     buf = col.buf
     X = buf.obs[:, :, 0].reshape(-1, 11)
     with torch.no_grad():
@@ -279,6 +286,7 @@ def test_fused_collector_replays_through_oracle(obst):
         probs = torch.softmax(agents[0].agent.logits(X), -1)
     assert torch.allclose(logp, buf.logp.reshape(-1), rtol=1e-4, atol=2e-5)
     assert torch.allclose(v, buf.val.reshape(-1), rtol=1e-4, atol=2e-5)
+    _stored_outputs_match_float64(buf, agents[0].agent, f"N{N} obst{obst}", boot, range(0, N, 3))
     # bootstrap values: where cut by timeout/epoch end, last_val == critic(standardised next obs) is covered
     # by the replay of obs at t+1 for non-reset envs; here check the action sampling rule on the stored rows
     cdf = torch.cumsum(probs, -1)
@@ -308,6 +316,67 @@ def test_fused_collector_replays_through_oracle(obst):
     col.collect()
     res = col.update()[0]
     assert 1 <= res.stop_iteration <= 40 and np.isfinite(res.loss_policy)
+
+
+def _stored_outputs_match_float64(buf, ac, name, boot, envs):
+    """K6's stored logp / val against the float64 twin on the stored observations, and its bootstrap values last_val against the
+    twin's critic on the observations the oracle replay handed to the critic (boot: _replay_check's return, for the envs it
+    replayed), within the forward constants of tests/_f64_ref.py (fwd_tolerance, the terms of ff_error_model) at this network's
+    scales: nn.Linear's default initialisation x 3, rms 0.52 / 0.22 / 0.22 per layer (R.K6_INIT_SCALES).
+
+    A bootstrap observation is the oracle's, not the kernel's own: the replay holds the kernel's standardised observations to
+    the oracle's within rtol 2e-7, atol 1e-7 (float64 Welford rounded to float32, 1 ulp).  That input distance, times
+    |d v / d x| of the float64 twin at the row, is added to the row's allowance; nothing else is."""
+    import sys
+    sys.path.insert(0, os.path.dirname(__file__))
+    import _f64_ref as R
+    t_out, t_lp = R.fwd_tolerance(R.K6_INIT_SCALES)
+    ac64 = R.f64(ac)
+    X = buf.obs[:, :, 0].reshape(-1, 11)
+    lg64, v64 = R.ff_forward_f64(ac64, X)
+    lp64 = torch.log_softmax(lg64, dim=-1).gather(-1, buf.act.reshape(-1).cpu().unsqueeze(-1)).squeeze(-1)
+    lastv, cut = buf.last_val[:, :, 0].cpu(), buf.cut[:, :, 0].cpu().bool()
+    assert not bool((lastv != 0)[~cut].any())                     # a bootstrap value exists at cuts only
+    rows = {(t, n) for t, n, _ in boot}
+    assert len(rows) == len(boot) >= 1
+    for n in envs:                                                # every non-zero last_val of a replayed env is compared below
+        assert all((int(t), n) in rows for t in torch.nonzero(lastv[:, n]).reshape(-1)), n
+    xb = torch.tensor(np.stack([x for _, _, x in boot]).astype(np.float32)).double().requires_grad_(True)
+    vb64 = ac64.critic(xb).squeeze(-1)
+    vb64.sum().backward()
+    dx = 2e-7 * xb.detach().abs() + 1e-7
+    t_boot = dict(t_out, tiny=t_out["tiny"] + (xb.grad.abs() * dx).sum(-1))
+    got_b = torch.stack([lastv[t, n] for t, n, _ in boot])
+    assert bool((got_b != 0).any())
+    print(f"K6 stored outputs {name} | logp {R.close_ratio(buf.logp.reshape(-1), lp64, **t_lp):.4f} "
+          f"val {R.close_ratio(buf.val.reshape(-1), v64, **t_out):.4f} "
+          f"last_val ({len(boot)} rows) {R.close_ratio(got_b, vb64.detach(), **t_boot):.4f}")
+    R.close(buf.logp.reshape(-1), lp64, f"logp {name}", **t_lp)
+    R.close(buf.val.reshape(-1), v64, f"val {name}", **t_out)
+    R.close(got_b, vb64.detach(), f"last_val {name}", **t_boot)
+
+
+def _fused_collector_small(obst):
+    """N = 16: one workgroup, the smallest rs_rollout accepts; replay, float32 and float64 checks of the stored policy outputs."""
+    from radiation_ppo_amd.envs import RadSearchVec
+    from radiation_ppo_amd.ppo import FusedCollector, VecAgentPPO
+    N, T, L = 16, 40, 12
+    torch.manual_seed(2)
+    env = RadSearchVec(N, number_agents=1, obstruction_count=obst, enforce_grid_boundaries=True, seed=SEED)
+    agents = {0: VecAgentPPO(id=0, steps_per_epoch=T, steps_per_episode=L, alpha=0.1)}
+    with torch.no_grad():
+        for p in agents[0].agent.parameters():
+            p.mul_(3.0)
+    col = FusedCollector(env, agents, T, L)
+    col.collect()
+    boot = _replay_check(col, agents, N, T, L, obst, stride=1)
+    buf = col.buf
+    X = buf.obs[:, :, 0].reshape(-1, 11)
+    with torch.no_grad():
+        logp, v, _ = agents[0].agent.evaluate(X, buf.act[:, :, 0].reshape(-1))
+    assert torch.allclose(logp, buf.logp.reshape(-1), rtol=1e-4, atol=2e-5)
+    assert torch.allclose(v, buf.val.reshape(-1), rtol=1e-4, atol=2e-5)
+    _stored_outputs_match_float64(buf, agents[0].agent, f"N{N} obst{obst}", boot, range(N))
 
 
 def _torch_loss_and_grads(ac, X, act, adv, ret, lpo, w, clip, alpha, vf=0.01):

@@ -173,6 +173,19 @@ typedef struct rs_mlp_params {
 int rs_policy_forward(const rs_mlp_params* actor, const rs_mlp_params* critic, const float* x, int32_t M,
                       float* logits, float* value, rs_stream_t stream);
 
+/* One round of ac.step for every agent of a feed-forward team (train.py:345-357, :476-480; FF_core.py:95-129): agent a's own actor
+ * and critic on its own rows x[n][a][:].  One launch, grid = (64-sample groups, agent); the forward pass is rs_policy_forward's.
+ *   actors, critics [A]   host arrays of rs_mlp_params (device pointers inside), A = num_agents in 1..RS_MAX_AGENTS
+ *   x [N][A][11]
+ *   u [N][A] != NULL: the step round.  act [A][N] int64 = #{j < 7 : cdf_j <= u}, logp_val_boot [A][3][N]: slot 0 = log-softmax at the
+ *        action, slot 1 = value; act8 [N][A] (rs_step's action rows) receives the action once more.  mask is ignored.
+ *   u == NULL: the bootstrap round.  slot 2 of logp_val_boot = value, for the envs with mask[n] != 0 (all when mask is NULL); nothing
+ *        else is written, rows of unmasked envs are left as they are.  act / act8 may be NULL.
+ * RS_ERR_INVALID_ARG, before anything is launched: NULL actors / critics / x / logp_val_boot, num_agents outside 1..RS_MAX_AGENTS,
+ * num_envs < 1, a step round with NULL act.  The layouts are the ones rs_store_rows reads. */
+int rs_ff_team_step(const rs_mlp_params* actors, const rs_mlp_params* critics, int32_t num_agents, const float* x, const float* u,
+                    int64_t* act, float* logp_val_boot, int8_t* act8, const uint8_t* mask, int32_t num_envs, rs_stream_t stream);
+
 /* ---- fused on-device collector ------------------------------------------------------------------
  * One launch = one epoch of the reference's collector loop (algos/multiagent/train.py:332-548) for all N
  * envs of the handle (single agent, N % 64 == 0, geom_group_size == 1): per lock-step the MLP forward on the

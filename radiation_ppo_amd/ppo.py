@@ -844,6 +844,118 @@ class FusedCollector:
             getattr(self, k).copy_(st[k])                          # in place: rs_rollout's argument block holds their addresses
 
 
+class TeamCollector:
+    """Same contract as Collector for a feed-forward team on the GPU, the lock-step in HIP: ONE policy launch for all agents
+    (rs_ff_team_step: every agent's own actor and critic on its own rows, the draw, rs_step's action rows) between the glue launches
+    RNNCollector._step_glued uses (rs_collect_pre / _post_step / _post_reset, rs_store_rows, rs_epoch_stats).  Ten launches per
+    lock-step, eleven at the epoch's last, on one stream, where Collector composes several dozen library ops per agent:
+    pre, uniforms, policy (step round), env step, post_step, policy (bootstrap round on the envs that need a value), store_rows,
+    epoch_stats, (epoch end) env reset, post_reset.  Every tensor keeps its address: the glue's argument block holds them."""
+
+    def __init__(self, env: RadSearchVec, agents: Dict[int, VecAgentPPO], steps_per_epoch: int, steps_per_episode: int,
+                 global_critic_flag: bool = False, standardize: bool = True):
+        self.env, self.agents = env, agents
+        self.T, self.L = steps_per_epoch, steps_per_episode
+        self.N, self.A = env.num_envs, env.number_agents
+        assert torch.device(env.device).type == "cuda" and sorted(agents) == list(range(self.A)) and 1 <= self.A <= _lib.RS_MAX_AGENTS
+        self.team_reward = global_critic_flag
+        self.standardize = standardize
+        self.lib = _lib.load()
+        dev, N, A = env.device, self.N, self.A
+        self.buf = RolloutBuffer(self.T, N, A, _lib.RS_OBS_DIM, dev)
+        self.stat = DeviceWelford((N, A), dev)
+        self.steps_in_ep = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.ep_ret = torch.zeros(N, A, dtype=torch.float32, device=dev)
+        self.obs = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)
+        self._u = torch.empty(N, A, dtype=torch.float32, device=dev)
+        self._act8 = torch.zeros(N, A, dtype=torch.int8, device=dev)
+        self._x = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)
+        self._xb = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)
+        self._flags = torch.zeros(3, N, dtype=torch.uint8, device=dev)                      # over, cut, boot
+        self._rew_used = torch.zeros(N, A, dtype=torch.float32, device=dev)
+        self._done_oob = torch.zeros(2, N, A, dtype=torch.uint8, device=dev)                # copies of the env's done / out_of_bounds rows
+        self._src_copy = torch.zeros(2, N, dtype=torch.int32, device=dev)
+        self._t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._acc = EpochStats(A, dev)
+        self._k_act = torch.zeros(A, N, dtype=torch.int64, device=dev)
+        self._k_f = torch.zeros(A, 3, N, dtype=torch.float32, device=dev)                   # logp, value, bootstrap value
+        p = lambda t: t.data_ptr()
+        st = self.stat
+        w = [p(st.count), p(st.mean), p(st.sq), p(st.std)] if standardize else [None] * 4
+        # no PFGRU, no GRU: pf_episode / pf_calls / episodes_begun stay NULL
+        self._cs = _lib.RsCollectState(N, A, self.L, 1 if self.team_reward else 0, p(env.obs), p(env.reward), p(env.team), p(env.done), p(self.obs),
+                                       p(self.ep_ret), p(self.steps_in_ep), *w, p(self._x), p(self._xb), p(self._rew_used), p(self._flags[0]),
+                                       p(self._flags[1]), p(self._flags[2]), None, None, None, p(self._t), p(env.oob), p(env.state("src_x")),
+                                       p(env.state("src_y")), p(self._done_oob[0]), p(self._done_oob[1]), p(self._src_copy), None)
+        b = self.buf
+        self._store_args = (p(self._t), p(self._k_act), p(self._k_f), p(self._x), p(self._src_copy[0]), p(self._src_copy[1]), p(self._rew_used),
+                            p(self._flags[1]), p(self._flags[2]), p(b.act), p(b.logp), p(b.val), p(b.last_val), p(b.obs), p(b.source_tar),
+                            p(b.rew), p(b.cut), N, A, self.T)
+        self._over = self._flags[0].view(torch.bool)
+        self.started = False
+
+    def start(self) -> None:
+        """train.py:273-312: first reset + first Welford update."""
+        obs, *_ = self.env.reset()
+        self.obs.copy_(obs)
+        self.stat.update(self.obs[..., 0])
+        self.started = True
+
+    def _nets(self):
+        """The agents' rs_mlp_params arrays over the live parameter tensors (update() changes them in place: valid for a collect())."""
+        arr = _lib.RsMlpParams * self.A
+        return (arr(*[mlp_params(self.agents[a].agent.actor) for a in range(self.A)]),
+                arr(*[mlp_params(self.agents[a].agent.critic) for a in range(self.A)]))
+
+    def _step(self, nets, epoch_ended: bool, st) -> None:
+        lib, env, cs, N, A = self.lib, self.env, C.byref(self._cs), self.N, self.A
+        pa, pc = nets
+        cut, boot = self._flags[1], self._flags[2]
+        _lib.check(lib.rs_collect_pre(cs, st), "rs_collect_pre")                                # train.py:334-341
+        env.action_uniforms(self._u)
+        _lib.check(lib.rs_ff_team_step(pa, pc, A, self._x.data_ptr(), self._u.data_ptr(), self._k_act.data_ptr(), self._k_f.data_ptr(),
+                                       self._act8.data_ptr(), None, N, st), "rs_ff_team_step")  # train.py:345-357
+        env.step(self._act8)
+        _lib.check(lib.rs_collect_post_step(cs, 1 if epoch_ended else 0, st), "rs_collect_post_step")
+        _lib.check(lib.rs_ff_team_step(pa, pc, A, self._xb.data_ptr(), None, None, self._k_f.data_ptr(), None, boot.data_ptr(), N, st),
+                   "rs_ff_team_step")                                                           # train.py:462-487: the bootstrap value
+        _lib.check(lib.rs_store_rows(*self._store_args, st), "rs_store_rows")
+        self._acc.step_and_episodes(self._done_oob[1], self._done_oob[0], self.ep_ret, self.steps_in_ep, self._over)
+        if epoch_ended:
+            env.set_epoch_end()                                                                 # train.py:482-484
+        env.reset(cut)                                                                          # train.py:530
+        _lib.check(lib.rs_collect_post_reset(cs, 0, st), "rs_collect_post_reset")
+
+    @torch.no_grad()
+    def collect(self) -> Dict[str, torch.Tensor]:
+        if not self.started:
+            self.start()
+        self._acc.zero_()
+        self._t.zero_()
+        nets = self._nets()
+        st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        for t in range(self.T):
+            self._step(nets, t == self.T - 1, st)
+        self.buf.finish(self.agents[0].gamma, self.agents[0].lam)
+        return self._acc.result()
+
+    def update(self) -> Dict[int, UpdateResult]:
+        return ppo_update_from_buffer(self)
+
+    def resume_state(self) -> Dict[str, Any]:
+        if not self.started:
+            self.start()
+        return dict(env=self.env.snapshot(), stat=_welford_state(self.stat), steps_in_ep=self.steps_in_ep.clone(),
+                    ep_ret=self.ep_ret.clone(), obs=self.obs.clone())
+
+    def load_resume_state(self, st: Dict[str, Any]) -> None:
+        if not self.started:
+            self.start()
+        self.env.restore(st["env"])
+        _welford_load(self.stat, st["stat"])
+        self.steps_in_ep.copy_(st["steps_in_ep"]); self.ep_ret.copy_(st["ep_ret"]); self.obs.copy_(st["obs"])   # in place: the glue holds addresses
+
+
 def prepare_update_hip(col):
     """(w, adv_n) of ppo_update_from_buffer for one rank and one agent as rs_ppo_prepare computes them: episode_weights() / n_total and
     normalize_advantages(buf.adv), bit for bit, in three launches.  The outputs and the workspace belong to the collector and are
@@ -877,7 +989,8 @@ def ppo_update_from_buffer(col) -> Dict[int, UpdateResult]:
     w = (buf.episode_weights() / n_total).reshape(-1)
     for a, ag in col.agents.items():
         adv = normalize_advantages(buf.adv[:, :, a]).reshape(-1)
-        X = buf.obs[:, :, a].reshape(-1, buf.obs.shape[-1])
-        out[a] = ag.update_agent(X, buf.act[:, :, a].reshape(-1), adv, buf.ret[:, :, a].reshape(-1),
-                                 buf.logp[:, :, a].reshape(-1), w)
+        # an agent's column of a team's [T, N, A] buffer reshapes to a strided view: K7 reads dense rows (one agent: already dense)
+        X = buf.obs[:, :, a].reshape(-1, buf.obs.shape[-1]).contiguous()
+        out[a] = ag.update_agent(X, buf.act[:, :, a].reshape(-1).contiguous(), adv.contiguous(), buf.ret[:, :, a].reshape(-1).contiguous(),
+                                 buf.logp[:, :, a].reshape(-1).contiguous(), w)
     return out

@@ -4,7 +4,7 @@
 `env` may be a radiation_ppo_amd.envs.RadSearchVec (N envs) or the 1-env RadSearch adapter.  The
 epoch x step double loop, the episode/epoch cut rules, the bootstrap rule, the epoch_end hand-shake,
 the update and the logger columns follow train.py:321-627; the per-step work runs batched on the
-device (radiation_ppo_amd.ppo.Collector / FusedCollector, radiation_ppo_amd.ppo_cnn.CNNCollector).  With
+device (radiation_ppo_amd.ppo.Collector / FusedCollector / TeamCollector, radiation_ppo_amd.ppo_cnn.CNNCollector).  With
 torch.distributed initialised (one process per GPU, backend "nccl" = RCCL) each rank owns a shard of the
 envs and gradients, the KL estimate and the advantage statistics are all-reduced (the reference's
 mpi_avg_grads / mpi_avg / mpi_statistics_scalar call sites, ppo.py:445,1250,1256).
@@ -26,7 +26,7 @@ import torch.distributed as dist
 from .envs import RadSearch, RadSearchVec
 from .logger import EpochLogger, convert_json, setup_logger_kwargs
 from .maps import CNNCritic, heat_map_geometry
-from .ppo import Collector, FusedCollector, VecAgentPPO
+from .ppo import Collector, FusedCollector, TeamCollector, VecAgentPPO
 from .ppo_cnn import CNNAgentPPO, CNNCollector
 from .rada2c import RNNAgentPPO, RNNCollector
 
@@ -152,6 +152,8 @@ class train_PPO:
         fusable = (self.number_of_agents == 1 and self.vec.num_envs % 16 == 0 and self.vec.cfg.geom_group_size == 1
                    and not self.global_critic_flag)
         cls = FusedCollector if fusable else Collector      # one launch per epoch (rs_rollout) when the config allows
+        if self.number_of_agents >= 2 and torch.device(self.vec.device).type == "cuda":
+            cls = TeamCollector                             # teams: one policy launch per lock-step (rs_ff_team_step) between the glue kernels
         self.collector = cls(self.vec, self.agents, self.steps_per_epoch, self.steps_per_episode,
                              global_critic_flag=self.global_critic_flag)
 

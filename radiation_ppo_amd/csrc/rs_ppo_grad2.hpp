@@ -46,8 +46,9 @@ __device__ __forceinline__ unsigned long long rs_k7_now() {
 #endif
 #endif
 #define RS_XRAW 400                                // per-wave landing zone of the group's 32 x 11 sample rows (352 floats, LDS-DMA);
-                                                   // between layer 1 and the next DMA it holds the [12][33] dz^T / statistics tile
-                                                   // (actor) or the tail of the stride-36 h2^T tile, the dz / loss rows and a row of ones (critic)
+                                                   // between layer 1 and the next DMA it holds the tail of the stride-36 h2^T tile and
+                                                   // behind it the [12][36] dz / statistics rows, which run on into xsc (actor), or
+                                                   // the dz / loss rows and a row of ones (critic)
 #define RS_XSC 192                                 // per-wave landing zone of the per-sample scalars: act (32 x int64), adv, logp_old, w, ret
 #define RS_G2_WAVE_FLOATS ((64 + 32) * RS_T2 + RS_XRAW + RS_XSC + 64)
 
@@ -61,6 +62,25 @@ __device__ __forceinline__ float rs_other_half(float x, int h) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(h ? r[0] : r[1]);
 }
+
+// The element-wise chains of the group loop run on explicit pairs, registers r and r + 1 of an accumulator: v_pk_add_f32 /
+// v_pk_mul_f32 / v_pk_fma_f32 do two values per issue slot (the translation unit is built without SLP packing, so nothing else
+// pairs up).  Every element keeps its operations and roundings.
+typedef float rs_f2 __attribute__((ext_vector_type(2)));
+
+// rs_tanh_scaled of the 16 values of an accumulator: 1 + e and fma(-2, rcp, 1) per pair around the two v_exp_f32 / v_rcp_f32
+__device__ __forceinline__ void rs_tanh_scaled16(f32x16& v) {
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        const rs_f2 e = (rs_f2){1.0f, 1.0f} + (rs_f2){__builtin_amdgcn_exp2f(v[r]), __builtin_amdgcn_exp2f(v[r + 1])};
+        const rs_f2 t = __builtin_elementwise_fma((rs_f2){-2.0f, -2.0f}, (rs_f2){__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)},
+                                                  (rs_f2){1.0f, 1.0f});
+        v[r] = t.x; v[r + 1] = t.y;
+    }
+}
+
+// d (1 - h^2) as fma(-(d h), h, d), a pair at a time
+__device__ __forceinline__ rs_f2 rs_dtanh2(rs_f2 d, rs_f2 hv) { return __builtin_elementwise_fma(-(d * hv), hv, d); }
 
 __device__ __forceinline__ void rs_stage32(float* T, const f32x16& v, int c, int h) {
 #pragma unroll
@@ -138,18 +158,20 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
     const int wave_g = bid * 8 + wid, n_waves = nblocks * 8;
 
     f32x16 acc2[2][2];
-    f32x4 acc1[4], acc3[4];
+    f32x4 acc1[4], acc3[2];                         // acc3: two 4x4x1 accumulators per network, see the dW3 phase
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc2[a][0][r] = 0.f; acc2[a][1][r] = 0.f; }
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
+    for (int r = 0; r < 4; ++r) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { acc1[a][r] = 0.f; acc3[a][r] = 0.f; }
-    // db3 and the loss statistics are per-sample scalars summed over samples: they ride in the dz^T tile (rows 0..NOUT-1: dz,
-    // rows 8..11: kl / entropy / clip fraction / surrogate terms, or the value-loss term) and are summed by eight extra
-    // 16x16x4 MFMAs per group against a B operand of ones -- no per-lane accumulators, no cross-lane reduction
+        for (int a = 0; a < 4; ++a) acc1[a][r] = 0.f;
+        acc3[0][r] = 0.f; acc3[1][r] = 0.f;
+    }
+    // db3 and the loss statistics are per-sample scalars summed over samples: they ride in the dz^T rows (rows 0..NOUT-1: dz,
+    // rows 8..11: kl / entropy / clip fraction / surrogate terms) and are summed by one more 4x4x1 chain per group against a B
+    // operand of ones -- no per-lane accumulators, no cross-lane reduction (actor; the critic's sums ride in acc3)
     f32x4 accs;
 #pragma unroll
     for (int r = 0; r < 4; ++r) accs[r] = 0.f;
@@ -253,8 +275,7 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         RS_STAMP(1);                                    // layer 1 MFMAs
 #pragma unroll
         for (int it = 0; it < 2; ++it)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) H1[it][r] = rs_tanh_scaled(H1[it][r]);
+            rs_tanh_scaled16(H1[it]);
 #pragma unroll
         for (int it = 0; it < 2; ++it)
 #pragma unroll
@@ -297,8 +318,7 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
 #endif
 #pragma unroll
         for (int it = 0; it < 2; ++it)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) H2[it][r] = rs_tanh_scaled(H2[it][r]);
+            rs_tanh_scaled16(H2[it]);
         RS_STAMP(4);                                    // tanh 2
         // output layer: out[o] = sum over the 32 units this lane holds of W3[o][unit] * h2[unit] (one fmaf chain per output, ascending
         // unit, from 0.0f), halves added across lane pairs.  Critic: on the VALU.  Actor: the same chains on the matrix pipe.
@@ -389,9 +409,7 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         RS_STAMP(6);                                    // loss derivative
 
         // ---------------- backward ----------------
-        // dz^T borrows the row landing zone (its rows were consumed by layer 1; the next group's DMA is issued after dW3):
-        // rows 0..NOUT-1 = dz, rows 8..11 = the statistics terms.  The critic lays the zone out differently, see its section
-        float* Dz = xraw;                                // [12][33]
+        // the dW3 operands borrow the row landing zone (its rows were consumed by layer 1; the next group's DMA is issued after dW3)
         if constexpr (NOUT == 1) {
             // One output row: dW3[unit] += sum_n dz[n] h2[unit][n], db3 += sum_n dz[n] and the value-loss sum as 2 x 32
             // v_mfma_f32_4x4x1_16b_f32 (K = 1: one instruction per sample, so instruction order is the chain order n = 0..31 the
@@ -430,42 +448,56 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
                 }
             }
         } else {
-        if (h == 0) {
+            // Eight output rows: dW3[o][unit] += sum_n dz[o][n] h2[unit][n] as two chains of 32 4x4x1 MFMAs, one per 32-unit half hf
+            // (K = 1: instruction order is the chain order n = 0..31 the 16x16x4 tiles had).  Lane l = 4b + j supplies
+            // A = dz[4 (b & 1) + j][n] = row l & 7 and B = h2[32 hf + 4 (b >> 1) + j][n], so register i of acc3[hf] in lane l is
+            // dW3[4 (b & 1) + i][32 hf + 4 (b >> 1) + j]: the 16 blocks are 2 output sets x 8 unit quads, no block is idle.
+            // db3 and the four statistics sums are ONE more chain of 32 onto accs with B = 1: lanes 0..11 supply rows 0..11 (dz, then
+            // the statistics terms), so register i of lanes 0 / 4 / 8 sums row i / 4 + i / 8 + i (what the lanes from 12 up
+            // collect is never read).  Its first 16 instructions sit between the first half's, its last 16 between the second
+            // half's, in ascending n: each chain fills the other's wait states.
+            // h2^T is staged one half at a time with a row stride of 36 floats and runs 96 floats into the row landing zone, as in
+            // the critic; the twelve A rows follow it, [12][36], and run on into xsc, whose scalars have been in registers since the
+            // top of the trip.  Both zones are free until the DMA issue below.  Every operand is an aligned ds_read_b128 of four
+            // samples; stride 36 puts the rows a 16-lane group reads into different banks.  Both lanes of a sample hold the same
+            // dz / sq, so both write all twelve rows: no branch on h.
+            constexpr int T4 = 36;
+            float* Az = xraw + 96;                       // [12][36]
+            static_assert(32 * T4 == 32 * RS_T2 + 96 && 96 + 12 * T4 <= RS_XRAW + RS_XSC, "h2^T tile and A rows end inside xraw + xsc");
 #pragma unroll
-            for (int o = 0; o < NOUT; ++o) Dz[o * RS_T2 + c] = dz[o];
-        } else {
+            for (int o = 0; o < NOUT; ++o) Az[o * T4 + c] = dz[o];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) Dz[(8 + q) * RS_T2 + c] = sq[q];
-        }
-        // R1/R2: dW3[o][unit] += sum_n dz[o][n] h2[unit][n]  (16x16x4 tiles, 8 k-steps), h2^T through Pt one 32-unit half at a time
+            for (int q = 0; q < 4; ++q) Az[(8 + q) * T4 + c] = sq[q];
+            const float* arow = Az + (lane & 7) * T4;
+            const float* srow = Az + min(l15, 11) * T4;
+            const float* brow = Pt + (4 * (lane >> 3) + (lane & 3)) * T4;
+            float4 av[8];
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            rs_wave_sync();                              // the previous readers of Pt are done
-            rs_stage32(Pt, H2[hf], c, h);
-            rs_wave_sync();
-            // A rows: o < NOUT -> dz, 8..11 -> statistics terms (they meet only the ones operand), everything else 0
-            const bool a_row = l15 < NOUT || (l15 >= 8 && l15 < 12);
-            float a_c = a_row ? Dz[l15 * RS_T2 + l4] : 0.0f;
-            float b_c[2];
+            for (int hf = 0; hf < 2; ++hf) {
+                rs_wave_sync();                          // the previous readers of Pt are done
 #pragma unroll
-            for (int u = 0; u < 2; ++u) b_c[u] = Pt[(16 * u + l15) * RS_T2 + l4];
+                for (int r = 0; r < 16; ++r) Pt[rs_kappa(r, h) * T4 + c] = H2[hf][r];
+                rs_wave_sync();
+                if (hf == 0) {
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                float a_n = 0.f, b_n[2] = {0.f, 0.f};
-                if (s + 1 < 8) {
-                    a_n = a_row ? Dz[l15 * RS_T2 + 4 * (s + 1) + l4] : 0.0f;
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) b_n[u] = Pt[(16 * u + l15) * RS_T2 + 4 * (s + 1) + l4];
+                    for (int q = 0; q < 8; ++q) av[q] = *reinterpret_cast<const float4*>(arow + 4 * q);
                 }
-                const float a_dz = (l15 < NOUT) ? a_c : 0.0f;      // the statistics rows must not leak into dW3
+                float4 bv[8], zv[4];
 #pragma unroll
-                for (int u = 0; u < 2; ++u) acc3[2 * hf + u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_dz, b_c[u], acc3[2 * hf + u], 0, 0, 0);
-                if (hf == 0) accs = __builtin_amdgcn_mfma_f32_16x16x4f32(a_c, 1.0f, accs, 0, 0, 0);   // row sums: db3 and the statistics
-                a_c = a_n;
+                for (int q = 0; q < 4; ++q) zv[q] = *reinterpret_cast<const float4*>(srow + 16 * hf + 4 * q);
 #pragma unroll
-                for (int u = 0; u < 2; ++u) b_c[u] = b_n[u];
+                for (int q = 0; q < 8; ++q) bv[q] = *reinterpret_cast<const float4*>(brow + 4 * q);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const float z0 = (q & 1) ? zv[q >> 1].z : zv[q >> 1].x, z1 = (q & 1) ? zv[q >> 1].w : zv[q >> 1].y;
+                    acc3[hf] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].x, bv[q].x, acc3[hf], 0, 0, 0);
+                    accs = __builtin_amdgcn_mfma_f32_4x4x1f32(z0, 1.0f, accs, 0, 0, 0);
+                    acc3[hf] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].y, bv[q].y, acc3[hf], 0, 0, 0);
+                    acc3[hf] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].z, bv[q].z, acc3[hf], 0, 0, 0);
+                    accs = __builtin_amdgcn_mfma_f32_4x4x1f32(z1, 1.0f, accs, 0, 0, 0);
+                    acc3[hf] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].w, bv[q].w, acc3[hf], 0, 0, 0);
+                }
             }
-        }
         }
         RS_STAMP(7);                                    // dW3
         // dh2 = W3^T dz, dpre2 = dh2 * (1 - h2^2) in place of H2
@@ -481,23 +513,26 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
                     t = __builtin_amdgcn_mfma_f32_32x32x2f32(w3tf[(it * 4 + s) * 64 + lane], b, t, 0, 0, 0);
                 }
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { const float hv = H2[it][r]; H2[it][r] = fmaf(-(t[r] * hv), hv, t[r]); }
+                for (int r = 0; r < 16; r += 2) {
+                    const rs_f2 d = rs_dtanh2((rs_f2){t[r], t[r + 1]}, (rs_f2){H2[it][r], H2[it][r + 1]});
+                    H2[it][r] = d.x; H2[it][r + 1] = d.y;
+                }
             }
         } else {
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float hv = H2[kt][r];
-                    const float d = w3v[kt * 16 + r] * dz[0];
-                    H2[kt][r] = fmaf(-(d * hv), hv, d);
+                for (int r = 0; r < 16; r += 2) {
+                    const rs_f2 d = (rs_f2){w3v[kt * 16 + r], w3v[kt * 16 + r + 1]} * (rs_f2){dz[0], dz[0]};
+                    const rs_f2 e = rs_dtanh2(d, (rs_f2){H2[kt][r], H2[kt][r + 1]});
+                    H2[kt][r] = e.x; H2[kt][r + 1] = e.y;
                 }
         }
         // the landing zones are free again: fetch the NEXT group's rows and scalars behind the rest of this group
         {
             const int gn_raw = wave_g + (trip + 1) * n_waves;
             const int gn = gn_raw < groups ? gn_raw : groups - 1;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // every ds_read of Dz / xsc has returned
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // every ds_read of the dW3 operands / xsc has returned
             dma_rows(gn);
             dma_scal(gn);
         }
@@ -552,10 +587,10 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
 #pragma unroll
         for (int it = 0; it < 2; ++it)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float hv = Qt[(32 * it + rs_kappa(r, h)) * RS_T2 + c];
-                const float d = D1[it][r];
-                D1[it][r] = fmaf(-(d * hv), hv, d);
+            for (int r = 0; r < 16; r += 2) {
+                const rs_f2 hv = {Qt[(32 * it + rs_kappa(r, h)) * RS_T2 + c], Qt[(32 * it + rs_kappa(r + 1, h)) * RS_T2 + c]};
+                const rs_f2 d = rs_dtanh2((rs_f2){D1[it][r], D1[it][r + 1]}, hv);
+                D1[it][r] = d.x; D1[it][r + 1] = d.y;
             }
         rs_wave_sync();
         RS_STAMP(9);                                    // R3 dh1 MFMAs + dpre2^T staging + dpre1
@@ -647,8 +682,8 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         for (int wv = 1; wv < 8; ++wv) v += smem_f[wv * (64 * 64) + i];
         outp[64 * RS_IN + 64 + i] = v;
     }
-    // accs (16x16 D layout: row 4*(lane>>4) + q, every column identical): rows 0..NOUT-1 = db3, rows 8..11 = statistics sums
-    // of this wave; bring them to lane 0 (row r lives in lanes with lane>>4 == r/4, register r%4)
+    // The actor's accs (4x4x1 blocks 0..2, every column identical): rows 0..NOUT-1 = db3, rows 8..11 = statistics sums of this
+    // wave; bring them to lane 0 (row r lives in lane 4 (r / 4), register r % 4)
     // The critic's 4x4x1 accumulators: acc3[hf][0] of lane l < 32 = dW3 of unit 32 hf + l, acc3[0][0] / acc3[0][1] of the upper lanes
     // = db3 / the value-loss sum.
     float db3r[NOUT];
@@ -658,8 +693,8 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         sv[0] = 0.0; sv[1] = 0.0; sv[2] = 0.0; sv[3] = (double)__shfl(acc3[0][1], 32); sv[4] = 0.0;
     } else {
 #pragma unroll
-        for (int o = 0; o < NOUT; ++o) db3r[o] = __shfl(accs[o & 3], 16 * (o >> 2));
-        const float t0 = __shfl(accs[0], 32), t1 = __shfl(accs[1], 32), t2 = __shfl(accs[2], 32), t3 = __shfl(accs[3], 32);
+        for (int o = 0; o < NOUT; ++o) db3r[o] = __shfl(accs[o & 3], 4 * (o >> 2));
+        const float t0 = __shfl(accs[0], 8), t1 = __shfl(accs[1], 8), t2 = __shfl(accs[2], 8), t3 = __shfl(accs[3], 8);
         sv[0] = (double)t0; sv[1] = (double)t1; sv[2] = (double)t2; sv[3] = 0.0; sv[4] = (double)t3;
     }
     constexpr int RS_RSTR = (RS_REST + 1) & ~1;       // slab stride of round two (even: the doubles behind the slabs stay aligned)
@@ -675,9 +710,15 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
                 const int row = 16 * u + 4 * l4_e + q;
                 if (l15_e < RS_IN) g_w1[row * RS_IN + l15_e] = acc1[u][q];
                 if (l15_e == RS_IN) g_b1[row] = acc1[u][q];
-                const int o = 4 * l4_e + q;
-                if (NOUT == 8 && o < NOUT) g_w3[o * 64 + 16 * u + l15_e] = acc3[u][q];
             }
+        if constexpr (NOUT == 8) {
+            // register i of acc3[hf] in lane 4b + j = dW3[4 (b & 1) + i][32 hf + 4 (b >> 1) + j]
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    g_w3[(4 * ((lane_e >> 2) & 1) + i) * 64 + 32 * hf + 4 * (lane_e >> 3) + (lane_e & 3)] = acc3[hf][i];
+        }
         if (NOUT == 1 && lane_e < 32) { g_w3[lane_e] = acc3[0][0]; g_w3[32 + lane_e] = acc3[1][0]; }
         if (lane_e == 0) {
 #pragma unroll

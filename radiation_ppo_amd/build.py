@@ -48,7 +48,10 @@ def _newer(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True, defines=(), suffix: str = "") -> str:
     """defines / suffix: a diagnostic variant next to the product library, e.g. build(defines=["RS_K7_STAMPS"],
-    suffix="_stamps") -> lib/librs_hip_stamps.so (selected with RS_LIB_PATH; see scripts/k7_stamps.py)."""
+    suffix="_stamps") -> lib/librs_hip_stamps.so (selected with RS_LIB_PATH; see scripts/k7_stamps.py).
+    --skew [--prio N] on the command line: -DRS_K7_SKEW (the partner-gap table of scripts/k7_partner_gap.py, no phase stamps)
+    with the priority rule RS_K7_PRIO=N of rs_ppo_grad2.hpp -> lib/librs_hip_skew[_prioN].so; --prio N alone: the product
+    kernels with that rule -> lib/librs_hip_prioN.so."""
     deps = _deps()
     lib = LIB.replace(".so", suffix + ".so")
     if not force and not _newer(lib, deps):
@@ -84,7 +87,12 @@ def build(force: bool = False, verbose: bool = True, defines=(), suffix: str = "
 
 
 if __name__ == "__main__":
+    prio = sys.argv[sys.argv.index("--prio") + 1] if "--prio" in sys.argv else None
     if "--stamps" in sys.argv:
         build(force="--force" in sys.argv, defines=["RS_K7_STAMPS"], suffix="_stamps")
+    elif "--skew" in sys.argv or prio is not None:
+        skew = "--skew" in sys.argv
+        build(force="--force" in sys.argv, defines=(["RS_K7_SKEW"] if skew else []) + ([f"RS_K7_PRIO={int(prio)}"] if prio is not None else []),
+              suffix=("_skew" if skew else "") + (f"_prio{int(prio)}" if prio is not None else ""))
     else:
         build(force="--force" in sys.argv)

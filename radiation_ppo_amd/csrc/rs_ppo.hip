@@ -351,7 +351,7 @@ static int rs_launch_k7(const rs_mlp_params* actor, const rs_mlp_params* critic,
                hipFuncSetAttribute(reinterpret_cast<const void*>(rs_ppo_grad2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess)
         return RS_ERR_HIP;
     int threads = 512;
-#ifdef RS_K7_STAMPS
+#if defined(RS_K7_STAMPS) || defined(RS_K7_SKEW)
     // diagnostic build only: RS_K7_THREADS=256 runs ONE wave per SIMD (half of the groups are skipped: results are wrong, the
     // per-phase cycle counts are those of a wave that has its SIMD to itself)
     if (const char* e = getenv("RS_K7_THREADS")) threads = atoi(e) == 256 ? 256 : 512;
@@ -405,6 +405,19 @@ int rs_debug_k7_stamps(unsigned long long* out, int clear) {
     if (clear) {
         unsigned long long z[2 * RS_K7_NPH] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(rs_k7_stamp_table), z, sizeof(z)) != hipSuccess) return RS_ERR_HIP;
+    }
+    return RS_OK;
+}
+#endif
+
+#ifdef RS_K7_SKEW
+// diagnostic build only: read (and optionally clear) the partner-gap table of rs_ppo_grad2_body; out[2][RS_K7_NSK = 66]
+int rs_debug_k7_skew(unsigned long long* out, int clear) {
+    if (hipDeviceSynchronize() != hipSuccess) return RS_ERR_HIP;
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(rs_k7_skew_table), sizeof(unsigned long long) * 2 * RS_K7_NSK) != hipSuccess) return RS_ERR_HIP;
+    if (clear) {
+        unsigned long long z[2 * RS_K7_NSK] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(rs_k7_skew_table), z, sizeof(z)) != hipSuccess) return RS_ERR_HIP;
     }
     return RS_OK;
 }

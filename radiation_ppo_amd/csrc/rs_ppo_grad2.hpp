@@ -45,6 +45,66 @@ __device__ __forceinline__ unsigned long long rs_k7_now() {
 #define RS_STAMP(i) __builtin_amdgcn_sched_barrier(0)
 #endif
 #endif
+// Diagnostic build only (-DRS_K7_SKEW, scripts/k7_partner_gap.py): how far apart do the waves of a workgroup leave the trip loop, and
+// how long do they then wait at the epilogue's first barrier?  Three s_memtime reads per wave and launch (end of the last trip,
+// release of that barrier, end of the kernel, each counted from kernel entry) and none inside the loop: no per-phase stamp, no fence,
+// so the trips overlap as in the product build.  Summed per network and wave slot in a table no other code reads:
+//   [0..7] loop end  [8..15] barrier release  [16..23] kernel end  [24..55] waves of slot w seen on SIMD s, at [24 + 4 w + s]
+//   [56..59] loop end of wave w + 4 minus loop end of wave w, per workgroup  [60..63] the same as |.|  [64] launches  [65] 100 MHz ticks
+// The loop ends cross the waves through eight LDS slots behind the progress words.
+#ifdef RS_K7_SKEW
+#define RS_K7_NSK 66
+__device__ unsigned long long rs_k7_skew_table[2][RS_K7_NSK];
+__device__ __forceinline__ unsigned long long rs_k7_clock() {
+    unsigned long long t;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    return t;
+}
+#define RS_SKEW_LDS_FLOATS 16
+#define RS_SKEW_ENTRY const unsigned long long sk_rt0 = __builtin_amdgcn_s_memrealtime(); const unsigned long long sk_t0 = rs_k7_clock();
+#define RS_SKEW_LOOP_END(slots) const unsigned long long sk_t1 = rs_k7_clock() - sk_t0; \
+    if ((threadIdx.x & 63) == 0) (slots)[threadIdx.x >> 6] = sk_t1;
+#define RS_SKEW_RELEASED const unsigned long long sk_tb = rs_k7_clock() - sk_t0;
+#define RS_SKEW_PAIRS(net, slots) if ((threadIdx.x & 63) == 0 && threadIdx.x < 256 && blockDim.x == 512) { \
+        const long long d_ = (long long)((slots)[(threadIdx.x >> 6) + 4] - (slots)[threadIdx.x >> 6]); \
+        atomicAdd(&rs_k7_skew_table[net][56 + (threadIdx.x >> 6)], (unsigned long long)d_); \
+        atomicAdd(&rs_k7_skew_table[net][60 + (threadIdx.x >> 6)], (unsigned long long)(d_ < 0 ? -d_ : d_)); }
+// HW_REG_HW_ID (register 4), bits 5:4 = SIMD_ID: s_getreg_b32 with simm16 = id | offset << 6 | (size - 1) << 11
+#define RS_SKEW_EXIT(net) do { const unsigned long long sk_t2 = rs_k7_clock() - sk_t0; if ((threadIdx.x & 63) == 0) { \
+        const int w_ = threadIdx.x >> 6; unsigned long long* T_ = rs_k7_skew_table[net]; \
+        atomicAdd(&T_[w_], sk_t1); atomicAdd(&T_[8 + w_], sk_tb); atomicAdd(&T_[16 + w_], sk_t2); \
+        atomicAdd(&T_[24 + 4 * w_ + (int)__builtin_amdgcn_s_getreg(4 | (4 << 6) | (1 << 11))], 1ull); \
+        atomicAdd(&T_[65], __builtin_amdgcn_s_memrealtime() - sk_rt0); \
+        if (bid == 0 && w_ == 0) atomicAdd(&T_[64], 1ull); } } while (0)
+#else
+#define RS_SKEW_LDS_FLOATS 0
+#define RS_SKEW_ENTRY
+#define RS_SKEW_LOOP_END(slots)
+#define RS_SKEW_RELEASED
+#define RS_SKEW_PAIRS(net, slots)
+#define RS_SKEW_EXIT(net)
+#endif
+
+// Partner balance.  The two waves of a SIMD (wave slots w and w + 4 of the 512-thread workgroup) share its issue slots by priority
+// first and age second, so at equal priority the older one runs ahead, ends its trips early and idles at the epilogue's barrier
+// while its partner finishes alone -- for 134 us of the actor's 585 at M = 1 966 080, and a wave alone on its SIMD delivers 0.88 of the
+// paired throughput (profiles/r13_k7_partner_balance_ab.txt).  Every wave therefore publishes its progress in an LDS word of its own, reads its partner's once per trip and takes priority 1 when it is
+// behind (on a tie: the younger wave), priority 0 when it is ahead.  Nothing waits on the word: the read races with the partner's
+// store by design (relaxed workgroup-scope atomics) and only moves issue slots between the two; which groups a wave sums, and in
+// which order, does not change.  RS_K7_PRIO selects the rule for A/B builds:
+//   0  none (both waves at priority 0 throughout)
+//   1  progress words, compared at the top of every trip (the product build)
+//   2  progress words, compared at the top of the trip and again after the loss
+//   3  no LDS: bit RS_K7_PRIO_BIT of s_memtime, flipped for the younger half, read at the top of the trip
+//   4  control: static priority 1 for wave slots 4..7
+#ifndef RS_K7_PRIO
+#define RS_K7_PRIO 1
+#endif
+#ifndef RS_K7_PRIO_BIT
+#define RS_K7_PRIO_BIT 15
+#endif
+#define RS_K7_PROG_FLOATS 8                        // the eight progress words, behind the last wave's zones
+
 #define RS_XRAW 400                                // per-wave landing zone of the group's 32 x 11 sample rows (352 floats, LDS-DMA);
                                                    // between layer 1 and the next DMA it holds the tail of the stride-36 h2^T tile and
                                                    // behind it the [12][36] dz / statistics rows, which run on into xsc (actor), or
@@ -53,7 +113,7 @@ __device__ __forceinline__ unsigned long long rs_k7_now() {
 #define RS_G2_WAVE_FLOATS ((64 + 32) * RS_T2 + RS_XRAW + RS_XSC + 64)
 
 __host__ __device__ constexpr int rs_grad2_lds_floats(int nout) {
-    return ((rs_mlp_lds_floats(nout) + 3) & ~3) + 2 * 2 * 16 * 64 + 2 * 4 * 64 + 8 * RS_G2_WAVE_FLOATS;
+    return ((rs_mlp_lds_floats(nout) + 3) & ~3) + 2 * 2 * 16 * 64 + 2 * 4 * 64 + 8 * RS_G2_WAVE_FLOATS + RS_K7_PROG_FLOATS + RS_SKEW_LDS_FLOATS;
 }
 
 // the value lane l ^ 32 holds (__shfl_xor(x, 32) without the LDS crossbar): v_permlane32_swap exchanges the upper half of its
@@ -103,6 +163,7 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
     if (snap && bid == 0 && threadIdx.x == 0) { snap[0] = ust->adam_step; snap[1] = ust->stopped; }
     if (stop && *stop) return;
     RS_STAMP_ENTRY
+    RS_SKEW_ENTRY
     RsMlpLds<NOUT> W;
     W.carve(smem_f);
     float* w2tf = smem_f + ((rs_mlp_lds_floats(NOUT) + 3) & ~3);   // 16-byte aligned; [2 it][2 kt][4 r4][64 lanes][4]: W2[32kt + kappa(r, l>>5)][32it + (l&31)]
@@ -116,6 +177,11 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
     float* xraw = Pt + 32 * RS_T2;                             // [32][11]  the group's sample rows as they lie in HBM (LDS-DMA target)
     float* xsc = xraw + RS_XRAW;                               // [192]     the group's per-sample scalars (LDS-DMA target)
     float* dbl = xsc + RS_XSC;                                 // [64]      db2 accumulators of this wave
+    // [8] progress words, one per wave: outside every zone the trip loop or the look-ahead DMA writes
+    int* prog = reinterpret_cast<int*>(w3tf + 2 * 4 * 64 + 8 * RS_G2_WAVE_FLOATS);
+#ifdef RS_K7_SKEW
+    unsigned long long* sk_slots = reinterpret_cast<unsigned long long*>(prog + RS_K7_PROG_FLOATS);      // [8] loop ends
+#endif
     // Fragment fill, one pass per array and ONE barrier.  Not RsMlpLds::fill (the forward kernel's): K7 wants W2 in the b128 form
     // below, the layer-1 bias inside w1f, and never reads W.b1.
     // layer-1 fragments with the bias in the padded input column k = 11 (k-step 5, upper lane half)
@@ -151,6 +217,7 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
     for (int i = threadIdx.x; i < 64; i += blockDim.x) W.b2[i] = RS_TANH_PRESCALE * prm.b2[i];
     for (int i = threadIdx.x; i < NOUT; i += blockDim.x) W.b3[i] = prm.b3[i];
     dbl[lane] = 0.0f;
+    if (threadIdx.x < RS_K7_PROG_FLOATS) prog[threadIdx.x] = 0;
     __syncthreads();
 
     const int M = B.M;
@@ -234,9 +301,28 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
             w3v[4 * b + 0] = t.x; w3v[4 * b + 1] = t.y; w3v[4 * b + 2] = t.z; w3v[4 * b + 3] = t.w;
         }
     }
+    // partner balance (see RS_K7_PRIO): publish `at`, read the partner's word once, act on whatever is there
+    auto balance = [&](const int at) {
+#if RS_K7_PRIO == 1 || RS_K7_PRIO == 2
+        if (lane == 0) __hip_atomic_store(prog + wid, at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const int theirs = __builtin_amdgcn_readfirstlane(__hip_atomic_load(prog + (wid ^ 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        // s_setprio is scalar and ignores EXEC: the condition is made of SGPR values only (wid and theirs come from readfirstlane)
+        // behind the partner, or level with it and the younger of the two (wid >> 2 is 1 for the wave slots 4..7)
+        if (theirs + (wid >> 2) > at) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+#elif RS_K7_PRIO == 3
+        const int bit = (int)(__builtin_amdgcn_readfirstlane((int)(__builtin_amdgcn_s_memtime() >> RS_K7_PRIO_BIT)) & 1) ^ (wid >> 2);
+        if (bit) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+#endif
+    };
+#if RS_K7_PRIO == 4
+    if (wid >= 4) __builtin_amdgcn_s_setprio(1);
+#endif
     RS_STAMP_DECL
     for (int trip = 0; trip < trips; ++trip) {
         RS_STAMP(15);                                   // loop overhead / tail of the previous group
+        balance(RS_K7_PRIO == 2 ? 2 * trip : trip);
         const int gi_raw = wave_g + trip * n_waves;
         const int gi = gi_raw < groups ? gi_raw : groups - 1;
         const int m = gi * 32 + c;
@@ -407,6 +493,9 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
             sq[0] = wi * diff * diff; sq[1] = 0.f; sq[2] = 0.f; sq[3] = 0.f;
         }
         RS_STAMP(6);                                    // loss derivative
+#if RS_K7_PRIO == 2
+        balance(2 * trip + 1);
+#endif
 
         // ---------------- backward ----------------
         // the dW3 operands borrow the row landing zone (its rows were consumed by layer 1; the next group's DMA is issued after dW3)
@@ -659,10 +748,16 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
     int tid_e = threadIdx.x;
     asm volatile("" : "+v"(tid_e));
     const int lane_e = tid_e & 63, h_e = lane_e >> 5, c_e = lane_e & 31, l15_e = lane_e & 15, l4_e = lane_e >> 4;
+#if RS_K7_PRIO != 0
+    __builtin_amdgcn_s_setprio(0);                    // the epilogue runs at equal priority
+#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last trip's look-ahead DMA has landed: nothing writes LDS behind our back
     // (dbl lives in the region being overwritten: read it first); the critic's sums are in registers, unit 32 it + c in lane (c, it)
     const float db2v = NOUT == 1 ? (h_e ? db2r[1] : db2r[0]) : dbl[lane_e];
+    RS_SKEW_LOOP_END(sk_slots)
     __syncthreads();                                  // every wave is done with its staging tiles and the fragments
+    RS_SKEW_RELEASED
+    RS_SKEW_PAIRS(NOUT == 8 ? 0 : 1, sk_slots)
     float* outp = partial + (size_t)bid * rs_net_params(NOUT);
     {
         float* g_w2 = smem_f + wid * (64 * 64);
@@ -741,6 +836,7 @@ __device__ __forceinline__ void rs_ppo_grad2_body(const RsMlpParams prm, const r
         stat_partial[(size_t)bid * 5 + tid_e] = v;
     }
     RS_STAMP_EXIT(NOUT == 8 ? 0 : 1);
+    RS_SKEW_EXIT(NOUT == 8 ? 0 : 1);
 }
 
 template <int NOUT>

@@ -1,5 +1,6 @@
 """Float64 references and the tolerance rule shared by the float64 tests of the sized kernels (test_rnn_sized_f64_gpu.py,
-test_pfgru_sized_f64_gpu.py) and their CPU self-checks (test_f64_references.py).
+test_pfgru_sized_f64_gpu.py), of the feed-forward PPO kernels and of the RAD-TEAM actor loss and heads (test_cnn_heads_f64_gpu.py), and
+their CPU self-checks (test_f64_references.py).
 
 The references are the project's own modules copied and cast (copy.deepcopy(m).double().cpu()); what is written out here by hand is
 the library branch of RNNAgentPPO.a2c_losses behind the GRU (heads_loss_f64), the collector's inverse-CDF draw (draw_f64), and the
@@ -734,3 +735,284 @@ def close_ratio(got, ref, rtol, noise, tiny):
     a, b = got.detach().double().cpu(), ref.detach().double().cpu()
     scale = float(b.abs().max()) if b.numel() else 0.0
     return float(((a - b).abs() / (rtol * b.abs() + noise * scale + tiny)).max()) if b.numel() else 0.0
+
+
+# ------------------------------------------------------------------------------------------------ RAD-TEAM actor loss, heads (rs_cnn_loss.hip)
+AL_SIZES = (1, 63, 64, 65, 255, 256, 257, 577)     # the edges of a 64-lane wave and of a 256-lane block; 577 = 2 x 256 + 64 + 1
+AL_CLIPS = (0.2, 0.1)
+AL_CASES = [(S, clip) for S in AL_SIZES for clip in AL_CLIPS]
+AL_ZERO = (257, 0.2, 40)             # the zero-weight-rows case: (S, clip, rows with w = 0)
+AL_STATS = ("kl", "entropy", "clipfrac", "loss")
+HEAD_SIZES = (1, 63, 64, 65, 130)
+HEAD_AGENTS = 3
+HEAD_K2 = 2.0 * (33 ** 0.5 + 1)      # SAFETY x a sequential fmaf chain of depth 32 behind the bias (+ 1: the result's own rounding), on mag2
+HEAD_K3 = 2.0 * (17 ** 0.5 + 1)      # the same for the chain of depth 16, on mag3
+
+
+def al_case_id(c):
+    return f"S{c[0]}-clip{c[1]:g}"
+
+
+def wave_start(S):
+    """First sample of the last 64-lane wave of rs_actor_loss (full or partial)."""
+    return (S + 63) // 64 * 64 - 64
+
+
+def wave_weights(S, g):
+    """ff_weights with the 64-lane wave as the group: float32 weights, sum 1, half of it on the last wave (full or partial), half on
+    the samples before it, each half spread as uniform(0.25, 1.75).  S <= 64: the one wave is the whole batch."""
+    def spread(n, total):
+        u = 0.25 + 1.5 * torch.rand(n, generator=g, dtype=torch.float64)
+        return u * (total / u.sum())
+    s = wave_start(S)
+    w = torch.empty(S, dtype=torch.float64)
+    if s == 0:
+        w[:] = spread(S, 1.0)
+    else:
+        w[:s] = spread(s, 0.5)
+        w[s:] = spread(S - s, 0.5)
+    return w.float()
+
+
+def bootstrap_mask(N, g):
+    """The bootstrap round's env mask [N] uint8 of the collector tests: p = 0.5, env 0 set, env 1 clear; past 128 envs one whole
+    64-group (64..127) is left without a masked env and the last env is set."""
+    mask = (torch.rand(N, generator=g) < 0.5).to(torch.uint8)
+    mask[0] = 1
+    if N > 1:
+        mask[1] = 0
+    if N > 128:
+        mask[64:128] = 0
+        mask[N - 1] = 1
+    return mask
+
+
+class ActorLoss64:
+    """What actor_loss_f64 returns.  stats [4]: kl, entropy, clip fraction, loss; stat_mags [4]: the sums of the absolute per-sample
+    terms they are rounded against (ff_loss_f64's, without the value-loss and alpha parts); dlogits [S, 8] and dl_mags [S, 8] =
+    |g_lp| (1[a = j] + p_j); ratio [S]: the float64 PPO ratios."""
+    stats = stat_mags = dlogits = dl_mags = ratio = None
+
+
+def actor_loss_f64(logits, act, adv, logp_old, w, clip):
+    """compute_loss_pi behind the logits (the unfused branch of CNNAgentPPO.update_agent: loss = -sum w min(ratio adv, clamp(ratio, 1 -
+    clip, 1 + clip) adv), statistics kl = sum w (logp_old - logp), sum w entropy, sum w [ratio outside the clip range]) on the float32
+    inputs widened, forward and backward written out by hand as ff_loss_f64 does behind its forward pass (test_f64_references.py
+    holds dlogits to float64 autograd): live = inside | (s1 < s2), g_lp = -w live adv ratio, d_j = g_lp (1[a = j] - p_j)."""
+    res = ActorLoss64()
+    with torch.no_grad():
+        lg, adv, lpo, w = (t.detach().double().cpu() for t in (logits, adv, logp_old, w))
+        act = act.detach().cpu().long()
+        S = lg.shape[0]
+        lp_all = torch.log_softmax(lg, dim=-1)
+        p = lp_all.exp()
+        logp = lp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1)
+        ratio = torch.exp(logp - lpo)
+        lo, hi = 1 - clip, 1 + clip
+        s1, s2 = ratio * adv, torch.clamp(ratio, lo, hi) * adv
+        surr = torch.minimum(s1, s2)
+        live = ((ratio >= lo) & (ratio <= hi)) | (s1 < s2)
+        g_lp = -w * torch.where(live, adv, torch.zeros_like(adv)) * ratio
+        onehot = torch.zeros(S, 8, dtype=torch.float64).scatter_(1, act.unsqueeze(-1), 1.0)
+        res.dlogits = g_lp.unsqueeze(-1) * (onehot - p)
+        res.dl_mags = g_lp.abs().unsqueeze(-1) * (onehot + p)
+        cf = (w * ((ratio > hi) | (ratio < lo)).double()).sum()
+        res.stats = torch.stack([(w * (lpo - logp)).sum(), (w * -(p * lp_all).sum(-1)).sum(), cf, -(w * surr).sum()])
+        res.stat_mags = torch.stack([(w * (lpo.abs() + logp.abs())).sum(), (w * (p * (1 + lp_all.abs())).sum(-1)).sum(), cf,
+                                     (w * surr.abs() * (1 + logp.abs())).sum()])
+        res.ratio = ratio
+    return res
+
+
+class ALCase:
+    pass
+
+
+_AL_CACHE = {}
+
+
+def al_case(S, clip, zero_rows=0):
+    """One case of the rs_actor_loss tests, built once on the CPU and shared: float32 logits = randn x 1.5, act, adv = randn, w =
+    wave_weights, logp_old = logp64(act) - log(target ratio) rounded to float32 with the targets of target_ratios(S, g, clip, margin =
+    0.02), as ff_case builds it.  The LAST sample's advantage gets the sign that leaves its gate live (ratio above the range: adv < 0,
+    below it: adv > 0): where the last wave is that one sample (S = 65, 257, 577) a lost wave must show in dlogits, which a clipped
+    sample's zero row would hide.  Asserted (conditions, not allowances): no float64 ratio from the ROUNDED logp_old within 0.01 of
+    1 +- clip; every input finite; S >= 63: all three ratio regions and both advantage signs occur.
+    zero_rows: that many scattered rows get w = 0 and adv x 1e6 (finite), the other weights are renormalised; the reference is
+    computed with those rows deleted (c.keep)."""
+    key = (S, clip, zero_rows)
+    if key in _AL_CACHE:
+        return _AL_CACHE[key]
+    c = ALCase()
+    g = torch.Generator().manual_seed(11 * S + int(round(1000 * clip)) + zero_rows)
+    c.S, c.clip = S, clip
+    c.logits = torch.randn(S, 8, generator=g) * 1.5
+    c.act = torch.randint(0, 8, (S,), generator=g)
+    c.adv = torch.randn(S, generator=g)
+    c.w = wave_weights(S, g)
+    target = target_ratios(S, g, clip, margin=0.02)
+    if float(target[-1]) > 1 + clip:
+        c.adv[-1] = -c.adv[-1].abs()
+    elif float(target[-1]) < 1 - clip:
+        c.adv[-1] = c.adv[-1].abs()
+    keep = torch.ones(S, dtype=torch.bool)
+    if zero_rows:
+        dead = torch.randperm(S, generator=g)[:zero_rows]
+        keep[dead] = False
+        c.adv[dead] *= 1e6
+        c.w[dead] = 0.0
+        c.w = (c.w.double() / c.w.double().sum()).float()
+    lp64 = torch.log_softmax(c.logits.double(), dim=-1).gather(-1, c.act.unsqueeze(-1)).squeeze(-1)
+    c.lpo = (lp64 - torch.log(target)).float()
+    c.keep = keep
+    c.batch = (c.logits, c.act, c.adv, c.lpo, c.w)
+    c.ref = actor_loss_f64(*(t[keep] for t in c.batch), clip)
+    r = torch.exp(lp64 - c.lpo.double())
+    assert float(torch.minimum((r - (1 - clip)).abs(), (r - (1 + clip)).abs()).min()) >= 0.01, "a ratio within 0.01 of a clip edge"
+    assert all(bool(torch.isfinite(t).all()) for t in (c.logits, c.adv, c.lpo, c.w))
+    if S >= 63:
+        assert bool((r < 1 - clip).any()) and bool((r > 1 + clip).any()) and bool(((r > 1 - clip) & (r < 1 + clip)).any()), "a ratio region is empty"
+        assert bool((c.adv > 0).any()) and bool((c.adv < 0).any())
+    c.spread = float((c.logits.max(dim=-1).values - c.logits.min(dim=-1).values).max())
+    _AL_CACHE[key] = c
+    return c
+
+
+def al_spread():
+    """The largest logit spread max_j lg_j - min_j lg_j over every case of the rs_actor_loss tests (AL_CASES and AL_ZERO)."""
+    return max([al_case(S, clip).spread for S, clip in AL_CASES] + [al_case(*AL_ZERO).spread])
+
+
+def actor_error_model(spread):
+    """The float32 error model of rs_actor_loss in units of U: the E_lp, E_p, E_glp, E_dz lines of ff_error_model with E_out = 0 (the
+    logits are inputs, exact), at its SAFETY = 2, plus the rounding of lg_j - mx, up to 0.5 ulp of the largest logit spread <= spread
+    U absolute (the feed-forward cases keep |lg - mx| near 1 and count it as 1).  k_dl: the multiple of U |g_lp| (1[a = j] + p_j) an
+    element of dlogits is allowed; k_stat: the same per-sample term plus the 64-lane butterfly that forms a wave's row of stats, depth
+    6, one rounding of the partial sum per level (the host adds the rows in float64: nothing)."""
+    SAFETY = 2.0
+    E_lp = _ff_lp_term(0.0) + spread
+    E_p = E_lp + 21
+    E_glp = E_lp + 3 + 2
+    E_dz = E_glp + E_p + 1
+    return dict(E_lp=SAFETY * E_lp, k_dl=SAFETY * E_dz, k_stat=SAFETY * (E_dz + 6))
+
+
+def actor_ratios(got_stats, got_dl, ref, model=None):
+    """[(block, worst |got - ref| / allowed)] over the four statistics and dlogits (left out when got_dl is None), allowed = FF_RTOL |ref|
+    + k U mag + FF_TINY with k = actor_error_model(al_spread())'s k_stat / k_dl."""
+    m = model or actor_error_model(al_spread())
+    out = []
+    gs = torch.as_tensor(got_stats).detach().double().cpu().reshape(4)
+    for q, name in enumerate(AL_STATS):
+        allowed = FF_RTOL * abs(float(ref.stats[q])) + m["k_stat"] * U * float(ref.stat_mags[q]) + FF_TINY
+        err = abs(float(gs[q]) - float(ref.stats[q]))
+        out.append((name, err / allowed if err == err else float("inf")))
+    if got_dl is not None:
+        gd = got_dl.detach().double().cpu()
+        assert gd.shape == ref.dlogits.shape, (gd.shape, ref.dlogits.shape)
+        ratio = (gd - ref.dlogits).abs() / (FF_RTOL * ref.dlogits.abs() + m["k_dl"] * U * ref.dl_mags + FF_TINY)
+        ratio = torch.where(torch.isfinite(gd), ratio, torch.full_like(ratio, float("inf")))
+        out.append(("dlogits", float(ratio.max())))
+    return out
+
+
+def check_actor(got_stats, got_dl, ref, name, report=None):
+    """Every statistic and dlogits within the rule (actor_ratios); every block over its allowance is named.  report: a list that
+    receives a line `name | block ratio ...`."""
+    ratios = actor_ratios(got_stats, got_dl, ref)
+    if report is not None:
+        report.append(f"{name} | " + " ".join(f"{b} {r:.4f}" for b, r in ratios))
+    bad = [(b, round(r, 3)) for b, r in ratios if not r <= 1.0]
+    assert not bad, (name, bad)
+    return ratios
+
+
+def actor_torch32(logits, act, adv, lpo, w, clip):
+    """The unfused branch of CNNAgentPPO.update_agent behind the logits, as ppo_cnn.py writes it, in the inputs' dtype on their
+    device: (stats [4] = kl, entropy, clip fraction, loss; d loss / d logits by autograd)."""
+    lg = logits.detach().clone().requires_grad_(True)
+    logp_all = torch.log_softmax(lg, dim=-1)
+    logp = logp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1)
+    ratio = torch.exp(logp - lpo)
+    clip_adv = torch.clamp(ratio, 1 - clip, 1 + clip) * adv
+    loss = -(w * torch.min(ratio * adv, clip_adv)).sum()
+    loss.backward()
+    with torch.no_grad():
+        ent = -(logp_all.exp() * logp_all).sum(-1)
+        clipped = (ratio > 1 + clip) | (ratio < 1 - clip)
+        stats = torch.stack([(w * (lpo - logp)).sum(), (w * ent).sum(), (w * clipped.to(w.dtype)).sum(), loss.detach()])
+    return stats, lg.grad
+
+
+def cnn_head_f64(seq64, y1):
+    """Layers [7:11] of CNNActor.actor / CNNCritic.critic (ReLU, Linear(32, 16), ReLU, Linear(16, OUT)) of the float64 twin seq64 on a
+    float32 y1 [N, 32] widened: (out [N, OUT], mag3 = |W3| h2 + |b3|, carried = |W3| mag2 with mag2 = |W2| relu(y1) + |b2|) -- the
+    sums of absolute terms the output layer's and the hidden layer's dot products are rounded against, the latter carried through
+    |W3| (ReLU passes an error on with slope <= 1)."""
+    with torch.no_grad():
+        W2, b2, W3, b3 = seq64[8].weight, seq64[8].bias, seq64[10].weight, seq64[10].bias
+        h1 = torch.relu(y1.detach().double().cpu())
+        h2 = torch.relu(h1 @ W2.t() + b2)
+        out = h2 @ W3.t() + b3
+        mag2 = h1 @ W2.abs().t() + b2.abs()
+        return out, h2 @ W3.abs().t() + b3.abs(), mag2 @ W3.abs().t()
+
+
+def head_ratio(got, out64, mag3, carried):
+    """Worst |got - ref| / (FF_RTOL |ref| + U (HEAD_K2 carried + HEAD_K3 mag3) + FF_TINY) over the outputs of a head."""
+    a = got.detach().double().cpu().reshape(out64.shape)
+    ratio = (a - out64).abs() / (FF_RTOL * out64.abs() + U * (HEAD_K2 * carried + HEAD_K3 * mag3) + FF_TINY)
+    ratio = torch.where(torch.isfinite(a), ratio, torch.full_like(ratio, float("inf")))
+    return float(ratio.max()) if ratio.numel() else 0.0
+
+
+def draw_ratios(act, logp, act64, lp64, cdf64, u):
+    """check_draw's two rules as numbers: (edge, logp, differing).  edge: over the lanes whose action differs from the float64 draw, the
+    largest distance of the uniform from its nearest CDF step / the 1e-5 inside which a differing draw is excused (0 when none
+    differs); logp: the worst error / (1e-5 |ref| + 5e-6) on the lanes with the same action; differing: their number (<= 2 allowed)."""
+    act, logp, u = act.cpu(), logp.cpu(), u.cpu()
+    dist = (cdf64[:, :-1] - u.double().unsqueeze(-1)).abs().amin(dim=1)
+    same = act == act64
+    edge = float(dist[~same].max()) / 1e-5 if bool((~same).any()) else 0.0
+    ref = lp64.gather(-1, act64.unsqueeze(-1)).squeeze(-1)
+    lp = close_ratio(logp[same], ref[same], rtol=1e-5, noise=0.0, tiny=5e-6)
+    return edge, lp, int((~same).sum())
+
+
+class HeadCase:
+    pass
+
+
+_HEAD_CACHE = {}
+
+
+def head_case(N, A=HEAD_AGENTS):
+    """One case of the rs_cnn_head tests, built once on the CPU and shared.  Every agent has its own CNNActor (the layers behind the
+    first Linear x 3: visibly non-uniform policies, as in the collector test) and its own CNNCritic, its own y1 = randn x 2 (both
+    ReLUs gate both ways) for either, and its own column of u [N, A]; mask: bootstrap_mask.  actor_ref[a] = (logits64, mag3, carried,
+    act64, lp64, cdf64), critic_ref[a] = (value64 [N], mag3 [N], carried [N])."""
+    if (N, A) in _HEAD_CACHE:
+        return _HEAD_CACHE[(N, A)]
+    from radiation_ppo_amd.maps import CNNActor, CNNCritic
+    c = HeadCase()
+    c.N, c.A = N, A
+    g = torch.Generator().manual_seed(1000 * N + A)
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(500 + N)
+        c.actors, c.critics = [CNNActor() for _ in range(A)], [CNNCritic() for _ in range(A)]
+    with torch.no_grad():
+        for ac in c.actors:
+            for p in ac.actor[7:].parameters():
+                p.mul_(3.0)
+    c.y1a, c.y1c = torch.randn(A, N, 32, generator=g) * 2, torch.randn(A, N, 32, generator=g) * 2
+    c.u = torch.rand(N, A, generator=g)
+    c.mask = bootstrap_mask(N, g)
+    c.actor_ref, c.critic_ref = [], []
+    for a in range(A):
+        out, mag3, car = cnn_head_f64(f64(c.actors[a].actor), c.y1a[a])
+        c.actor_ref.append((out, mag3, car) + tuple(draw_f64(out, c.u[:, a])))
+        v, m3, cr = cnn_head_f64(f64(c.critics[a].critic), c.y1c[a])
+        c.critic_ref.append((v.squeeze(-1), m3.squeeze(-1), cr.squeeze(-1)))
+    assert bool(torch.isfinite(c.y1a).all()) and bool(torch.isfinite(c.y1c).all())
+    _HEAD_CACHE[(N, A)] = c
+    return c

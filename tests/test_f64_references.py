@@ -3,7 +3,9 @@ hand-written heads loss against the library branch of RNNAgentPPO.a2c_losses, th
 inverse-CDF composition, the ratio targets, the PFGRU step with its kink mask against PFGRUCell in float32, and the quad layout of
 the particle sets; and those of the default-width tests (test_rnn_default_f64_gpu.py, test_pfgru_default_f64_gpu.py): the PFGRU training
 loss written out in float64 (model_loss_f64) against RNNAgentPPO.model_loss + autograd in float32, held to a tenth of K13's bound, and
-its kink counter against a brute-force count.  A wrong reference fails here, before a GPU test relies on it."""
+its kink counter against a brute-force count; and those of test_cnn_heads_f64_gpu.py: the RAD-TEAM actor loss behind the logits and the
+heads behind their first Linear layer against float64 autograd / the module slice, the float32 torch compositions under the rule the
+kernels are held to, and the mutations that rule must see.  A wrong reference fails here, before a GPU test relies on it."""
 import os
 import sys
 
@@ -288,3 +290,158 @@ def test_ff_forward_f64_against_the_float32_torch_path(pset):
     R.close(torch.log_softmax(lg, -1), torch.log_softmax(lg64, -1), "logp", **t_lp)
     print(f"torch32 forward {pset}: logits {R.close_ratio(lg, lg64, **t_out):.4f} value {R.close_ratio(v, v64, **t_out):.4f} "
           f"logp {R.close_ratio(torch.log_softmax(lg, -1), torch.log_softmax(lg64, -1), **t_lp):.4f}")
+
+
+# ------------------------------------------------------------------------------------------------ RAD-TEAM actor loss and heads (tests/test_cnn_heads_f64_gpu.py)
+AL_ALL = R.AL_CASES + [R.AL_ZERO]
+AL_MULTI = [c for c in R.AL_CASES if c[0] > 64]
+HEAD_MULTI = [N for N in R.HEAD_SIZES if N > 64]
+SENTINEL = -12345.678
+
+
+def _al_id(c):
+    return R.al_case_id(c) + (f"-{c[2]}-zero-rows" if len(c) > 2 else "")
+
+
+def _al_torch32(c):
+    """The float32 torch composition on case c's kept rows (the zero-weight rows are left out, as in the reference)."""
+    return R.actor_torch32(*(t[c.keep] for t in c.batch), c.clip)
+
+
+def _draw32(logits32, u):
+    """CNNAgentPPO.act's float32 sampling tail behind the logits."""
+    logp_all = torch.log_softmax(logits32, dim=-1)
+    cdf = torch.cumsum(logp_all.exp(), dim=-1)
+    a = (cdf <= u.unsqueeze(-1)).sum(dim=-1).clamp_(max=7)
+    return a, logp_all.gather(-1, a.unsqueeze(-1)).squeeze(-1)
+
+
+def test_actor_loss_f64_equals_float64_autograd_and_its_inputs_hold_their_conditions():
+    """R.actor_loss_f64's dlogits and statistics against float64 autograd of the torch composition of CNNAgentPPO.update_agent's unfused
+    branch (1e-12 of each magnitude), |dlogits| <= its magnitude; every case's generator conditions (asserted in R.al_case); the weights
+    put half of their sum on the last wave; the zero-weight case has its 40 rows."""
+    c = R.al_case(257, 0.2)
+    logits, act, adv, lpo, w = (t.double() if t.is_floating_point() else t for t in c.batch)
+    st, g = R.actor_torch32(logits, act, adv, lpo, w, c.clip)
+    assert float(((c.ref.dlogits - g).abs() / (1e-12 * c.ref.dl_mags + 1e-300)).max()) <= 1.0
+    assert float(((c.ref.stats - st).abs() / (1e-12 * c.ref.stat_mags + 1e-300)).max()) <= 1.0
+    assert bool((c.ref.dlogits.abs() <= c.ref.dl_mags * (1 + 1e-12)).all())
+    assert bool((c.ref.stats.abs() <= c.ref.stat_mags * (1 + 1e-12)).all())
+    for case in AL_ALL:
+        k = R.al_case(*case)
+        s = R.wave_start(k.S)
+        wt = k.w.double()
+        assert abs(float(wt.sum()) - 1) < 1e-5 and float(wt[k.keep].min()) > 0
+        if len(case) == 2:
+            assert s == 0 or abs(float(wt[s:].sum()) - 0.5) < 1e-5, case
+        live = ((k.ref.ratio >= 1 - k.clip) & (k.ref.ratio <= 1 + k.clip)) | (k.ref.dlogits.abs().sum(-1) > 0)
+        assert bool(live[-1]) or not bool(k.keep[-1]), case                 # the last sample's gate is live
+    z = R.al_case(*R.AL_ZERO)
+    assert int((z.w == 0).sum()) == 40 == int((~z.keep).sum()) and float(z.adv[~z.keep].abs().max()) > 1e5
+    assert [R.wave_start(S) for S in R.AL_SIZES] == [0, 0, 0, 64, 192, 192, 256, 576]
+    assert 8.0 < R.al_spread() < 14.0                                        # randn x 1.5 over eight logits of up to 577 samples
+
+
+def test_cnn_head_f64_equals_the_module_slice():
+    """R.cnn_head_f64 against layers [7:11] of the float64 twins, its magnitudes against a brute-force sum of absolute terms, and the
+    inputs: y1 = randn x 2 drives both ReLUs both ways."""
+    c = R.head_case(65)
+    for seq, y1, (out, mag3, car) in ((c.actors[0].actor, c.y1a[0], c.actor_ref[0][:3]),
+                                      (c.critics[2].critic, c.y1c[2], tuple(t.unsqueeze(-1) for t in c.critic_ref[2]))):
+        s64 = R.f64(seq)
+        with torch.no_grad():
+            want = s64[7:11](y1.double())
+            z2 = s64[8](torch.relu(y1.double()))
+        assert want.shape == out.shape and float(((want - out).abs() / (1e-12 * mag3 + 1e-300)).max()) <= 1.0
+        assert bool((out.abs() <= mag3 * (1 + 1e-12)).all())
+        assert 0.3 < float((y1 > 0).float().mean()) < 0.7 and 0.1 < float((z2 > 0).float().mean()) < 0.9
+        W2, b2, W3, b3 = (t.detach() for t in (s64[8].weight, s64[8].bias, s64[10].weight, s64[10].bias))
+        for n in (0, 64):
+            h1 = torch.relu(y1[n].double())
+            mag2 = [sum(abs(float(W2[o, k])) * float(h1[k]) for k in range(32)) + abs(float(b2[o])) for o in range(16)]
+            h2 = [max(sum(float(W2[o, k]) * float(h1[k]) for k in range(32)) + float(b2[o]), 0.0) for o in range(16)]
+            for o in range(out.shape[1]):
+                m3 = sum(abs(float(W3[o, k])) * h2[k] for k in range(16)) + abs(float(b3[o]))
+                cr = sum(abs(float(W3[o, k])) * mag2[k] for k in range(16))
+                assert abs(m3 - float(mag3[n, o])) <= 1e-10 * m3 and abs(cr - float(car[n, o])) <= 1e-10 * cr
+
+
+@pytest.mark.parametrize("case", AL_ALL, ids=_al_id)
+def test_actor_loss_f64_against_the_float32_torch_path(case):
+    """R.actor_loss_f64 against the float32 torch composition on the CPU under the rule the GPU test holds rs_actor_loss to
+    (R.check_actor), at every case of that test: float32 torch rounds with the same unit roundoff in another order, so it must pass."""
+    c = R.al_case(*case)
+    st, g = _al_torch32(c)
+    rep = []
+    R.check_actor(st, g, c.ref, "torch32 rs_actor_loss " + _al_id(case), report=rep)
+    print(rep[0])
+
+
+@pytest.mark.parametrize("N", R.HEAD_SIZES)
+def test_cnn_head_f64_against_the_float32_torch_path(N):
+    """The float32 module slice and CNNAgentPPO.act's sampling tail on the CPU against R.cnn_head_f64 / R.draw_f64 under the rules the GPU
+    test holds rs_cnn_head to: R.head_ratio on logits and values, R.check_draw on actions and log-probabilities."""
+    c = R.head_case(N)
+    worst = dict(logits=0.0, value=0.0, edge=0.0, logp=0.0)
+    differ = 0
+    for a in range(c.A):
+        out, mag3, car, act64, lp64, cdf64 = c.actor_ref[a]
+        with torch.no_grad():
+            lg32 = c.actors[a].actor[7:11](c.y1a[a])
+            v32 = c.critics[a].critic[7:11](c.y1c[a]).squeeze(-1)
+        a32, lp32 = _draw32(lg32, c.u[:, a])
+        e, lp, d = R.draw_ratios(a32, lp32, act64, lp64, cdf64, c.u[:, a])
+        worst["logits"] = max(worst["logits"], R.head_ratio(lg32, out, mag3, car))
+        worst["value"] = max(worst["value"], R.head_ratio(v32, *c.critic_ref[a]))
+        worst["edge"], worst["logp"], differ = max(worst["edge"], e), max(worst["logp"], lp), differ + d
+        R.check_draw(a32, lp32, act64, lp64, cdf64, c.u[:, a], f"torch32 N{N} agent {a}")
+    print(f"torch32 rs_cnn_head N{N} | " + " ".join(f"{k} {v:.4f}" for k, v in worst.items()) + f" draws differing {differ}")
+    assert worst["logits"] <= 1.0 and worst["value"] <= 1.0, worst
+
+
+@pytest.mark.parametrize("case", AL_MULTI, ids=_al_id)
+def test_actor_rule_sees_a_lost_wave_a_wrong_gate_and_a_flipped_entropy(case):
+    """Mutations of the float32 torch result, each at least 100 x over its allowance (test_ff_rule_sees_a_lost_or_repeated_tail's bar) at
+    every case of more than one wave: the last wave's samples dropped from the four statistics (the worst of the four), the last wave's
+    dlogits rows zeroed, the gate reduced to `inside` alone (the rows of clipped-side samples whose minimum is the unclipped term
+    zeroed), the entropy's sign flipped."""
+    c = R.al_case(*case)
+    s = R.wave_start(c.S)
+    st, g = _al_torch32(c)
+    st_lost, _ = R.actor_torch32(*(t[:s] for t in c.batch), c.clip)
+    g_lost = g.clone()
+    g_lost[s:] = 0
+    inside = (c.ref.ratio >= 1 - c.clip) & (c.ref.ratio <= 1 + c.clip)
+    g_gate = g * inside.unsqueeze(-1)
+    st_ent = st.clone()
+    st_ent[1] = -st_ent[1]
+    got = {"lost wave, statistics": max(r for _, r in R.actor_ratios(st_lost, None, c.ref)),
+           "lost wave, dlogits": dict(R.actor_ratios(st, g_lost, c.ref))["dlogits"],
+           "gate inside only": dict(R.actor_ratios(st, g_gate, c.ref))["dlogits"],
+           "entropy sign": dict(R.actor_ratios(st_ent, None, c.ref))["entropy"]}
+    print(f"rs_actor_loss mutations {_al_id(case)} | " + " ".join(f"{k}: {v:.0f} x" for k, v in got.items()))
+    assert all(v >= 100.0 for v in got.values()), got
+
+
+@pytest.mark.parametrize("N", HEAD_MULTI)
+def test_head_rule_sees_a_neighbour_s_uniform_and_a_missing_value_copy(N):
+    """Mutations of the float32 torch result at the cases of more than one wave, each at least 100 x over its allowance: agent a's
+    draw taken with agent a + 1's column of u (a differing action is excused within 1e-5 of a CDF step: the distance of the uniform
+    from its nearest step on a differing lane / 1e-5), and a global critic's value written for copy 0 only (the other copies keep the
+    sentinel)."""
+    c = R.head_case(N)
+    for a in range(c.A):
+        out, mag3, car, act64, lp64, cdf64 = c.actor_ref[a]
+        with torch.no_grad():
+            lg32 = c.actors[a].actor[7:11](c.y1a[a])
+        a32, lp32 = _draw32(lg32, c.u[:, (a + 1) % c.A])
+        edge, _, differ = R.draw_ratios(a32, lp32, act64, lp64, cdf64, c.u[:, a])
+        print(f"rs_cnn_head mutations N{N} agent {a} | neighbour's uniform: {edge:.0f} x, {differ} draws differing")
+        assert edge >= 100.0 and differ > 2, (a, edge, differ)
+    with torch.no_grad():
+        v32 = c.critics[0].critic[7:11](c.y1c[0]).squeeze(-1)
+    got = torch.full((c.A, N), SENTINEL)
+    got[0] = v32
+    ratios = [R.head_ratio(got[k], *c.critic_ref[0]) for k in range(c.A)]
+    print(f"rs_cnn_head mutations N{N} | value for copy 0 only: " + " ".join(f"copy {k}: {r:.0f} x" for k, r in enumerate(ratios)))
+    assert ratios[0] <= 1.0 and all(r >= 100.0 for r in ratios[1:]), ratios

@@ -37,13 +37,7 @@ def _case(N, A):
         lg64, v64 = R.ff_forward_f64(R.f64(ac), x[:, a])
         act64, lp64, cdf64 = R.draw_f64(lg64, u[:, a])
         ref.append((v64, act64, lp64, cdf64))
-    mask = (torch.rand(N, generator=g) < 0.5).to(torch.uint8)
-    mask[0] = 1
-    if N > 1:
-        mask[1] = 0
-    if N > 128:
-        mask[64:128] = 0                                            # one whole 64-group without a masked env
-        mask[N - 1] = 1
+    mask = R.bootstrap_mask(N, g)                                   # past 128 envs: one whole 64-group without a masked env
     return x, u, agents, ref, mask
 
 

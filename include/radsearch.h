@@ -662,6 +662,45 @@ int rs_collect_pre(const rs_collect_state* c, rs_stream_t stream);
 int rs_collect_post_step(const rs_collect_state* c, int32_t epoch_ended, rs_stream_t stream);
 int rs_collect_post_reset(const rs_collect_state* c, int32_t reset_hidden, rs_stream_t stream);
 
+/* ---- Monte-Carlo evaluation of feed-forward agents and teams (algos/multiagent/evaluate.py:355-475) --------------------------------
+ * One evaluation lock-step is rs_action_uniforms, rs_ff_eval_step, rs_step, rs_eval_post_step on one stream
+ * (radiation_ppo_amd/evaluate.py: run_test_environments_team); a lane is one (saved environment, Monte-Carlo run) pair.
+ *
+ * rs_ff_eval_step: the policy round for every agent of the team in one launch, grid = (64-sample groups, agent); forward pass and
+ * sampler are rs_ff_team_step's, the critic is not evaluated.
+ *   actors [A]            host array of rs_mlp_params (device pointers inside), A = num_agents in 1..RS_MAX_AGENTS
+ *   obs [N][A][11]        the raw current observation
+ *   w_mean, w_std [N][A]  float64 running statistics of the reading (DeviceWelford's layout): element 0 of a row enters the network as
+ *                         (float)(((double)obs0 - mean) / std), rs_welford_standardize's expression; both NULL: no standardisation
+ *   u [N][A], alive [N]   the uniforms of rs_action_uniforms; alive[n] != 0 while lane n's episode runs
+ *   act8 [N][A]           rs_step's action rows: #{j < 7 : cdf_j <= u} where alive, else 8 (idle)
+ * RS_ERR_INVALID_ARG, before anything is launched: NULL actors / obs / u / alive / act8, exactly one of w_mean / w_std NULL,
+ * num_agents outside 1..RS_MAX_AGENTS, num_envs < 1. */
+int rs_ff_eval_step(const rs_mlp_params* actors, int32_t num_agents, const float* obs, const double* w_mean, const double* w_std,
+                    const float* u, const uint8_t* alive, int8_t* act8, int32_t num_envs, rs_stream_t stream);
+
+/* rs_eval_post_step: everything between rs_step and the next policy round, one launch, one thread per lane, in this order:
+ *   r = use_team_reward ? env_team[n] : env_reward[n][0] (`episode_return[0]`, evaluate.py:400-447); where alive: ep_ret += r (float32),
+ *   ep_len += 1; found = alive and any agent's env_done; success |= found, alive &= !found; where still alive the Welford update of
+ *   rs_welford_update on every agent's new reading; cur_obs <- env_obs on every lane; finished[0] += the lanes that stopped in this
+ *   launch (a monotonic counter: the host reads it once every few lock-steps and never zeroes it inside the loop).
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL struct or required field, A outside 1..RS_MAX_AGENTS, N < 1, some but not
+ * all of the four Welford pointers. */
+typedef struct {
+    int32_t N, A, use_team_reward;
+    const float* env_obs;         /* [N][A][11] the env's output rows (rs_step) */
+    const float* env_reward;      /* [N][A] */
+    const float* env_team;        /* [N] */
+    const uint8_t* env_done;      /* [N][A] */
+    float* cur_obs;               /* [N][A][11] the observation the next policy round reads */
+    double* w_count; double* w_mean; double* w_sq; double* w_std;     /* [N][A] Welford state of the readings; all NULL: none kept */
+    uint8_t* alive; uint8_t* success;                                 /* [N] */
+    int32_t* ep_len;              /* [N] */
+    float* ep_ret;                /* [N] */
+    int32_t* finished;            /* [1] */
+} rs_eval_state;
+int rs_eval_post_step(const rs_eval_state* s, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,13 @@ class RsCollectState(C.Structure):
                                   "env_oob", "env_src_x", "env_src_y", "done_copy", "oob_copy", "src_copy", "complete_len")]
 
 
+class RsEvalState(C.Structure):
+    """rs_eval_state (include/radsearch.h)."""
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("use_team_reward", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("env_obs", "env_reward", "env_team", "env_done", "cur_obs", "w_count", "w_mean", "w_sq", "w_std", "alive",
+                                  "success", "ep_len", "ep_ret", "finished")]
+
+
 class RsMlpParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
@@ -167,6 +174,8 @@ SYMBOLS = [
     ("rs_a2c_sized_heads_loss", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10
      + [C.c_int64, C.c_double, C.c_double, C.c_void_p]),
     ("rs_gru_h0_reset_sized", C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    ("rs_ff_eval_step", C.c_int, [C.POINTER(RsMlpParams), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
+    ("rs_eval_post_step", C.c_int, [C.POINTER(RsEvalState), C.c_void_p]),
 ]
 
 _lib = None

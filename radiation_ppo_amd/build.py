@@ -15,16 +15,17 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "librs_hip.so")
 
 SOURCES = ["rs_env.hip", "rs_ppo.hip", "rs_maps.hip", "rs_cnn.hip", "rs_cnn_sized.hip", "rs_pfgru.hip", "rs_gru.hip", "rs_pfgru_train.hip", "rs_rnn_policy.hip", "rs_welford.hip", "rs_cnn_loss.hip",
-           "rs_rnn_sized.hip", "rs_pfgru_sized.hip", "rs_pfgru_sized_train.hip", "rs_ff_team.hip"]
+           "rs_rnn_sized.hip", "rs_pfgru_sized.hip", "rs_pfgru_sized_train.hip", "rs_ff_team.hip", "rs_eval.hip"]
 # -ffp-contract=off: float64 env arithmetic must round like the reference's Python floats (no FMA fusing)
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
           "-Wno-unused-function"]
 # rs_ppo.hip: no SLP packing.  hipcc otherwise pairs the scalar f32 FMAs of the output layer into v_pk_fma_f32 + v_mov shuffles,
 # which costs more issue slots than it saves next to f32 MFMAs (measured: scripts/micro/mfma_valu_coissue.hip)
-# rs_ff_team.hip: the same output layer (rs_mlp.hpp) next to the same MFMAs, the same flag
+# rs_ff_team.hip, rs_eval.hip: the same output layer (rs_mlp.hpp) next to the same MFMAs, the same flag
 # rs_rnn_sized.hip: the 64-unit tier's unrolled block loops exceed the default full-unroll budget; left rolled, the register arrays they
 # index go to scratch (528 bytes per lane at 64 units)
-EXTRA_CFLAGS = {"rs_ppo.hip": ["-fno-slp-vectorize"], "rs_ff_team.hip": ["-fno-slp-vectorize"], "rs_rnn_sized.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
+EXTRA_CFLAGS = {"rs_ppo.hip": ["-fno-slp-vectorize"], "rs_ff_team.hip": ["-fno-slp-vectorize"], "rs_eval.hip": ["-fno-slp-vectorize"],
+                "rs_rnn_sized.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
                 "rs_pfgru_sized.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"]}
 
 

@@ -10,9 +10,11 @@ with its own Philox stream -- and the same per-environment records come out (`Mo
 Saved sets use the reference's layout `env_dict["env_<i>"] = (src_coords, det_coords, intensity, bkg[, obstacles])`
 (algos/test_environment/eval/test_env_gen.py:13-24).  `sample_test_environments` draws such a set from the
 environment's own spawn rules; the reference's own pickled sets are read by radiation_ppo_amd.testsets WITHOUT unpickling.
-`run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `summarize` the result statistics
+`run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `run_test_environments_team` for feed-forward agents and
+teams of up to 8 with its lock-step in HIP (csrc/rs_eval.hip), `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
 """
+import ctypes as C
 import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, List
@@ -22,7 +24,7 @@ import torch
 
 from . import _lib
 from .envs import RadSearchVec
-from .ppo import DeviceWelford, VecAgentPPO
+from .ppo import DeviceWelford, VecAgentPPO, mlp_params
 
 
 @dataclass
@@ -331,6 +333,99 @@ def run_test_environments_cnn(agents: Dict[int, Any], env_sets: Dict[str, tuple]
     return out, summary
 
 
+@torch.no_grad()
+def run_test_environments_team(agents: Dict[int, VecAgentPPO], env_sets: Dict[str, tuple], montecarlo_runs: int = 100,
+                               steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
+                               enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0", return_actions: bool = False,
+                               falloff: str = "reference", fused: bool = True):
+    """EpisodeRunner.run (evaluate.py:355-475) for feed-forward agents and teams of 1..8: every agent has its own network and its own
+    statistics buffer, an episode ends when any agent's terminal flag is raised or at `steps_per_episode`.  One lane per (saved
+    environment, Monte-Carlo run), as run_test_environments does for 'ff' -- exact, because a feed-forward policy has no hidden state
+    and the statistics buffer restarts with every run.  team_mode "individual": agent 0's own reward is accumulated, otherwise the
+    team reward.  agents: {id: VecAgentPPO}, ids 0..A-1.
+
+    fused=True: a lock-step is four launches on one stream -- rs_action_uniforms, rs_ff_eval_step (standardisation, every agent's
+    actor, the draw, idle rows for finished lanes), rs_step, rs_eval_post_step (returns, lengths, terminal rule, Welford update, new
+    observation, finished-lane count) -- and the host reads the finished-lane count once every 16 lock-steps; nothing else
+    synchronises.  fused=False: the same lock-step composed from DeviceWelford, rs_ff_team_step's step round (value and
+    log-probability dropped) and torch bookkeeping, with the same stopping rule: the A/B baseline, identical results.
+
+    Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log of rs_step's action rows
+    (8 where a lane had finished)."""
+    A = len(agents)
+    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
+        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}")
+    E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
+    N = E * R
+    dev = torch.device(device)
+    with_obs = obstruction_count != 0
+    lib = _lib.load()
+    vec = RadSearchVec(N, number_agents=A, obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries,
+                       seed=seed, device=device, falloff=falloff)
+    keys, src, det, inten, bkg, nob, rects = _pack(env_sets, R, with_obs, dev)
+    vec.reset()                                                   # a valid handle state; every episode is then loaded
+    obs = vec.refresh(src, det, inten, bkg, nob, rects)[0].clone()
+    stat = DeviceWelford((N, A), dev)                             # evaluate.py:362-367: one statistics buffer per agent
+    stat.update(obs[..., 0])
+    alive = torch.ones(N, dtype=torch.bool, device=dev)
+    ep_len = torch.zeros(N, dtype=torch.int32, device=dev)
+    ep_ret = torch.zeros(N, dtype=torch.float32, device=dev)
+    success = torch.zeros(N, dtype=torch.bool, device=dev)
+    u = torch.empty(N, A, dtype=torch.float32, device=dev)
+    # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads
+    log = torch.full((L, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
+    act8 = None if return_actions else torch.empty(N, A, dtype=torch.int8, device=dev)
+    arr = _lib.RsMlpParams * A
+    pa = arr(*[mlp_params(agents[a].agent.actor) for a in range(A)])
+    use_team = team_mode != "individual"
+    p = lambda t: t.data_ptr()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    if fused:
+        finished = torch.zeros(1, dtype=torch.int32, device=dev)
+        alive8, success8 = alive.view(torch.uint8), success.view(torch.uint8)
+        state = _lib.RsEvalState(N, A, 1 if use_team else 0, p(vec.obs), p(vec.reward), p(vec.team), p(vec.done), p(obs), p(stat.count),
+                                 p(stat.mean), p(stat.sq), p(stat.std), p(alive8), p(success8), p(ep_len), p(ep_ret), p(finished))
+    else:
+        pc = arr(*[mlp_params(agents[a].agent.critic) for a in range(A)])
+        x = torch.empty_like(obs)
+        k_act = torch.empty(A, N, dtype=torch.int64, device=dev)
+        k_f = torch.empty(A, 3, N, dtype=torch.float32, device=dev)
+    it = 0
+    while it < L:
+        if it and it % 16 == 0:                                   # one host read per 16 lock-steps
+            if (int(finished.item()) if fused else N - int(alive.sum().item())) == N:
+                break
+        a8 = log[it] if return_actions else act8
+        vec.action_uniforms(u)
+        if fused:
+            _lib.check(lib.rs_ff_eval_step(pa, A, p(obs), p(stat.mean), p(stat.std), p(u), p(alive8), p(a8), N, st), "rs_ff_eval_step")
+            vec.step(a8)
+            _lib.check(lib.rs_eval_post_step(C.byref(state), st), "rs_eval_post_step")
+        else:
+            x.copy_(obs)
+            stat.standardize(obs[..., 0], out=x[..., 0])
+            _lib.check(lib.rs_ff_team_step(pa, pc, A, p(x), p(u), p(k_act), p(k_f), None, None, N, st), "rs_ff_team_step")
+            a8.copy_(torch.where(alive.view(N, 1), k_act.t(), torch.full_like(k_act.t(), 8)).to(torch.int8))   # finished episodes idle
+            obs_n, rew, team, done, _ = vec.step(a8)
+            r = team if use_team else rew[:, 0]
+            ep_ret += torch.where(alive, r, torch.zeros_like(r))  # :400-406 (float32 accumulation)
+            ep_len += alive.int()
+            found = done.bool().any(dim=1) & alive
+            success |= found
+            alive &= ~found
+            stat.update(obs_n[..., 0], mask=alive)
+            obs.copy_(obs_n)
+        it += 1
+    flags = vec.error_flags() & ~_lib.ENVERR_IDLE_STALL        # finished episodes idle on purpose; stacked agents may "stall"
+    if flags:
+        raise RuntimeError(f"RadSearch env error flags 0x{flags:x}")
+    out = _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg)
+    summary = summarize(out)
+    if return_actions:
+        return out, summary, log[:it].cpu().numpy()
+    return out, summary
+
+
 def _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg) -> List[MonteCarloResults]:
     ep_len_c, ep_ret_c, suc = ep_len.cpu().numpy(), ep_ret.cpu().numpy(), success.cpu().numpy()
     i_c, b_c = inten.cpu().numpy(), bkg.cpu().numpy()
@@ -451,6 +546,18 @@ class evaluate_PPO:
             ag.load(agent_dir(0))                                       # pyt_save/model.pt (epoch_logger.py:216-284)
             self.results, self.summary = run_test_environments(ag, sets, carry_hidden_across_runs=bool(kw.get("carry_hidden_across_runs", True)),
                                                                **common)
+        elif A >= 2:
+            # a feed-forward team: every agent's own network on its own rows (evaluate.py:305-331); recurrent teams are not built
+            team_mode = kw.get("team_mode", "individual")
+            if team_mode != "individual":
+                raise ValueError("team_mode must be 'individual' for a feed-forward team: no global critic for RAD-A2C")   # evaluate.py:279-280
+            agents = {}
+            for i in range(A):
+                agents[i] = VecAgentPPO(id=i, device=dev)
+                d = agent_dir(i)
+                f = os.path.join(d, "pyt_save", "model.pt")
+                agents[i].load(f if os.path.exists(f) else os.path.join(d, "model.pt"))
+            self.results, self.summary = run_test_environments_team(agents, sets, team_mode=team_mode, **common)
         else:
             ag = VecAgentPPO(id=0, device=dev)
             d = agent_dir(0)

@@ -701,6 +701,46 @@ typedef struct {
 } rs_eval_state;
 int rs_eval_post_step(const rs_eval_state* s, rs_stream_t stream);
 
+/* ---- Monte-Carlo evaluation of the recurrent agent, RAD-A2C (algos/multiagent/evaluate.py:333-476) -----------------------------------
+ * A lane is one agent (A = 1) working through runs_per_lane consecutive runs of one saved environment: runs_per_lane = R on N = E lanes
+ * keeps the reference's hidden-state lifetime (`hiddens` is created once per EpisodeRunner.run, :357), runs_per_lane = 1 on N = E R
+ * lanes gives every run a lane of its own.  One lock-step is rs_action_uniforms, rs_pfgru_step (mask = active), rs_rnn_policy_step_rows
+ * or rs_rnn_sized_step (mask = active, act8 = the step's action row), rs_step, rs_rnn_eval_post_step and, when runs_per_lane > 1,
+ * rs_refresh(mask = again) and rs_rnn_eval_post_refresh, all on one stream (radiation_ppo_amd/evaluate.py: run_test_environments_rnn).
+ *
+ * rs_rnn_eval_post_step: one launch after rs_step, one thread per lane, in this order (a = active[n] on entry):
+ *   where a: ret += env_reward (float32), steps += 1, pf_calls += 1; found = a and env_done, over = found or (a and steps ==
+ *   steps_per_episode); where a: the Welford update of rs_welford_update with env_obs[n][0] (before the episode-over test, :392-397;
+ *   the first sample sets the mean only); where over: rec_len / rec_ret / rec_suc [n][run] = steps, ret, found, then run += 1,
+ *   steps = 0, ret = 0; again = over and run < runs_per_lane; where over and run == runs_per_lane: active = 0, idle_act8[n] = 8 and
+ *   the lane counts once into finished[0] (a monotonic counter: the host reads it once every few lock-steps and never zeroes it inside
+ *   the loop); on every lane cur_obs <- env_obs and x <- env_obs with x[0] = (float)(((double)obs0 - mean) / std), the statistics as
+ *   just updated (rs_welford_standardize's expression).
+ * rs_rnn_eval_post_refresh: one launch after rs_refresh(mask = again), which rewrites the env rows of those lanes only.  Where
+ *   again != 0: the statistics restart (count = mean = sq = 0, std = 1) and take the refreshed reading as their first sample,
+ *   cur_obs <- env_obs, x <- its standardised form (:455-468).  The other lanes are untouched, and so are all hidden states.
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL struct or required field, N < 1, runs_per_lane < 1, steps_per_episode < 1.
+ * Only pf_calls and idle_act8 may be NULL. */
+typedef struct {
+    int32_t N, runs_per_lane, steps_per_episode;
+    const float* env_obs;         /* [N][11] the env's output rows (rs_step / rs_refresh) */
+    const float* env_reward;      /* [N] */
+    const uint8_t* env_done;      /* [N] */
+    float* cur_obs;               /* [N][11] the current observation */
+    float* x;                     /* [N][11] the PFGRU's and the policy's input: cur_obs with the reading standardised */
+    double* w_count; double* w_mean; double* w_sq; double* w_std;     /* [N] Welford state of the reading; all required */
+    uint8_t* active;              /* [N] != 0 while the lane has runs left */
+    uint8_t* again;               /* [N] written by rs_rnn_eval_post_step, read by rs_refresh (its mask) and rs_rnn_eval_post_refresh */
+    int32_t* run; int32_t* steps; /* [N] index of the current run, steps taken in it */
+    float* ret;                   /* [N] its return so far */
+    int32_t* rec_len; float* rec_ret; uint8_t* rec_suc;               /* [N][runs_per_lane] the records of the runs that ended */
+    int64_t* pf_calls;            /* [N] or NULL: the predictor bank's per-lane call counter */
+    int8_t* idle_act8;            /* [N] or NULL: rs_step's action row where one fixed buffer serves every lock-step */
+    int32_t* finished;            /* [1] lanes whose last run has ended */
+} rs_rnn_eval_state;
+int rs_rnn_eval_post_step(const rs_rnn_eval_state* s, rs_stream_t stream);
+int rs_rnn_eval_post_refresh(const rs_rnn_eval_state* s, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,13 @@ class RsEvalState(C.Structure):
                                   "success", "ep_len", "ep_ret", "finished")]
 
 
+class RsRnnEvalState(C.Structure):
+    """rs_rnn_eval_state (include/radsearch.h)."""
+    _fields_ = [("N", C.c_int32), ("runs_per_lane", C.c_int32), ("steps_per_episode", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("env_obs", "env_reward", "env_done", "cur_obs", "x", "w_count", "w_mean", "w_sq", "w_std", "active", "again",
+                                  "run", "steps", "ret", "rec_len", "rec_ret", "rec_suc", "pf_calls", "idle_act8", "finished")]
+
+
 class RsMlpParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
@@ -176,6 +183,8 @@ SYMBOLS = [
     ("rs_gru_h0_reset_sized", C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("rs_ff_eval_step", C.c_int, [C.POINTER(RsMlpParams), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
     ("rs_eval_post_step", C.c_int, [C.POINTER(RsEvalState), C.c_void_p]),
+    ("rs_rnn_eval_post_step", C.c_int, [C.POINTER(RsRnnEvalState), C.c_void_p]),
+    ("rs_rnn_eval_post_refresh", C.c_int, [C.POINTER(RsRnnEvalState), C.c_void_p]),
 ]
 
 _lib = None

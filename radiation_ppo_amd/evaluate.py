@@ -11,7 +11,7 @@ Saved sets use the reference's layout `env_dict["env_<i>"] = (src_coords, det_co
 (algos/test_environment/eval/test_env_gen.py:13-24).  `sample_test_environments` draws such a set from the
 environment's own spawn rules; the reference's own pickled sets are read by radiation_ppo_amd.testsets WITHOUT unpickling.
 `run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `run_test_environments_team` for feed-forward agents and
-teams of up to 8 with its lock-step in HIP (csrc/rs_eval.hip), `summarize` the result statistics
+teams of up to 8 and `run_test_environments_rnn` for the recurrent agent with their lock-steps in HIP (csrc/rs_eval.hip), `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
 """
 import ctypes as C
@@ -261,6 +261,113 @@ def _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruc
     if return_actions:
         return out, summarize(out), torch.stack(log).cpu().numpy()
     return out, summarize(out)
+
+
+@torch.no_grad()
+def run_test_environments_rnn(agent, env_sets: Dict[str, tuple], montecarlo_runs: int = 100, steps_per_episode: int = 120,
+                              obstruction_count: int = 0, enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0",
+                              return_actions: bool = False, falloff: str = "reference", carry_hidden_across_runs: bool = True,
+                              fused=None):
+    """EpisodeRunner.run (evaluate.py:333-476) for the recurrent agent (RAD-A2C) with its lock-step in HIP.  carry_hidden_across_runs
+    as in run_test_environments: True = one lane per saved environment, its R runs one after the other on carried hidden states (the
+    reference's lifetime of `hiddens`, :357); False = one lane per (environment, run) pair with a fresh hidden state.
+
+    fused=True: a lock-step is rs_action_uniforms, the PFGRU step on the lanes with runs left, the policy step on the same lanes
+    (GRU cell, policy head and draw; its action goes straight into rs_step's row), rs_step, rs_rnn_eval_post_step (return, length, the
+    per-run records, Welford update, the next observation raw and standardised, the bank's call counter, finished-lane count) and, with
+    more than one run per lane, rs_refresh on the lanes that begin their next run and rs_rnn_eval_post_refresh (statistics restart) --
+    5 or 7 launches on one stream.  The host reads the finished-lane count once every 16 lock-steps; nothing else synchronises.  It
+    needs a cuda device and a kernel for both halves of the agent (fused_policy or sized_policy, fused_pfgru or sized_pfgru);
+    ValueError otherwise.  fused=False: today's run_test_environments, identical records.  fused=None: the fused form where it can run.
+
+    Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N] int8 log of rs_step's action rows, 8
+    (idle) where a lane had no run going -- N = E with carried hidden states, else E * R."""
+    E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
+    dev = torch.device(device)
+    ac = getattr(agent, "agent", None)
+    can = (dev.type == "cuda" and hasattr(ac, "gru_cell") and hasattr(agent, "policy_step_masked")
+           and (ac.fused_policy or ac.sized_policy) and (ac.fused_pfgru or ac.sized_pfgru))
+    if fused is None:
+        fused = can
+    if fused and not can:
+        raise ValueError("the fused evaluation needs a cuda device, a GRU of 1..64 units with single-layer heads of 2..64 units and a "
+                         "PFGRU of 8, 16, .., 64 hidden units")
+    if not fused:
+        res = run_test_environments(agent, env_sets, montecarlo_runs=R, steps_per_episode=L, obstruction_count=obstruction_count,
+                                    enforce_grid_boundaries=enforce_grid_boundaries, seed=seed, device=device, return_actions=return_actions,
+                                    falloff=falloff, carry_hidden_across_runs=carry_hidden_across_runs)
+        if not return_actions:
+            return res
+        out, summary, log = res
+        if carry_hidden_across_runs and hasattr(ac, "gru_cell"):
+            log = np.where(log < 0, 8, log)                       # _run_sequential marks a lane without a run with -1
+        else:                                                     # the lane-per-run log keeps the draws of finished lanes: idle past the end
+            lens = np.array([l for r in out for l in r.total_episode_length])
+            log = np.where(np.arange(log.shape[0]).reshape(-1, 1) >= lens.reshape(1, -1), 8, log)
+        return out, summary, log.astype(np.int8)
+    from .pfgru import PredictorBank, hash_uniform
+    Rl = R if carry_hidden_across_runs else 1                     # runs per lane
+    N = E * R // Rl
+    with_obs = obstruction_count != 0
+    lib = _lib.load()
+    vec = RadSearchVec(N, number_agents=1, obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries,
+                       seed=seed, device=device, falloff=falloff)
+    keys, src, det, inten, bkg, nob, rects = _pack(env_sets, R // Rl, with_obs, dev)
+    vec.reset()                                                   # a valid handle state; every episode is then loaded
+    obs = vec.refresh(src, det, inten, bkg, nob, rects)[0].clone()
+    stat = DeviceWelford((N, 1), dev)                             # evaluate.py:362-367
+    stat.update(obs[..., 0])
+    bank = PredictorBank(N, 1, hidden_size=ac.rec, seed=seed, carry_hidden=True, device=dev, impl="hip")
+    bank.cells[0] = ac.model
+    bank.reset()                                                  # `hiddens` is created once (:357): particle sets and h0 are drawn here only
+    gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(ac.hid, dtype=torch.int64, device=dev).view(1, -1)
+    hid = ac.gru_h0(hash_uniform(gk)).contiguous()
+    x = obs.clone()
+    stat.standardize(obs[..., 0], out=x[..., 0])
+    active = torch.ones(N, dtype=torch.uint8, device=dev)
+    again = torch.zeros(N, dtype=torch.uint8, device=dev)
+    run = torch.zeros(N, dtype=torch.int32, device=dev)
+    steps = torch.zeros(N, dtype=torch.int32, device=dev)
+    ret = torch.zeros(N, dtype=torch.float32, device=dev)
+    rec_len = torch.zeros(N, Rl, dtype=torch.int32, device=dev)
+    rec_ret = torch.zeros(N, Rl, dtype=torch.float32, device=dev)
+    rec_suc = torch.zeros(N, Rl, dtype=torch.uint8, device=dev)
+    finished = torch.zeros(1, dtype=torch.int32, device=dev)
+    u = torch.empty(N, 1, dtype=torch.float32, device=dev)
+    act = torch.empty(N, dtype=torch.int64, device=dev)           # scratch: asking for it makes K14 evaluate the policy head
+    bound = L * Rl
+    # with return_actions the action row of lock-step t is written straight into row t of the log, which rs_step then reads; a lane
+    # that is masked out is never written and reads 8.  Otherwise one fixed row, where rs_rnn_eval_post_step parks a finished lane on 8
+    log = torch.full((bound, N), 8, dtype=torch.int8, device=dev) if return_actions else None
+    act8 = None if return_actions else torch.full((N,), 8, dtype=torch.int8, device=dev)
+    p = lambda t: t.data_ptr()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    state = _lib.RsRnnEvalState(N, Rl, L, p(vec.obs), p(vec.reward), p(vec.done), p(obs), p(x), p(stat.count), p(stat.mean), p(stat.sq),
+                                p(stat.std), p(active), p(again), p(run), p(steps), p(ret), p(rec_len), p(rec_ret), p(rec_suc),
+                                p(bank.calls), None if return_actions else p(act8), p(finished))
+    it = 0
+    while it < bound:
+        if it and it % 16 == 0 and int(finished.item()) == N:     # one host read per 16 lock-steps
+            break
+        a8 = log[it] if return_actions else act8
+        vec.action_uniforms(u)
+        loc = bank.predict_kernel(x, mask8=active)                # the draw counters are rs_rnn_eval_post_step's
+        agent.policy_step_masked(x, loc, hid, u, act, a8, active)
+        vec.step(a8)
+        _lib.check(lib.rs_rnn_eval_post_step(C.byref(state), st), "rs_rnn_eval_post_step")
+        if Rl > 1:                                                # :455-468: the lanes that begin their next run
+            vec.refresh(src, det, inten, bkg, nob, rects, mask=again)
+            _lib.check(lib.rs_rnn_eval_post_refresh(C.byref(state), st), "rs_rnn_eval_post_refresh")
+        it += 1
+    flags = vec.error_flags()                                     # one agent's idle step is a move by (0, 0): it never stalls
+    if flags:
+        raise RuntimeError(f"RadSearch env error flags 0x{flags:x}")
+    rep = lambda t: t.repeat_interleave(Rl) if Rl > 1 else t
+    out = _collect_results(keys, E, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1).bool(), rep(inten), rep(bkg))
+    summary = summarize(out)
+    if return_actions:
+        return out, summary, log[:it].cpu().numpy()
+    return out, summary
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -544,8 +651,8 @@ class evaluate_PPO:
             from .rada2c import RNNAgentPPO
             ag = RNNAgentPPO(id=0, device=dev)
             ag.load(agent_dir(0))                                       # pyt_save/model.pt (epoch_logger.py:216-284)
-            self.results, self.summary = run_test_environments(ag, sets, carry_hidden_across_runs=bool(kw.get("carry_hidden_across_runs", True)),
-                                                               **common)
+            self.results, self.summary = run_test_environments_rnn(ag, sets, fused=None,
+                                                                   carry_hidden_across_runs=bool(kw.get("carry_hidden_across_runs", True)), **common)
         elif A >= 2:
             # a feed-forward team: every agent's own network on its own rows (evaluate.py:305-331); recurrent teams are not built
             team_mode = kw.get("team_mode", "individual")

@@ -4,11 +4,11 @@
 // rs_ff_eval_step: the policy round.  rs_ff_team_step_kernel's grid, staging, forward pass and sampler (grid = (sample groups, agent),
 // a one-wave workgroup stages ITS agent's actor into LDS and serves 64-sample groups of that agent, lane = lane of the evaluation),
 // without the critic -- an evaluation throws the value away -- so 21.8 KB of LDS where the step round needs 42.3 KB.  The reading
-// (element 0 of a row) is standardised on the way in with rs_welford_standardize_kernel's expression, and the action row of a lane
+// (element 0 of a row) is standardised on the way in (rs_welford.hpp), and the action row of a lane
 // whose episode has ended is 8 (idle): no standardised copy of the observation and no masking pass exist.
 //
 // rs_eval_post_step: everything between rs_step and the next policy round, one thread per lane: return and length, the any-agent
-// terminal rule, the Welford update of rs_welford_update_kernel on the lanes still running, the new current observation, and a
+// terminal rule, the Welford update (rs_welford.hpp) on the lanes still running, the new current observation, and a
 // monotonic count of finished lanes that the host reads once every few lock-steps instead of reducing `alive` every step.
 //
 // rs_rnn_eval_post_step / rs_rnn_eval_post_refresh: the same place in the lock-step of the recurrent agent (RAD-A2C;
@@ -23,6 +23,7 @@
 
 #include "../../include/radsearch.h"
 #include "rs_mlp.hpp"
+#include "rs_welford.hpp"
 
 namespace {
 
@@ -53,7 +54,7 @@ rs_ff_eval_step_kernel(RsEvalNets nets, int A, const float* __restrict__ obs, co
         float xo[RS_IN_PAD], xp[RS_IN_PAD];
 #pragma unroll
         for (int k = 0; k < RS_IN; ++k) xo[k] = row[k];
-        if (w_mean) xo[0] = (float)(((double)xo[0] - w_mean[i]) / w_std[i]);
+        if (w_mean) xo[0] = rs_welford_standardized(w_mean, w_std, i, xo[0]);
         xo[11] = 0.0f;
 #pragma unroll
         for (int k = 0; k < RS_IN_PAD; ++k) xp[k] = __shfl_xor(xo[k], 32);
@@ -104,21 +105,7 @@ __global__ void __launch_bounds__(256) rs_eval_post_step_kernel(rs_eval_state s)
             const size_t i = (size_t)n * A + a;
             const float* src = s.env_obs + i * RS_OBS_DIM;
             float* dst = s.cur_obs + i * RS_OBS_DIM;
-            if (alive && s.w_count) {
-                // rs_welford_update_kernel, expression by expression
-                const double x = (double)src[0];
-                const double c = s.w_count[i] + 1.0, m = s.w_mean[i];
-                s.w_count[i] = c;
-                if (c == 1.0) {
-                    s.w_mean[i] = x;
-                } else {
-                    const double mn = m + (x - m) / c;
-                    const double q = s.w_sq[i] + (x - m) * (x - mn);
-                    s.w_mean[i] = mn;
-                    s.w_sq[i] = q;
-                    s.w_std[i] = fmax(sqrt(q / fmax(c - 1.0, 1.0)), 1.0);
-                }
-            }
+            if (alive && s.w_count) rs_welford_push(s.w_count, s.w_mean, s.w_sq, s.w_std, i, (double)src[0]);
 #pragma unroll
             for (int k = 0; k < RS_OBS_DIM; ++k) dst[k] = src[k];
         }
@@ -137,7 +124,7 @@ __device__ __forceinline__ void re_rows(const rs_rnn_eval_state& s, int n, const
     for (int k = 0; k < RS_OBS_DIM; ++k) cur[k] = src[k];
 #pragma unroll
     for (int k = 1; k < RS_OBS_DIM; ++k) x[k] = src[k];
-    x[0] = (float)(((double)src[0] - s.w_mean[n]) / s.w_std[n]);       // rs_welford_standardize_kernel's expression
+    x[0] = rs_welford_standardized(s.w_mean, s.w_std, n, src[0]);
 }
 
 __global__ void __launch_bounds__(256) rs_rnn_eval_post_step_kernel(rs_rnn_eval_state s) {
@@ -156,21 +143,7 @@ __global__ void __launch_bounds__(256) rs_rnn_eval_post_step_kernel(rs_rnn_eval_
         const bool found = a && s.env_done[n] != 0;
         const bool over = found || (a && steps == s.steps_per_episode);
         const float* src = s.env_obs + (size_t)n * RS_OBS_DIM;
-        if (a) {
-            // rs_welford_update_kernel, expression by expression; before the episode-over test (evaluate.py:392-397)
-            const double x = (double)src[0];
-            const double c = s.w_count[n] + 1.0, m = s.w_mean[n];
-            s.w_count[n] = c;
-            if (c == 1.0) {
-                s.w_mean[n] = x;
-            } else {
-                const double mn = m + (x - m) / c;
-                const double q = s.w_sq[n] + (x - m) * (x - mn);
-                s.w_mean[n] = mn;
-                s.w_sq[n] = q;
-                s.w_std[n] = fmax(sqrt(q / fmax(c - 1.0, 1.0)), 1.0);
-            }
-        }
+        if (a) rs_welford_push(s.w_count, s.w_mean, s.w_sq, s.w_std, n, (double)src[0]);      // before the episode-over test (evaluate.py:392-397)
         if (over) {
             if (run >= 0 && run < R) {                                  // an active lane has run < R; never write past the lane's records
                 const size_t slot = (size_t)n * R + run;
@@ -206,10 +179,7 @@ __global__ void __launch_bounds__(256) rs_rnn_eval_post_refresh_kernel(rs_rnn_ev
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= s.N || s.again[n] == 0) return;
     const float* src = s.env_obs + (size_t)n * RS_OBS_DIM;
-    s.w_count[n] = 1.0;
-    s.w_mean[n] = (double)src[0];
-    s.w_sq[n] = 0.0;
-    s.w_std[n] = 1.0;
+    rs_welford_restart(s.w_count, s.w_mean, s.w_sq, s.w_std, n, (double)src[0]);
     re_rows(s, n, src);
 }
 

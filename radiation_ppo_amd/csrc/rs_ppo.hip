@@ -54,23 +54,8 @@ __global__ void __launch_bounds__(64) rs_policy_forward_kernel(RsMlpParams pa, R
 }
 
 // ------------------------------------------------------------------------------------------------
-// K6: fused collector (rs_rollout16.hpp).  Per-episode Welford standardisation state of one env:
-struct RsWelford {
-    double count, mean, sq, std;
-    __device__ __forceinline__ void update(double x) {          // StatisticStandardization.update (RADTEAM_core.py:215-251)
-        count += 1.0;
-        if (count == 1.0) { mean = x; }
-        else {
-            double mean_new = mean + (x - mean) / count;
-            sq = sq + (x - mean) * (x - mean_new);
-            mean = mean_new;
-            std = fmax(sqrt(sq / (count - 1.0)), 1.0);
-        }
-    }
-    __device__ __forceinline__ float standardize(float x) const { return (float)(((double)x - mean) / std); }
-    __device__ __forceinline__ void reset() { count = 0.0; mean = 0.0; sq = 0.0; std = 1.0; }
-};
-
+// K6: fused collector (rs_rollout16.hpp), with its per-episode Welford standardisation state of one env (RsWelford, rs_welford.hpp)
+#include "rs_welford.hpp"
 #include "rs_rollout16.hpp"
 
 // ------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_welford.hpp"
 
 namespace {
 
@@ -18,18 +19,7 @@ __global__ void __launch_bounds__(256) rs_welford_update_kernel(double* __restri
                                                                 const uint8_t* __restrict__ mask, int M, int A) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M || (mask && !mask[i / A])) return;
-    const double x = (double)reading[(long long)i * stride];
-    const double c = count[i] + 1.0, m = mean[i];
-    count[i] = c;
-    if (c == 1.0) {                                         // first sample: mean = x, sq and std stay (:237-240)
-        mean[i] = x;
-        return;
-    }
-    const double mn = m + (x - m) / c;
-    const double s = sq[i] + (x - m) * (x - mn);
-    mean[i] = mn;
-    sq[i] = s;
-    sd[i] = fmax(sqrt(s / fmax(c - 1.0, 1.0)), 1.0);
+    rs_welford_push(count, mean, sq, sd, i, (double)reading[(long long)i * stride]);
 }
 
 __global__ void __launch_bounds__(256) rs_welford_reset_kernel(double* __restrict__ count, double* __restrict__ mean, double* __restrict__ sq,
@@ -44,7 +34,7 @@ __global__ void __launch_bounds__(256) rs_welford_standardize_kernel(const doubl
                                                                      float* __restrict__ out, long long out_stride, int M) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
-    out[(long long)i * out_stride] = (float)(((double)reading[(long long)i * stride] - mean[i]) / sd[i]);
+    out[(long long)i * out_stride] = rs_welford_standardized(mean, sd, i, reading[(long long)i * stride]);
 }
 
 // The per-epoch logger statistics of the collectors (train.py:386-398, :494-501, :519-526; ppo.py: EpochStats) for one lock-step:
@@ -165,23 +155,11 @@ __global__ void __launch_bounds__(256) rs_store_rows_kernel(StoreArgs a_) {
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // The element-wise bookkeeping of a collector lock-step (train.py:332-548 between the library calls), three launches instead of
-// ~30 (each ~4.6 us inside the replayed graph: half of the RAD-A2C collector's lock-step).  One thread per env; the Welford arithmetic
-// is rs_welford_update_kernel's, operation by operation.
-__device__ __forceinline__ void cs_welford_update(const rs_collect_state& c, int i, double x) {
-    const double cnt = c.w_count[i] + 1.0, m = c.w_mean[i];
-    c.w_count[i] = cnt;
-    if (cnt == 1.0) { c.w_mean[i] = x; return; }
-    const double mn = m + (x - m) / cnt;
-    const double s = c.w_sq[i] + (x - m) * (x - mn);
-    c.w_mean[i] = mn;
-    c.w_sq[i] = s;
-    c.w_std[i] = fmax(sqrt(s / fmax(cnt - 1.0, 1.0)), 1.0);
-}
-
+// ~30 (each ~4.6 us inside the replayed graph: half of the RAD-A2C collector's lock-step).  One thread per env.
 __device__ __forceinline__ void cs_standardized_row(const rs_collect_state& c, int i, const float* __restrict__ src, float* __restrict__ dst) {
 #pragma unroll
     for (int k = 1; k < RS_OBS_DIM; ++k) dst[k] = src[k];
-    dst[0] = c.w_count ? (float)(((double)src[0] - c.w_mean[i]) / c.w_std[i]) : src[0];
+    dst[0] = c.w_count ? rs_welford_standardized(c.w_mean, c.w_std, i, src[0]) : src[0];
 }
 
 // x <- obs with the reading standardised by the running statistics (train.py:334-341)
@@ -220,7 +198,7 @@ __global__ void __launch_bounds__(256) rs_collect_post_step_kernel(rs_collect_st
         const int i = n * A + a;
         const float* src = c.env_obs + (size_t)i * RS_OBS_DIM;
         float* dst = c.obs + (size_t)i * RS_OBS_DIM;
-        if (c.w_count) cs_welford_update(c, i, (double)src[0]);
+        if (c.w_count) rs_welford_push(c.w_count, c.w_mean, c.w_sq, c.w_std, i, (double)src[0]);
 #pragma unroll
         for (int k = 0; k < RS_OBS_DIM; ++k) dst[k] = src[k];
         if (c.xb) cs_standardized_row(c, i, src, c.xb + (size_t)i * RS_OBS_DIM);
@@ -245,7 +223,7 @@ __global__ void __launch_bounds__(256) rs_collect_post_reset_kernel(rs_collect_s
 #pragma unroll
         for (int k = 0; k < RS_OBS_DIM; ++k) dst[k] = src[k];
         c.ep_ret[i] = 0.0f;
-        if (c.w_count) { c.w_count[i] = 1.0; c.w_mean[i] = (double)src[0]; c.w_sq[i] = 0.0; c.w_std[i] = 1.0; }     // reset + first update
+        if (c.w_count) rs_welford_restart(c.w_count, c.w_mean, c.w_sq, c.w_std, i, (double)src[0]);
     }
     c.steps_in_ep[n] = 0;
     if (reset_hidden) {

@@ -99,6 +99,77 @@ def _pack(env_sets: Dict[str, tuple], runs: int, with_obstacles: bool, device):
     return keys, rep(src), rep(det), rep(inten), rep(bkg), (rep(nob) if with_obstacles else None), (rep(rects) if with_obstacles else None)
 
 
+def _open(env_sets, lanes_per_env, number_agents, obstruction_count, enforce_grid_boundaries, seed, device, welford=True, **vec_kwargs):
+    """The opening of every runner: a RadSearchVec of `lanes_per_env` lanes per saved environment with every lane's episode loaded.
+    Returns (vec, keys, saved, obs, stat): the set's keys in order, saved = (src, det, inten, bkg, nob, rects) per lane -- what
+    vec.refresh takes --, the first observation and, with welford, every agent's statistics buffer holding its first reading."""
+    dev = torch.device(device)
+    N = len(env_sets) * lanes_per_env
+    vec = RadSearchVec(N, number_agents=number_agents, obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries,
+                       seed=seed, device=device, **vec_kwargs)
+    keys, *saved = _pack(env_sets, lanes_per_env, obstruction_count != 0, dev)
+    vec.reset()                                                   # a valid handle state; every episode is then loaded
+    obs = vec.refresh(*saved)[0].clone()
+    stat = None
+    if welford:
+        stat = DeviceWelford((N, number_agents), dev)             # evaluate.py:362-367: one statistics buffer per agent
+        stat.update(obs[..., 0])
+    return vec, keys, saved, obs, stat
+
+
+def _has_policy_kernel(ac, dev) -> bool:
+    """The recurrent agent's policy step (GRU cell, heads, draw) has a HIP kernel on this device: K14 at the default widths, the sized
+    step at the others."""
+    return ac.fused_policy or (ac.sized_policy and dev.type == "cuda")
+
+
+def _has_pfgru_kernel(ac, dev) -> bool:
+    """The same for the agent's PFGRU location predictor: K11 at 24 hidden units, the sized step at the other widths."""
+    return ac.fused_pfgru or (ac.sized_pfgru and dev.type == "cuda")
+
+
+def recurrent_start(ac, N, seed, dev, impl):
+    """`hiddens` of N lanes of the recurrent agent `ac` as an evaluation creates them, once (evaluate.py:357): a one-agent PredictorBank
+    around the agent's own PFGRU with its particle sets drawn, and the GRU's initial state from the hash of the bank's lane keys.  The
+    composed and the fused runners start from this one definition, so their initial states cannot drift apart.  Returns (bank, hid)."""
+    from .pfgru import PredictorBank, hash_uniform
+    bank = PredictorBank(N, 1, hidden_size=ac.rec, seed=seed, carry_hidden=True, device=dev, impl=impl)
+    bank.cells[0] = ac.model
+    bank.reset()
+    gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(ac.hid, dtype=torch.int64, device=dev).view(1, -1)
+    return bank, ac.gru_h0(hash_uniform(gk)).contiguous()
+
+
+def _lane_records(N, dev):
+    """(alive, ep_len, ep_ret, success) of N lanes that run one episode each."""
+    return (torch.ones(N, dtype=torch.bool, device=dev), torch.zeros(N, dtype=torch.int32, device=dev),
+            torch.zeros(N, dtype=torch.float32, device=dev), torch.zeros(N, dtype=torch.bool, device=dev))
+
+
+def _book_step(alive, ep_len, ep_ret, success, r, done) -> None:
+    """One lock-step of the lane-per-run records, in place: reward r and the episode-over flag `done` count on the lanes still alive
+    (finished lanes keep stepping; their records are frozen)."""
+    ep_ret += torch.where(alive, r, torch.zeros_like(r))          # evaluate.py:400-406 (float32 accumulation)
+    ep_len += alive.int()
+    found = done & alive
+    success |= found
+    alive &= ~found
+
+
+def _close(vec, keys, saved, R, ep_len, ep_ret, success, log=None, ignore_flags=0):
+    """The closing of every runner: the env's error flags (those in ignore_flags excepted) raise, the records of the E * R runs, in
+    (environment, run) order, become the per-environment results and their summary; a runner that kept an action log passes it as a
+    device tensor.  keys and saved are _open's."""
+    flags = vec.error_flags() & ~ignore_flags
+    if flags:
+        raise RuntimeError(f"RadSearch env error flags 0x{flags:x}")
+    inten, bkg = (t.repeat_interleave(len(ep_len) // len(t)) for t in saved[2:4])     # a lane that ran several runs: once per run
+    out = _collect_results(keys, len(keys), R, ep_len, ep_ret, success, inten, bkg)
+    if log is None:
+        return out, summarize(out)
+    return out, summarize(out), log.cpu().numpy()
+
+
 @torch.no_grad()
 def run_test_environments(agent: VecAgentPPO, env_sets: Dict[str, tuple], montecarlo_runs: int = 100, steps_per_episode: int = 120,
                           obstruction_count: int = 0, enforce_grid_boundaries: bool = True, seed: int = 0,
@@ -116,67 +187,42 @@ def run_test_environments(agent: VecAgentPPO, env_sets: Dict[str, tuple], montec
     if carry_hidden_across_runs and hasattr(agent.agent, "gru_cell"):
         return _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruction_count, enforce_grid_boundaries, seed,
                                device, falloff, return_actions)
-    E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
-    N = E * R
+    R, L = montecarlo_runs, steps_per_episode
+    N = len(env_sets) * R
     dev = torch.device(device)
-    with_obs = obstruction_count != 0
-    vec = RadSearchVec(N, number_agents=1, obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries,
-                       seed=seed, device=device, falloff=falloff)
-    keys, src, det, inten, bkg, nob, rects = _pack(env_sets, R, with_obs, dev)
-    vec.reset()                                                   # a valid handle state; every episode is then loaded
-    obs = vec.refresh(src, det, inten, bkg, nob, rects)[0].clone()
-    stat = DeviceWelford((N, 1), dev)                             # evaluate.py:362-367
-    stat.update(obs[..., 0])
-    alive = torch.ones(N, dtype=torch.bool, device=dev)
-    ep_len = torch.zeros(N, dtype=torch.int32, device=dev)
-    ep_ret = torch.zeros(N, dtype=torch.float32, device=dev)
-    success = torch.zeros(N, dtype=torch.bool, device=dev)
+    ac = agent.agent
+    vec, keys, saved, obs, stat = _open(env_sets, R, 1, obstruction_count, enforce_grid_boundaries, seed, device, falloff=falloff)
+    alive, ep_len, ep_ret, success = _lane_records(N, dev)
     u = torch.empty(N, 1, dtype=torch.float32, device=dev)
     act8 = torch.empty(N, 1, dtype=torch.int8, device=dev)
     log = []
-    recurrent = hasattr(agent.agent, "gru_cell")                  # RAD-A2C: hidden = ac.reset_hidden() per episode (evaluate.py:357-360)
+    recurrent = hasattr(ac, "gru_cell")                           # RAD-A2C: hidden = ac.reset_hidden() per episode (evaluate.py:357-360)
     if recurrent:
-        from .pfgru import PredictorBank, hash_uniform
-        bank = PredictorBank(N, 1, hidden_size=agent.agent.rec, seed=seed, carry_hidden=True, device=dev,
-                             impl="hip" if (agent.agent.fused_pfgru or (agent.agent.sized_pfgru and dev.type == "cuda")) else "torch")
-        bank.cells[0] = agent.agent.model
-        bank.reset()
-        gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(agent.agent.hid, dtype=torch.int64, device=dev).view(1, -1)
-        hid = agent.agent.gru_h0(hash_uniform(gk))
+        bank, hid = recurrent_start(ac, N, seed, dev, "hip" if _has_pfgru_kernel(ac, dev) else "torch")
+        fused = _has_policy_kernel(ac, dev) and hasattr(agent, "policy_step_hip")
     for _ in range(L):
         x = obs.clone()
         stat.standardize(obs[..., 0], out=x[..., 0])
         vec.action_uniforms(u)
-        if recurrent and (agent.agent.fused_policy or (agent.agent.sized_policy and dev.type == "cuda")) and hasattr(agent, "policy_step_hip"):
+        if recurrent and fused:
             a = torch.empty(N, dtype=torch.int64, device=dev)             # K14 (or the sized step): GRU cell + heads + draw in one launch
             agent.policy_step_hip(x[:, 0].contiguous(), bank.predict(x)[:, 0].contiguous(), hid, u=u[:, 0].contiguous(), h_out=hid, act=a)
         elif recurrent:
-            logits, _, hid = agent.agent.policy_step(x[:, 0], bank.predict(x)[:, 0], hid)
+            logits, _, hid = ac.policy_step(x[:, 0], bank.predict(x)[:, 0], hid)
             cdf = torch.cumsum(torch.softmax(logits, dim=-1), dim=-1)
             a = (cdf[:, :-1] <= u[:, 0].unsqueeze(-1)).sum(dim=-1)
         else:
-            a, _, _ = agent.agent.act(x[:, 0], u[:, 0])           # ac.step: sample from the policy (evaluate.py:373-383)
+            a, _, _ = ac.act(x[:, 0], u[:, 0])                    # ac.step: sample from the policy (evaluate.py:373-383)
         act8[:, 0] = torch.where(alive, a, torch.full_like(a, 8)).to(torch.int8)      # finished episodes idle in place
         if return_actions:
             log.append(a.clone())
-        obs_n, rew, _, done, _ = vec.step(act8)                   # finished envs keep stepping; their records are frozen
-        ep_ret += torch.where(alive, rew[:, 0], torch.zeros_like(rew[:, 0]))       # :400-406 (float32 accumulation)
-        ep_len += alive.int()
-        found = done[:, 0].bool() & alive
-        success |= found
-        alive &= ~found
+        obs_n, rew, _, done, _ = vec.step(act8)
+        _book_step(alive, ep_len, ep_ret, success, rew[:, 0], done[:, 0].bool())
         stat.update(obs_n[..., 0], mask=alive)
         obs = obs_n.clone()
         if not bool(alive.any()):
             break
-    flags = vec.error_flags()
-    if flags:
-        raise RuntimeError(f"RadSearch env error flags 0x{flags:x}")
-    out = _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg)
-    summary = summarize(out)
-    if return_actions:
-        return out, summary, torch.stack(log).cpu().numpy()
-    return out, summary
+    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=torch.stack(log) if return_actions else None)
 
 
 @torch.no_grad()
@@ -187,24 +233,12 @@ def _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruc
     (:455), its statistics buffer restarts on the fresh observation (:462-468) -- and the GRU state and the PFGRU's particle
     set are left as the finished run left them (`hiddens` is assigned once, :357).  With return_actions the third result is the
     [lock-steps, E] action log with -1 where a lane had finished all its runs."""
-    from .pfgru import PredictorBank, hash_uniform
     E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
     dev = torch.device(device)
-    with_obs = obstruction_count != 0
-    vec = RadSearchVec(E, number_agents=1, obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries,
-                       seed=seed, device=device, falloff=falloff)
-    keys, src, det, inten, bkg, nob, rects = _pack(env_sets, 1, with_obs, dev)
-    vec.reset()
-    obs = vec.refresh(src, det, inten, bkg, nob, rects)[0].clone()
-    stat = DeviceWelford((E, 1), dev)
-    stat.update(obs[..., 0])
-    bank = PredictorBank(E, 1, hidden_size=agent.agent.rec, seed=seed, carry_hidden=True, device=dev,
-                         impl="hip" if (agent.agent.fused_pfgru or (agent.agent.sized_pfgru and dev.type == "cuda")) else "torch")
-    bank.cells[0] = agent.agent.model
-    bank.reset()
-    gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(agent.agent.hid, dtype=torch.int64, device=dev).view(1, -1)
-    hid = agent.agent.gru_h0(hash_uniform(gk)).contiguous()
-    fused = (agent.agent.fused_policy or (agent.agent.sized_policy and dev.type == "cuda")) and hasattr(agent, "policy_step_hip")
+    ac = agent.agent
+    vec, keys, saved, obs, stat = _open(env_sets, 1, 1, obstruction_count, enforce_grid_boundaries, seed, device, falloff=falloff)
+    bank, hid = recurrent_start(ac, E, seed, dev, "hip" if _has_pfgru_kernel(ac, dev) else "torch")
+    fused = _has_policy_kernel(ac, dev) and hasattr(agent, "policy_step_hip")
     run = torch.zeros(E, dtype=torch.int64, device=dev)
     steps = torch.zeros(E, dtype=torch.int32, device=dev)
     ret = torch.zeros(E, dtype=torch.float32, device=dev)
@@ -229,7 +263,7 @@ def _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruc
             agent.policy_step_hip(x[:, 0].contiguous(), bank.predict(x, mask=active)[:, 0].contiguous(), hid, u=u[:, 0].contiguous(),
                                   h_out=hid, act=a)
         else:
-            logits, _, hid = agent.agent.policy_step(x[:, 0], bank.predict(x, mask=active)[:, 0], hid)
+            logits, _, hid = ac.policy_step(x[:, 0], bank.predict(x, mask=active)[:, 0], hid)
             cdf = torch.cumsum(torch.softmax(logits, dim=-1), dim=-1)
             a = (cdf[:, :-1] <= u[:, 0].unsqueeze(-1)).sum(dim=-1)
         act8[:, 0] = torch.where(active, a, torch.full_like(a, 8)).to(torch.int8)       # lanes with all runs done idle in place
@@ -247,20 +281,14 @@ def _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruc
         rec_suc[lane, slot] = torch.where(over, found, rec_suc[lane, slot])
         run += over.long()
         again = over & (run < R)                                                        # :455-468: refresh, statistics restart
-        obs_r = vec.refresh(src, det, inten, bkg, nob, rects, mask=again.to(torch.uint8))[0]
+        obs_r = vec.refresh(*saved, mask=again.to(torch.uint8))[0]
         stat.reset(again)
         stat.update(obs_r[..., 0], mask=again)
         obs = torch.where(again.view(E, 1, 1), obs_r, obs_n).clone()
         steps.masked_fill_(over, 0)
         ret.masked_fill_(over, 0.0)
-    flags = vec.error_flags()
-    if flags:
-        raise RuntimeError(f"RadSearch env error flags 0x{flags:x}")
-    rep = lambda t: t.repeat_interleave(R)
-    out = _collect_results(keys, E, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1), rep(inten), rep(bkg))
-    if return_actions:
-        return out, summarize(out), torch.stack(log).cpu().numpy()
-    return out, summarize(out)
+    return _close(vec, keys, saved, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1),
+                  log=torch.stack(log) if return_actions else None)
 
 
 @torch.no_grad()
@@ -286,7 +314,7 @@ def run_test_environments_rnn(agent, env_sets: Dict[str, tuple], montecarlo_runs
     dev = torch.device(device)
     ac = getattr(agent, "agent", None)
     can = (dev.type == "cuda" and hasattr(ac, "gru_cell") and hasattr(agent, "policy_step_masked")
-           and (ac.fused_policy or ac.sized_policy) and (ac.fused_pfgru or ac.sized_pfgru))
+           and _has_policy_kernel(ac, dev) and _has_pfgru_kernel(ac, dev))
     if fused is None:
         fused = can
     if fused and not can:
@@ -305,23 +333,11 @@ def run_test_environments_rnn(agent, env_sets: Dict[str, tuple], montecarlo_runs
             lens = np.array([l for r in out for l in r.total_episode_length])
             log = np.where(np.arange(log.shape[0]).reshape(-1, 1) >= lens.reshape(1, -1), 8, log)
         return out, summary, log.astype(np.int8)
-    from .pfgru import PredictorBank, hash_uniform
     Rl = R if carry_hidden_across_runs else 1                     # runs per lane
     N = E * R // Rl
-    with_obs = obstruction_count != 0
     lib = _lib.load()
-    vec = RadSearchVec(N, number_agents=1, obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries,
-                       seed=seed, device=device, falloff=falloff)
-    keys, src, det, inten, bkg, nob, rects = _pack(env_sets, R // Rl, with_obs, dev)
-    vec.reset()                                                   # a valid handle state; every episode is then loaded
-    obs = vec.refresh(src, det, inten, bkg, nob, rects)[0].clone()
-    stat = DeviceWelford((N, 1), dev)                             # evaluate.py:362-367
-    stat.update(obs[..., 0])
-    bank = PredictorBank(N, 1, hidden_size=ac.rec, seed=seed, carry_hidden=True, device=dev, impl="hip")
-    bank.cells[0] = ac.model
-    bank.reset()                                                  # `hiddens` is created once (:357): particle sets and h0 are drawn here only
-    gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(ac.hid, dtype=torch.int64, device=dev).view(1, -1)
-    hid = ac.gru_h0(hash_uniform(gk)).contiguous()
+    vec, keys, saved, obs, stat = _open(env_sets, R // Rl, 1, obstruction_count, enforce_grid_boundaries, seed, device, falloff=falloff)
+    bank, hid = recurrent_start(ac, N, seed, dev, "hip")          # particle sets and h0 are drawn here only
     x = obs.clone()
     stat.standardize(obs[..., 0], out=x[..., 0])
     active = torch.ones(N, dtype=torch.uint8, device=dev)
@@ -356,18 +372,12 @@ def run_test_environments_rnn(agent, env_sets: Dict[str, tuple], montecarlo_runs
         vec.step(a8)
         _lib.check(lib.rs_rnn_eval_post_step(C.byref(state), st), "rs_rnn_eval_post_step")
         if Rl > 1:                                                # :455-468: the lanes that begin their next run
-            vec.refresh(src, det, inten, bkg, nob, rects, mask=again)
+            vec.refresh(*saved, mask=again)
             _lib.check(lib.rs_rnn_eval_post_refresh(C.byref(state), st), "rs_rnn_eval_post_refresh")
         it += 1
-    flags = vec.error_flags()                                     # one agent's idle step is a move by (0, 0): it never stalls
-    if flags:
-        raise RuntimeError(f"RadSearch env error flags 0x{flags:x}")
-    rep = lambda t: t.repeat_interleave(Rl) if Rl > 1 else t
-    out = _collect_results(keys, E, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1).bool(), rep(inten), rep(bkg))
-    summary = summarize(out)
-    if return_actions:
-        return out, summary, log[:it].cpu().numpy()
-    return out, summary
+    # no flag is masked: one agent's idle step is a move by (0, 0), it never stalls
+    return _close(vec, keys, saved, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1).bool(),
+                  log=log[:it] if return_actions else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -386,15 +396,10 @@ def run_test_environments_cnn(agents: Dict[int, Any], env_sets: Dict[str, tuple]
     from .maps import HeatMaps
     from .pfgru import PredictorBank
     A = len(agents)
-    E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
-    N = E * R
+    R, L = montecarlo_runs, steps_per_episode
+    N = len(env_sets) * R
     dev = torch.device(device)
-    with_obs = obstruction_count != 0
-    vec = RadSearchVec(N, number_agents=A, obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries,
-                       seed=seed, device=device)
-    keys, src, det, inten, bkg, nob, rects = _pack(env_sets, R, with_obs, dev)
-    vec.reset()
-    obs = vec.refresh(src, det, inten, bkg, nob, rects)[0].clone()
+    vec, keys, saved, obs, _ = _open(env_sets, R, A, obstruction_count, enforce_grid_boundaries, seed, device, welford=False)
     maps = HeatMaps(vec, L, enforce_boundaries=bool(enforce_grid_boundaries))
     bank = None
     if use_predictor:
@@ -403,10 +408,7 @@ def run_test_environments_cnn(agents: Dict[int, Any], env_sets: Dict[str, tuple]
             if getattr(ag, "model", None) is not None:                # the agent's own (saved) predictor weights
                 bank.load_state_dict(a, ag.model.state_dict())
         bank.reset()
-    alive = torch.ones(N, dtype=torch.bool, device=dev)
-    ep_len = torch.zeros(N, dtype=torch.int32, device=dev)
-    ep_ret = torch.zeros(N, dtype=torch.float32, device=dev)
-    success = torch.zeros(N, dtype=torch.bool, device=dev)
+    alive, ep_len, ep_ret, success = _lane_records(N, dev)
     u = torch.empty(N, A, dtype=torch.float32, device=dev)
     act8 = torch.empty(N, A, dtype=torch.int8, device=dev)
     log = []
@@ -421,23 +423,13 @@ def run_test_environments_cnn(agents: Dict[int, Any], env_sets: Dict[str, tuple]
         if return_actions:
             log.append(act8.clone())
         obs_n, rew, team, done, _ = vec.step(act8)
-        r = rew[:, 0] if team_mode == "individual" else team
-        ep_ret += torch.where(alive, r, torch.zeros_like(r))
-        ep_len += alive.int()
-        found = done.bool().any(dim=1) & alive
-        success |= found
-        alive &= ~found
+        _book_step(alive, ep_len, ep_ret, success, rew[:, 0] if team_mode == "individual" else team, done.bool().any(dim=1))
         obs = obs_n.clone()
         if not bool(alive.any()):
             break
-    flags = vec.error_flags() & ~_lib.ENVERR_IDLE_STALL        # finished episodes idle on purpose; stacked agents may "stall"
-    if flags:
-        raise RuntimeError(f"RadSearch env error flags 0x{flags:x}")
-    out = _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg)
-    summary = summarize(out)
-    if return_actions:
-        return out, summary, torch.stack(log).cpu().numpy()
-    return out, summary
+    # finished episodes idle on purpose; stacked agents may "stall"
+    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=torch.stack(log) if return_actions else None,
+                  ignore_flags=_lib.ENVERR_IDLE_STALL)
 
 
 @torch.no_grad()
@@ -462,22 +454,12 @@ def run_test_environments_team(agents: Dict[int, VecAgentPPO], env_sets: Dict[st
     A = len(agents)
     if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
         raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}")
-    E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
-    N = E * R
+    R, L = montecarlo_runs, steps_per_episode
+    N = len(env_sets) * R
     dev = torch.device(device)
-    with_obs = obstruction_count != 0
     lib = _lib.load()
-    vec = RadSearchVec(N, number_agents=A, obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries,
-                       seed=seed, device=device, falloff=falloff)
-    keys, src, det, inten, bkg, nob, rects = _pack(env_sets, R, with_obs, dev)
-    vec.reset()                                                   # a valid handle state; every episode is then loaded
-    obs = vec.refresh(src, det, inten, bkg, nob, rects)[0].clone()
-    stat = DeviceWelford((N, A), dev)                             # evaluate.py:362-367: one statistics buffer per agent
-    stat.update(obs[..., 0])
-    alive = torch.ones(N, dtype=torch.bool, device=dev)
-    ep_len = torch.zeros(N, dtype=torch.int32, device=dev)
-    ep_ret = torch.zeros(N, dtype=torch.float32, device=dev)
-    success = torch.zeros(N, dtype=torch.bool, device=dev)
+    vec, keys, saved, obs, stat = _open(env_sets, R, A, obstruction_count, enforce_grid_boundaries, seed, device, falloff=falloff)
+    alive, ep_len, ep_ret, success = _lane_records(N, dev)
     u = torch.empty(N, A, dtype=torch.float32, device=dev)
     # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads
     log = torch.full((L, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
@@ -514,23 +496,13 @@ def run_test_environments_team(agents: Dict[int, VecAgentPPO], env_sets: Dict[st
             _lib.check(lib.rs_ff_team_step(pa, pc, A, p(x), p(u), p(k_act), p(k_f), None, None, N, st), "rs_ff_team_step")
             a8.copy_(torch.where(alive.view(N, 1), k_act.t(), torch.full_like(k_act.t(), 8)).to(torch.int8))   # finished episodes idle
             obs_n, rew, team, done, _ = vec.step(a8)
-            r = team if use_team else rew[:, 0]
-            ep_ret += torch.where(alive, r, torch.zeros_like(r))  # :400-406 (float32 accumulation)
-            ep_len += alive.int()
-            found = done.bool().any(dim=1) & alive
-            success |= found
-            alive &= ~found
+            _book_step(alive, ep_len, ep_ret, success, team if use_team else rew[:, 0], done.bool().any(dim=1))
             stat.update(obs_n[..., 0], mask=alive)
             obs.copy_(obs_n)
         it += 1
-    flags = vec.error_flags() & ~_lib.ENVERR_IDLE_STALL        # finished episodes idle on purpose; stacked agents may "stall"
-    if flags:
-        raise RuntimeError(f"RadSearch env error flags 0x{flags:x}")
-    out = _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg)
-    summary = summarize(out)
-    if return_actions:
-        return out, summary, log[:it].cpu().numpy()
-    return out, summary
+    # finished episodes idle on purpose; stacked agents may "stall"
+    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=log[:it] if return_actions else None,
+                  ignore_flags=_lib.ENVERR_IDLE_STALL)
 
 
 def _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg) -> List[MonteCarloResults]:
@@ -636,6 +608,12 @@ class evaluate_PPO:
             if not cands:
                 raise FileNotFoundError(f"no {i}_agent* directory under {kw['model_path']}")
             return os.path.join(kw["model_path"], cands[0])
+
+        def ff_agent(i):                                                # <id>_agent*/pyt_save/model.pt, or model.pt beside it
+            ag = VecAgentPPO(id=i, device=dev)
+            f = os.path.join(agent_dir(i), "pyt_save", "model.pt")
+            ag.load(f if os.path.exists(f) else os.path.join(agent_dir(i), "model.pt"))
+            return ag
         if arch == "cnn":
             from .maps import CNNCritic
             from .pfgru import PFGRUCell
@@ -658,17 +636,8 @@ class evaluate_PPO:
             team_mode = kw.get("team_mode", "individual")
             if team_mode != "individual":
                 raise ValueError("team_mode must be 'individual' for a feed-forward team: no global critic for RAD-A2C")   # evaluate.py:279-280
-            agents = {}
-            for i in range(A):
-                agents[i] = VecAgentPPO(id=i, device=dev)
-                d = agent_dir(i)
-                f = os.path.join(d, "pyt_save", "model.pt")
-                agents[i].load(f if os.path.exists(f) else os.path.join(d, "model.pt"))
+            agents = {i: ff_agent(i) for i in range(A)}
             self.results, self.summary = run_test_environments_team(agents, sets, team_mode=team_mode, **common)
         else:
-            ag = VecAgentPPO(id=0, device=dev)
-            d = agent_dir(0)
-            f = os.path.join(d, "pyt_save", "model.pt")
-            ag.load(f if os.path.exists(f) else os.path.join(d, "model.pt"))
-            self.results, self.summary = run_test_environments(ag, sets, **common)
+            self.results, self.summary = run_test_environments(ff_agent(0), sets, **common)
         return self.results, self.summary

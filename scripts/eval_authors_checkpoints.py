@@ -76,7 +76,7 @@ def original_pipeline_episode_stats(N=8192, L=120, seed=5, whole_vector=False, c
     of K11 / K14 and the HIP env under the env's own spawn rules (U{1..5} rectangles): one episode per env, to set beside the last rows
     of og/progress.txt (DoneCount / episodes, EpLen)."""
     from radiation_ppo_amd.envs import RadSearchVec
-    from radiation_ppo_amd.pfgru import PredictorBank, hash_uniform
+    from radiation_ppo_amd.evaluate import recurrent_start
     from radiation_ppo_amd.rada2c import RNNAgentPPO
     dev = torch.device("cuda:0")
     ag = RNNAgentPPO(id=0, device=dev)
@@ -86,11 +86,7 @@ def original_pipeline_episode_stats(N=8192, L=120, seed=5, whole_vector=False, c
     obs = vec.reset()[0].clone()
     cnt = torch.ones(N, dtype=torch.float64, device=dev)
     mu = obs[:, 0, 0].double().clone(); sq = torch.zeros_like(mu); sig = torch.ones_like(mu)
-    bank = PredictorBank(N, 1, seed=seed, carry_hidden=True, device=dev)
-    bank.cells[0] = ag.agent.model
-    bank.reset()
-    gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(24, dtype=torch.int64, device=dev).view(1, -1)
-    hid = ag.agent.gru_h0(hash_uniform(gk)).contiguous()
+    bank, hid = recurrent_start(ag.agent, N, seed, dev, "hip")
     alive = torch.ones(N, dtype=torch.bool, device=dev)
     ep_len = torch.zeros(N, dtype=torch.int32, device=dev); ep_ret = torch.zeros(N, device=dev)
     success = torch.zeros(N, dtype=torch.bool, device=dev)

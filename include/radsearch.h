@@ -741,6 +741,63 @@ typedef struct {
 int rs_rnn_eval_post_step(const rs_rnn_eval_state* s, rs_stream_t stream);
 int rs_rnn_eval_post_refresh(const rs_rnn_eval_state* s, rs_stream_t stream);
 
+/* ---- Monte-Carlo evaluation of RAD-A2C teams of 2 to 8 recurrent agents (algos/multiagent/evaluate.py:305-318, :333-476) -------------
+ * Every agent has its own network (:305-318), its own `hiddens` entry, created once per EpisodeRunner.run (:353), and its own statistics
+ * buffer (:361-364, :395-397, :461-466); an episode ends when any agent's terminal flag rises (:411-423) or at steps_per_episode, and
+ * agent 0's return is recorded (`episode_return[0]`, :441-444).  A lane is one team working through runs_per_lane consecutive runs of one
+ * saved environment, as for the single agent above.  One lock-step is rs_action_uniforms, rs_pfgru_step (every owner, mask = active),
+ * rs_rnn_team_eval_step (or, at other widths, one rs_rnn_sized_step per agent on its rows), rs_step, rs_rnn_team_eval_post_step and,
+ * when runs_per_lane > 1, rs_refresh(mask = again) and rs_rnn_team_eval_post_refresh, all on one stream
+ * (radiation_ppo_amd/evaluate.py: run_test_environments_rnn_team).
+ *
+ * rs_rnn_team_eval_step: the policy round of every agent of a default-width team (GRU 24, heads 32 / 32) in one launch,
+ * grid = (64-lane groups, agent); the arithmetic is rs_rnn_policy_step_rows', operation by operation, without the value head: the
+ * result equals num_agents calls of rs_rnn_policy_step_rows (mask = active, h_out = h) bit for bit.
+ *   weights [A]           host array of device pointers, each to RS_RNN_POLICY_WEIGHT_FLOATS packed floats, A = num_agents
+ *   x [N][A][11]          the standardised observation
+ *   loc [N][A][2]         the location predictions (rs_pfgru_step's pred)
+ *   h [A][N][24]          the GRU states, updated in place on the active lanes (a lane reads its row before it stores)
+ *   u [N][A], active [N]  the uniforms of rs_action_uniforms; active[n] != 0 while lane n has runs left
+ *   act8 [N][A]           rs_step's action rows: #{j < 7 : cdf_j <= u} on the active lanes
+ * An inactive lane writes neither h nor act8; a wave without an active lane leaves at once.
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL pointer, a NULL entry among the first num_agents weights, num_agents outside
+ * 1..RS_MAX_AGENTS, num_envs < 1. */
+int rs_rnn_team_eval_step(const float* const* weights, int32_t num_agents, const float* x, const float* loc, float* h, const float* u,
+                          const uint8_t* active, int8_t* act8, int32_t num_envs, rs_stream_t stream);
+
+/* rs_rnn_team_eval_post_step: one launch after rs_step, one thread per lane, in this order (a = active[n] on entry):
+ *   where a: ret += env_reward[n][0] (float32), steps += 1, pf_calls += 1 (the bank keeps one counter per lane, not one per owner);
+ *   found = a and any agent's env_done[n][.], over = found or (a and steps == steps_per_episode); where a: every agent's statistics take
+ *   env_obs[n][agent][0] (the Welford update of rs_welford_update, before the episode-over test, :395-397); where over: rec_len /
+ *   rec_ret / rec_suc [n][run] = steps, ret, found, then run += 1, steps = 0, ret = 0; again = over and run < runs_per_lane; where
+ *   over and run == runs_per_lane: active = 0, all A entries of idle_act8[n] = 8 and the lane counts once into finished[0] (a monotonic
+ *   counter); on every lane cur_obs <- env_obs and x <- env_obs with x[n][agent][0] = (float)(((double)obs0 - mean) / std), that
+ *   agent's statistics as just updated.
+ * rs_rnn_team_eval_post_refresh: one launch after rs_refresh(mask = again).  Where again != 0: every agent's statistics restart
+ *   (count = mean = sq = 0, std = 1) and take the refreshed reading as their first sample, cur_obs <- env_obs, x <- its standardised
+ *   form (:456-466).  The other lanes are untouched, and so are all hidden states.
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL struct or required field, A outside 1..RS_MAX_AGENTS, N < 1,
+ * runs_per_lane < 1, steps_per_episode < 1.  Only pf_calls and idle_act8 may be NULL. */
+typedef struct {
+    int32_t N, A, runs_per_lane, steps_per_episode;
+    const float* env_obs;         /* [N][A][11] the env's output rows (rs_step / rs_refresh) */
+    const float* env_reward;      /* [N][A] */
+    const uint8_t* env_done;      /* [N][A] */
+    float* cur_obs;               /* [N][A][11] the current observation */
+    float* x;                     /* [N][A][11] the PFGRUs' and the policies' input: cur_obs with the readings standardised */
+    double* w_count; double* w_mean; double* w_sq; double* w_std;     /* [N][A] Welford state of the readings; all required */
+    uint8_t* active;              /* [N] != 0 while the lane has runs left */
+    uint8_t* again;               /* [N] written by the post-step, read by rs_refresh (its mask) and the post-refresh */
+    int32_t* run; int32_t* steps; /* [N] index of the current run, steps taken in it */
+    float* ret;                   /* [N] agent 0's return so far */
+    int32_t* rec_len; float* rec_ret; uint8_t* rec_suc;               /* [N][runs_per_lane] the records of the runs that ended */
+    int64_t* pf_calls;            /* [N] or NULL: the predictor bank's per-lane call counter */
+    int8_t* idle_act8;            /* [N][A] or NULL: rs_step's action rows where one fixed buffer serves every lock-step */
+    int32_t* finished;            /* [1] lanes whose last run has ended */
+} rs_rnn_team_eval_state;
+int rs_rnn_team_eval_post_step(const rs_rnn_team_eval_state* s, rs_stream_t stream);
+int rs_rnn_team_eval_post_refresh(const rs_rnn_team_eval_state* s, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

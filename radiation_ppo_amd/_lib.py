@@ -53,6 +53,13 @@ class RsRnnEvalState(C.Structure):
                                   "run", "steps", "ret", "rec_len", "rec_ret", "rec_suc", "pf_calls", "idle_act8", "finished")]
 
 
+class RsRnnTeamEvalState(C.Structure):
+    """rs_rnn_team_eval_state (include/radsearch.h)."""
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("runs_per_lane", C.c_int32), ("steps_per_episode", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("env_obs", "env_reward", "env_done", "cur_obs", "x", "w_count", "w_mean", "w_sq", "w_std", "active", "again",
+                                  "run", "steps", "ret", "rec_len", "rec_ret", "rec_suc", "pf_calls", "idle_act8", "finished")]
+
+
 class RsMlpParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
@@ -185,6 +192,9 @@ SYMBOLS = [
     ("rs_eval_post_step", C.c_int, [C.POINTER(RsEvalState), C.c_void_p]),
     ("rs_rnn_eval_post_step", C.c_int, [C.POINTER(RsRnnEvalState), C.c_void_p]),
     ("rs_rnn_eval_post_refresh", C.c_int, [C.POINTER(RsRnnEvalState), C.c_void_p]),
+    ("rs_rnn_team_eval_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
+    ("rs_rnn_team_eval_post_step", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),
+    ("rs_rnn_team_eval_post_refresh", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),
 ]
 
 _lib = None

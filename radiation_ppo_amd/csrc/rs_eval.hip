@@ -16,6 +16,10 @@
 // hidden states carried (evaluate.py:357, :455-470): returns, step counts, the per-run records, the Welford update and restart, the
 // next observation raw and standardised, the predictor bank's call counter and the finished-lane count, one thread per lane.
 //
+// rs_rnn_team_eval_post_step / rs_rnn_team_eval_post_refresh: the same for a team of A recurrent agents per lane
+// (radiation_ppo_amd/evaluate.py: run_test_environments_rnn_team): every agent's own statistics and rows, the any-agent terminal rule,
+// agent 0's reward.  The team's policy round, rs_rnn_team_eval_step, lives beside K14 in rs_rnn_policy.hip.
+//
 // The float64 arithmetic is the reference's, operation by operation (the build disables FMA contraction): the results equal
 // DeviceWelford's and the torch composition's bit for bit.
 #include <hip/hip_runtime.h>
@@ -183,6 +187,85 @@ __global__ void __launch_bounds__(256) rs_rnn_eval_post_refresh_kernel(rs_rnn_ev
     re_rows(s, n, src);
 }
 
+// ---- RAD-A2C teams (A recurrent agents per lane): rs_rnn_eval_post_step / _post_refresh with every agent's own statistics and rows,
+// the any-agent terminal rule and agent 0's reward (evaluate.py:395-397, :411-423, :441-444)
+__device__ __forceinline__ void rte_rows(const rs_rnn_team_eval_state& s, size_t i) {
+    const float* src = s.env_obs + i * RS_OBS_DIM;
+    float* cur = s.cur_obs + i * RS_OBS_DIM;
+    float* x = s.x + i * RS_OBS_DIM;
+#pragma unroll
+    for (int k = 0; k < RS_OBS_DIM; ++k) cur[k] = src[k];
+#pragma unroll
+    for (int k = 1; k < RS_OBS_DIM; ++k) x[k] = src[k];
+    x[0] = rs_welford_standardized(s.w_mean, s.w_std, i, src[0]);
+}
+
+__global__ void __launch_bounds__(256) rs_rnn_team_post_step_kernel(rs_rnn_team_eval_state s) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    bool ended = false;
+    if (n < s.N) {
+        const int R = s.runs_per_lane, A = s.A;
+        const bool a = s.active[n] != 0;
+        int run = s.run[n], steps = s.steps[n];
+        float ret = s.ret[n];
+        if (a) {
+            ret += s.env_reward[(size_t)n * A];                         // `episode_return[0]` (evaluate.py:400-447)
+            steps += 1;
+            if (s.pf_calls) s.pf_calls[n] += 1;                         // one counter per lane serves every owner
+        }
+        bool any = false;
+        for (int g = 0; g < A; ++g) any = any || s.env_done[(size_t)n * A + g] != 0;
+        const bool found = a && any;
+        const bool over = found || (a && steps == s.steps_per_episode);
+        if (a) {                                                        // before the episode-over test (evaluate.py:395-397)
+            for (int g = 0; g < A; ++g) {
+                const size_t i = (size_t)n * A + g;
+                rs_welford_push(s.w_count, s.w_mean, s.w_sq, s.w_std, i, (double)s.env_obs[i * RS_OBS_DIM]);
+            }
+        }
+        if (over) {
+            if (run >= 0 && run < R) {                                  // an active lane has run < R; never write past the lane's records
+                const size_t slot = (size_t)n * R + run;
+                s.rec_len[slot] = steps;
+                s.rec_ret[slot] = ret;
+                s.rec_suc[slot] = found ? 1 : 0;
+            }
+            run += 1;
+            steps = 0;
+            ret = 0.0f;
+        }
+        s.again[n] = (over && run < R) ? 1 : 0;
+        if (over && run == R) {
+            s.active[n] = 0;
+            if (s.idle_act8) {
+                for (int g = 0; g < A; ++g) s.idle_act8[(size_t)n * A + g] = 8;
+            }
+            ended = true;
+        }
+        if (a) {
+            s.run[n] = run;
+            s.steps[n] = steps;
+            s.ret[n] = ret;
+        }
+        for (int g = 0; g < A; ++g) rte_rows(s, (size_t)n * A + g);
+    }
+    // one ballot per wave, one atomic by one of its lanes (every lane of the wave is here: nothing returned early)
+    const unsigned long long b = __ballot(ended);
+    if ((threadIdx.x & 63) == 0 && b != 0ull) atomicAdd(s.finished, (int)__popcll(b));
+}
+
+// after rs_refresh(mask = again): every agent's statistics of the lanes that begin their next run restart on the refreshed reading
+// (evaluate.py:456-466); hidden states are not touched (:353)
+__global__ void __launch_bounds__(256) rs_rnn_team_post_refresh_kernel(rs_rnn_team_eval_state s) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= s.N || s.again[n] == 0) return;
+    for (int g = 0; g < s.A; ++g) {
+        const size_t i = (size_t)n * s.A + g;
+        rs_welford_restart(s.w_count, s.w_mean, s.w_sq, s.w_std, i, (double)s.env_obs[i * RS_OBS_DIM]);
+        rte_rows(s, i);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,6 +313,24 @@ int rs_rnn_eval_post_step(const rs_rnn_eval_state* s, rs_stream_t stream) {
 int rs_rnn_eval_post_refresh(const rs_rnn_eval_state* s, rs_stream_t stream) {
     if (!rnn_eval_ok(s)) return RS_ERR_INVALID_ARG;
     hipLaunchKernelGGL(rs_rnn_eval_post_refresh_kernel, dim3((s->N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *s);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+static bool rnn_team_eval_ok(const rs_rnn_team_eval_state* s) {
+    return s && s->N >= 1 && s->A >= 1 && s->A <= RS_MAX_AGENTS && s->runs_per_lane >= 1 && s->steps_per_episode >= 1 && s->env_obs &&
+           s->env_reward && s->env_done && s->cur_obs && s->x && s->w_count && s->w_mean && s->w_sq && s->w_std && s->active && s->again &&
+           s->run && s->steps && s->ret && s->rec_len && s->rec_ret && s->rec_suc && s->finished;
+}
+
+int rs_rnn_team_eval_post_step(const rs_rnn_team_eval_state* s, rs_stream_t stream) {
+    if (!rnn_team_eval_ok(s)) return RS_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(rs_rnn_team_post_step_kernel, dim3((s->N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *s);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_rnn_team_eval_post_refresh(const rs_rnn_team_eval_state* s, rs_stream_t stream) {
+    if (!rnn_team_eval_ok(s)) return RS_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(rs_rnn_team_post_refresh_kernel, dim3((s->N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *s);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -150,6 +150,89 @@ __global__ void __launch_bounds__(64) rs_rnn_policy_kernel(PolArgs a_) {
     }
 }
 
+// The policy round of a whole team in one launch: grid = (64-lane groups, agent), blockIdx.y's agent works on its rows of
+// x [N][A][11], loc [N][A][2], u [N][A] and act8 [N][A] with its own weights and its own slab of h [A][N][24], updated in place (a
+// lane has its row in registers before it stores).  K14's arithmetic, operation by operation and in K14's order, for the outputs an
+// evaluation keeps -- the new state and the drawn action; no value head, no log-probability.  A body of its own, not K14's shared:
+// with the body shared K14's code moved (298 -> 300 SGPR spills) and this kernel kept 14 SGPR spills; here a lane turns its row
+// addresses and its uniform into vector registers before the products, whose weight stream needs the scalar file.
+struct TeamArgs {
+    const float* w[RS_MAX_AGENTS];   // the weight pointers travel in the argument block (8 x 8 bytes)
+    const float* x;
+    const float* loc;
+    float* h;
+    const float* u;
+    const uint8_t* active;
+    int8_t* act8;
+    int N, A;
+};
+
+__global__ void __launch_bounds__(64) rs_rnn_team_step_kernel(TeamArgs t) {
+    const int e = blockIdx.x * 64 + threadIdx.x, a = blockIdx.y;
+    const bool live = e < t.N && t.active[e] != 0;
+    if (!__any(live)) return;
+    const int ec = e < t.N ? e : t.N - 1;                  // idle lanes shadow a real lane, store nothing
+    const cmem_t W = as_cmem(t.w[a]);
+    const size_t i = (size_t)ec * t.A + a;
+    float* hrow = t.h + ((size_t)a * t.N + ec) * GH;
+    int8_t* arow = t.act8 + i;
+    const float uu = t.u[i];
+    int keep = live ? 1 : 0;                               // the lane's flag and its action's address in vector registers now: neither a
+    asm volatile("" : "+v"(keep), "+v"(arow));             // mask pair nor the argument block's address is held across the products
+    float x[NX], h[GH];
+#pragma unroll
+    for (int k = 0; k < RS_OBS_DIM; ++k) x[k] = t.x[i * RS_OBS_DIM + k];
+    x[RS_OBS_DIM] = t.loc[i * 2]; x[RS_OBS_DIM + 1] = t.loc[i * 2 + 1];
+#pragma unroll
+    for (int u = 0; u < GH; u += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(hrow + u);
+        h[u] = v.x; h[u + 1] = v.y; h[u + 2] = v.z; h[u + 3] = v.w;
+    }
+    float gi[80], gh[80];
+#pragma unroll
+    for (int o = 0; o < 80; ++o) { gi[o] = W[P_BIH + o]; gh[o] = W[P_BHH + o]; }
+    mv<NX, 80, 72>(W + P_IH, [&](int k) -> float { return x[k]; }, gi);
+    mv<GH, 80, 72>(W + P_HH, [&](int k) -> float { return h[k]; }, gh);
+#pragma unroll
+    for (int j = 0; j < GH; ++j) {
+        const float r = sigm(gi[j] + gh[j]);
+        const float z = sigm(gi[GH + j] + gh[GH + j]);
+        const float n = tanh_(gi[2 * GH + j] + r * gh[2 * GH + j]);
+        h[j] = (1.0f - z) * n + z * h[j];
+    }
+    if (keep) {
+#pragma unroll
+        for (int u = 0; u < GH; u += 4) *reinterpret_cast<float4*>(hrow + u) = make_float4(h[u], h[u + 1], h[u + 2], h[u + 3]);
+    }
+    // ---- policy head, log-softmax, inverse-CDF draw
+    float tt[HD];
+#pragma unroll
+    for (int o = 0; o < HD; ++o) tt[o] = W[P_B1 + o];
+    mv<GH, HD>(W + P_W1, [&](int k) -> float { return h[k]; }, tt);
+#pragma unroll
+    for (int o = 0; o < HD; ++o) tt[o] = tanh_(tt[o]);
+    float lg[16];
+#pragma unroll
+    for (int o = 0; o < 16; ++o) lg[o] = W[P_B2 + o];
+    mv<HD, 16>(W + P_W2, [&](int k) -> float { return tt[k]; }, lg);
+    float mx = lg[0];
+#pragma unroll
+    for (int o = 1; o < NA; ++o) mx = fmaxf(mx, lg[o]);
+    float se = 0.0f;
+#pragma unroll
+    for (int o = 0; o < NA; ++o) se += expf(lg[o] - mx);
+    const float lse = logf(se);
+    float cdf = 0.0f;
+    int act = 0;
+#pragma unroll
+    for (int o = 0; o < NA; ++o) {
+        const float lp = (lg[o] - mx) - lse;
+        cdf += expf(lp);
+        if (o < NA - 1 && cdf <= uu) { act = o + 1; }
+    }
+    if (keep) *arow = (int8_t)act;
+}
+
 // out[k] += sum_o W[k][o] c(o) on a k-major [K][OUTP] block (the transposed product: a dot product along each row)
 template <int K, int OUTP, typename F>
 __device__ __forceinline__ void mvt(cmem_t W, F cval, float (&out)[K]) { rs_ss_mvt<K, OUTP>(W, cval, out); }
@@ -349,6 +432,20 @@ int rs_rnn_policy_step_rows(const float* weights, const float* x, int32_t x_stri
     if ((act || logp || act8) && !u) return RS_ERR_INVALID_ARG;
     PolArgs a{weights, x, loc, h, u, h_out, nullptr, value, act, logp, num_envs, x_stride, loc_stride, u_stride, act8, act8_stride, mask};
     hipLaunchKernelGGL(rs_rnn_policy_kernel, dim3((num_envs + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_rnn_team_eval_step(const float* const* weights, int32_t num_agents, const float* x, const float* loc, float* h, const float* u,
+                          const uint8_t* active, int8_t* act8, int32_t num_envs, rs_stream_t stream) {
+    if (!weights || !x || !loc || !h || !u || !active || !act8 || num_agents < 1 || num_agents > RS_MAX_AGENTS || num_envs < 1)
+        return RS_ERR_INVALID_ARG;
+    TeamArgs t{};
+    for (int a = 0; a < RS_MAX_AGENTS; ++a) {
+        if (a < num_agents && !weights[a]) return RS_ERR_INVALID_ARG;
+        t.w[a] = weights[a < num_agents ? a : 0];                  // the slots behind the team repeat agent 0 (never read)
+    }
+    t.x = x; t.loc = loc; t.h = h; t.u = u; t.active = active; t.act8 = act8; t.N = num_envs; t.A = num_agents;
+    hipLaunchKernelGGL(rs_rnn_team_step_kernel, dim3((num_envs + 63) / 64, num_agents), dim3(64), 0, static_cast<hipStream_t>(stream), t);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -11,7 +11,8 @@ Saved sets use the reference's layout `env_dict["env_<i>"] = (src_coords, det_co
 (algos/test_environment/eval/test_env_gen.py:13-24).  `sample_test_environments` draws such a set from the
 environment's own spawn rules; the reference's own pickled sets are read by radiation_ppo_amd.testsets WITHOUT unpickling.
 `run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `run_test_environments_team` for feed-forward agents and
-teams of up to 8 and `run_test_environments_rnn` for the recurrent agent with their lock-steps in HIP (csrc/rs_eval.hip), `summarize` the result statistics
+teams of up to 8, `run_test_environments_rnn` for the recurrent agent and `run_test_environments_rnn_team` for recurrent teams of up to 8 with
+their lock-steps in HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip), `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
 """
 import ctypes as C
@@ -138,6 +139,22 @@ def recurrent_start(ac, N, seed, dev, impl):
     bank.reset()
     gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(ac.hid, dtype=torch.int64, device=dev).view(1, -1)
     return bank, ac.gru_h0(hash_uniform(gk)).contiguous()
+
+
+def recurrent_team_start(agents, N, seed, dev, impl):
+    """recurrent_start for a team {id: RNNAgentPPO} of equal widths: ONE PredictorBank of A owners around the agents' own PFGRUs, its
+    particle sets drawn once, and every agent's GRU state from the hash of ITS row of the bank's lane keys (every agent has its own
+    `hiddens` entry, evaluate.py:353).  Returns (bank, hid [A, N, hid]); with one agent hid[0] is recurrent_start's."""
+    from .pfgru import PredictorBank, hash_uniform
+    A = len(agents)
+    ac0 = agents[0].agent
+    bank = PredictorBank(N, A, hidden_size=ac0.rec, seed=seed, carry_hidden=True, device=dev, impl=impl)
+    for a in range(A):
+        bank.cells[a] = agents[a].agent.model
+    bank.reset()
+    unit = torch.arange(ac0.hid, dtype=torch.int64, device=dev).view(1, -1)
+    hid = torch.stack([agents[a].agent.gru_h0(hash_uniform((bank._base[a] * 1000003 + 5).view(-1, 1) * 1048583 + unit)) for a in range(A)])
+    return bank, hid.contiguous()
 
 
 def _lane_records(N, dev):
@@ -378,6 +395,148 @@ def run_test_environments_rnn(agent, env_sets: Dict[str, tuple], montecarlo_runs
     # no flag is masked: one agent's idle step is a move by (0, 0), it never stalls
     return _close(vec, keys, saved, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1).bool(),
                   log=log[:it] if return_actions else None)
+
+
+@torch.no_grad()
+def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, tuple], montecarlo_runs: int = 100, steps_per_episode: int = 120,
+                                   obstruction_count: int = 0, enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0",
+                                   return_actions: bool = False, falloff: str = "reference", carry_hidden_across_runs: bool = True,
+                                   fused=None):
+    """EpisodeRunner.run (evaluate.py:333-476) for a team of 1..8 recurrent agents (RAD-A2C, team_mode "individual": :279-280) with
+    its lock-step in HIP.  agents: {id: RNNAgentPPO}, ids 0..A-1, all of the same widths.  Every agent has its own network (:305-318),
+    its own GRU state and particle set, created once (:353), and its own statistics buffer (:361-364, :395-397, :461-466); a run ends
+    when any agent's terminal flag rises (:411-423) or at `steps_per_episode`; agent 0's return is recorded (:441-444).
+    carry_hidden_across_runs as in run_test_environments_rnn: True = N = E lanes with R runs each on carried hidden states, False =
+    N = E R lanes with one run each.
+
+    fused=True: a lock-step is rs_action_uniforms, the PFGRU step of every owner on the lanes with runs left (one launch), the policy
+    round -- rs_rnn_team_eval_step at the default widths (one launch for the team), one rs_rnn_sized_step per agent at the others --,
+    rs_step, rs_rnn_team_eval_post_step and, with more than one run per lane, rs_refresh on the lanes that begin their next run and
+    rs_rnn_team_eval_post_refresh: 5 or 7 launches at the default widths, on one stream.  The host reads the finished-lane count once
+    every 16 lock-steps; nothing else synchronises.  It needs a cuda device and kernels for both halves of the agents; ValueError
+    otherwise.  fused=False: the same lock-step composed from DeviceWelford, PredictorBank.predict, one policy step per agent and
+    torch bookkeeping in _run_sequential's order, with the same stopping rule: the A/B baseline, identical records and log.
+    fused=None: the fused form where it can run.
+
+    Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log of rs_step's action rows,
+    8 (idle) where a lane had no run going."""
+    A = len(agents)
+    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
+        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}")
+    acs = [getattr(agents[a], "agent", None) for a in range(A)]
+    if not all(hasattr(ac, "gru_cell") for ac in acs):
+        raise ValueError("run_test_environments_rnn_team evaluates recurrent (RAD-A2C) agents")
+    if len({(ac.hid, tuple(ac.pol), tuple(ac.val), ac.rec) for ac in acs}) != 1:
+        raise ValueError("the agents of a team must have the same GRU, head and PFGRU widths: the bank and the state tensor hold one width")
+    E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
+    dev = torch.device(device)
+    pol_kernel = all(_has_policy_kernel(ac, dev) for ac in acs)
+    pf_kernel = all(_has_pfgru_kernel(ac, dev) for ac in acs)
+    can = dev.type == "cuda" and pol_kernel and pf_kernel and all(hasattr(agents[a], "policy_step_masked_rows") for a in range(A))
+    if fused is None:
+        fused = can
+    if fused and not can:
+        raise ValueError("the fused evaluation needs a cuda device, a GRU of 1..64 units with single-layer heads of 2..64 units and a "
+                         "PFGRU of 8, 16, .., 64 hidden units")
+    Rl = R if carry_hidden_across_runs else 1                     # runs per lane
+    N = E * R // Rl
+    vec, keys, saved, obs, stat = _open(env_sets, R // Rl, A, obstruction_count, enforce_grid_boundaries, seed, device, falloff=falloff)
+    bank, hid = recurrent_team_start(agents, N, seed, dev, "hip" if pf_kernel else "torch")   # particle sets and h0 are drawn here only
+    run = torch.zeros(N, dtype=torch.int32, device=dev)
+    steps = torch.zeros(N, dtype=torch.int32, device=dev)
+    ret = torch.zeros(N, dtype=torch.float32, device=dev)
+    rec_len = torch.zeros(N, Rl, dtype=torch.int32, device=dev)
+    rec_ret = torch.zeros(N, Rl, dtype=torch.float32, device=dev)
+    rec_suc = torch.zeros(N, Rl, dtype=torch.uint8, device=dev)
+    u = torch.empty(N, A, dtype=torch.float32, device=dev)
+    act = torch.empty(N, dtype=torch.int64, device=dev)           # scratch: asking for it makes the per-agent steps evaluate the policy head
+    bound = L * Rl
+    # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads; a lane
+    # that is masked out is never written and reads 8.  Otherwise one fixed buffer, where the post-step parks a finished lane on 8
+    log = torch.full((bound, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
+    act8 = None if return_actions else torch.full((N, A), 8, dtype=torch.int8, device=dev)
+    it = 0
+    if fused:
+        lib = _lib.load()
+        x = obs.clone()
+        stat.standardize(obs[..., 0], out=x[..., 0])
+        active = torch.ones(N, dtype=torch.uint8, device=dev)
+        again = torch.zeros(N, dtype=torch.uint8, device=dev)
+        finished = torch.zeros(1, dtype=torch.int32, device=dev)
+        p = lambda t: t.data_ptr()
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        state = _lib.RsRnnTeamEvalState(N, A, Rl, L, p(vec.obs), p(vec.reward), p(vec.done), p(obs), p(x), p(stat.count), p(stat.mean),
+                                        p(stat.sq), p(stat.std), p(active), p(again), p(run), p(steps), p(ret), p(rec_len), p(rec_ret),
+                                        p(rec_suc), p(bank.calls), None if return_actions else p(act8), p(finished))
+        one_launch = all(ac.fused_policy for ac in acs)
+        if one_launch:
+            wts = [agents[a].policy_weights() for a in range(A)]  # kept alive for the run: the kernel reads them by address
+            wp = (C.c_void_p * A)(*[p(w) for w in wts])
+        while it < bound:
+            if it and it % 16 == 0 and int(finished.item()) == N: # one host read per 16 lock-steps
+                break
+            a8 = log[it] if return_actions else act8
+            vec.action_uniforms(u)
+            loc = bank.predict_kernel(x, mask8=active)            # every owner in one launch; the draw counters are the post-step's
+            if one_launch:
+                _lib.check(lib.rs_rnn_team_eval_step(wp, A, p(x), p(loc), p(hid), p(u), p(active), p(a8), N, st), "rs_rnn_team_eval_step")
+            else:
+                for a in range(A):
+                    agents[a].policy_step_masked_rows(x, loc, hid[a], u, a, act, a8, active)
+            vec.step(a8)
+            _lib.check(lib.rs_rnn_team_eval_post_step(C.byref(state), st), "rs_rnn_team_eval_post_step")
+            if Rl > 1:                                            # :455-466: the lanes that begin their next run
+                vec.refresh(*saved, mask=again)
+                _lib.check(lib.rs_rnn_team_eval_post_refresh(C.byref(state), st), "rs_rnn_team_eval_post_refresh")
+            it += 1
+    else:
+        lane = torch.arange(N, device=dev)
+        k_act = torch.zeros(A, N, dtype=torch.int64, device=dev)
+        val = torch.empty(N, dtype=torch.float32, device=dev)     # policy_step_rows always writes the value; it is dropped
+        while it < bound:
+            active = run < Rl
+            if it and it % 16 == 0 and not bool(active.any()):    # the fused form's stopping rule
+                break
+            a8 = log[it] if return_actions else act8
+            x = obs.clone()
+            stat.standardize(obs[..., 0], out=x[..., 0])
+            vec.action_uniforms(u)
+            loc = bank.predict(x, mask=active)
+            active8 = active.to(torch.uint8)
+            for a in range(A):
+                if pol_kernel:
+                    agents[a].policy_step_rows(x, loc, hid[a], u, a, val, act=k_act[a], mask8=active8)
+                else:
+                    logits, _, h1 = acs[a].policy_step(x[:, a], loc[:, a], hid[a])
+                    hid[a] = torch.where(active.view(N, 1), h1, hid[a])
+                    cdf = torch.cumsum(torch.softmax(logits, dim=-1), dim=-1)
+                    k_act[a] = (cdf[:, :-1] <= u[:, a].unsqueeze(-1)).sum(dim=-1)
+            a8.copy_(torch.where(active.view(N, 1), k_act.t(), torch.full_like(k_act.t(), 8)).to(torch.int8))   # lanes without a run idle
+            obs_n, rew, _, done, _ = vec.step(a8)
+            ret += torch.where(active, rew[:, 0], torch.zeros_like(rew[:, 0]))       # `episode_return[0]`
+            steps += active.int()
+            found = done.bool().any(dim=1) & active
+            over = found | ((steps == L) & active)
+            stat.update(obs_n[..., 0], mask=active)                                  # :395-397 (before the episode-over test)
+            slot = run.long().clamp(max=Rl - 1)
+            rec_len[lane, slot] = torch.where(over, steps, rec_len[lane, slot])
+            rec_ret[lane, slot] = torch.where(over, ret, rec_ret[lane, slot])
+            rec_suc[lane, slot] = torch.where(over, found.to(torch.uint8), rec_suc[lane, slot])
+            run += over.int()
+            again = over & (run < Rl)                                                # :455-466: refresh, statistics restart
+            if Rl > 1:
+                obs_r = vec.refresh(*saved, mask=again.to(torch.uint8))[0]
+                stat.reset(again)
+                stat.update(obs_r[..., 0], mask=again)
+                obs = torch.where(again.view(N, 1, 1), obs_r, obs_n).clone()
+            else:
+                obs = obs_n.clone()
+            steps.masked_fill_(over, 0)
+            ret.masked_fill_(over, 0.0)
+            it += 1
+    # lanes whose runs are over idle on purpose; stacked agents may "stall"
+    return _close(vec, keys, saved, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1).bool(),
+                  log=log[:it] if return_actions else None, ignore_flags=_lib.ENVERR_IDLE_STALL)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -627,12 +786,22 @@ class evaluate_PPO:
             self.results, self.summary = run_test_environments_cnn(agents, sets, team_mode=kw.get("team_mode", "individual"), **common)
         elif arch == "rnn":
             from .rada2c import RNNAgentPPO
-            ag = RNNAgentPPO(id=0, device=dev)
-            ag.load(agent_dir(0))                                       # pyt_save/model.pt (epoch_logger.py:216-284)
-            self.results, self.summary = run_test_environments_rnn(ag, sets, fused=None,
-                                                                   carry_hidden_across_runs=bool(kw.get("carry_hidden_across_runs", True)), **common)
+
+            def rnn_agent(i):                                           # pyt_save/model.pt (epoch_logger.py:216-284)
+                ag = RNNAgentPPO(id=i, device=dev)
+                ag.load(agent_dir(i))
+                return ag
+            carry = bool(kw.get("carry_hidden_across_runs", True))
+            if A >= 2:
+                # a recurrent team: one RNNModelActorCritic per agent on its own rows (evaluate.py:305-318)
+                if kw.get("team_mode", "individual") != "individual":
+                    raise ValueError("team_mode must be 'individual' for a recurrent team: no global critic for RAD-A2C")    # evaluate.py:279-280
+                self.results, self.summary = run_test_environments_rnn_team({i: rnn_agent(i) for i in range(A)}, sets, fused=None,
+                                                                            carry_hidden_across_runs=carry, **common)
+            else:
+                self.results, self.summary = run_test_environments_rnn(rnn_agent(0), sets, fused=None, carry_hidden_across_runs=carry, **common)
         elif A >= 2:
-            # a feed-forward team: every agent's own network on its own rows (evaluate.py:305-331); recurrent teams are not built
+            # a feed-forward team: every agent's own network on its own rows (evaluate.py:305-331)
             team_mode = kw.get("team_mode", "individual")
             if team_mode != "individual":
                 raise ValueError("team_mode must be 'individual' for a feed-forward team: no global critic for RAD-A2C")   # evaluate.py:279-280

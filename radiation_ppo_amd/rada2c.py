@@ -822,6 +822,26 @@ class RNNAgentPPO:
                                                        h.data_ptr(), None, act.data_ptr(), None, act8.data_ptr(), 1, mask8.data_ptr(), N, st),
                    "rs_rnn_policy_step_rows")
 
+    def policy_step_masked_rows(self, x, loc, h, u, a: int, act, act8, mask8) -> None:
+        """policy_step_masked on agent a's rows of a team's [N, A, .] tensors (no contiguous copies): x [N, A, 11], loc [N, A, 2],
+        u [N, A], act8 [N, A] int8; h [N, hid] is agent a's own state, act [N] int64 scratch, mask8 [N] uint8."""
+        ac = self.agent
+        w = self.policy_weights()
+        for t in (x, loc, h, u, act, act8, mask8):
+            assert t.is_cuda and t.is_contiguous()
+        N, A = x.shape[0], x.shape[1]
+        assert 0 <= a < A and loc.shape[1] == A and u.shape[1] == A and act8.shape[1] == A
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        xa, la, ua, a8 = x.data_ptr() + 4 * a * _lib.RS_OBS_DIM, loc.data_ptr() + 4 * a * 2, u.data_ptr() + 4 * a, act8.data_ptr() + a
+        if not ac.fused_policy:
+            assert ac.sized_policy
+            _lib.check(_lib.load().rs_rnn_sized_step(w.data_ptr(), ac.hid, ac.pol[0], ac.val[0], xa, A * _lib.RS_OBS_DIM, la, 2 * A, h.data_ptr(),
+                                                     ua, A, h.data_ptr(), None, None, act.data_ptr(), None, a8, A, mask8.data_ptr(), N, st),
+                       "rs_rnn_sized_step")
+            return
+        _lib.check(_lib.load().rs_rnn_policy_step_rows(w.data_ptr(), xa, A * _lib.RS_OBS_DIM, la, 2 * A, h.data_ptr(), ua, A, h.data_ptr(), None,
+                                                       act.data_ptr(), None, a8, A, mask8.data_ptr(), N, st), "rs_rnn_policy_step_rows")
+
     def reduce_pfgru_training(self) -> None:
         """ppo.py:685-689."""
         if self.reduce_pfgru_iters:

@@ -303,14 +303,26 @@ int rs_ppo_update_step(const rs_mlp_params* actor, const rs_mlp_params* critic, 
  * visit_table: float32 [(steps_per_episode+1)*A + 1], visit_table[c] = the reference's
  * normalize_incremental_logscale(current_value = 2c, base, 2) evaluated by the caller (host Python math.log). */
 typedef struct rs_maps rs_maps;
+/* bits of the per-env "err" field (rs_maps_field): set by rs_maps_update, sticky -- rs_maps_reset leaves them -- until the caller
+ * clears the field.  The maps of a flagged env no longer equal the reference's. */
+enum {
+    RS_MAPERR_RING_FULL = 1,      /* more than steps_per_episode + 2 updates without a reset: the reading was dropped             */
+    RS_MAPERR_VISIT_OVERFLOW = 2, /* a cell visited more than (steps_per_episode + 1) * A + 1 times: the last table entry is used */
+    RS_MAPERR_OFF_MAP = 4         /* a detector cell outside [-X, X) x [-Y, Y) (the reference's numpy indexing raises IndexError):
+                                     clamped to the nearest edge cell                                                             */
+};
 size_t rs_maps_state_bytes(int32_t num_envs, int32_t num_agents, int32_t steps_per_episode, int32_t map_x, int32_t map_y);
 int rs_maps_create(int32_t num_envs, int32_t num_agents, int32_t steps_per_episode, int32_t map_x, int32_t map_y,
                    double resolution_accuracy, const float* visit_table, void* workspace, size_t workspace_bytes,
                    rs_stream_t stream, rs_maps** out);
 void rs_maps_destroy(rs_maps* m);
 int rs_maps_reset(rs_maps* m, const uint8_t* mask, rs_stream_t stream);
-/* obs [N,A,11] float32 (the env's observation rows); pred [N,A,2] float32 scaled coordinates or NULL;
- * mask [N] or NULL (all).  Detector cells come from the env handle's integer coordinates. */
+/* obs [N,A,11] float32 (the env's observation rows); mask [N] or NULL (all).  Detector cells come from the env handle's integer
+ * coordinates (from the observation rows when the env was created with coord_noise).
+ * pred [N,A,2] float32 or NULL: owner a's location prediction in scaled coordinates.  Its cell is int(pred * resolution_accuracy) per
+ * axis (truncation towards zero), and a negative cell -k with k <= X (Y) is cell X - k (Y - k), as numpy indexes
+ * prediction_map[p0][p1] (RADTEAM_core.py:765).  A prediction outside that range, a NaN or an infinity -- where the reference raises --
+ * and pred == NULL leave the owner's last prediction cell as it was (-1, an empty channel, after a reset); no flag is set. */
 int rs_maps_update(rs_maps* m, rs_handle* env, const float* obs, const float* pred, const uint8_t* mask, rs_stream_t stream);
 int rs_maps_stack(rs_maps* m, float* actor_stack, float* critic_stack, rs_stream_t stream);
 /* introspection for tests: "pred_cell","cell" ([N,A] int32), "combined","readings","visits","obstacles" ([N,X*Y] f32) */

@@ -82,12 +82,13 @@ class MapsOracle:
             self.cell_readings.setdefault(key, []).append(float(obs[0]))
         for agent_id in observation:
             cur = self._inflate(observation[agent_id])
-            pred = self._inflate(loc_prediction)
             last = self.last_coords.get(agent_id)
-            # prediction map (:747-766)
-            if len(self.last_prediction) > 0:
-                self.prediction[self.last_prediction[0]][self.last_prediction[1]] -= 1
-            self.prediction[pred[0]][pred[1]] = 1
+            # prediction map (:747-766); loc_prediction None = the reference's `if PFGRU:` switch (:563) off for this call
+            if loc_prediction is not None:
+                pred = self._inflate(loc_prediction)
+                if len(self.last_prediction) > 0:
+                    self.prediction[self.last_prediction[0]][self.last_prediction[1]] -= 1
+                self.prediction[pred[0]][pred[1]] = 1
             # location maps (:768-842)
             if id == agent_id:
                 if last:
@@ -118,5 +119,6 @@ class MapsOracle:
                     if d != 0:
                         self.obstacles[cur[0]][cur[1]] = d
             self.last_coords[agent_id] = cur
-            self.last_prediction = pred
+            if loc_prediction is not None:
+                self.last_prediction = pred
         return (self.prediction, self.location, self.others, self.readings_map, self.visits, self.obstacles, self.combined)

@@ -21,6 +21,10 @@ ENVERR_CORRECT_CAP = 4
 ENVERR_BAD_ACTION = 8
 ENVERR_NO_PATH = 16
 
+MAPERR_RING_FULL = 1
+MAPERR_VISIT_OVERFLOW = 2
+MAPERR_OFF_MAP = 4
+
 
 class RsConfig(C.Structure):
     _fields_ = [

@@ -34,10 +34,6 @@ struct rs_maps {
     rs_field fields[24];
 };
 
-#define RS_MAPERR_RING_FULL 1u
-#define RS_MAPERR_VISIT_OVERFLOW 2u
-#define RS_MAPERR_OFF_MAP 4u            // a coordinate beyond the map (the reference's numpy indexing raises IndexError there)
-
 // ------------------------------------------------------------------------------------------------
 // median of the readings recorded in `cell` (statistics.median: mean of the two middle values when even).
 // The chain of the cell is walked ONCE (a pointer chase: one memory latency per entry) into the lane's column of an LDS buffer;
@@ -57,6 +53,7 @@ __device__ __forceinline__ double rs_cell_median(const RsMapsParams& M, int n, i
         if (m < medcap) buf[m][lane] = val[j - 1];
         ++m;
     }
+    if (m == 0) return 0.0;             // an empty chain (only after RS_MAPERR_RING_FULL dropped the cell's reading): nothing in the column to select from
     const int k_lo = (m - 1) / 2, k_hi = m / 2;
     double v_lo = 0.0, v_hi = 0.0;
     if (m <= medcap) {
@@ -190,10 +187,18 @@ __global__ void __launch_bounds__(64) rs_maps_update_kernel(RsMapsParams M, RsPa
         if (dv != 0.0f) obst[c] = dv;
         M.cell[(size_t)n * A + a] = c;
         // prediction cell of owner a (the prediction map is a one-hot at the last prediction, :747-766)
+        // prediction_map[p0][p1] = 1 with p = int(pred * resolution_accuracy): a negative p indexes from the end like the detector cells
+        // above.  Where the reference raises (IndexError beyond [-X, X), int() of a NaN / inf) the owner's last prediction cell stays;
+        // the range test runs on the double so that no NaN or out-of-range value reaches the (int) conversion.
         if (pred) {
-            const int px = (int)((double)pred[((size_t)n * A + a) * 2 + 0] * M.ra);
-            const int py = (int)((double)pred[((size_t)n * A + a) * 2 + 1] * M.ra);
-            if (px >= 0 && px < M.X && py >= 0 && py < M.Y) M.pred_cell[(size_t)n * A + a] = px * M.Y + py;
+            const double fx = (double)pred[((size_t)n * A + a) * 2 + 0] * M.ra;
+            const double fy = (double)pred[((size_t)n * A + a) * 2 + 1] * M.ra;
+            if (fx > -(double)M.X - 1.0 && fx < (double)M.X && fy > -(double)M.Y - 1.0 && fy < (double)M.Y) {
+                int px = (int)fx, py = (int)fy;
+                if (px < 0) px += M.X;
+                if (py < 0) py += M.Y;
+                M.pred_cell[(size_t)n * A + a] = px * M.Y + py;
+            }
         }
     }
     M.wcount[n] = wc; M.wmean[n] = wmean; M.wsq[n] = wsq; M.wstd[n] = wstd;

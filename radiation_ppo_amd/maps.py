@@ -109,6 +109,12 @@ class HeatMaps:
         dt = torch.float32 if name in ("combined", "readings", "visits", "obstacles") else (torch.int16 if e.value == 2 else torch.int32)
         return raw.view(dt).view(r.value, c.value)
 
+    def error_flags(self) -> int:
+        """OR over the envs of the RS_MAPERR_* bits (include/radsearch.h) that rs_maps_update has set so far; one host read-back."""
+        f = self.field("err").reshape(-1, 1)
+        set_bits = ((f >> torch.arange(32, dtype=torch.int32, device=f.device)) & 1).amax(dim=0).tolist()
+        return sum(b << k for k, b in enumerate(set_bits))
+
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:
         """MapsBuffer.reset (RADTEAM_core.py:510-523) for the masked envs."""
         if mask is not None and mask.dtype == torch.bool:

@@ -258,6 +258,10 @@ class train_PPO:
             flags = self.vec.error_flags()      # the reference raises on these states (rad_search_env.py:544-565)
             if flags:
                 raise RuntimeError(f"RadSearch env error flags 0x{flags:x} (see RS_ENVERR_* in include/radsearch.h)")
+            maps = getattr(self.collector, "maps", None)            # the CNN collector's heat maps: their inputs to the CNNs are wrong once a flag is set
+            flags = maps.error_flags() if maps is not None else 0
+            if flags:
+                raise RuntimeError(f"heat-map error flags 0x{flags:x} (see RS_MAPERR_* in include/radsearch.h)")
             dt = time.time() - t0
             n_v = T * N
             for i in self.agents:

@@ -501,6 +501,93 @@ def gen_maps():
                         maps=np.array(maps_log), reset_after=np.array(reset_log), ra=ra, offset=offset,
                         map_dim=np.array(bufs[0].map_dimensions), base=bufs[0].base, logscale=logs, A=A, L=L)
     print("wrote maps.npz", np.array(maps_log).shape, "ra", repr(ra), "dims", bufs[0].map_dimensions)
+    gen_maps_edge()
+
+
+def gen_maps_edge():
+    """mapsedge.npz: the reference's own MapsBuffer on the inputs maps.npz does not reach -- negative coordinates and predictions (numpy
+    indexes from the end), coordinates exactly on k / resolution_accuracy, a non-square grid_bounds = (1, 2) (27 x 49 cells), chains of
+    tied readings 24 entries long -- and the exception it raises on each input it refuses.  Recorded inputs, maps and exception names only."""
+    from algos.multiagent.NeuralNetworkCores import RADTEAM_core as R
+    scale = 1 / 2200.0
+    ra = R.calculate_resolution_accuracy(resolution_multiplier=0.01, scale=scale)
+    offset = scale * max((200.0, 500.0))
+    f32 = lambda v: float(np.float32(v))
+    mid = lambda c: f32((c + (0.5 if c >= 0 else -0.5)) / ra)
+    out = {"ra": ra, "offset": offset}
+
+    def run(tag, A, L, gb, steps):
+        """steps: list of (cells [(cx, cy) or raw (x, y) floats per agent], readings, pred (x, y), reset_after)."""
+        bufs = {i: R.MapsBuffer(observation_dimension=11, steps_per_episode=L, number_of_agents=A, grid_bounds=gb, resolution_accuracy=ra,
+                                offset=offset, resolution_multiplier=0.01) for i in range(A)}
+        obs_log, pred_log, maps_log, reset_log = [], [], [], []
+        for xy, readings, pred, reset_after in steps:
+            od = {}
+            for i in range(A):
+                o = np.zeros(11)
+                o[0], o[1], o[2] = readings[i], xy[i][0], xy[i][1]
+                if (len(obs_log) + i) % 4 == 1:
+                    o[3 + (len(obs_log) % 8)] = f32(0.25 + 0.0625 * i)
+                od[i] = o
+            stacks = []
+            for i in range(A):
+                m = bufs[i].observation_to_map(od, i, pred)
+                stacks.append(np.stack([np.array(x, dtype=np.float32) for x in m]))
+            obs_log.append(np.stack([od[i] for i in range(A)])); pred_log.append(pred); maps_log.append(np.stack(stacks))
+            reset_log.append(int(reset_after))
+            if reset_after:
+                for b in bufs.values():
+                    b.reset()
+        out.update({tag + "_obs": np.array(obs_log), tag + "_pred": np.array(pred_log), tag + "_maps": np.array(maps_log),
+                    tag + "_reset_after": np.array(reset_log), tag + "_A": A, tag + "_L": L, tag + "_grid_bounds": np.array(gb),
+                    tag + "_map_dim": np.array(bufs[0].map_dimensions)})
+        return bufs[0].map_dimensions
+
+    # ---- 27 x 27: edges of both axes, negative predictions, tied chains
+    X = 27
+    below_one = f32(-1.0 / ra)
+    while below_one * ra > -1.0:
+        below_one = float(np.nextafter(np.float32(below_one), np.float32(-np.inf)))
+    last = f32(X / ra)
+    while last * ra >= X:
+        last = float(np.nextafter(np.float32(last), np.float32(-np.inf)))
+    rng = np.random.default_rng(12)
+    steps = []
+    for t in range(12):                                   # both agents in one cell: a chain of 24 readings from {1, 2, 3}
+        steps.append(([(mid(4), mid(6))] * 2, [float(rng.integers(1, 4)), float(rng.integers(1, 4))], (mid(-1 - t % 3), mid(-(t % 5))), t == 11))
+    edge = [f32(-0.5 / ra), below_one, mid(-(X - 1)), mid(-X), f32(1 / ra), f32(2 / ra), f32(11 / ra), f32(20 / ra), last, 0.0]
+    for t, v in enumerate(edge):
+        steps.append(([(v, mid(5)), (mid(9), v)], [float(rng.integers(0, 5)), float(rng.integers(0, 5))], (v, mid(3 + t)), t == 4))
+    out["sq_edge_values"] = np.array(edge)
+    assert run("sq", 2, 20, (1, 1), steps) == (27, 27)
+    # ---- 27 x 49
+    steps = []
+    for t in range(12):
+        cells = [(int(rng.integers(-27, 27)), int(rng.integers(-49, 49))) for _ in range(3)]
+        if t == 5:
+            cells[0] = (26, 48)
+        steps.append(([(mid(cx), mid(cy)) for cx, cy in cells], [float(rng.integers(0, 4)) for _ in range(3)],
+                      (mid(int(rng.integers(-27, 27))), mid(int(rng.integers(-49, 49)))), t == 7))
+    assert run("rect", 3, 14, (1, 2), steps) == (27, 49)
+    # ---- what the reference refuses
+    refused = []
+    cases = {"coordinate x at X / ra": ((f32(X / ra), mid(5)), (mid(1), mid(1))), "coordinate x below -X / ra": ((mid(-(X + 1)), mid(5)), (mid(1), mid(1))),
+             "prediction x at X / ra": ((mid(1), mid(1)), (f32(X / ra), mid(1))), "prediction y below -Y / ra": ((mid(1), mid(1)), (mid(1), mid(-(X + 1)))),
+             "prediction NaN": ((mid(1), mid(1)), (float("nan"), mid(1))), "prediction +inf": ((mid(1), mid(1)), (float("inf"), mid(1))),
+             "prediction -inf": ((mid(1), mid(1)), (mid(1), float("-inf")))}
+    for name, (xy, pred) in cases.items():
+        b = R.MapsBuffer(observation_dimension=11, steps_per_episode=20, number_of_agents=1, grid_bounds=(1, 1), resolution_accuracy=ra,
+                         offset=offset, resolution_multiplier=0.01)
+        o = np.zeros(11)
+        o[0], o[1], o[2] = 1.0, xy[0], xy[1]
+        try:
+            b.observation_to_map({0: o}, 0, pred)
+            refused.append(name + ": accepted")
+        except Exception as ex:  # noqa: BLE001  (the point is to record which one)
+            refused.append(name + ": " + type(ex).__name__)
+    out["refused"] = np.array(refused)
+    np.savez_compressed(os.path.join(OUT, "mapsedge.npz"), **out)
+    print("wrote mapsedge.npz", os.path.getsize(os.path.join(OUT, "mapsedge.npz")), "bytes;", refused)
 
 
 def gen_cnn():
@@ -1073,6 +1160,8 @@ if __name__ == "__main__":
         gen_round2()
     if "maps" in which:
         gen_maps()
+    elif "mapsedge" in which:
+        gen_maps_edge()
     if "cnn" in which:
         gen_cnn()
     if "pfgru" in which:

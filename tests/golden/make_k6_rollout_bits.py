@@ -17,9 +17,10 @@ two (seed, weight scale) pairs.  steps_per_epoch = 23 with steps_per_episode = 5
 epoch end all occur in every case.  Weights are uniform(+-1/sqrt(fan_in)) times the scale; at scale 4 the logits span several
 units (main() asserts that the recorded log-probabilities reach below -4), so the output layer's sums carry real rounding.
 
+The weights come from params() of tests/_k7_bits.py, which every bit-identity suite shares.
+
     python tests/golden/make_k6_rollout_bits.py [OUT.npz]   # on the MI355X, with the library whose results are the reference
 """
-import importlib.util
 import os
 import sys
 
@@ -29,9 +30,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(HERE, "k6_rollout_bits.npz")
 
-_spec = importlib.util.spec_from_file_location("make_k7_bits", os.path.join(HERE, "make_k7_bits.py"))
-K7 = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(K7)
+sys.path.insert(0, os.path.dirname(HERE))
+import _k7_bits as K  # noqa: E402
 
 T, L = 23, 5
 SEEDS = ((101, 1.0), (202, 4.0))                      # (seed of env and weights, weight scale)
@@ -74,7 +74,7 @@ def run(N: int, walls: bool, obst: int, seed: int, scale: float):
     ps = [ac.actor[0].weight, ac.actor[0].bias, ac.actor[2].weight, ac.actor[2].bias, ac.actor[4].weight, ac.actor[4].bias,
           ac.critic[0].weight, ac.critic[0].bias, ac.critic[2].weight, ac.critic[2].bias, ac.critic[4].weight, ac.critic[4].bias]
     with torch.no_grad():
-        for p, v in zip(ps, K7.params(seed)):
+        for p, v in zip(ps, K.params(seed)):
             p.copy_(torch.from_numpy((v.astype(np.float64) * scale).astype(np.float32)))
     col = FusedCollector(env, agents, T, L)
     out = {}

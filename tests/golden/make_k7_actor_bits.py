@@ -6,7 +6,7 @@ bits.  The inputs of the small cases (M <= 33) are stored too; the large case is
 
 Cases:
   m1 .. m65569   M = 1, 31, 32, 33 and 65536 + 33 (2048 waves of 32-sample groups: one wave takes a second trip, the last group is
-                 ragged), inputs from the seeded generators of make_k7_bits.py.
+                 ragged), inputs from the seeded generators of tests/_k7_bits.py.
   w3_distinct    W3[o][u] = +-(64 o + u + 1) / 4096: every (output, unit) has a magnitude of its own, so a wrong lane, output set
                  or unit mapping of the 4x4x1 operands cannot cancel.
   w3_denorm      W3 scaled to <= 1e-38 and b3 = 0: every product W3 * h2 is subnormal, the partial sums run through the subnormal
@@ -15,39 +15,35 @@ Cases:
                  collapses to zeros, and the chains add signed-zero products.
   x_nan, x_inf   one row holds a NaN, two rows hold +inf / -inf.
 
+params(), batch() and run() live in tests/_k7_bits.py, which every bit-identity suite shares.
+
     python tests/golden/make_k7_actor_bits.py [OUT.npz]   # on the MI355X, with the library whose results are the reference
 """
-import importlib.util
 import os
 import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(HERE, "k7_actor_bits.npz")
 
-_spec = importlib.util.spec_from_file_location("make_k7_bits", os.path.join(HERE, "make_k7_bits.py"))
-K7 = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(K7)
+sys.path.insert(0, os.path.dirname(HERE))
+import _k7_bits as K  # noqa: E402
 
 # (name, M, seed, variant)
 CASES = [("m1", 1, 31, "plain"), ("m31", 31, 32, "plain"), ("m32", 32, 33, "plain"), ("m33", 33, 34, "plain"),
          ("m65569", 65536 + 33, 35, "plain"), ("w3_distinct", 33, 36, "w3_distinct"), ("w3_denorm", 33, 37, "w3_denorm"),
          ("x_tiny", 33, 38, "x_tiny"), ("x_nan", 33, 39, "x_nan"), ("x_inf", 33, 40, "x_inf")]
 PATHS = ("grad", "pair", "split")
-ACTOR_PARAMS = 5448
-N_PARAMS = 10441
+KINDS = ("g", "s", "p")                  # what is stored: actor gradients, statistics, all parameters after Adam
 LR = 1e-3
 STORE_INPUTS_UP_TO = 33
-PARAM_NAMES = ("aw1", "ab1", "aw2", "ab2", "aw3", "ab3", "cw1", "cb1", "cw2", "cb2", "cw3", "cb3")
-BATCH_NAMES = ("x", "act", "adv", "ret", "lpo", "w")
 
 
 def inputs(M: int, seed: int, variant: str):
     """(12 parameter arrays, 6 batch arrays) of one case."""
-    p = K7.params(seed)
-    b = list(K7.batch(M, seed))
+    p = K.params(seed)
+    b = list(K.batch(M, seed))
     if variant == "w3_distinct":
         o, u = np.meshgrid(np.arange(8), np.arange(64), indexing="ij")
         p[4] = (np.where((o + u) % 3 == 0, -1.0, 1.0) * (64 * o + u + 1) / 4096.0).astype(np.float32)
@@ -71,46 +67,9 @@ def inputs(M: int, seed: int, variant: str):
 
 def run(M: int, seed: int, variant: str, path: str):
     """(actor gradients float32 [5448], statistics float64 [5], parameters after Adam float32 [10441] or None) on cuda:0."""
-    import torch
-    sys.path.insert(0, ROOT)
-    from radiation_ppo_amd.ppo import FFActorCritic, FusedPPOGrad
     pv, bv = inputs(M, seed, variant)
-    ac = FFActorCritic().cuda()
-    ps = [ac.actor[0].weight, ac.actor[0].bias, ac.actor[2].weight, ac.actor[2].bias, ac.actor[4].weight, ac.actor[4].bias,
-          ac.critic[0].weight, ac.critic[0].bias, ac.critic[2].weight, ac.critic[2].bias, ac.critic[4].weight, ac.critic[4].bias]
-    with torch.no_grad():
-        for p, v in zip(ps, pv):
-            p.copy_(torch.from_numpy(v))
-    b = [torch.from_numpy(a).cuda() for a in bv]
-    f = FusedPPOGrad(ac)
-    f.bucket.fill_(7.0)
-    f.stats.fill_(7.0)
-    old = os.environ.pop("RS_PPO_SPLIT_GRAD", None)
-    try:
-        if path == "grad":
-            f(*b, K7.CLIP, K7.ALPHA, K7.VF)
-        else:
-            if path == "split":
-                os.environ["RS_PPO_SPLIT_GRAD"] = "1"
-            f.begin_update()
-            f.step(*b, K7.CLIP, K7.ALPHA, K7.VF, lr=LR, kl_threshold=1e30)
-        torch.cuda.synchronize()
-    finally:
-        os.environ.pop("RS_PPO_SPLIT_GRAD", None)
-        if old is not None:
-            os.environ["RS_PPO_SPLIT_GRAD"] = old
-    g = f.bucket[:ACTOR_PARAMS].cpu().numpy().copy()
-    s = f.stats.cpu().numpy().copy()
-    after = None if path == "grad" else np.concatenate([p.detach().cpu().numpy().ravel() for p in ps])
-    return g, s, after
-
-
-def expected(golden, name: str, path: str):
-    """(g, s, p) bits of one case and path: a path's own entry where the recorder found it to differ from the first path's."""
-    def pick(kind, first):
-        key = f"{kind}_{name}_{path}"
-        return golden[key] if key in golden.files else golden[f"{kind}_{name}_{first}"]
-    return pick("g", "grad"), pick("s", "grad"), (None if path == "grad" else pick("p", "pair"))
+    r = K.run(pv, K.device_batch(bv), path, lr=LR)
+    return r["g"][:K.ACTOR_PARAMS], r["s"], r.get("p")
 
 
 def main():
@@ -118,23 +77,17 @@ def main():
     for name, M, seed, variant in CASES:
         if M <= STORE_INPUTS_UP_TO:
             pv, bv = inputs(M, seed, variant)
-            for k, v in zip(PARAM_NAMES[:6], pv[:6]):
+            for k, v in zip(K.PARAM_NAMES[:6], pv[:6]):
                 out[f"in_{name}_{k}"] = v
-            for k, v in zip(BATCH_NAMES, bv):
+            for k, v in zip(K.BATCH_NAMES, bv):
                 out[f"in_{name}_{k}"] = v
         for path in PATHS:
             g, s, p = run(M, seed, variant, path)
             got = {"g": g.view(np.uint32), "s": s.view(np.uint64)}
             if p is not None:
-                assert p.shape == (N_PARAMS,)
+                assert p.shape == (K.N_PARAMS,)
                 got["p"] = p.view(np.uint32)
-            for kind, v in got.items():
-                first = f"{kind}_{name}_{'pair' if kind == 'p' else 'grad'}"
-                if first not in out:
-                    out[first] = v
-                elif not np.array_equal(out[first], v):
-                    out[f"{kind}_{name}_{path}"] = v
-                    print("   ", name, path, kind, "differs from the first path in", int((out[first] != v).sum()), "words: stored on its own")
+            K.record(out, name, path, got)
             print(name, M, path, "finite grads", int(np.isfinite(g).sum()), "/", g.size, "grad |max|", float(np.nanmax(np.abs(g))) if
                   np.isfinite(g).any() else float("nan"), "stats", s.tolist(), flush=True)
         if variant in ("plain", "w3_distinct", "w3_denorm", "x_tiny"):

@@ -24,22 +24,20 @@ dW3, db3 and statistics words that then differ from the forward order is stored 
 15 up, asserted to be nonzero in all three: the inputs can see a summation-order error.  (Swapping two neighbouring samples would
 not show that: a + b commutes.  Below M = 15 a sum has so few terms that its reversal may round the same.)
 
+params(), batch() and run() live in tests/_k7_bits.py, which every bit-identity suite shares.
+
     python tests/golden/make_k7_actor_dw3_bits.py [OUT.npz]   # on the MI355X, with the library whose results are the reference
 """
-import hashlib
-import importlib.util
 import os
 import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(HERE, "k7_actor_dw3_bits.npz")
 
-_spec = importlib.util.spec_from_file_location("make_k7_bits", os.path.join(HERE, "make_k7_bits.py"))
-K7 = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(K7)
+sys.path.insert(0, os.path.dirname(HERE))
+import _k7_bits as K  # noqa: E402
 
 # (name, M, batch seed, variant)
 CASES = [("m1", 1, 51, "plain"), ("m3", 3, 52, "plain"), ("m4", 4, 53, "plain"), ("m5", 5, 54, "plain"),
@@ -49,22 +47,19 @@ CASES = [("m1", 1, 51, "plain"), ("m3", 3, 52, "plain"), ("m4", 4, 53, "plain"),
          ("decades", 64, 62, "decades"), ("all_actions", 64, 63, "all_actions"), ("zero_w_clip", 64, 64, "zero_w_clip"),
          ("x_nan", 64, 65, "x_nan"), ("x_inf", 64, 66, "x_inf"), ("w3_denorm", 64, 67, "w3_denorm")]
 PATHS = ("grad", "pair", "split")
+KINDS = ("g", "s", "p", "c")             # what is stored: actor gradients, statistics, actor parameters after Adam, the critic's digest
 FINITE = ("plain", "decades", "all_actions", "zero_w_clip", "w3_denorm")
 PARAM_SEED = 50
-ACTOR_PARAMS = 5448
-N_PARAMS = 10441
 W3_OFF, B3_OFF = 4928, 5440          # actor slab: w1 704, b1 64, w2 4096, b2 64, w3 512, b3 8
 LR = 1e-3
 STORE_INPUTS_UP_TO = 64
 REV_ASSERT_FROM = 15
-PARAM_NAMES = ("aw1", "ab1", "aw2", "ab2", "aw3", "ab3", "cw1", "cb1", "cw2", "cb2", "cw3", "cb3")
-BATCH_NAMES = ("x", "act", "adv", "ret", "lpo", "w")
 
 
 def inputs(M: int, seed: int, variant: str):
     """(12 parameter arrays, 6 batch arrays) of one case."""
-    p = K7.params(PARAM_SEED)
-    b = list(K7.batch(M, seed))
+    p = K.params(PARAM_SEED)
+    b = list(K.batch(M, seed))
     rng = np.random.default_rng(1000 + seed)
     i = np.arange(M)
     if variant == "decades":
@@ -104,37 +99,8 @@ def reversed_groups(bv):
 
 def run_arrays(pv, bv, path: str):
     """(actor gradients float32 [5448], statistics float64 [5], parameters after Adam float32 [10441] or None) on cuda:0."""
-    import torch
-    sys.path.insert(0, ROOT)
-    from radiation_ppo_amd.ppo import FFActorCritic, FusedPPOGrad
-    ac = FFActorCritic().cuda()
-    ps = [ac.actor[0].weight, ac.actor[0].bias, ac.actor[2].weight, ac.actor[2].bias, ac.actor[4].weight, ac.actor[4].bias,
-          ac.critic[0].weight, ac.critic[0].bias, ac.critic[2].weight, ac.critic[2].bias, ac.critic[4].weight, ac.critic[4].bias]
-    with torch.no_grad():
-        for p, v in zip(ps, pv):
-            p.copy_(torch.from_numpy(v))
-    b = [torch.from_numpy(a).cuda() for a in bv]
-    f = FusedPPOGrad(ac)
-    f.bucket.fill_(7.0)
-    f.stats.fill_(7.0)
-    old = os.environ.pop("RS_PPO_SPLIT_GRAD", None)
-    try:
-        if path == "grad":
-            f(*b, K7.CLIP, K7.ALPHA, K7.VF)
-        else:
-            if path == "split":
-                os.environ["RS_PPO_SPLIT_GRAD"] = "1"
-            f.begin_update()
-            f.step(*b, K7.CLIP, K7.ALPHA, K7.VF, lr=LR, kl_threshold=1e30)
-        torch.cuda.synchronize()
-    finally:
-        os.environ.pop("RS_PPO_SPLIT_GRAD", None)
-        if old is not None:
-            os.environ["RS_PPO_SPLIT_GRAD"] = old
-    g = f.bucket[:ACTOR_PARAMS].cpu().numpy().copy()
-    s = f.stats.cpu().numpy().copy()
-    after = None if path == "grad" else np.concatenate([p.detach().cpu().numpy().ravel() for p in ps])
-    return g, s, after
+    r = K.run(pv, K.device_batch(bv), path, lr=LR)
+    return r["g"][:K.ACTOR_PARAMS], r["s"], r.get("p")
 
 
 def run(M: int, seed: int, variant: str, path: str, reverse: bool = False):
@@ -146,50 +112,33 @@ def words(g, s, p):
     """what is stored and compared: {kind: array of raw words}"""
     out = {"g": g.view(np.uint32), "s": s.view(np.uint64)}
     if p is not None:
-        assert p.shape == (N_PARAMS,)
-        out["p"] = p[:ACTOR_PARAMS].view(np.uint32)
-        out["c"] = np.frombuffer(hashlib.sha256(p[ACTOR_PARAMS:].tobytes()).digest(), dtype=np.uint8)
+        assert p.shape == (K.N_PARAMS,)
+        out["p"] = p[:K.ACTOR_PARAMS].view(np.uint32)
+        out["c"] = K.digest(p[K.ACTOR_PARAMS:])
     return out
 
 
 def order_words(g, s):
     """(dW3, db3, statistics) words: what the moved phase sums over the samples of a group"""
     w = g.view(np.uint32)
-    return w[W3_OFF:B3_OFF], w[B3_OFF:ACTOR_PARAMS], s.view(np.uint64)
-
-
-def expected(golden, name: str, path: str):
-    """{kind: words} of one case and path: a path's own entry where the recorder found it to differ from the first path's."""
-    def pick(kind, first):
-        key = f"{kind}_{name}_{path}"
-        return golden[key] if key in golden.files else golden[f"{kind}_{name}_{first}"]
-    out = {"g": pick("g", "grad"), "s": pick("s", "grad")}
-    if path != "grad":
-        out["p"], out["c"] = pick("p", "pair"), pick("c", "pair")
-    return out
+    return w[W3_OFF:B3_OFF], w[B3_OFF:K.ACTOR_PARAMS], s.view(np.uint64)
 
 
 def main():
     out = {}
-    for k, v in zip(PARAM_NAMES, K7.params(PARAM_SEED)):
+    for k, v in zip(K.PARAM_NAMES, K.params(PARAM_SEED)):
         out[f"in_params_{k}"] = v
     for name, M, seed, variant in CASES:
         pv, bv = inputs(M, seed, variant)
         if M <= STORE_INPUTS_UP_TO:
-            for k, v in zip(BATCH_NAMES, bv):
+            for k, v in zip(K.BATCH_NAMES, bv):
                 out[f"in_{name}_{k}"] = v
-            for k, v, v0 in zip(PARAM_NAMES, pv, K7.params(PARAM_SEED)):
+            for k, v, v0 in zip(K.PARAM_NAMES, pv, K.params(PARAM_SEED)):
                 if v.tobytes() != v0.tobytes():
                     out[f"in_{name}_{k}"] = v
         for path in PATHS:
             g, s, p = run_arrays(pv, bv, path)
-            for kind, v in words(g, s, p).items():
-                first = f"{kind}_{name}_{'grad' if kind in 'gs' else 'pair'}"
-                if first not in out:
-                    out[first] = v
-                elif not np.array_equal(out[first], v):
-                    out[f"{kind}_{name}_{path}"] = v
-                    print("   ", name, path, kind, "differs from the first path in", int((out[first] != v).sum()), "words: stored on its own")
+            K.record(out, name, path, words(g, s, p))
             print(name, M, path, "finite grads", int(np.isfinite(g).sum()), "/", g.size, "grad |max|", float(np.nanmax(np.abs(g))) if
                   np.isfinite(g).any() else float("nan"), "stats", s.tolist(), flush=True)
         if variant in FINITE:

@@ -8,7 +8,7 @@ per group, 65 536 samples per trip of the whole grid):
   m196609   M = 196 609  four trips, three full and one nearly empty: priorities flip several times, partners end on different work
   m196608   M = 196 608  three trips, an odd count
 
-Inputs: the seeded generators of make_k7_bits.py, then all eight actions in every group of 32, |adv| = 10^U(-4, 2) with either sign,
+Inputs: the seeded generators of tests/_k7_bits.py, then all eight actions in every group of 32, |adv| = 10^U(-4, 2) with either sign,
 every seventh row at weight 0 (row 10 at -0.0).  Nothing but seeds is stored.  Every case runs three ways: rs_ppo_grad, and
 rs_ppo_update_step (lr = 1e-3, first Adam step) as the pair launch and as one launch per network (RS_PPO_SPLIT_GRAD=1).  Stored as raw
 bits: the whole gradient bucket (10 441 gradients and the (hi, lo) statistics tail), the five statistics, the 10 441 parameters after
@@ -21,29 +21,26 @@ stored on its own only where it differs from the first path's.
             threshold between (stored: lr, threshold, the call that stops) and records the run with it.  Stored: the five statistics and the update state after every call, and after the sixth the
             gradient bucket, the parameters, m and v in full.  The calls after the stop are no-ops.
 
+params(), batch() and run() live in tests/_k7_bits.py, which every bit-identity suite shares.
+
     python tests/golden/make_k7_partner_balance_bits.py [OUT.npz]   # on the MI355X, with the library whose results are the reference
 """
-import hashlib
-import importlib.util
 import os
 import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(HERE, "k7_partner_balance_bits.npz")
 
-_spec = importlib.util.spec_from_file_location("make_k7_bits", os.path.join(HERE, "make_k7_bits.py"))
-K7 = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(K7)
+sys.path.insert(0, os.path.dirname(HERE))
+import _k7_bits as K  # noqa: E402
 
 # (name, M, batch seed)
 CASES = [("m1", 1, 71), ("m65553", 65536 + 17, 72), ("m196609", 3 * 65536 + 1, 73), ("m196608", 3 * 65536, 74)]
 PATHS = ("grad", "pair", "split")
+KINDS = ("g", "s", "p", "m", "v")        # what is stored: the bucket, statistics, parameters after Adam, digests of Adam's m and v
 PARAM_SEED = 70
-N_PARAMS = 10441
-BUCKET = 10441 + 16
 LR = 1e-3
 SEQ_M, SEQ_SEED, SEQ_STEPS = 3 * 65536 + 1, 75, 6
 SEQ_LRS = (3e-2, 2e-2, 5e-2, 1.5e-2, 1e-2)
@@ -51,8 +48,8 @@ SEQ_LRS = (3e-2, 2e-2, 5e-2, 1.5e-2, 1e-2)
 
 def inputs(M: int, seed: int, negative: float = 0.5):
     """(12 parameter arrays, 6 batch arrays); negative: the share of rows with a negative advantage."""
-    p = K7.params(PARAM_SEED)
-    b = list(K7.batch(M, seed))
+    p = K.params(PARAM_SEED)
+    b = list(K.batch(M, seed))
     rng = np.random.default_rng(2000 + seed)
     i = np.arange(M)
     b[1] = ((3 * i + i // 8) % 8).astype(np.int64)
@@ -65,104 +62,37 @@ def inputs(M: int, seed: int, negative: float = 0.5):
     return p, b
 
 
-def _setup(pv):
-    import torch
-    sys.path.insert(0, ROOT)
-    from radiation_ppo_amd.ppo import FFActorCritic, FusedPPOGrad
-    ac = FFActorCritic().cuda()
-    ps = [ac.actor[0].weight, ac.actor[0].bias, ac.actor[2].weight, ac.actor[2].bias, ac.actor[4].weight, ac.actor[4].bias,
-          ac.critic[0].weight, ac.critic[0].bias, ac.critic[2].weight, ac.critic[2].bias, ac.critic[4].weight, ac.critic[4].bias]
-    with torch.no_grad():
-        for p, v in zip(ps, pv):
-            p.copy_(torch.from_numpy(v))
-    f = FusedPPOGrad(ac)
-    f.bucket.fill_(7.0)
-    f.stats.fill_(7.0)
-    return ac, ps, f
-
-
-def device_batch(bv):
-    import torch
-    return [torch.from_numpy(a).cuda() for a in bv]
-
-
-def _flat(ps):
-    return np.concatenate([p.detach().cpu().numpy().ravel() for p in ps])
-
-
-class _split_env:
-    def __init__(self, path):
-        self.path = path
-
-    def __enter__(self):
-        self.old = os.environ.pop("RS_PPO_SPLIT_GRAD", None)
-        if self.path == "split":
-            os.environ["RS_PPO_SPLIT_GRAD"] = "1"
-
-    def __exit__(self, *exc):
-        os.environ.pop("RS_PPO_SPLIT_GRAD", None)
-        if self.old is not None:
-            os.environ["RS_PPO_SPLIT_GRAD"] = self.old
-        return False
-
-
 def run_arrays(pv, b, path: str):
     """{kind: float array}: g bucket [10457], s statistics float64 [5] and, for the update step, p parameters, m, v [10441] each.
-    b: the batch on the device (device_batch)."""
-    import torch
-    ac, ps, f = _setup(pv)
-    with _split_env(path):
-        if path == "grad":
-            f(*b, K7.CLIP, K7.ALPHA, K7.VF)
-        else:
-            f.begin_update()
-            f.step(*b, K7.CLIP, K7.ALPHA, K7.VF, lr=LR, kl_threshold=1e30)
-        torch.cuda.synchronize()
-    out = {"g": f.bucket.cpu().numpy().copy(), "s": f.stats.cpu().numpy().copy()}
-    if path != "grad":
-        out.update(p=_flat(ps), m=f.m.cpu().numpy().copy(), v=f.v.cpu().numpy().copy())
-    return out
-
-
-def _digest(a):
-    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), dtype=np.uint8)
+    b: the batch on the device (K.device_batch), built once per case and reused across the paths."""
+    return K.run(pv, b, path, lr=LR)
 
 
 def words(r):
     """what is stored and compared: {kind: raw words}; the Adam moments as digests"""
-    assert r["g"].shape == (BUCKET,) and r["s"].shape == (5,)
+    assert r["g"].shape == (K.BUCKET,) and r["s"].shape == (5,)
     out = {"g": r["g"].view(np.uint32), "s": r["s"].view(np.uint64)}
     if "p" in r:
-        assert r["p"].shape == r["m"].shape == r["v"].shape == (N_PARAMS,)
-        out.update(p=r["p"].view(np.uint32), m=_digest(r["m"]), v=_digest(r["v"]))
-    return out
-
-
-def expected(golden, name: str, path: str):
-    def pick(kind, first):
-        key = f"{kind}_{name}_{path}"
-        return golden[key] if key in golden.files else golden[f"{kind}_{name}_{first}"]
-    out = {"g": pick("g", "grad"), "s": pick("s", "grad")}
-    if path != "grad":
-        out.update(p=pick("p", "pair"), m=pick("m", "pair"), v=pick("v", "pair"))
+        assert r["p"].shape == r["m"].shape == r["v"].shape == (K.N_PARAMS,)
+        out.update(p=r["p"].view(np.uint32), m=K.digest(r["m"]), v=K.digest(r["v"]))
     return out
 
 
 def run_sequence(pv, b, lr: float, thr: float, path: str = "pair"):
     """six update steps; ({kind: array} after the sixth, statistics [6][5] float64, update state int32 [6][3] = adam_step, stopped, iters)"""
     import torch
-    ac, ps, f = _setup(pv)
+    ac, ps, f = K.load(pv)
     stats, states = [], []
-    with _split_env(path):
+    with K.split_grad(path):
         f.begin_update()
-        f.bind(*b, K7.CLIP, K7.ALPHA, K7.VF)
+        f.bind(*b, K.CLIP, K.ALPHA, K.VF)
         for _ in range(SEQ_STEPS):
             f.step_bound(lr, thr)
             stats.append(f.stats.cpu().numpy().copy())
             states.append(f.state_i32[:3].cpu().numpy().copy())
         torch.cuda.synchronize()
-    fin = {"g": f.bucket.cpu().numpy().copy(), "p": _flat(ps), "m": f.m.cpu().numpy().copy(), "v": f.v.cpu().numpy().copy()}
-    return fin, np.stack(stats), np.stack(states)
+    assert K.SPLIT_ENV not in os.environ
+    return K.read_back(ps, f), np.stack(stats), np.stack(states)
 
 
 def seq_words(fin, stats, states):
@@ -174,21 +104,15 @@ def main():
     out = {}
     for name, M, seed in CASES:
         pv, bv = inputs(M, seed)
-        b = device_batch(bv)
+        b = K.device_batch(bv)
         for path in PATHS:
             r = run_arrays(pv, b, path)
-            for kind, v in words(r).items():
-                first = f"{kind}_{name}_{'grad' if kind in 'gs' else 'pair'}"
-                if first not in out:
-                    out[first] = v
-                elif not np.array_equal(out[first], v):
-                    out[f"{kind}_{name}_{path}"] = v
-                    print("   ", name, path, kind, "differs from the first path in", int((out[first] != v).sum()), "words: stored on its own")
+            K.record(out, name, path, words(r))
             assert np.all(np.isfinite(r["g"])) and np.all(np.isfinite(r["s"])), name
-            print(name, M, path, "grad |max|", float(np.abs(r["g"][:N_PARAMS]).max()), "stats", r["s"].tolist(), flush=True)
+            print(name, M, path, "grad |max|", float(np.abs(r["g"][:K.N_PARAMS]).max()), "stats", r["s"].tolist(), flush=True)
     # the sequence: the learning rate and a threshold with which the loop stops as late as it can between its second and fifth call
     pv, bv = inputs(SEQ_M, SEQ_SEED, negative=0.85)
-    b = device_batch(bv)
+    b = K.device_batch(bv)
     best = None
     for lr_try in SEQ_LRS:
         _, stats, states = run_sequence(pv, b, lr_try, 1e30)

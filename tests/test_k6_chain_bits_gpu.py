@@ -6,29 +6,22 @@ the cases: 16 and 48 envs, walls on and off, obstruction_count 0 and -1 (both te
 23 steps per epoch with 5 per episode, and two collect() calls in a row so that the carried state crosses a launch.  Compared as
 bytes after each launch: every rollout buffer field, cur_obs, the Welford and episode-statistic carries, the env state arrays and
 error_flags()."""
-import importlib.util
 import os
+import sys
 
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(__file__))
+import _k7_bits as K  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _maker():
-    spec = importlib.util.spec_from_file_location("make_k6_rollout_bits", os.path.join(ROOT, "tests", "golden", "make_k6_rollout_bits.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-MK = _maker()
+MK = K.maker("make_k6_rollout_bits")
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(ROOT, "tests", "golden", "k6_rollout_bits.npz"))
+    return K.golden("k6_rollout_bits.npz")
 
 
 def test_golden_holds_every_case_and_field(golden):

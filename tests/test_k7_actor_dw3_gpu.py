@@ -6,35 +6,22 @@ describes the cases): M = 1, 3, 4, 5, 15, 16, 17, 31, 32, 33 and 65536 + 17; adv
 every group; zero-weight and clipped rows; a NaN row, two infinite rows; a W3 of subnormal scale.  Every case runs through
 rs_ppo_grad and through rs_ppo_update_step as a pair launch and as one launch per network.  Equality is on the raw bits (the
 critic's parameters after Adam: on their SHA-256 digest)."""
-import importlib.util
 import os
+import sys
 
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(__file__))
+import _k7_bits as K  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _maker():
-    spec = importlib.util.spec_from_file_location("make_k7_actor_dw3_bits", os.path.join(ROOT, "tests", "golden", "make_k7_actor_dw3_bits.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-MK = _maker()
+MK = K.maker("make_k7_actor_dw3_bits")
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(ROOT, "tests", "golden", "k7_actor_dw3_bits.npz"))
-
-
-def _same_bits(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape)
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad.size, bad[:8].tolist(), [hex(int(v)) for v in got[bad[:4]]], [hex(int(v)) for v in want[bad[:4]]])
+    return K.golden("k7_actor_dw3_bits.npz")
 
 
 def test_golden_inputs_are_the_generators(golden):
@@ -44,11 +31,11 @@ def test_golden_inputs_are_the_generators(golden):
         if M > MK.STORE_INPUTS_UP_TO:
             continue
         pv, bv = MK.inputs(M, seed, variant)
-        for k, v in zip(MK.PARAM_NAMES, pv):
+        for k, v in zip(K.PARAM_NAMES, pv):
             own = f"in_{name}_{k}"
             want = golden[own] if own in golden.files else golden[f"in_params_{k}"]
             assert v.dtype == want.dtype and v.tobytes() == want.tobytes(), (name, k)
-        for k, v in zip(MK.BATCH_NAMES, bv):
+        for k, v in zip(K.BATCH_NAMES, bv):
             want = golden[f"in_{name}_{k}"]
             assert v.dtype == want.dtype and v.tobytes() == want.tobytes(), (name, k)
 
@@ -65,14 +52,14 @@ def test_golden_sees_the_summation_order(golden):
 @pytest.mark.parametrize("name,M,seed,variant", MK.CASES, ids=[c[0] for c in MK.CASES])
 def test_k7_actor_dw3_bitwise(golden, name, M, seed, variant, path):
     g, s, p = MK.run(M, seed, variant, path)
-    got, want = MK.words(g, s, p), MK.expected(golden, name, path)
+    got, want = MK.words(g, s, p), K.expected(golden, name, path, MK.KINDS)
     print(name, path, "finite gradients", int(np.isfinite(g).sum()), "of", g.size, "statistics", s.tolist())
-    assert want["g"].shape == (MK.ACTOR_PARAMS,) and want["s"].shape == (5,) and sorted(got) == sorted(want)
-    _same_bits(got["g"], want["g"], (name, path, "actor gradients"))
-    _same_bits(got["s"], want["s"], (name, path, "statistics"))
+    assert want["g"].shape == (K.ACTOR_PARAMS,) and want["s"].shape == (5,) and sorted(got) == sorted(want)
+    K.same_bits(got["g"], want["g"], (name, path, "actor gradients"))
+    K.same_bits(got["s"], want["s"], (name, path, "statistics"))
     if path != "grad":
-        _same_bits(got["p"], want["p"], (name, path, "actor parameters after Adam"))
-        _same_bits(got["c"], want["c"], (name, path, "digest of the critic's parameters after Adam"))
+        K.same_bits(got["p"], want["p"], (name, path, "actor parameters after Adam"))
+        K.same_bits(got["c"], want["c"], (name, path, "digest of the critic's parameters after Adam"))
     if variant in MK.FINITE:
         assert np.all(np.isfinite(g)) and np.all(np.isfinite(s))
 

@@ -4,35 +4,22 @@ and the parameters after one Adam step as recorded from that earlier library (te
 builds the inputs and describes the cases): (a) M = 1, 31, 32, 33 and 65536 + 33, (b) a W3 with a magnitude of its own per
 (output, unit), (c) a W3 of subnormal scale, inputs of about 1e-30, a NaN row and two infinite rows.  Every case runs through
 rs_ppo_grad and through rs_ppo_update_step as a pair launch and as one launch per network.  Equality is on the raw bits."""
-import importlib.util
 import os
+import sys
 
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(__file__))
+import _k7_bits as K  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _maker():
-    spec = importlib.util.spec_from_file_location("make_k7_actor_bits", os.path.join(ROOT, "tests", "golden", "make_k7_actor_bits.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-MK = _maker()
+MK = K.maker("make_k7_actor_bits")
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(ROOT, "tests", "golden", "k7_actor_bits.npz"))
-
-
-def _same_bits(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape)
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad.size, bad[:8].tolist(), [hex(int(v)) for v in got[bad[:4]]], [hex(int(v)) for v in want[bad[:4]]])
+    return K.golden("k7_actor_bits.npz")
 
 
 def test_golden_inputs_are_the_generators(golden):
@@ -41,7 +28,7 @@ def test_golden_inputs_are_the_generators(golden):
         if M > MK.STORE_INPUTS_UP_TO:
             continue
         pv, bv = MK.inputs(M, seed, variant)
-        for k, v in list(zip(MK.PARAM_NAMES[:6], pv[:6])) + list(zip(MK.BATCH_NAMES, bv)):
+        for k, v in list(zip(K.PARAM_NAMES[:6], pv[:6])) + list(zip(K.BATCH_NAMES, bv)):
             want = golden[f"in_{name}_{k}"]
             assert v.dtype == want.dtype and v.tobytes() == want.tobytes(), (name, k)
 
@@ -50,13 +37,14 @@ def test_golden_inputs_are_the_generators(golden):
 @pytest.mark.parametrize("name,M,seed,variant", MK.CASES, ids=[c[0] for c in MK.CASES])
 def test_k7_actor_bitwise(golden, name, M, seed, variant, path):
     g, s, p = MK.run(M, seed, variant, path)
-    ge, se, pe = MK.expected(golden, name, path)
+    want = K.expected(golden, name, path, MK.KINDS)
+    ge, se, pe = want["g"], want["s"], want.get("p")
     print(name, path, "finite gradients", int(np.isfinite(g).sum()), "of", g.size, "statistics", s.tolist())
-    assert ge.shape == (MK.ACTOR_PARAMS,) and se.shape == (5,)
-    _same_bits(g.view(np.uint32), ge, (name, path, "actor gradients"))
-    _same_bits(s.view(np.uint64), se, (name, path, "statistics"))
+    assert ge.shape == (K.ACTOR_PARAMS,) and se.shape == (5,)
+    K.same_bits(g.view(np.uint32), ge, (name, path, "actor gradients"))
+    K.same_bits(s.view(np.uint64), se, (name, path, "statistics"))
     if path != "grad":
-        assert pe.shape == (MK.N_PARAMS,)
-        _same_bits(p.view(np.uint32), pe, (name, path, "parameters after Adam"))
+        assert pe.shape == (K.N_PARAMS,)
+        K.same_bits(p.view(np.uint32), pe, (name, path, "parameters after Adam"))
     if variant in ("plain", "w3_distinct", "w3_denorm", "x_tiny"):
         assert np.all(np.isfinite(g)) and np.all(np.isfinite(s))

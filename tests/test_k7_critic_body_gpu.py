@@ -5,29 +5,22 @@ workgroup slabs) and the value-loss statistic as recorded from that earlier libr
 Cases, each as a pair launch and as one launch per network: M = 1 (one clamped group, every other wave runs a zero-weight trip),
 M = 33 (a ragged second group), M = 32 * 2048 + 5 (some of the 2048 waves take a second trip, with a ragged tail), and one step with
 the stop flag set (zeros are published, the filler in the bucket is overwritten)."""
-import importlib.util
 import os
+import sys
 
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(__file__))
+import _k7_bits as K  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _maker():
-    spec = importlib.util.spec_from_file_location("make_k7_critic_bits", os.path.join(ROOT, "tests", "golden", "make_k7_critic_bits.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-MK = _maker()
+MK = K.maker("make_k7_critic_bits")
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(ROOT, "tests", "golden", "k7_critic_bits.npz"))
+    return K.golden("k7_critic_bits.npz")
 
 
 @pytest.mark.parametrize("form", MK.FORMS)
@@ -36,10 +29,9 @@ def test_k7_critic_bitwise(golden, name, M, seed, stop, form):
     g, s, bucket = MK.run(M, seed, stop, form)
     ge, se = golden["g_" + name], golden["s_" + name]
     assert g.dtype == ge.dtype and g.shape == ge.shape == (4993,) and se.shape == (1,)
-    bad = np.flatnonzero(g.view(np.uint32) != ge.view(np.uint32))
-    assert bad.size == 0, (name, form, bad.size, bad[:8].tolist(), g[bad[:4]].tolist(), ge[bad[:4]].tolist())
-    v = s[MK.STAT_VALUE_LOSS:MK.STAT_VALUE_LOSS + 1]
-    assert np.array_equal(v.view(np.uint64), se.view(np.uint64)), (name, form, v.tolist(), se.tolist())
+    K.same_bits(g.view(np.uint32), ge.view(np.uint32), (name, form, "critic gradients"))
+    v = s[K.STAT_VALUE_LOSS:K.STAT_VALUE_LOSS + 1]
+    K.same_bits(v.view(np.uint64), se.view(np.uint64), (name, form, "value loss", v.tolist(), se.tolist()))
     if stop:
         assert not bucket.any() and not s.any()
     else:

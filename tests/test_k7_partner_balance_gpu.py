@@ -6,30 +6,22 @@ statistics, the parameters and the Adam moments after a step for M = 1, 65 553, 
 per wave -- through rs_ppo_grad, the pair launch and one launch per network, and a sequence of six update steps that runs into the
 KL stop.  Equality is on the raw bits (the moments of the single steps: on their SHA-256 digests).  The priority decisions race by
 design; the last test runs the same calls five times in one process and wants every output equal."""
-import importlib.util
 import os
+import sys
 
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(__file__))
+import _k7_bits as K  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _maker():
-    spec = importlib.util.spec_from_file_location("make_k7_partner_balance_bits",
-                                                  os.path.join(ROOT, "tests", "golden", "make_k7_partner_balance_bits.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-MK = _maker()
+MK = K.maker("make_k7_partner_balance_bits")
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(ROOT, "tests", "golden", "k7_partner_balance_bits.npz"))
+    return K.golden("k7_partner_balance_bits.npz")
 
 
 @pytest.fixture(scope="module")
@@ -38,17 +30,10 @@ def batches():
     out = {}
     for name, M, seed in MK.CASES:
         pv, bv = MK.inputs(M, seed)
-        out[name] = (pv, MK.device_batch(bv))
+        out[name] = (pv, K.device_batch(bv))
     pv, bv = MK.inputs(MK.SEQ_M, MK.SEQ_SEED, negative=0.85)
-    out["seq"] = (pv, MK.device_batch(bv))
+    out["seq"] = (pv, K.device_batch(bv))
     return out
-
-
-def _same_bits(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    bad = np.flatnonzero(got.ravel() != want.ravel())
-    assert bad.size == 0, (what, bad.size, bad[:8].tolist(), [hex(int(v)) for v in got.ravel()[bad[:4]]],
-                           [hex(int(v)) for v in want.ravel()[bad[:4]]])
 
 
 def test_inputs_have_what_the_cases_need(batches):
@@ -69,14 +54,14 @@ def test_inputs_have_what_the_cases_need(batches):
 def test_k7_partner_balance_bitwise(golden, batches, name, M, seed, path):
     pv, b = batches[name]
     r = MK.run_arrays(pv, b, path)
-    got, want = MK.words(r), MK.expected(golden, name, path)
+    got, want = MK.words(r), K.expected(golden, name, path, MK.KINDS)
     print(name, path, "statistics", r["s"].tolist())
     assert sorted(got) == sorted(want)
-    assert np.all(np.isfinite(r["g"])) and np.all(np.isfinite(r["s"])) and np.any(r["g"][:MK.N_PARAMS] != 0)
+    assert np.all(np.isfinite(r["g"])) and np.all(np.isfinite(r["s"])) and np.any(r["g"][:K.N_PARAMS] != 0)
     for kind, what in (("g", "gradient bucket"), ("s", "statistics"), ("p", "parameters after Adam"), ("m", "digest of Adam's m"),
                        ("v", "digest of Adam's v")):
         if kind in want:
-            _same_bits(got[kind], want[kind], (name, path, what))
+            K.same_bits(got[kind], want[kind], (name, path, what))
 
 
 @pytest.mark.parametrize("path", ("pair", "split"))
@@ -90,7 +75,7 @@ def test_six_steps_into_the_kl_stop(golden, batches, path):
         assert states[k].tolist() == states[j].tolist()
     got = MK.seq_words(fin, stats, states)
     for kind in ("state", "stats", "g", "p", "m", "v"):
-        _same_bits(got[kind], golden[f"seq_{kind}"], ("seq", path, kind))
+        K.same_bits(got[kind], golden[f"seq_{kind}"], ("seq", path, kind))
 
 
 def test_five_runs_agree(batches):

@@ -6,9 +6,14 @@ M = 33 is one full and one partial sample group (every other wave works on clamp
 waves without a group, M = 70 001 has more groups (2188) than a network has waves (2048): some waves take a second trip, the others a
 clamped one."""
 import copy
+import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(__file__))
+import _k7_bits as K  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -19,24 +24,6 @@ PLANS = {
 }
 
 
-def _batch(M):
-    g = torch.Generator(device="cuda").manual_seed(4321)
-    X = torch.randn(M, 11, device="cuda", generator=g)
-    act = torch.randint(0, 8, (M,), device="cuda", generator=g)
-    adv = torch.randn(M, device="cuda", generator=g)
-    ret = torch.randn(M, device="cuda", generator=g)
-    lpo = -2.0 + 0.1 * torch.randn(M, device="cuda", generator=g)
-    w = torch.rand(M, device="cuda", generator=g)
-    return X, act, adv, ret, lpo, w / w.sum()
-
-
-def _bits(f):
-    torch.cuda.synchronize()
-    out = {"bucket": f.bucket, "stats": f.stats, "m": f.m, "v": f.v, "state": f.state}
-    out.update({f"param{i}": p.data for i, (p, _) in enumerate(f.views)})
-    return {k: t.detach().cpu().contiguous().view(torch.uint8).clone() for k, t in out.items()}
-
-
 @pytest.mark.parametrize("plan", sorted(PLANS))
 @pytest.mark.parametrize("M", [33, 4096 + 17, 70_001])
 def test_pair_launch_bitwise_equals_one_launch_per_network(monkeypatch, M, plan):
@@ -45,7 +32,7 @@ def test_pair_launch_bitwise_equals_one_launch_per_network(monkeypatch, M, plan)
     ac_a = FFActorCritic().cuda()
     ac_b = copy.deepcopy(ac_a)
     fa, fb = FusedPPOGrad(ac_a), FusedPPOGrad(ac_b)
-    b = _batch(M)
+    b = K.torch_batch(M, 4321)
     lr = 3e-3
     fa.begin_update(); fb.begin_update()
     for k, thr in enumerate(PLANS[plan]):
@@ -53,7 +40,7 @@ def test_pair_launch_bitwise_equals_one_launch_per_network(monkeypatch, M, plan)
         fa.step(*b, 0.2, 0.1, lr=lr, kl_threshold=thr)
         monkeypatch.delenv("RS_PPO_SPLIT_GRAD")
         fb.step(*b, 0.2, 0.1, lr=lr, kl_threshold=thr)
-        xa, xb = _bits(fa), _bits(fb)
+        xa, xb = K.state_bytes(fa), K.state_bytes(fb)
         for name in xa:
             assert torch.equal(xa[name], xb[name]), (k, name)
     iters, stopped, adam_step, last = fb.read_state()

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_draws.hpp"
 #include "rs_sstream.hpp"
 
 namespace {
@@ -30,10 +31,6 @@ __device__ __forceinline__ cmem_t as_cmem(const float* p) { return (cmem_t)(uint
 // out[OUTP] += W^T c through the scalar-unit weight stream (csrc/rs_sstream.hpp: wait -> request -> FMA blocks of two rows)
 template <int K, int OUTP, int OUTR = OUTP, typename F>
 __device__ __forceinline__ void gru_matvec(cmem_t W, F cval, float (&out)[OUTP]) { rs_ss_mv<K, OUTP, OUTR>(W, cval, out); }
-
-// sigmoid / tanh on the hardware transcendentals (v_exp_f32, v_rcp_f32: 1 ulp each), branch free
-__device__ __forceinline__ float gru_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }
-__device__ __forceinline__ float gru_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008f * x)); }
 
 template <int N>
 __device__ __forceinline__ void ld_row(const float* __restrict__ src, float (&dst)[N]) {
@@ -75,10 +72,10 @@ __global__ void __launch_bounds__(64) rs_gru_fwd_kernel(const float* __restrict_
         float go[4 * GH];
 #pragma unroll
         for (int j = 0; j < GH; ++j) {
-            const float r = gru_sigmoid(g[j] + gh[j]);
-            const float z = gru_sigmoid(g[GH + j] + gh[GH + j]);
+            const float r = rs_sigmoid(g[j] + gh[j]);
+            const float z = rs_sigmoid(g[GH + j] + gh[GH + j]);
             const float hn = gh[2 * GH + j];
-            const float n = gru_tanh(g[2 * GH + j] + r * hn);
+            const float n = rs_tanh(g[2 * GH + j] + r * hn);
             h[j] = (1.0f - z) * n + z * h[j];
             go[j] = r; go[GH + j] = z; go[2 * GH + j] = n; go[3 * GH + j] = hn;
         }

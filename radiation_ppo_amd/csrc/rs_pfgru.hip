@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_draws.hpp"
 #include "rs_sstream.hpp"
 
 namespace {
@@ -42,25 +43,8 @@ constexpr int PF_ZR = 0, PF_ZRB = PF_ZR + PF_KP * 48, PF_N = PF_ZRB + 48, PF_NB 
               PF_H2B = PF_H2 + 48, PF_STRIDE = ((PF_H2B + 2 + 15) / 16) * 16;
 static_assert(PF_STRIDE == RS_PFGRU_WEIGHT_FLOATS, "include/radsearch.h: RS_PFGRU_WEIGHT_FLOATS");
 
-typedef const float __attribute__((address_space(4))) * cmem_t;
-__device__ __forceinline__ cmem_t as_cmem(const float* p) { return (cmem_t)(uintptr_t)p; }
-
-// splitmix64 finaliser on wrapping 64-bit arithmetic == pfgru.py: hash_bits
-__device__ __forceinline__ uint64_t pf_hash(uint64_t key) {
-    uint64_t x = key * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-
-// sigmoid on the hardware transcendentals: v_exp_f32, v_rcp_f32 (1 ulp each)
-__device__ __forceinline__ float pf_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * v)); }
-// the softmax / soft-resampling exponentials, logarithms and the one f32 quotient on the hardware transcendentals too (1 ulp each; the
-// library expf / logf / IEEE division were ~110 instructions per lane and step).  The float64 CDF quotient stays IEEE: it decides indices.
-__device__ __forceinline__ float pf_exp(float x) { return __builtin_amdgcn_exp2f(1.44269504f * x); }
-__device__ __forceinline__ float pf_log(float x) { return 0.69314718f * __builtin_amdgcn_logf(x); }
-
+// The gates' sigmoids, the softmax / soft-resampling exponentials and logarithms and the one f32 quotient run on the hardware
+// transcendentals (rs_draws.hpp; the library expf / logf / IEEE division were ~110 instructions per lane and step).
 struct PfArgs {
     const float* w;           // [A][PF_STRIDE]
     const float* obs;         // [N][A][11]
@@ -97,25 +81,6 @@ constexpr int PK_SETS = 6, PK_NT = 256;
 constexpr int PK_TILE = 0, PK_CDF = PF_P * PF_ROW, PK_VA = PK_CDF + 2 * PF_P, PK_VB = PK_VA + PF_P, PK_VC = PK_VB + PF_P,
               PK_VM = PK_VC + PF_P, PK_STRIDE = 1228;
 static_assert(PK_VM + PF_H <= PK_STRIDE && PK_STRIDE % 4 == 0 && PK_STRIDE % 32 == 12 && PK_CDF % 2 == 0, "LDS layout of a particle set");
-
-__device__ __forceinline__ float pk_max40(const float* v) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < PF_P / 4; ++i) {
-        const float4 t = reinterpret_cast<const float4*>(v)[i];
-        m = fmaxf(fmaxf(m, fmaxf(t.x, t.y)), fmaxf(t.z, t.w));
-    }
-    return m;
-}
-__device__ __forceinline__ float pk_sum40(const float* v) {          // index order
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < PF_P / 4; ++i) {
-        const float4 t = reinterpret_cast<const float4*>(v)[i];
-        s = (((s + t.x) + t.y) + t.z) + t.w;
-    }
-    return s;
-}
 
 // STEPS > 1 (rs_pfgru_pass only, one owner): consecutive time steps of the carried sets from one launch, the particle set staying in
 // registers in between -- a launch costs ~17 us before its first round of workgroups is at speed (profiles/r03_k11_rounds.txt), a pass
@@ -169,7 +134,7 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
         // (the single hashing step takes the laundering too: 125 VGPRs and no scratch instead of 128 + 40 B, 105 -> 98 us with carried sets)
         if constexpr (!REC || STEPS > 1) asm volatile("" : "+s"(wl), "+v"(p0), "+v"(ql), "+v"(nl));
         const int q = ql, n = nl;
-        cmem_t W = as_cmem(wl);
+        rs_cmem_t W = rs_as_cmem(wl);
         float x[PF_IN];
         {
             const float* o = a_.obs + (size_t)s_ * a_.step_stride * RS_OBS_DIM + ((size_t)n * a_.A + own) * RS_OBS_DIM;
@@ -179,11 +144,10 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
         // keys (pfgru.py: PredictorBank._key): kind 1 = reparameterisation noise, 2 = resampling uniforms
         uint64_t k_res = 0, pk = 0;
         if constexpr (!REC) {
-            const uint64_t kb = (uint64_t)a_.base[slot] * 1000003ull;
-            const uint64_t ctr8 = ((uint64_t)a_.episode[n] * 100003ull + (uint64_t)a_.calls[n + (size_t)s_ * a_.step_stride]) * 8ull;
-            const uint64_t k_eps = kb ^ ((ctr8 + 1ull) * 0xA24BAED4963EE407ull);
-            k_res = kb ^ ((ctr8 + 2ull) * 0xA24BAED4963EE407ull);
-            pk = k_eps * 1048583ull + (uint64_t)q * 4096ull;
+            const uint64_t kb = rs_draw_base(a_.base[slot]);
+            const uint64_t ctr8 = rs_draw_counter(a_.episode[n], a_.calls[n + (size_t)s_ * a_.step_stride]);
+            k_res = rs_draw_key(kb, ctr8 + 2ull);
+            pk = rs_draw_lane(rs_draw_key(kb, ctr8 + 1ull), q);
         }
 
         // ---- gates: z | r = sigmoid(W_zr [h0, x] + b), consumed chunk by chunk (16 accumulators = 8 pairs live, not 48: the kernel
@@ -196,17 +160,17 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
             for (int o = 0; o < 16; ++o) acc[o] = W[PF_ZRB + o];
             rs_ss_mv_cols<PF_K, 48, 0, 16>(W + PF_ZR, cv1, acc);
 #pragma unroll
-            for (int o = 0; o < 16; ++o) z[o] = pf_sigmoid(acc[o]);
+            for (int o = 0; o < 16; ++o) z[o] = rs_sigmoid(acc[o]);
 #pragma unroll
             for (int o = 0; o < 16; ++o) acc[o] = W[PF_ZRB + 16 + o];
             rs_ss_mv_cols<PF_K, 48, 16, 16>(W + PF_ZR, cv1, acc);
 #pragma unroll
-            for (int o = 0; o < 8; ++o) { z[16 + o] = pf_sigmoid(acc[o]); rh[o] = pf_sigmoid(acc[8 + o]) * h0[o]; }
+            for (int o = 0; o < 8; ++o) { z[16 + o] = rs_sigmoid(acc[o]); rh[o] = rs_sigmoid(acc[8 + o]) * h0[o]; }
 #pragma unroll
             for (int o = 0; o < 16; ++o) acc[o] = W[PF_ZRB + 32 + o];
             rs_ss_mv_cols<PF_K, 48, 32, 16>(W + PF_ZR, cv1, acc);
 #pragma unroll
-            for (int o = 0; o < 16; ++o) rh[8 + o] = pf_sigmoid(acc[o]) * h0[8 + o];
+            for (int o = 0; o < 16; ++o) rh[8 + o] = rs_sigmoid(acc[o]) * h0[8 + o];
         }
         // ---- candidate: n = tanh(mu + eps * softplus(var)), [mu | var] = W_n [r * h0, x] + b; the columns arrive as three chunks of
         // [mu(8j .. 8j+7) | var(8j .. 8j+7)] (pfgru.py: pack_weights), each finishing eight units of h1
@@ -222,14 +186,7 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
                     eps8[w] = a_.eps_in[(slot * PF_P + q) * PF_H + u];
                     eps8[w + 1] = a_.eps_in[(slot * PF_P + q) * PF_H + u + 1];
                 } else {
-                    // pfgru.py: hash_normal -- one hash per PAIR of units, Box-Muller's cosine for the even unit and sine for the odd one, on
-                    // the hardware transcendentals (1 ulp each; v_cos_f32 / v_sin_f32 take revolutions: no range reduction): |error| ~ 1e-6
-                    const uint64_t hx = pf_hash(pk + (uint64_t)u);
-                    const float u1 = (float)((uint32_t)(hx >> 40) + 1u) * (1.0f / 16777216.0f);          // (0, 1]
-                    const float u2 = (float)((uint32_t)(hx >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);   // [0, 1)
-                    const float r = __builtin_amdgcn_sqrtf(-1.38629436f * __builtin_amdgcn_logf(u1));
-                    eps8[w] = r * __builtin_amdgcn_cosf(u2);
-                    eps8[w + 1] = r * __builtin_amdgcn_sinf(u2);
+                    rs_hash_normal_pair(rs_hash_bits(pk + (uint64_t)u), eps8[w], eps8[w + 1]);      // one hash per PAIR of units
                 }
             }
 #pragma unroll
@@ -239,7 +196,7 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
                 const float var = acc[8 + w];
                 const float sp = (var > 20.0f) ? var : 0.69314718f * __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(1.44269504f * var));   // F.softplus
                 const float y = acc[w] + eps * sp;
-                const float nv = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008f * y));                          // tanh
+                const float nv = rs_tanh(y);
                 h1[u] = (1.0f - z[u]) * nv + z[u] * h0[u];
             }
         };
@@ -265,15 +222,15 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
         lg += p0;
         if (act) va[q] = lg;
         __syncthreads();                                                // 1
-        const float mx = pk_max40(va);
-        const float e1 = pf_exp(lg - mx);
+        const float mx = rs_max40(va);
+        const float e1 = rs_exp(lg - mx);
         if (act) vb[q] = e1;
         __syncthreads();                                                // 2
-        float p1 = (lg - mx) - pf_log(pk_sum40(vb));
+        float p1 = (lg - mx) - rs_log(rs_sum40(vb));
         // ---- soft resampling: indices by inverse CDF of alpha * w + (1 - alpha) / P
         const float al = a_.alpha, floor_ = a_.floor_;
         if (act) {
-            va[q] = al * pf_exp(p1) + floor_;
+            va[q] = al * rs_exp(p1) + floor_;
             vc[q] = p1;
 #pragma unroll
             for (int u = 0; u < PF_H; ++u) tile[q * PF_ROW + u] = h1[u];
@@ -283,37 +240,23 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
         if constexpr (REC) {
             idx = min(max(a_.idx_in[slot * PF_P + q], 0), PF_P - 1);
         } else {
-            double run = 0.0, mine = 0.0;                               // float64 prefix sums in index order (torch.cumsum of the .double() weights)
-#pragma unroll
-            for (int i = 0; i < PF_P / 4; ++i) {
-                const float4 t = reinterpret_cast<const float4*>(va)[i];
-                run += (double)t.x; mine = (4 * i == q) ? run : mine;
-                run += (double)t.y; mine = (4 * i + 1 == q) ? run : mine;
-                run += (double)t.z; mine = (4 * i + 2 == q) ? run : mine;
-                run += (double)t.w; mine = (4 * i + 3 == q) ? run : mine;
-            }
+            double mine, run;                                           // float64 prefix sums in index order
+            rs_prefix40(va, q, mine, run);
             if (act) cdf[q] = mine / run;
             __syncthreads();                                            // 4
-            const double ru = (double)(pf_hash(k_res * 1048583ull + (uint64_t)q * 4096ull) >> 11) * (1.0 / 9007199254740992.0);
-#pragma unroll
-            for (int j = 0; j < PF_P / 2; ++j) {                        // searchsorted(..., right=True)
-                const double2 c2 = reinterpret_cast<const double2*>(cdf)[j];
-                idx += (c2.x <= ru) ? 1 : 0;
-                idx += (c2.y <= ru) ? 1 : 0;
-            }
-            idx = min(idx, PF_P - 1);
+            idx = min(rs_search40(cdf, rs_hash_uniform(rs_draw_lane(k_res, q))), PF_P - 1);      // searchsorted(..., right=True)
         }
 #pragma unroll
         for (int u = 0; u < PF_H; ++u) h1[u] = tile[idx * PF_ROW + u];
-        float pn = pf_exp(vc[idx]);
-        pn = pf_log(pn * __builtin_amdgcn_rcpf(al * pn + floor_));
+        float pn = rs_exp(vc[idx]);
+        pn = rs_log(pn * __builtin_amdgcn_rcpf(al * pn + floor_));
         if (act) vb[q] = pn;
         __syncthreads();                                                // 5
-        const float mx2 = pk_max40(vb);
-        const float e2 = pf_exp(pn - mx2);
+        const float mx2 = rs_max40(vb);
+        const float e2 = rs_exp(pn - mx2);
         if (act) va[q] = e2;
         __syncthreads();                                                // 6
-        p1 = pn - (pf_log(pk_sum40(va)) + mx2);
+        p1 = pn - (rs_log(rs_sum40(va)) + mx2);
         if (s_ == STEPS - 1 && a_.carry && live) {
             float4* hw = reinterpret_cast<float4*>(a_.h + slot * PF_P * PF_H) + q;
 #pragma unroll
@@ -321,7 +264,7 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
             a_.p[slot * PF_P + q] = p1;
         }
         // ---- weighted mean of the particles, then hid_obs: Linear(24, 24)-ReLU-Linear(24, 2)-ReLU
-        const float wgt = pf_exp(p1);
+        const float wgt = rs_exp(p1);
         if (act) {
 #pragma unroll
             for (int u = 0; u < PF_H; ++u) tile[q * PF_ROW + u] = wgt * h1[u];      // every lane gathered its row before barrier 5
@@ -358,91 +301,9 @@ __global__ void __launch_bounds__(PK_NT, RS_K11_OCC) rs_pfgru_kernel(PfArgs a_, 
     if constexpr (STEPS > 5) step(std::integral_constant<int, 5>{});
 }
 
-// reset_hidden (RADTEAM_core.py:2030-2033) for the masked envs: h0 ~ U[0,1) from the hash (kind 0), p0 = log(1 / P).
-// One lane per (owner, env, particle); the caller has already advanced episode[] and zeroed calls[] for those envs.
-__global__ void __launch_bounds__(256) rs_pfgru_reset_kernel(float* h, float* p, const int64_t* base, const int64_t* episode,
-                                                             const int64_t* calls, const uint8_t* mask, int N, int A) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)A * N * PF_P) return;
-    const int pl = (int)(i % PF_P);
-    const long long slot = i / PF_P;
-    const int n = (int)(slot % N);
-    if (mask && !mask[n]) return;
-    const uint64_t kb = (uint64_t)base[slot] * 1000003ull;
-    const uint64_t ctr8 = ((uint64_t)episode[n] * 100003ull + (uint64_t)calls[n]) * 8ull;
-    const uint64_t pk = (kb ^ (ctr8 * 0xA24BAED4963EE407ull)) * 1048583ull + (uint64_t)pl * 4096ull;
-    float4* hw = reinterpret_cast<float4*>(h + slot * PF_P * PF_H) + pl;           // quad-major, as the step kernel reads it
-#pragma unroll
-    for (int u = 0; u < PF_H; u += 4) {
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = (float)((double)(pf_hash(pk + (uint64_t)(u + q)) >> 11) * (1.0 / 9007199254740992.0));
-        hw[(u / 4) * PF_P] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    p[i] = -3.6888794541139363f;                                   // float32(log(1 / 40))
-}
-
-// The draws of one training pass over an episode-major batch (rada2c.HashDraws) in one launch instead of ~25 int64 element-wise
-// launches per step: key[e] -> h0 [E][P][H] (uniforms, kind 0), eps [L][E][P][H] (standard normals, kind 1, step t) and
-// u [L][E][P] (resampling uniforms, kind 2, step t).  One lane per (t, episode, particle).
-__global__ void __launch_bounds__(256) rs_pfgru_draws_kernel(const int64_t* __restrict__ key, int E, int L, float* __restrict__ h0,
-                                                             float* __restrict__ eps, double* __restrict__ u) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)L * E * PF_P) return;
-    const int pl = (int)(i % PF_P);
-    const long long te = i / PF_P;
-    const int e = (int)(te % E), t = (int)(te / E);
-    const uint64_t kb = (uint64_t)key[e] * 1000003ull;
-    const uint64_t pu = (uint64_t)pl * 4096ull;
-    const uint64_t k1 = (kb ^ ((uint64_t)(t * 8 + 1) * 0xA24BAED4963EE407ull)) * 1048583ull + pu;
-    float* ew = eps + i * PF_H;
-#pragma unroll
-    for (int q = 0; q < PF_H; q += 4) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-            // pfgru.py: hash_normal -- one hash per pair of units (cosine / sine of Box-Muller), on the hardware transcendentals as the
-            // step kernel evaluates it (v_log_f32 is log2, v_cos_f32 / v_sin_f32 take revolutions; 1 ulp each): with the library logf /
-            // cosf this kernel was instruction bound at a quarter of the HBM fill rate
-            const uint64_t hx = pf_hash(k1 + (uint64_t)(q + j));
-            const float u1 = (float)((uint32_t)(hx >> 40) + 1u) * (1.0f / 16777216.0f);
-            const float u2 = (float)((uint32_t)(hx >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-            const float r = __builtin_amdgcn_sqrtf(-1.38629436f * __builtin_amdgcn_logf(u1));
-            v[j] = r * __builtin_amdgcn_cosf(u2);
-            v[j + 1] = r * __builtin_amdgcn_sinf(u2);
-        }
-        *reinterpret_cast<float4*>(ew + q) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    const uint64_t k2 = (kb ^ ((uint64_t)(t * 8 + 2) * 0xA24BAED4963EE407ull)) * 1048583ull + pu;
-    u[i] = (double)(pf_hash(k2) >> 11) * (1.0 / 9007199254740992.0);
-    if (t == 0) {
-        const uint64_t k0 = kb * 1048583ull + pu;                                 // kind 0, t 0: (0 * 8 + 0) * C = 0
-        float* hw = h0 + ((long long)e * PF_P + pl) * PF_H;
-#pragma unroll
-        for (int q = 0; q < PF_H; ++q) hw[q] = (float)((double)(pf_hash(k0 + (uint64_t)q) >> 11) * (1.0 / 9007199254740992.0));
-    }
-}
-
 }  // namespace
 
 extern "C" {
-
-int rs_pfgru_draws(const int64_t* keys, int32_t episodes, int32_t steps, float* h0, float* eps, double* u, rs_stream_t stream) {
-    if (!keys || !h0 || !eps || !u || episodes < 1 || steps < 1) return RS_ERR_INVALID_ARG;
-    const long long lanes = (long long)steps * episodes * PF_P;
-    hipLaunchKernelGGL(rs_pfgru_draws_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), keys,
-                       episodes, steps, h0, eps, u);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
-}
-
-int rs_pfgru_reset(float* h, float* p, const int64_t* base_key, const int64_t* episode, const int64_t* calls, const uint8_t* mask,
-                   int32_t num_envs, int32_t num_agents, rs_stream_t stream) {
-    if (!h || !p || !base_key || !episode || !calls || num_envs < 1 || num_agents < 1) return RS_ERR_INVALID_ARG;
-    const long long lanes = (long long)num_envs * num_agents * PF_P;
-    hipLaunchKernelGGL(rs_pfgru_reset_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       h, p, base_key, episode, calls, mask, num_envs, num_agents);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
-}
 
 int rs_pfgru_step(const float* weights, const float* obs, float* h, float* p, const int64_t* base_key, const int64_t* episode,
                   const int64_t* calls, const uint8_t* mask, int32_t carry_hidden, double alpha, float* pred, int32_t num_envs,
@@ -461,7 +322,7 @@ int rs_pfgru_pass(const float* weights, const float* obs, float* h, float* p, co
     if (!weights || !obs || !h || !p || !base_key || !episode || !calls || !pred || !alive || steps < 1 || episodes < 1) return RS_ERR_INVALID_ARG;
     for (int t = 0; t < steps; ++t)
         if (alive[t] < 0 || alive[t] > episodes || (t > 0 && alive[t] > alive[t - 1])) return RS_ERR_INVALID_ARG;
-    int rc = rs_pfgru_reset(h, p, base_key, episode, calls, nullptr, episodes, 1, stream);
+    int rc = rs_pfgru_reset(h, p, base_key, episode, calls, nullptr, episodes, 1, stream);      // csrc/rs_draws.hip
     int t = 0;
     // steps in groups of PASS_STEPS while the group's last one still has episodes (the multi-step instantiation: the sets alive at t, of
     // which the first alive[t + s] also take -- and report -- step t + s; the others' sets are dead by then, their extra steps are discarded)

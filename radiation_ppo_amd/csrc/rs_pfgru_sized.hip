@@ -1,5 +1,5 @@
 // rs_pfgru_sized.hip -- K11's PFGRU location predictor at hidden widths H = 8, 16, .., 64 (a multiple of 8):
-// the particle-filter step, its multi-step pass and its reset.  40 particles, 3 inputs, alpha 0.7, tanh and the hid_obs head
+// the particle-filter step and its multi-step pass (the reset: rs_draws.hip).  40 particles, 3 inputs, alpha 0.7, tanh and the hid_obs head
 // Linear(H, 24)-ReLU-Linear(24, 2)-ReLU stay what the reference fixes (RADTEAM_core.py:1533-1584; PFGRUCell's default width is 64,
 // RAD-TEAM's --hid-rec).  The draw contract is K11's: the counter hash of radiation_ppo_amd/pfgru.py keyed by particle * 4096 + unit,
 // one hash_normal hash per PAIR of units, one resampling uniform per particle, h0 ~ hash_uniform at reset; the particle sets are
@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_draws.hpp"
 #include "rs_sstream.hpp"
 
 namespace {
@@ -48,16 +49,6 @@ __host__ __device__ constexpr SLayout slayout(int H) {
 }
 bool width_ok(int H) { return H >= 8 && H <= 64 && H % 8 == 0; }
 
-__device__ __forceinline__ uint64_t sz_hash(uint64_t key) {          // splitmix64 finaliser == pfgru.py: hash_bits
-    uint64_t x = key * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// the hardware transcendentals, as K11 (1 ulp each); the float64 CDF quotient stays IEEE
-__device__ __forceinline__ float sz_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * v)); }
-__device__ __forceinline__ float sz_exp(float x) { return __builtin_amdgcn_exp2f(1.44269504f * x); }
-__device__ __forceinline__ float sz_log(float x) { return 0.69314718f * __builtin_amdgcn_logf(x); }
 
 constexpr int SZ_MAXSTEPS = 16;
 #ifndef RS_PFGRU_SIZED_PASS_STEPS
@@ -91,24 +82,6 @@ __host__ __device__ constexpr int sz_lds_stride(int H) {
 }
 __host__ __device__ constexpr int sz_occ(int H) { return H <= 16 ? 4 : (H <= 32 ? 3 : (H <= 56 ? 2 : 1)); }
 
-__device__ __forceinline__ float sz_max40(const float* v) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < SP / 4; ++i) {
-        const float4 t = reinterpret_cast<const float4*>(v)[i];
-        m = fmaxf(fmaxf(m, fmaxf(t.x, t.y)), fmaxf(t.z, t.w));
-    }
-    return m;
-}
-__device__ __forceinline__ float sz_sum40(const float* v) {           // index order
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < SP / 4; ++i) {
-        const float4 t = reinterpret_cast<const float4*>(v)[i];
-        s = (((s + t.x) + t.y) + t.z) + t.w;
-    }
-    return s;
-}
 
 template <int H, bool REC>
 __global__ void __launch_bounds__(SZ_NT, sz_occ(H)) rs_pfgru_sized_kernel(SzArgs a_, int groups) {
@@ -168,11 +141,10 @@ __global__ void __launch_bounds__(SZ_NT, sz_occ(H)) rs_pfgru_sized_kernel(SzArgs
         }
         uint64_t k_res = 0, pk = 0;
         if constexpr (!REC) {
-            const uint64_t kb = (uint64_t)a_.base[slot] * 1000003ull;
-            const uint64_t ctr8 = ((uint64_t)a_.episode[nn] * 100003ull + (uint64_t)a_.calls[nn + (size_t)s_ * a_.step_stride]) * 8ull;
-            const uint64_t k_eps = kb ^ ((ctr8 + 1ull) * 0xA24BAED4963EE407ull);
-            k_res = kb ^ ((ctr8 + 2ull) * 0xA24BAED4963EE407ull);
-            pk = k_eps * 1048583ull + (uint64_t)qq * 4096ull;
+            const uint64_t kb = rs_draw_base(a_.base[slot]);
+            const uint64_t ctr8 = rs_draw_counter(a_.episode[nn], a_.calls[nn + (size_t)s_ * a_.step_stride]);
+            k_res = rs_draw_key(kb, ctr8 + 2ull);
+            pk = rs_draw_lane(rs_draw_key(kb, ctr8 + 1ull), qq);
         }
         // h0 into the lane's own tile row: pass 2 reads it back by runtime unit index (the previous step's last tile reads were
         // before its barrier 8)
@@ -190,7 +162,7 @@ __global__ void __launch_bounds__(SZ_NT, sz_occ(H)) rs_pfgru_sized_kernel(SzArgs
             for (int o = 0; o < NC; ++o) { acc[o] = W[L.RB + C0 + o]; asm volatile("" : "+v"(acc[o])); }
             rs_ss_mv_cols<K, H, C0, NC>(W + L.R, cv1, acc);
 #pragma unroll
-            for (int o = 0; o < NC; ++o) rh[C0 + o] = sz_sigmoid(acc[o]) * h0[C0 + o];
+            for (int o = 0; o < NC; ++o) rh[C0 + o] = rs_sigmoid(acc[o]) * h0[C0 + o];
         };
         using I16 = std::integral_constant<int, 16>;
         if constexpr (H >= 16) rchunk(std::integral_constant<int, 0>{}, I16{});
@@ -226,23 +198,17 @@ __global__ void __launch_bounds__(SZ_NT, sz_occ(H)) rs_pfgru_sized_kernel(SzArgs
                     eps8[w] = a_.eps_in[(slot * SP + qq) * H + u];
                     eps8[w + 1] = a_.eps_in[(slot * SP + qq) * H + u + 1];
                 } else {
-                    // pfgru.py: hash_normal -- one hash per pair of units, Box-Muller's cosine (even unit) and sine (odd unit)
-                    const uint64_t hx = sz_hash(pk + (uint64_t)u);
-                    const float u1 = (float)((uint32_t)(hx >> 40) + 1u) * (1.0f / 16777216.0f);
-                    const float u2 = (float)((uint32_t)(hx >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-                    const float r = __builtin_amdgcn_sqrtf(-1.38629436f * __builtin_amdgcn_logf(u1));
-                    eps8[w] = r * __builtin_amdgcn_cosf(u2);
-                    eps8[w + 1] = r * __builtin_amdgcn_sinf(u2);
+                    rs_hash_normal_pair(rs_hash_bits(pk + (uint64_t)u), eps8[w], eps8[w + 1]);      // one hash per pair of units
                 }
             }
 #pragma unroll
             for (int w = 0; w < 8; ++w) {
                 const int u = 8 * b + w;
-                const float z = sz_sigmoid(az[w]);
+                const float z = rs_sigmoid(az[w]);
                 const float var = an[8 + w];
                 const float sp = (var > 20.0f) ? var : 0.69314718f * __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(1.44269504f * var));
                 const float y = an[w] + eps8[w] * sp;
-                const float nv = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008f * y));
+                const float nv = rs_tanh(y);
                 const float h1 = (1.0f - z) * nv + z * trow[u];
                 if (act_v) trow[u] = h1;
                 lg = fmaf(W[L.O + u], h1, lg);
@@ -254,13 +220,13 @@ __global__ void __launch_bounds__(SZ_NT, sz_occ(H)) rs_pfgru_sized_kernel(SzArgs
         lg += p0;
         if (act_v) va[qq] = lg;
         __syncthreads();                                                // 1
-        const float mx = sz_max40(va);
-        const float e1 = sz_exp(lg - mx);
+        const float mx = rs_max40(va);
+        const float e1 = rs_exp(lg - mx);
         if (act_v) vb[qq] = e1;
         __syncthreads();                                                // 2
-        float p1 = (lg - mx) - sz_log(sz_sum40(vb));
+        float p1 = (lg - mx) - rs_log(rs_sum40(vb));
         if (act_v) {
-            va[qq] = al * sz_exp(p1) + floor_;
+            va[qq] = al * rs_exp(p1) + floor_;
             vc[qq] = p1;
         }
         __syncthreads();                                                // 3
@@ -268,41 +234,27 @@ __global__ void __launch_bounds__(SZ_NT, sz_occ(H)) rs_pfgru_sized_kernel(SzArgs
         if constexpr (REC) {
             idx = min(max(a_.idx_in[slot * SP + qq], 0), SP - 1);
         } else {
-            double run = 0.0, mine = 0.0;                               // float64 prefix sums in index order
-#pragma unroll
-            for (int i = 0; i < SP / 4; ++i) {
-                const float4 t = reinterpret_cast<const float4*>(va)[i];
-                run += (double)t.x; mine = (4 * i == qq) ? run : mine;
-                run += (double)t.y; mine = (4 * i + 1 == qq) ? run : mine;
-                run += (double)t.z; mine = (4 * i + 2 == qq) ? run : mine;
-                run += (double)t.w; mine = (4 * i + 3 == qq) ? run : mine;
-            }
+            double mine, run;                                           // float64 prefix sums in index order
+            rs_prefix40(va, qq, mine, run);
             if (act_v) cdf[qq] = mine / run;
             __syncthreads();                                            // 4
-            const double ru = (double)(sz_hash(k_res * 1048583ull + (uint64_t)qq * 4096ull) >> 11) * (1.0 / 9007199254740992.0);
-#pragma unroll
-            for (int j = 0; j < SP / 2; ++j) {                          // searchsorted(..., right=True)
-                const double2 c2 = reinterpret_cast<const double2*>(cdf)[j];
-                idx += (c2.x <= ru) ? 1 : 0;
-                idx += (c2.y <= ru) ? 1 : 0;
-            }
-            idx = min(idx, SP - 1);
+            idx = min(rs_search40(cdf, rs_hash_uniform(rs_draw_lane(k_res, qq))), SP - 1);      // searchsorted(..., right=True)
         }
         const float* grow = tile + idx * ROW;
 #pragma unroll
         for (int u = 0; u < H; ++u) h0[u] = grow[u];                   // the resampled particle: the carried state / next step's input
-        float pn = sz_exp(vc[idx]);
-        pn = sz_log(pn * __builtin_amdgcn_rcpf(al * pn + floor_));
+        float pn = rs_exp(vc[idx]);
+        pn = rs_log(pn * __builtin_amdgcn_rcpf(al * pn + floor_));
         if (act_v) vb[qq] = pn;
         __syncthreads();                                                // 5
-        const float mx2 = sz_max40(vb);
-        const float e2 = sz_exp(pn - mx2);
+        const float mx2 = rs_max40(vb);
+        const float e2 = rs_exp(pn - mx2);
         if (act_v) va[qq] = e2;
         __syncthreads();                                                // 6
-        p1 = pn - (sz_log(sz_sum40(va)) + mx2);
+        p1 = pn - (rs_log(rs_sum40(va)) + mx2);
         p0 = p1;
         // ---- weighted mean of the particles, then hid_obs: Linear(H, 24)-ReLU-Linear(24, 2)-ReLU
-        const float wgt = sz_exp(p1);
+        const float wgt = rs_exp(p1);
         if (act_v) {
 #pragma unroll
             for (int u = 0; u < H; ++u) trow[u] = wgt * h0[u];         // every lane gathered its row before barrier 5
@@ -334,28 +286,6 @@ __global__ void __launch_bounds__(SZ_NT, sz_occ(H)) rs_pfgru_sized_kernel(SzArgs
         for (int u = 0; u < H; u += 4) hw[(u / 4) * SP] = make_float4(h0[u], h0[u + 1], h0[u + 2], h0[u + 3]);
         a_.p[slot * SP + q] = p0;
     }
-}
-
-// reset_hidden for the masked envs at width H: h0 ~ U[0,1) from the hash (kind 0), p0 = log(1 / P); one lane per (owner, env, particle)
-__global__ void __launch_bounds__(256) rs_pfgru_sized_reset_kernel(float* h, float* p, const int64_t* base, const int64_t* episode,
-                                                                   const int64_t* calls, const uint8_t* mask, int N, int A, int H) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)A * N * SP) return;
-    const int pl = (int)(i % SP);
-    const long long slot = i / SP;
-    const int n = (int)(slot % N);
-    if (mask && !mask[n]) return;
-    const uint64_t kb = (uint64_t)base[slot] * 1000003ull;
-    const uint64_t ctr8 = ((uint64_t)episode[n] * 100003ull + (uint64_t)calls[n]) * 8ull;
-    const uint64_t pk = (kb ^ (ctr8 * 0xA24BAED4963EE407ull)) * 1048583ull + (uint64_t)pl * 4096ull;
-    float4* hw = reinterpret_cast<float4*>(h + slot * SP * H) + pl;
-    for (int u = 0; u < H; u += 4) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (float)((double)(sz_hash(pk + (uint64_t)(u + j)) >> 11) * (1.0 / 9007199254740992.0));
-        hw[(u / 4) * SP] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    p[i] = -3.6888794541139363f;                                   // float32(log(1 / 40))
 }
 
 template <bool REC>
@@ -391,16 +321,6 @@ extern "C" {
 
 int32_t rs_pfgru_sized_weight_floats(int32_t hidden) { return width_ok(hidden) ? (int32_t)slayout(hidden).stride : 0; }
 
-int rs_pfgru_sized_reset(float* h, float* p, const int64_t* base_key, const int64_t* episode, const int64_t* calls, const uint8_t* mask,
-                         int32_t num_envs, int32_t num_agents, int32_t hidden, rs_stream_t stream) {
-    if (!width_ok(hidden)) return RS_ERR_UNSUPPORTED;
-    if (!h || !p || !base_key || !episode || !calls || num_envs < 1 || num_agents < 1 || num_agents > RS_MAX_AGENTS) return RS_ERR_INVALID_ARG;
-    const long long lanes = (long long)num_envs * num_agents * SP;
-    hipLaunchKernelGGL(rs_pfgru_sized_reset_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       h, p, base_key, episode, calls, mask, num_envs, num_agents, hidden);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
-}
-
 int rs_pfgru_sized_step(const float* weights, const float* obs, float* h, float* p, const int64_t* base_key, const int64_t* episode,
                         const int64_t* calls, const uint8_t* mask, int32_t carry_hidden, double alpha, float* pred, int32_t num_envs,
                         int32_t num_agents, int32_t hidden, rs_stream_t stream) {
@@ -419,7 +339,7 @@ int rs_pfgru_sized_pass(const float* weights, const float* obs, float* h, float*
     if (!weights || !obs || !h || !p || !base_key || !episode || !calls || !pred || !alive || steps < 1 || episodes < 1) return RS_ERR_INVALID_ARG;
     for (int t = 0; t < steps; ++t)
         if (alive[t] < 0 || alive[t] > episodes || (t > 0 && alive[t] > alive[t - 1])) return RS_ERR_INVALID_ARG;
-    int rc = rs_pfgru_sized_reset(h, p, base_key, episode, calls, nullptr, episodes, 1, hidden, stream);
+    int rc = rs_pfgru_sized_reset(h, p, base_key, episode, calls, nullptr, episodes, 1, hidden, stream);      // csrc/rs_draws.hip
     // launches of up to PASS_STEPS steps over the episodes alive at their first step; an episode that ends inside a launch's steps
     // reports only its own steps (its extra steps are computed and discarded), a workgroup whose sets have all ended leaves
     constexpr int PASS_STEPS = RS_PFGRU_SIZED_PASS_STEPS;

@@ -2,7 +2,7 @@
 // whole episodes, a forward-walk launch and a backward-walk launch per pass of update_model) at hidden widths H = 8, 16, .., 64, the
 // width a template parameter.  40 particles, 3 inputs, alpha from the caller, tanh and hid_obs = Linear(H, 24)-ReLU-Linear(24, 2)-ReLU as
 // the reference fixes them; the loss is the one of include/radsearch.h (rs_pfgru_train); resampling indices are constants of the backward
-// pass, as in autograd.  Also rs_pfgru_sized_draws: rs_pfgru_draws at width H.
+// pass, as in autograd.  The pass's draws as buffers: rs_pfgru_sized_draws (rs_draws.hip).
 //
 // Built for correctness first: none of K13's tuning (one wave per episode, 24 units in registers, matrix cores, scalar weight streams)
 // carries to 64 units, where the weight-gradient accumulators alone are 17.4 k floats per episode.
@@ -47,6 +47,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_draws.hpp"
 
 namespace {
 
@@ -72,17 +73,9 @@ __host__ __device__ constexpr GLayout glayout(int H) {
     return GLayout{ZR, N, H0, H2, O, end, r16(end)};
 }
 
-__device__ __forceinline__ uint64_t st_hash(uint64_t key) {          // splitmix64 finaliser == pfgru.py: hash_bits
-    uint64_t x = key * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, 1 ulp each), as K11s / K13; the float64 CDF quotient stays IEEE
-__device__ __forceinline__ float st_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * v)); }
-__device__ __forceinline__ float st_exp(float x) { return __builtin_amdgcn_exp2f(1.44269504f * x); }
-__device__ __forceinline__ float st_log(float x) { return 0.69314718f * __builtin_amdgcn_logf(x); }
+// the hardware transcendentals as K11s / K13 (rs_draws.hpp); the float64 CDF quotient stays IEEE
 __device__ __forceinline__ float st_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+// rolled, one value per read: the backward walk's rows (s.ve1 + Q, Q = 41) are not 16-byte aligned as rs_max40 / rs_sum40 need them
 __device__ __forceinline__ float st_max40(const float* v) {
     float m = -INFINITY;
 #pragma unroll 8
@@ -159,7 +152,7 @@ __global__ void __launch_bounds__(NT, 2) rs_pfgru_sized_train_fwd_kernel(StArgs 
     const float al = a_.alpha, floor_ = a_.floor_;
     const size_t PH = (size_t)P * H;
     for (int i = tid; i < P * H; i += NT) hin[(i / H) * HS + i % H] = a_.h0[(size_t)e * PH + i];
-    float p0 = -3.6888794541139363f;                                 // float32(log(1 / 40)); thread q < 40 carries particle q's log weight
+    float p0 = RS_LOG_INV_P;                                         // thread q < 40 carries particle q's log weight
     __syncthreads();
     for (int t = 0; t < len; ++t) {
         const size_t te = (size_t)t * E + e;
@@ -179,7 +172,7 @@ __global__ void __launch_bounds__(NT, 2) rs_pfgru_sized_train_fwd_kernel(StArgs 
 #pragma unroll
             for (int j = 0; j < PG; ++j) {
                 const int p = pg * PG + j;
-                const float s = st_sigmoid(acc[j]);
+                const float s = rs_sigmoid(acc[j]);
                 if (o < H) {
                     zz[p * HS + o] = s;
                     gz[(size_t)p * H + o] = s;
@@ -209,7 +202,7 @@ __global__ void __launch_bounds__(NT, 2) rs_pfgru_sized_train_fwd_kernel(StArgs 
             const float sp = big ? var : 0.69314718f * __builtin_amdgcn_logf(1.0f + ex);
             const float es = big ? ep : ep * (1.0f - __builtin_amdgcn_rcpf(1.0f + ex));
             const float y = an[p * AS + u] + ep * sp;
-            const float n = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008f * y));      // tanh
+            const float n = rs_tanh(y);
             const float z = zz[p * HS + u];
             h1s[p * HS + u] = (1.0f - z) * n + z * hin[p * HS + u];
             gz[2 * PH + i] = n;
@@ -227,13 +220,13 @@ __global__ void __launch_bounds__(NT, 2) rs_pfgru_sized_train_fwd_kernel(StArgs 
         if (tid < P) va[tid] = lg;
         __syncthreads();
         const float mx = st_max40(va);
-        const float e1 = st_exp(lg - mx);
+        const float e1 = rs_exp(lg - mx);
         if (tid < P) vb[tid] = e1;
         __syncthreads();
-        const float p1 = (lg - mx) - st_log(st_sum40(vb));
+        const float p1 = (lg - mx) - rs_log(st_sum40(vb));
         __syncthreads();
         if (tid < P) {
-            va[tid] = al * st_exp(p1) + floor_;
+            va[tid] = al * rs_exp(p1) + floor_;
             vc[tid] = p1;
         }
         __syncthreads();
@@ -255,19 +248,19 @@ __global__ void __launch_bounds__(NT, 2) rs_pfgru_sized_train_fwd_kernel(StArgs 
         } else {
             idx = min(max(a_.idx[te * P + q], 0), P - 1);
         }
-        float pn = st_exp(vc[idx]);
-        pn = st_log(st_div(pn, al * pn + floor_));
+        float pn = rs_exp(vc[idx]);
+        pn = rs_log(st_div(pn, al * pn + floor_));
         if (tid < P) {
             vb[tid] = pn;
             vidx[tid] = idx;
         }
         __syncthreads();
         const float mx2 = st_max40(vb);
-        const float e2 = st_exp(pn - mx2);
+        const float e2 = rs_exp(pn - mx2);
         __syncthreads();
         if (tid < P) va[tid] = e2;
         __syncthreads();
-        p0 = pn - (st_log(st_sum40(va)) + mx2);
+        p0 = pn - (rs_log(st_sum40(va)) + mx2);
         if (tid < P) {
             a_.ps[te * 2 * P + tid] = p1;
             a_.ps[te * 2 * P + P + tid] = p0;
@@ -385,7 +378,7 @@ __global__ void __launch_bounds__(NT, H <= 56 ? 2 : 1) rs_pfgru_sized_train_bwd_
         // ---- the resampled set [v | 1], its log weights, the indices
         if (tid < P) {
             s.vp1[tid] = a_.ps[te * 2 * P + tid];
-            s.pi[tid] = st_exp(a_.ps[te * 2 * P + P + tid]);
+            s.pi[tid] = rs_exp(a_.ps[te * 2 * P + P + tid]);
             s.vidx[tid] = min(max(a_.idx[te * P + tid], 0), P - 1);
         }
         for (int i = tid; i < P * H; i += NT) s.I[(i / H) * IS + i % H] = a_.hs[te * PH + i];
@@ -423,8 +416,8 @@ __global__ void __launch_bounds__(NT, H <= 56 ? 2 : 1) rs_pfgru_sized_train_bwd_
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const float d = s.out[tid * 2 + c] - tr[c];
-                s.ve2[c * Q + tid] = st_exp(-d * d * bpt);
-                s.ve1[c * Q + tid] = st_exp(-fabsf(d) * bpt);
+                s.ve2[c * Q + tid] = rs_exp(-d * d * bpt);
+                s.ve1[c * Q + tid] = rs_exp(-fabsf(d) * bpt);
             }
         }
         __syncthreads();
@@ -444,8 +437,8 @@ __global__ void __launch_bounds__(NT, H <= 56 ? 2 : 1) rs_pfgru_sized_train_bwd_
                     }
                     dout = G * elbo * gpart * inv_nel;
                 } else {                                             // the mean prediction; this thread also keeps the episode's loss sums
-                    l2ps += -st_log(y2);
-                    if (l1w != 0.0f) l1ps += -st_log(st_sum40(s.ve1 + c * Q) * (1.0f / P));
+                    l2ps += -rs_log(y2);
+                    if (l1w != 0.0f) l1ps += -rs_log(st_sum40(s.ve1 + c * Q) * (1.0f / P));
                     const float sgm = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
                     l2s += d * d * bpt;
                     l1s += fabsf(d) * bpt;
@@ -503,7 +496,7 @@ __global__ void __launch_bounds__(NT, H <= 56 ? 2 : 1) rs_pfgru_sized_train_bwd_
         {
             const float Ssum = st_sum40(s.vtmp);
             const float dpn = dp1r - s.pi[q] * Ssum;                 // through p1r = pn - logsumexp(pn)
-            const float wj = st_exp(s.vp1[s.vidx[q]]);
+            const float wj = rs_exp(s.vp1[s.vidx[q]]);
             if (tid < P) s.dhr[tid * RS + H] = st_div(dpn * floor_, al * wj + floor_);      // through pn = log(w / (alpha w + floor))
         }
         __syncthreads();
@@ -519,7 +512,7 @@ __global__ void __launch_bounds__(NT, H <= 56 ? 2 : 1) rs_pfgru_sized_train_bwd_
         }
         __syncthreads();
         {
-            const float dlp = s.vdp1[q] - st_exp(s.vp1[q]) * st_sum40(s.vdp1);      // through p1 = lp - logsumexp(lp); also d / d p0
+            const float dlp = s.vdp1[q] - rs_exp(s.vp1[q]) * st_sum40(s.vdp1);      // through p1 = lp - logsumexp(lp); also d / d p0
             dp = dlp;
             if (tid < P) s.vdlp[tid] = dlp;
         }
@@ -607,41 +600,6 @@ __global__ void __launch_bounds__(NT, H <= 56 ? 2 : 1) rs_pfgru_sized_train_bwd_
     }
 }
 
-// rs_pfgru_draws_kernel (csrc/rs_pfgru.hip) at width H: one lane per (step, episode, particle)
-__global__ void __launch_bounds__(256) rs_pfgru_sized_draws_kernel(const int64_t* __restrict__ key, int E, int L, int H, float* __restrict__ h0,
-                                                                   float* __restrict__ eps, double* __restrict__ u) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)L * E * P) return;
-    const int pl = (int)(i % P);
-    const long long te = i / P;
-    const int e = (int)(te % E), t = (int)(te / E);
-    const uint64_t kb = (uint64_t)key[e] * 1000003ull;
-    const uint64_t pu = (uint64_t)pl * 4096ull;
-    const uint64_t k1 = (kb ^ ((uint64_t)(t * 8 + 1) * 0xA24BAED4963EE407ull)) * 1048583ull + pu;
-    float* ew = eps + i * H;
-    for (int q = 0; q < H; q += 4) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-            // pfgru.py: hash_normal -- one hash per pair of units (cosine / sine of Box-Muller) on the hardware transcendentals
-            const uint64_t hx = st_hash(k1 + (uint64_t)(q + j));
-            const float u1 = (float)((uint32_t)(hx >> 40) + 1u) * (1.0f / 16777216.0f);
-            const float u2 = (float)((uint32_t)(hx >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-            const float r = __builtin_amdgcn_sqrtf(-1.38629436f * __builtin_amdgcn_logf(u1));
-            v[j] = r * __builtin_amdgcn_cosf(u2);
-            v[j + 1] = r * __builtin_amdgcn_sinf(u2);
-        }
-        *reinterpret_cast<float4*>(ew + q) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    const uint64_t k2 = (kb ^ ((uint64_t)(t * 8 + 2) * 0xA24BAED4963EE407ull)) * 1048583ull + pu;
-    u[i] = (double)(st_hash(k2) >> 11) * (1.0 / 9007199254740992.0);
-    if (t == 0) {
-        const uint64_t k0 = kb * 1048583ull + pu;                                 // kind 0, t 0
-        float* hw = h0 + ((long long)e * P + pl) * H;
-        for (int q = 0; q < H; ++q) hw[q] = (float)((double)(st_hash(k0 + (uint64_t)q) >> 11) * (1.0 / 9007199254740992.0));
-    }
-}
-
 template <int H>
 void launch_pass(const StArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(rs_pfgru_sized_train_fwd_kernel<H>, dim3((unsigned)a.E), dim3(NT), 0, st, a);
@@ -654,16 +612,6 @@ extern "C" {
 
 int32_t rs_pfgru_sized_train_weight_floats(int32_t hidden) { return width_ok(hidden) ? (int32_t)wlayout(hidden).stride : 0; }
 int32_t rs_pfgru_sized_train_grad_floats(int32_t hidden) { return width_ok(hidden) ? (int32_t)glayout(hidden).stride : 0; }
-
-int rs_pfgru_sized_draws(const int64_t* keys, int32_t episodes, int32_t steps, int32_t hidden, float* h0, float* eps, double* u,
-                         rs_stream_t stream) {
-    if (!width_ok(hidden) || !keys || !h0 || !eps || !u || episodes < 0 || steps < 1) return RS_ERR_INVALID_ARG;
-    if (episodes == 0) return RS_OK;
-    const long long lanes = (long long)steps * episodes * P;
-    hipLaunchKernelGGL(rs_pfgru_sized_draws_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), keys,
-                       episodes, steps, hidden, h0, eps, u);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
-}
 
 int rs_pfgru_sized_train(const float* weights, const float* obs, const float* target, const float* bp, const int64_t* lens, const float* w_ep,
                          const float* h0, const float* eps, const double* u, float* hs, float* ps, float* gates, int32_t* idx, float* loss,

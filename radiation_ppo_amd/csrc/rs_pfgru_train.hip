@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_draws.hpp"
 #include "rs_wave.hpp"
 #include "rs_sstream.hpp"
 
@@ -79,18 +80,8 @@ __device__ __forceinline__ void mv(cmem_t W, F cval, float (&out)[OUTP]) { rs_ss
 template <int L>
 __device__ __forceinline__ float lane_bcast(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), L)); }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }
-// splitmix64 finaliser on wrapping 64-bit arithmetic == pfgru.py: hash_bits == csrc/rs_pfgru.hip: pf_hash
-__device__ __forceinline__ uint64_t tr_hash(uint64_t key) {
-    uint64_t x = key * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// Both walks' exponentials, logarithms and f32 quotients on the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, 1 ulp each, as
-// K11's cell): the library expf / logf / IEEE division are 10-20 instructions each, ~200 of a step's 5 000 at the lone-wave issue rate
-__device__ __forceinline__ float bw_exp(float x) { return __builtin_amdgcn_exp2f(1.44269504f * x); }
-__device__ __forceinline__ float bw_log(float x) { return 0.69314718f * __builtin_amdgcn_logf(x); }
+// Both walks' exponentials, logarithms and f32 quotients on the hardware transcendentals (rs_draws.hpp; v_exp_f32 / v_log_f32 / v_rcp_f32, 1 ulp
+// each, as K11's cell): the library expf / logf / IEEE division are 10-20 instructions each, ~200 of a step's 5 000 at the lone-wave issue rate
 __device__ __forceinline__ float bw_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
 // gates and candidate state of one particle: z, r, n, es = eps * d softplus(var) / d var, h1 = (1 - z) n + z h0, lg = fc_obs([h1, x])
@@ -108,7 +99,7 @@ __device__ __forceinline__ void pf_cell(cmem_t W, const float (&h0)[H], const fl
     for (int u = 0; u < H; u += 4) {
         float r4[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { z[u + j] = sigmoidf_(g[u + j]); r4[j] = sigmoidf_(g[H + u + j]); rh[u + j] = r4[j] * h0[u + j]; }
+        for (int j = 0; j < 4; ++j) { z[u + j] = rs_sigmoid(g[u + j]); r4[j] = rs_sigmoid(g[H + u + j]); rh[u + j] = r4[j] * h0[u + j]; }
         if (store) {
             gw[(u / 4) * P] = make_float4(z[u], z[u + 1], z[u + 2], z[u + 3]);
             gw[(6 + u / 4) * P] = make_float4(r4[0], r4[1], r4[2], r4[3]);
@@ -130,7 +121,7 @@ __device__ __forceinline__ void pf_cell(cmem_t W, const float (&h0)[H], const fl
             const float sp = big ? var : 0.69314718f * __builtin_amdgcn_logf(1.0f + e);
             es4[j] = big ? eps[u + j] : eps[u + j] * (1.0f - __builtin_amdgcn_rcpf(1.0f + e));
             const float y = m[u + j] + eps[u + j] * sp;
-            n4[j] = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008f * y));      // tanh
+            n4[j] = rs_tanh(y);
             h1[u + j] = (1.0f - z[u + j]) * n4[j] + z[u + j] * h0[u + j];
             lg = fmaf(W[T_O + u + j], h1[u + j], lg);
         }
@@ -154,7 +145,7 @@ struct TrArgs {
     const float* eps;         // [L][E][P][H]
     const double* u;          // [L][E][P]  resampling uniforms; NULL: idx[] holds the indices to take (recorded draws)
     const int64_t* keys;      // [E] or NULL.  Given (rs_pfgru_train_keyed): h0 / eps / u are NOT read -- the forward walk evaluates the counter hash
-                              // of rs_pfgru_draws itself (same keys, same arithmetic, bit-identical values; csrc/rs_pfgru.hip: rs_pfgru_draws_kernel)
+                              // of rs_pfgru_draws itself (same keys, same arithmetic, bit-identical values; csrc/rs_draws.hip: rs_pfgru_draws_kernel)
     float* hs;                // [L][E][H / 4][P] float4 scratch: resampled particles after every step, quad-major
     float* ps;                // [L][E][P]    scratch: their log weights
     float* gates;             // [L][E][4 H / 4][P] float4 scratch: z | r | n | eps * softplus'(var) of the forward walk, QUAD-major (quad j of all 40
@@ -313,25 +304,6 @@ constexpr int FW_SETS = 6, FW_NT = 256;
 constexpr int FW_TILE = 0, FW_CDF = P * ROW, FW_VA = FW_CDF + 2 * P, FW_VB = FW_VA + P, FW_VC = FW_VB + P, FW_STRIDE = 1228;
 static_assert(FW_VC + P <= FW_STRIDE && FW_STRIDE % 4 == 0 && FW_STRIDE % 32 == 12 && FW_CDF % 2 == 0, "LDS layout of an episode's particle set");
 
-__device__ __forceinline__ float fw_max40(const float* v) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < P / 4; ++i) {
-        const float4 t = reinterpret_cast<const float4*>(v)[i];
-        m = fmaxf(fmaxf(m, fmaxf(t.x, t.y)), fmaxf(t.z, t.w));
-    }
-    return m;
-}
-__device__ __forceinline__ float fw_sum40(const float* v) {          // index order
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < P / 4; ++i) {
-        const float4 t = reinterpret_cast<const float4*>(v)[i];
-        s = (((s + t.x) + t.y) + t.z) + t.w;
-    }
-    return s;
-}
-
 // KEYED: the pass's draws (initial particles, reparameterisation noise, resampling uniforms) are hashed here instead of read: the draws
 // launch wrote 8.2 GB per pass at 16.5 k episodes (2.3 ms) for this kernel to read back -- K11 has always hashed in the kernel
 template <bool KEYED>
@@ -371,10 +343,10 @@ __global__ void __launch_bounds__(FW_NT, K13_FW_OCC) rs_pfgru_train_fwd_kernel(T
     float h0[H];
     uint64_t kb = 0;
     if constexpr (KEYED) {
-        kb = (uint64_t)a_.keys[e] * 1000003ull;
-        const uint64_t k0 = kb * 1048583ull + (uint64_t)q * 4096ull;                      // kind 0, step 0
+        kb = rs_draw_base(a_.keys[e]);
+        const uint64_t k0 = rs_draw_lane(rs_draw_key(kb, 0), q);                          // kind 0, step 0
 #pragma unroll
-        for (int u = 0; u < H; ++u) h0[u] = (float)((double)(tr_hash(k0 + (uint64_t)u) >> 11) * (1.0 / 9007199254740992.0));
+        for (int u = 0; u < H; ++u) h0[u] = (float)rs_hash_uniform(k0 + (uint64_t)u);
         if (has) {                                                    // the backward walk's last step reads the initial particles
             float4* dst = reinterpret_cast<float4*>(const_cast<float*>(a_.h0) + ((size_t)e * P + q) * H);
 #pragma unroll
@@ -383,7 +355,7 @@ __global__ void __launch_bounds__(FW_NT, K13_FW_OCC) rs_pfgru_train_fwd_kernel(T
     } else {
         load24(a_.h0 + ((size_t)e * P + q) * H, h0);
     }
-    float p0 = -3.6888794541139363f;                                 // float32(log(1 / 40))
+    float p0 = RS_LOG_INV_P;
     for (int t = 0; t < lmax; ++t) {
         const bool on = t < len;                                      // this episode is still running (uniform over its 40 lanes)
         const int tc = on ? t : (len > 0 ? len - 1 : 0);              // finished episodes re-read their last step (nothing is stored)
@@ -396,16 +368,9 @@ __global__ void __launch_bounds__(FW_NT, K13_FW_OCC) rs_pfgru_train_fwd_kernel(T
             for (int k = 0; k < IN; ++k) x[k] = o[k];
         }
         if constexpr (KEYED) {
-            const uint64_t k1 = (kb ^ ((uint64_t)(tc * 8 + 1) * 0xA24BAED4963EE407ull)) * 1048583ull + (uint64_t)q * 4096ull;
+            const uint64_t k1 = rs_draw_lane(rs_draw_key(kb, (uint64_t)(tc * 8 + 1)), q);
 #pragma unroll
-            for (int u = 0; u < H; u += 2) {                          // one hash per pair of units: Box-Muller's cosine and sine
-                const uint64_t hx = tr_hash(k1 + (uint64_t)u);
-                const float u1 = (float)((uint32_t)(hx >> 40) + 1u) * (1.0f / 16777216.0f);
-                const float u2 = (float)((uint32_t)(hx >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-                const float r = __builtin_amdgcn_sqrtf(-1.38629436f * __builtin_amdgcn_logf(u1));
-                eps[u] = r * __builtin_amdgcn_cosf(u2);
-                eps[u + 1] = r * __builtin_amdgcn_sinf(u2);
-            }
+            for (int u = 0; u < H; u += 2) rs_hash_normal_pair(rs_hash_bits(k1 + (uint64_t)u), eps[u], eps[u + 1]);      // one hash per pair of units
         } else {
             load24(a_.eps + te * PH + (size_t)q * H, eps);
         }
@@ -414,13 +379,13 @@ __global__ void __launch_bounds__(FW_NT, K13_FW_OCC) rs_pfgru_train_fwd_kernel(T
         lg += p0;
         if (act) va[q] = lg;
         __syncthreads();                                             // 1
-        const float mx = fw_max40(va);
-        const float e1 = bw_exp(lg - mx);
+        const float mx = rs_max40(va);
+        const float e1 = rs_exp(lg - mx);
         if (act) vb[q] = e1;
         __syncthreads();                                             // 2
-        const float p1 = (lg - mx) - bw_log(fw_sum40(vb));
+        const float p1 = (lg - mx) - rs_log(rs_sum40(vb));
         if (act) {
-            va[q] = al * bw_exp(p1) + floor_;
+            va[q] = al * rs_exp(p1) + floor_;
             vc[q] = p1;
 #pragma unroll
             for (int u = 0; u < H; ++u) tile[q * ROW + u] = h1[u];
@@ -428,45 +393,31 @@ __global__ void __launch_bounds__(FW_NT, K13_FW_OCC) rs_pfgru_train_fwd_kernel(T
         __syncthreads();                                             // 3
         int idx = 0;
         if (KEYED || a_.u) {
-            double run = 0.0, mine = 0.0;                            // float64 prefix sums in index order
-#pragma unroll
-            for (int i = 0; i < P / 4; ++i) {
-                const float4 w4 = reinterpret_cast<const float4*>(va)[i];
-                run += (double)w4.x; mine = (4 * i == q) ? run : mine;
-                run += (double)w4.y; mine = (4 * i + 1 == q) ? run : mine;
-                run += (double)w4.z; mine = (4 * i + 2 == q) ? run : mine;
-                run += (double)w4.w; mine = (4 * i + 3 == q) ? run : mine;
-            }
+            double mine, run;                                           // float64 prefix sums in index order
+            rs_prefix40(va, q, mine, run);
             if (act) cdf[q] = mine / run;
             __syncthreads();                                         // 4 (a_.u is a launch argument: every lane takes this branch or none)
             double ru;
             if constexpr (KEYED) {
-                const uint64_t k2 = (kb ^ ((uint64_t)(tc * 8 + 2) * 0xA24BAED4963EE407ull)) * 1048583ull + (uint64_t)q * 4096ull;
-                ru = (double)(tr_hash(k2) >> 11) * (1.0 / 9007199254740992.0);
+                ru = rs_hash_uniform(rs_draw_lane(rs_draw_key(kb, (uint64_t)(tc * 8 + 2)), q));
             } else {
                 ru = a_.u[te * P + q];
             }
-#pragma unroll
-            for (int j = 0; j < P / 2; ++j) {                        // searchsorted(..., right=True)
-                const double2 c2 = reinterpret_cast<const double2*>(cdf)[j];
-                idx += (c2.x <= ru) ? 1 : 0;
-                idx += (c2.y <= ru) ? 1 : 0;
-            }
-            idx = min(idx, P - 1);
+            idx = min(rs_search40(cdf, ru), P - 1);                  // searchsorted(..., right=True)
         } else {
             idx = min(max(a_.idx[te * P + q], 0), P - 1);            // what torch.multinomial returned in the reference's run
         }
 #pragma unroll
         for (int u = 0; u < H; ++u) h0[u] = tile[idx * ROW + u];
-        float pn = bw_exp(vc[idx]);
-        pn = bw_log(bw_div(pn, al * pn + floor_));
+        float pn = rs_exp(vc[idx]);
+        pn = rs_log(bw_div(pn, al * pn + floor_));
         if (act) vb[q] = pn;
         __syncthreads();                                             // 5
-        const float mx2 = fw_max40(vb);
-        const float e2 = bw_exp(pn - mx2);
+        const float mx2 = rs_max40(vb);
+        const float e2 = rs_exp(pn - mx2);
         if (act) va[q] = e2;
         __syncthreads();                                             // 6
-        p0 = pn - (bw_log(fw_sum40(va)) + mx2);
+        p0 = pn - (rs_log(rs_sum40(va)) + mx2);
         if (on) {
             float4* hw = reinterpret_cast<float4*>(a_.hs + te * PH) + q;          // quad-major, as the gates: quad j of all particles contiguous
 #pragma unroll
@@ -592,7 +543,7 @@ __global__ void __launch_bounds__(64) rs_pfgru_train_kernel(TrArgs a_) {
                 p0 = a_.ps[(te - E) * P + pl];
             } else {
                 load24(a_.h0 + ((size_t)e * P + pl) * H, h0);      // (a keyed pass: written by the forward walk)
-                p0 = -3.6888794541139363f;
+                p0 = RS_LOG_INV_P;
             }
             load_x(t, x);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the DMA of this step's gates (and the loads above) have landed
@@ -624,9 +575,9 @@ __global__ void __launch_bounds__(64) rs_pfgru_train_kernel(TrArgs a_) {
         K13_STAMP(2)                                                 // backward: loads of the step's gates, h1 and logit
         lg += p0;
         const float mx = wave_max(act ? lg : -INFINITY);
-        const float se = wave_sum(act ? bw_exp(lg - mx) : 0.0f);
-        const float p1 = (lg - mx) - bw_log(se);
-        const float pi = act ? bw_exp(ps_t) : 0.0f;
+        const float se = wave_sum(act ? rs_exp(lg - mx) : 0.0f);
+        const float p1 = (lg - mx) - rs_log(se);
+        const float pi = act ? rs_exp(ps_t) : 0.0f;
 
         float wf[2][6];
         f4 bf[2];
@@ -668,16 +619,16 @@ __global__ void __launch_bounds__(64) rs_pfgru_train_kernel(TrArgs a_) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const float d = out[c] - tr[c];
-            const float e2 = act ? bw_exp(-d * d * bpt) : 0.0f;
+            const float e2 = act ? rs_exp(-d * d * bpt) : 0.0f;
             const float y2 = wave_sum(e2) * (1.0f / P);
             float gpart = bw_div(l2w * 2.0f * d * bpt * e2, P * y2);
-            l2ps += -bw_log(y2);
+            l2ps += -rs_log(y2);
             if (l1w != 0.0f) {
-                const float e1 = act ? bw_exp(-fabsf(d) * bpt) : 0.0f;
+                const float e1 = act ? rs_exp(-fabsf(d) * bpt) : 0.0f;
                 const float y1 = wave_sum(e1) * (1.0f / P);
                 const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
                 gpart += bw_div(l1w * 10.0f * sg * bpt * e1, P * y1);
-                l1ps += -bw_log(y1);
+                l1ps += -rs_log(y1);
             }
             const float dm = lane_bcast<P>(d);                           // the mean prediction's error (lane 40)
             const float sgm = dm > 0.0f ? 1.0f : (dm < 0.0f ? -1.0f : 0.0f);
@@ -726,7 +677,7 @@ __global__ void __launch_bounds__(64) rs_pfgru_train_kernel(TrArgs a_) {
         const float dpn = dp1r - pi * S;                             // through p1r = pn - logsumexp(pn)
         vec[lane] = p1;
         __builtin_amdgcn_wave_barrier();
-        const float wj = bw_exp(vec[idx]);
+        const float wj = rs_exp(vec[idx]);
         const float gp = bw_div(dpn * floor_, al * wj + floor_);          // through pn = log(w / (alpha w + floor))
         // ---- back through the gather: every source particle sums the gradients of the lanes that resampled it.  Not by LDS float atomics
         // (25 x ds_add_f32 per lane took ~360 cycles each: 9 000 of the step's 61 000 cycles): one INTEGER atomic per lane builds the list of
@@ -756,7 +707,7 @@ __global__ void __launch_bounds__(64) rs_pfgru_train_kernel(TrArgs a_) {
             }
         }
         __builtin_amdgcn_wave_barrier();
-        const float dlp = dp1 - bw_exp(p1) * wave_sum(dp1);            // through p1 = lp - logsumexp(lp); also d / d p0
+        const float dlp = dp1 - rs_exp(p1) * wave_sum(dp1);            // through p1 = lp - logsumexp(lp); also d / d p0
         dp = dlp;
         K13_STAMP(6)                                                 // resampling backwards: scatter-add, softmax derivatives
         // ---- fc_obs: d fc_obs = sum over particles of dlp (x) [h1 | x | 1] (row 0 of a tile, as d hid_obs[2] above)

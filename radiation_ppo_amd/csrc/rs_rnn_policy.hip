@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_draws.hpp"
 #include "rs_sstream.hpp"
 
 namespace {
@@ -39,9 +40,6 @@ __device__ __forceinline__ cmem_t as_cmem(const float* p) { return (cmem_t)(uint
 // out[OUTP] += W^T c through the scalar-unit weight stream (csrc/rs_sstream.hpp: wait -> request -> FMA blocks of two rows)
 template <int K, int OUTP, int OUTR = OUTP, typename F>
 __device__ __forceinline__ void mv(cmem_t W, F cval, float (&out)[OUTP]) { rs_ss_mv<K, OUTP, OUTR>(W, cval, out); }
-
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }
-__device__ __forceinline__ float tanh_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008f * x)); }
 
 struct PolArgs {
     const float* w;        // [RS_RNN_POLICY_WEIGHT_FLOATS]
@@ -83,9 +81,9 @@ __global__ void __launch_bounds__(64) rs_rnn_policy_kernel(PolArgs a_) {
     mv<GH, 80, 72>(W + P_HH, [&](int k) -> float { return h[k]; }, gh);
 #pragma unroll
     for (int j = 0; j < GH; ++j) {
-        const float r = sigm(gi[j] + gh[j]);
-        const float z = sigm(gi[GH + j] + gh[GH + j]);
-        const float n = tanh_(gi[2 * GH + j] + r * gh[2 * GH + j]);
+        const float r = rs_sigmoid(gi[j] + gh[j]);
+        const float z = rs_sigmoid(gi[GH + j] + gh[GH + j]);
+        const float n = rs_tanh(gi[2 * GH + j] + r * gh[2 * GH + j]);
         h[j] = (1.0f - z) * n + z * h[j];
     }
     if (a_.h_out && live) {
@@ -101,8 +99,8 @@ __global__ void __launch_bounds__(64) rs_rnn_policy_kernel(PolArgs a_) {
         float v0 = W[P_V2 + HD], v1 = 0.0f;
 #pragma unroll
         for (int k = 0; k < HD; k += 2) {
-            v0 = fmaf(W[P_V2 + k], tanh_(t[k]), v0);
-            v1 = fmaf(W[P_V2 + k + 1], tanh_(t[k + 1]), v1);
+            v0 = fmaf(W[P_V2 + k], rs_tanh(t[k]), v0);
+            v1 = fmaf(W[P_V2 + k + 1], rs_tanh(t[k + 1]), v1);
         }
         if (live) a_.value[e] = v0 + v1;
     }
@@ -113,7 +111,7 @@ __global__ void __launch_bounds__(64) rs_rnn_policy_kernel(PolArgs a_) {
         for (int o = 0; o < HD; ++o) t[o] = W[P_B1 + o];
         mv<GH, HD>(W + P_W1, [&](int k) -> float { return h[k]; }, t);
 #pragma unroll
-        for (int o = 0; o < HD; ++o) t[o] = tanh_(t[o]);
+        for (int o = 0; o < HD; ++o) t[o] = rs_tanh(t[o]);
         float lg[16];
 #pragma unroll
         for (int o = 0; o < 16; ++o) lg[o] = W[P_B2 + o];
@@ -195,9 +193,9 @@ __global__ void __launch_bounds__(64) rs_rnn_team_step_kernel(TeamArgs t) {
     mv<GH, 80, 72>(W + P_HH, [&](int k) -> float { return h[k]; }, gh);
 #pragma unroll
     for (int j = 0; j < GH; ++j) {
-        const float r = sigm(gi[j] + gh[j]);
-        const float z = sigm(gi[GH + j] + gh[GH + j]);
-        const float n = tanh_(gi[2 * GH + j] + r * gh[2 * GH + j]);
+        const float r = rs_sigmoid(gi[j] + gh[j]);
+        const float z = rs_sigmoid(gi[GH + j] + gh[GH + j]);
+        const float n = rs_tanh(gi[2 * GH + j] + r * gh[2 * GH + j]);
         h[j] = (1.0f - z) * n + z * h[j];
     }
     if (keep) {
@@ -210,7 +208,7 @@ __global__ void __launch_bounds__(64) rs_rnn_team_step_kernel(TeamArgs t) {
     for (int o = 0; o < HD; ++o) tt[o] = W[P_B1 + o];
     mv<GH, HD>(W + P_W1, [&](int k) -> float { return h[k]; }, tt);
 #pragma unroll
-    for (int o = 0; o < HD; ++o) tt[o] = tanh_(tt[o]);
+    for (int o = 0; o < HD; ++o) tt[o] = rs_tanh(tt[o]);
     float lg[16];
 #pragma unroll
     for (int o = 0; o < 16; ++o) lg[o] = W[P_B2 + o];
@@ -277,7 +275,7 @@ __global__ void __launch_bounds__(64) rs_a2c_heads_kernel(HeadArgs a_) {
     mv<GH, HD>(W + P_W1, [&](int k) -> float { return h[k]; }, tp);
     mv<GH, HD>(W + P_V1, [&](int k) -> float { return h[k]; }, tv);
 #pragma unroll
-    for (int o = 0; o < HD; ++o) { tp[o] = tanh_(tp[o]); tv[o] = tanh_(tv[o]); }
+    for (int o = 0; o < HD; ++o) { tp[o] = rs_tanh(tp[o]); tv[o] = rs_tanh(tv[o]); }
     float lg[16];
 #pragma unroll
     for (int o = 0; o < 16; ++o) lg[o] = W[P_B2 + o];
@@ -368,30 +366,6 @@ __global__ void __launch_bounds__(64) rs_a2c_heads_kernel(HeadArgs a_) {
     }
 }
 
-// splitmix64 finaliser == pfgru.py: hash_bits (csrc/rs_pfgru.hip: pf_hash)
-__device__ __forceinline__ uint64_t gh_hash(uint64_t key) {
-    uint64_t x = key * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// _get_init_states (RADA2C_core.py:458-461) for the envs that begin an episode: h0 ~ U(-scale, scale) from the counter hash
-// (kind 5 of the env's key, episode counter = episodes_begun[n]); one lane per (agent, env, unit).  The torch composition of the
-// same hash was ~30 int64 element-wise launches per lock-step of the collector.
-__global__ void __launch_bounds__(256) rs_gru_h0_kernel(float* __restrict__ h, const int64_t* __restrict__ base, const int64_t* __restrict__ begun,
-                                                        const uint8_t* __restrict__ mask, float scale, int N, int A) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)A * N * GH) return;
-    const int j = (int)(i % GH);
-    const long long slot = i / GH;
-    const int n = (int)(slot % N);
-    if (mask && !mask[n]) return;
-    const uint64_t key = ((uint64_t)base[slot] * 1000003ull) ^ (((uint64_t)begun[n] * 8ull + 5ull) * 0xA24BAED4963EE407ull);
-    const double u = (double)(gh_hash(key * 1048583ull + (uint64_t)j) >> 11) * (1.0 / 9007199254740992.0);
-    h[i] = ((float)u * 2.0f - 1.0f) * scale;
-}
-
 }  // namespace
 
 extern "C" {
@@ -403,15 +377,6 @@ int rs_a2c_heads_loss(const float* weights, const float* hs, const int64_t* act,
         return RS_ERR_INVALID_ARG;
     HeadArgs a{weights, hs, act, adv, ret, logp_old, sample_weight, dhs, dfac, tfac, stats, (long long)samples, (float)clip_ratio, (float)vf_coef};
     hipLaunchKernelGGL(rs_a2c_heads_kernel, dim3((unsigned)((samples + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
-}
-
-int rs_gru_h0_reset(float* h, const int64_t* base_key, const int64_t* episodes_begun, const uint8_t* mask, double scale, int32_t num_envs,
-                    int32_t num_agents, rs_stream_t stream) {
-    if (!h || !base_key || !episodes_begun || num_envs < 1 || num_agents < 1) return RS_ERR_INVALID_ARG;
-    const long long lanes = (long long)num_envs * num_agents * GH;
-    hipLaunchKernelGGL(rs_gru_h0_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), h, base_key,
-                       episodes_begun, mask, (float)scale, num_envs, num_agents);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -1,6 +1,6 @@
 // rs_rnn_sized.hip -- the RAD-A2C actor-critic (GRU + one-hidden-layer policy and value heads) at widths other than the CLI default
-// (SURVEY section 8 row f2): the counterparts of K14 (policy step), K12 (GRU time loop + BPTT), K15 (heads + PPO loss + backward)
-// and rs_gru_h0 for a GRU of 1..64 units and heads of 2..64 units (main.py --hid-gru / --hid-pol / --hid-val; RADA2C_core.py:484-495
+// (SURVEY section 8 row f2): the counterparts of K14 (policy step), K12 (GRU time loop + BPTT) and K15 (heads + PPO loss + backward)
+// for a GRU of 1..64 units and heads of 2..64 units (main.py --hid-gru / --hid-pol / --hid-val; RADA2C_core.py:484-495
 // defaults to 32 / 64 / 64).  The default-size kernels (rs_gru.hip, rs_rnn_policy.hip) are untouched and still serve (24, 32, 32).
 //
 // Mapping: one env / episode / sample per lane, as K12 - K15.  The GRU width is padded to a compile-time tier HT (16, 32, 48, 64):
@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_draws.hpp"
 #include "rs_sstream.hpp"
 
 namespace {
@@ -41,9 +42,6 @@ __host__ __device__ constexpr long long policy_floats(int hid, int pol, int val)
 __host__ __device__ constexpr long long gru_floats(int hid) { return (long long)(tier_of(hid) / 8) * (48 * tier_of(hid) + 24); }
 
 bool widths_ok(int hid, int pol, int val) { return hid >= 1 && hid <= 64 && pol >= 2 && pol <= 64 && val >= 2 && val <= 64; }
-
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }
-__device__ __forceinline__ float tanh_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008f * x)); }
 
 // acc[24] += W^T c over a k-major [K][24] block (16 + 8 columns)
 template <int K, typename F>
@@ -96,9 +94,9 @@ __device__ __forceinline__ void gru_cell(rs_cmem_t W, const float (&x)[NX], cons
         mv24<HT>(Wb + (NX + 1) * 24, [&](int k) -> float { return h[k]; }, gh);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const float r = sigm(gi[i] + gh[i]);
-            const float z = sigm(gi[8 + i] + gh[8 + i]);
-            const float n = tanh_(gi[16 + i] + r * gh[16 + i]);
+            const float r = rs_sigmoid(gi[i] + gh[i]);
+            const float z = rs_sigmoid(gi[8 + i] + gh[8 + i]);
+            const float n = rs_tanh(gi[16 + i] + r * gh[16 + i]);
             hn[8 * b + i] = (1.0f - z) * n + z * h[8 * b + i];
         }
     }
@@ -121,7 +119,7 @@ __device__ __forceinline__ void heads_fwd(const float* w, int pol_at, int npb, i
             for (int i = 0; i < 8; ++i) t[i] = P[8 * HT + i];
             rs_ss_mv_cols<HT, 8, 0, 8>(P, [&](int k) -> float { return h[k]; }, t);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) t[i] = tanh_(t[i]);
+            for (int i = 0; i < 8; ++i) t[i] = rs_tanh(t[i]);
             rs_ss_mv_cols<8, 8, 0, 8>(P + 8 * HT + 8, [&](int k) -> float { return t[k]; }, lg);
         }
     }
@@ -136,8 +134,8 @@ __device__ __forceinline__ void heads_fwd(const float* w, int pol_at, int npb, i
             rs_ss_mv_cols<HT, 8, 0, 8>(V, [&](int k) -> float { return h[k]; }, t);
 #pragma unroll
             for (int i = 0; i < 8; i += 2) {
-                v0 = fmaf(V[8 * HT + 8 + i], tanh_(t[i]), v0);
-                v1 = fmaf(V[8 * HT + 8 + i + 1], tanh_(t[i + 1]), v1);
+                v0 = fmaf(V[8 * HT + 8 + i], rs_tanh(t[i]), v0);
+                v1 = fmaf(V[8 * HT + 8 + i + 1], rs_tanh(t[i + 1]), v1);
             }
         }
         value = v0 + v1;
@@ -267,10 +265,10 @@ __global__ void __launch_bounds__(64) rs_gru_sized_fwd_kernel(const float* __res
             float go[32];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float r = sigm(g[i] + gh[i]);
-                const float z = sigm(g[8 + i] + gh[8 + i]);
+                const float r = rs_sigmoid(g[i] + gh[i]);
+                const float z = rs_sigmoid(g[8 + i] + gh[8 + i]);
                 const float hh = gh[16 + i];
-                const float n = tanh_(g[16 + i] + r * hh);
+                const float n = rs_tanh(g[16 + i] + r * hh);
                 hn[8 * b + i] = (1.0f - z) * n + z * h[8 * b + i];
                 go[i] = r; go[8 + i] = z; go[16 + i] = n; go[24 + i] = hh;
             }
@@ -368,7 +366,7 @@ __device__ __forceinline__ void head_block_fwd(rs_cmem_t P, const float (&h)[HT]
     for (int i = 0; i < 8; ++i) t[i] = P[8 * HT + i];
     rs_ss_mv_cols<HT, 8, 0, 8>(P, [&](int k) -> float { return h[k]; }, t);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = tanh_(t[i]);
+    for (int i = 0; i < 8; ++i) t[i] = rs_tanh(t[i]);
 }
 
 template <int HT>
@@ -489,28 +487,6 @@ __global__ void __launch_bounds__(64) rs_a2c_sized_heads_kernel(HeadArgs a_) {
     }
 }
 
-// splitmix64 finaliser == pfgru.py: hash_bits (csrc/rs_rnn_policy.hip: gh_hash)
-__device__ __forceinline__ uint64_t gh_hash(uint64_t key) {
-    uint64_t x = key * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// rs_gru_h0 with the width as an argument: one lane per (agent, env, unit), the same counter hash (kind 5, episodes_begun[n])
-__global__ void __launch_bounds__(256) rs_gru_h0_sized_kernel(float* __restrict__ h, const int64_t* __restrict__ base, const int64_t* __restrict__ begun,
-                                                              const uint8_t* __restrict__ mask, float scale, int hid, int N, int A) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)A * N * hid) return;
-    const int j = (int)(i % hid);
-    const long long slot = i / hid;
-    const int n = (int)(slot % N);
-    if (mask && !mask[n]) return;
-    const uint64_t key = ((uint64_t)base[slot] * 1000003ull) ^ (((uint64_t)begun[n] * 8ull + 5ull) * 0xA24BAED4963EE407ull);
-    const double u = (double)(gh_hash(key * 1048583ull + (uint64_t)j) >> 11) * (1.0 / 9007199254740992.0);
-    h[i] = ((float)u * 2.0f - 1.0f) * scale;
-}
-
 }  // namespace
 
 #define RS_TIER_SWITCH(hid, KERNEL, GRID, BLOCK, ...)                                                                              \
@@ -579,16 +555,6 @@ int rs_a2c_sized_heads_loss(const float* weights, int32_t hid, int32_t pol, int3
     HeadArgs a{weights, hs, act, adv, ret, logp_old, sample_weight, dhs, dfac, tfac, stats, (long long)samples, hid, (float)clip_ratio,
                (float)vf_coef, layout_rt(hid, pol, val)};
     RS_TIER_SWITCH(hid, rs_a2c_sized_heads_kernel, dim3((unsigned)((samples + 63) / 64)), dim3(64), a);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
-}
-
-int rs_gru_h0_reset_sized(float* h, const int64_t* base_key, const int64_t* episodes_begun, const uint8_t* mask, double scale, int32_t hid,
-                          int32_t num_envs, int32_t num_agents, rs_stream_t stream) {
-    if (hid < 1 || hid > 64) return RS_ERR_UNSUPPORTED;
-    if (!h || !base_key || !episodes_begun || num_envs < 1 || num_agents < 1) return RS_ERR_INVALID_ARG;
-    const long long lanes = (long long)num_envs * num_agents * hid;
-    hipLaunchKernelGGL(rs_gru_h0_sized_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), h,
-                       base_key, episodes_begun, mask, (float)scale, hid, num_envs, num_agents);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

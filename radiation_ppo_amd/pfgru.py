@@ -43,7 +43,7 @@ def _lsr(x: torch.Tensor, s: int) -> torch.Tensor:
 
 def hash_bits(key: torch.Tensor) -> torch.Tensor:
     """int64 keys -> 64 mixed bits: the splitmix64 finaliser (Steele et al. 2014) on wrapping int64 arithmetic
-    (csrc/rs_pfgru.hip: pf_hash is the same function)."""
+    (csrc/rs_draws.hpp: rs_hash_bits is the same function; that header states the whole draw contract)."""
     x = key * _s64(0x9E3779B97F4A7C15) + _s64(0xD1B54A32D192ED03)
     x = (x ^ _lsr(x, 30)) * _s64(0xBF58476D1CE4E5B9)
     x = (x ^ _lsr(x, 27)) * _s64(0x94D049BB133111EB)
@@ -68,6 +68,20 @@ def hash_normal(key: torch.Tensor) -> torch.Tensor:
     r = torch.sqrt(-2.0 * torch.log(u1))
     ang = 6.2831855 * u2
     return torch.stack((r * torch.cos(ang), r * torch.sin(ang)), dim=-1).reshape(key.shape)
+
+
+def draw_key(base: torch.Tensor, counter) -> torch.Tensor:
+    """The key of a stream's draws at `counter` (csrc/rs_draws.hpp: rs_draw_key of rs_draw_base): base = the stream's int64 identities,
+    counter = when * 8 + kind, an int or an int64 tensor that broadcasts against base.  A draw's hash key is
+    draw_key(..) * 1048583 + lane_offsets(..)."""
+    mix = 0xA24BAED4963EE407
+    return (base * 1000003) ^ (_s64(counter * mix) if isinstance(counter, int) else counter * _s64(mix))
+
+
+def lane_offsets(P: int, H: int, device) -> torch.Tensor:
+    """[P, H] int64: particle * 4096 + unit, what a draw's key adds for its lane (csrc/rs_draws.hpp: rs_draw_lane, + unit)."""
+    return (torch.arange(P, dtype=torch.int64, device=device).view(P, 1) * 4096
+            + torch.arange(H, dtype=torch.int64, device=device).view(1, H))
 
 
 # packed per-owner weights of csrc/rs_pfgru.hip (floats): offsets of the blocks and the owner stride
@@ -267,8 +281,7 @@ class PredictorBank:
         own = torch.arange(number_agents, dtype=torch.int64, device=self.dev)
         # key layout: seed | global env id | owner, then (episode, step, kind) and (particle, unit) are mixed in per call
         self._base = hash_uniform((env.view(1, -1) * 64 + own.view(-1, 1)) ^ _s64(int(seed) * 0x2545F4914F6CDD1D)).mul(2.0 ** 52).long()   # [A, N]
-        self._pu = (torch.arange(P, dtype=torch.int64, device=self.dev).view(P, 1) * 4096
-                    + torch.arange(H, dtype=torch.int64, device=self.dev).view(1, H))                                                          # [P, H]
+        self._pu = lane_offsets(P, H, self.dev)                                                                                                # [P, H]
         # the kernels keep the particle sets quad-major ([A, N, H / 4, P, 4], include/radsearch.h); `h` is the logical [A, N, P, H] view of it
         self._hq = torch.zeros(number_agents, num_envs, H // 4, P, 4, dtype=torch.float32, device=self.dev) if impl == "hip" else None
         self._h = None if impl == "hip" else torch.zeros(number_agents, num_envs, P, H, dtype=torch.float32, device=self.dev)
@@ -306,7 +319,7 @@ class PredictorBank:
 
     def _key(self, kind: int) -> torch.Tensor:
         ctr = (self.episode.view(1, -1) * 100003 + self.calls.view(1, -1)) * 8 + kind                       # [1, N]
-        return (self._base * 1000003) ^ (ctr * _s64(0xA24BAED4963EE407))                                   # [A, N]
+        return draw_key(self._base, ctr)                                                                    # [A, N]
 
     @torch.no_grad()
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:

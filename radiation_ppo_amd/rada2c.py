@@ -42,7 +42,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .envs import RadSearchVec
-from .pfgru import SIZED_WIDTHS, PFGRUCell, PredictorBank, _s64, hash_normal, hash_uniform
+from .pfgru import SIZED_WIDTHS, PFGRUCell, PredictorBank, _s64, draw_key, hash_normal, hash_uniform, lane_offsets
 from .ppo import (DeviceWelford, EpochStats, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
                   reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
 
@@ -338,11 +338,11 @@ class HashDraws:
     def __init__(self, keys: torch.Tensor, P: int = 40, H: int = 24, hid: int = 24):
         self.k = keys
         dev = keys.device
-        self._pu = (torch.arange(P, dtype=torch.int64, device=dev).view(P, 1) * 4096 + torch.arange(H, dtype=torch.int64, device=dev).view(1, H))
+        self._pu = lane_offsets(P, H, dev)
         self._g = torch.arange(hid, dtype=torch.int64, device=dev)
 
     def _key(self, kind: int, t: int = 0) -> torch.Tensor:
-        return (self.k * 1000003) ^ _s64((t * 8 + kind) * 0xA24BAED4963EE407)
+        return draw_key(self.k, t * 8 + kind)
 
     def pf_h0(self) -> torch.Tensor:
         return hash_uniform(self._key(0).view(-1, 1, 1) * 1048583 + self._pu.unsqueeze(0)).float()
@@ -400,7 +400,7 @@ class KernelDraws:
         if H == 24:
             _lib.check(_lib.load().rs_pfgru_draws(self.k.data_ptr(), E, L, self._pf.data_ptr(), self._eps.data_ptr(), self._u.data_ptr(), st),
                        "rs_pfgru_draws")
-        else:                                                                # the same hash at width H (csrc/rs_pfgru_sized_train.hip)
+        else:                                                                # the same kernel at width H (csrc/rs_draws.hip)
             _lib.check(_lib.load().rs_pfgru_sized_draws(self.k.data_ptr(), E, L, H, self._pf.data_ptr(), self._eps.data_ptr(),
                                                         self._u.data_ptr(), st), "rs_pfgru_sized_draws")
 
@@ -1435,7 +1435,7 @@ class RNNCollector:
                                                          m8.data_ptr(), 1.0 / math.sqrt(hid), hid, self.N, self.A,
                                                          C.c_void_p(torch.cuda.current_stream(self.h.device).cuda_stream)), "rs_gru_h0_reset_sized")
             return
-        key = (self.bank._base * 1000003) ^ ((self.episodes_begun.view(1, -1) * 8 + 5) * _s64(0xA24BAED4963EE407))      # [A, N]
+        key = draw_key(self.bank._base, self.episodes_begun.view(1, -1) * 8 + 5)                                        # [A, N]
         u = hash_uniform(key.unsqueeze(-1) * 1048583 + self._gidx.view(1, 1, -1))
         h0 = self.agents[0].agent.gru_h0(u)
         self.h.copy_(torch.where(m.view(1, -1, 1), h0, self.h))

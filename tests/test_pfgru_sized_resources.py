@@ -25,7 +25,7 @@ def test_sized_pfgru_kernels_fit_their_occupancy(H, rec):
 
 
 def test_sized_pfgru_reset_has_no_scratch():
-    k = M.one(M.library_kernels(), "rs_pfgru_sized_reset_kernel")
+    k = M.one(M.library_kernels(), "rs_pfgru_reset_kernelILi0E")
     assert k["scratch"] == 0, k
 
 

@@ -29,5 +29,5 @@ def test_sized_train_kernels_fit_their_stated_resources(H, walk):
 
 
 def test_sized_draws_kernel_has_no_scratch():
-    k = M.one(M.library_kernels(), "rs_pfgru_sized_draws_kernel")
+    k = M.one(M.library_kernels(), "rs_pfgru_draws_kernelILi0E")
     assert k["scratch"] == 0 and k["lds"] == 0, k

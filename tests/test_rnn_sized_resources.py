@@ -29,7 +29,7 @@ def test_sized_rnn_kernels_fit_their_occupancy(kernel):
 
 
 def test_sized_h0_kernel_has_no_scratch():
-    k = M.one(M.library_kernels(), "rs_gru_h0_sized_kernel")
+    k = M.one(M.library_kernels(), "rs_gru_h0_kernel")
     assert k["scratch"] == 0 and k["vgpr_spill"] == 0, k
 
 

@@ -810,6 +810,38 @@ typedef struct {
 int rs_rnn_team_eval_post_step(const rs_rnn_team_eval_state* s, rs_stream_t stream);
 int rs_rnn_team_eval_post_refresh(const rs_rnn_team_eval_state* s, rs_stream_t stream);
 
+/* ---- Monte-Carlo evaluation of RAD-TEAM (CNN) teams of 1 to 8 agents on 27 x 27 maps (algos/multiagent/evaluate.py:333-476) ---------
+ * One lock-step is rs_action_uniforms, rs_pfgru_step (every owner), rs_maps_update, rs_maps_stack, rs_cnn_team_trunk_infer,
+ * rs_cnn_team_eval_head, rs_step, rs_eval_post_step (its four Welford pointers NULL) on one stream
+ * (radiation_ppo_amd/evaluate.py: run_test_environments_cnn_team); every agent's convolution weights are prepared once per run, one
+ * rs_cnn_trunk_prepare(6, ...) per agent into wscratch [A][rs_cnn_trunk_scratch_floats(6)].
+ *
+ * rs_cnn_team_trunk_infer: every agent's actor trunk in one launch, grid = (image rounds, agent); the arithmetic is rs_cnn_trunk_infer's:
+ * the result equals num_agents calls of it (agent = a, a's prepared weights) bit for bit.
+ *   maps [N][4][729]          the shared maps (rs_maps_stack's critic stack)
+ *   cells, pcells [N][A]      int32: the heat maps' own "cell" / "pred_cell" fields (rs_maps_field), -1 = none
+ *   wscratch [A][scratch]     the prepared weights, scratch = rs_cnn_trunk_scratch_floats(6)
+ *   a2 [A][N][2704]           every agent's flattened trunk output
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL pointer, num_agents outside 1..RS_MAX_AGENTS, num_samples < 0;
+ * num_samples == 0 returns RS_OK and launches nothing. */
+int rs_cnn_team_trunk_infer(const float* maps, const int32_t* cells, const int32_t* pcells, int32_t num_agents, int64_t num_samples,
+                            const float* wscratch, float* a2, rs_stream_t stream);
+
+/* rs_cnn_team_eval_head: every agent's policy head behind the trunk in one launch, grid = (64-image tiles, agent): Linear(2704, 32) on
+ * the f32 matrix cores (exact f32; four k-quarters added in a fixed order, then the bias: no atomics, an image's bits depend on neither
+ * num_envs nor the grid), then rs_cnn_head's arithmetic (out_dim 8) operation for operation and the evaluation's idle rule.
+ *   heads [A]             host array (device pointers inside), torch layouts: w1 [32][2704], b1 [32], w2 [16][32], b2 [16], w3 [8][16], b3 [8]
+ *   a2 [A][N][2704]       rs_cnn_team_trunk_infer's output
+ *   u [N][A], alive [N]   the uniforms of rs_action_uniforms; alive[n] != 0 while lane n's episode runs
+ *   act8 [N][A]           rs_step's action rows: #{j < 7 : cdf_j <= u} where alive, else 8 (idle)
+ *   act [A][N], logp [A][N], y1_out [A][N][32]   or NULL: the draw and its log-probability on EVERY lane, alive or not, and the first
+ *                         layer's pre-activation output (for tests; the evaluation passes NULL)
+ * RS_ERR_INVALID_ARG, before anything is launched: NULL heads / a2 / u / alive / act8, a NULL pointer inside the first num_agents heads,
+ * num_agents outside 1..RS_MAX_AGENTS, num_envs < 1. */
+typedef struct { const float *w1, *b1, *w2, *b2, *w3, *b3; } rs_cnn_head_params;
+int rs_cnn_team_eval_head(const rs_cnn_head_params* heads, int32_t num_agents, const float* a2, const float* u, const uint8_t* alive,
+                          int8_t* act8, int64_t* act, float* logp, float* y1_out, int32_t num_envs, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@
 //     workgroup), dW1 through the pool's argmax: only one of the four conv1 pixels of a cell carries gradient, so
 //     dW1 costs 8*169*Cin*9 MACs per image instead of 8*676*Cin*9; per-workgroup partial sums go to a slab that
 //     the caller reduces (deterministic, no atomics).
+// rs_cnn_team_fwd_kernel is K9's forward pass for every agent of a team in one launch (the Monte-Carlo evaluation's policy round,
+// radiation_ppo_amd/evaluate.py: run_test_environments_cnn_team; its heads: rs_cnn_eval.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -229,8 +231,9 @@ struct FwFetch {
     int loc, pc;
 };
 
-template <int CIN>
-__device__ __forceinline__ void fw_fetch(const CnnIn& in, long long s0, int img, FwFetch& f) {
+// IN: CnnIn (int64 cell columns, as the collectors store them) or CnnIn32 (the heat maps' own int32 fields: the team kernel)
+template <int CIN, typename IN>
+__device__ __forceinline__ void fw_fetch(const IN& in, long long s0, int img, FwFetch& f) {
     const long long left = in.S - s0;                               // images left from s0 on (>= 1)
     const int lim = (int)(left < FW_IMG ? left : FW_IMG) * 4 * MAPC;
     const float* src = in.maps + (size_t)s0 * 4 * MAPC;
@@ -259,10 +262,20 @@ __device__ __forceinline__ void fw_stage(const FwFetch& f, float* xp) {
     }
 }
 
-template <int CIN>
-__global__ void __launch_bounds__(FW_NT, 4) rs_cnn_fwd_kernel(CnnIn in, const float* __restrict__ wt, float* __restrict__ a2,
-                                                            float* __restrict__ p1g, uint8_t* __restrict__ amax,
-                                                            uint16_t* __restrict__ relu_mask) {
+// CnnIn with the cell columns as the heat maps keep them (rs_maps_field "cell" / "pred_cell"): what the team kernel reads
+struct CnnIn32 {
+    const float* maps;        // [S][4][729]
+    const int32_t* cells;     // [S][A] owner cells, -1 = none
+    const int32_t* pcells;    // [S][A] prediction cell or -1
+    int A, agent;
+    long long S;
+};
+
+// The forward pass of one workgroup: image rounds rd0, rd0 + rstride, ... of the batch (a round = FW_IMG consecutive images).  K9 walks
+// the rounds by its one-dimensional grid; the team kernel gives every agent a grid row of its own.
+template <int CIN, typename IN>
+__device__ __forceinline__ void cnn_fwd_rounds(const IN& in, const float* wt, float* a2, float* p1g, uint8_t* amax, uint16_t* relu_mask,
+                                               const unsigned rd0, const unsigned rstride) {
     extern __shared__ __align__(16) float smem[];
     float* xp = smem;                               // [FW_IMG][4 dense planes][28][28]
     float* pp = xp + FW_IMG * DP * XP_PLANE;        // [FW_IMG][8][15][15]
@@ -280,14 +293,14 @@ __global__ void __launch_bounds__(FW_NT, 4) rs_cnn_fwd_kernel(CnnIn in, const fl
     float* ppi = pp + (img < FW_IMG ? img : 0) * C1 * PP_PLANE;
     const long long rounds = (in.S + FW_IMG - 1) / FW_IMG;
     FwFetch f;
-    if ((long long)blockIdx.x < rounds) fw_fetch<CIN>(in, (long long)blockIdx.x * FW_IMG, img, f);
+    if ((long long)rd0 < rounds) fw_fetch<CIN>(in, (long long)rd0 * FW_IMG, img, f);
     CNN_DECL
-    for (long long rd = blockIdx.x; rd < rounds; rd += gridDim.x) {
+    for (long long rd = rd0; rd < rounds; rd += rstride) {
         const long long s = rd * FW_IMG + img;
         const bool own = tid < FW_OWN && s < in.S;
         const int loc = f.loc, pc = f.pc;
         fw_stage(f, xp);
-        if (rd + gridDim.x < rounds) fw_fetch<CIN>(in, (rd + gridDim.x) * FW_IMG, img, f);      // next round: in flight during the compute
+        if (rd + rstride < rounds) fw_fetch<CIN>(in, (rd + rstride) * FW_IMG, img, f);      // next round: in flight during the compute
         CNN_STAMP(0)
         __syncthreads();
         CNN_STAMP(1)
@@ -440,6 +453,27 @@ __global__ void __launch_bounds__(FW_NT, 4) rs_cnn_fwd_kernel(CnnIn in, const fl
         CNN_STAMP(5)
     }
     CNN_FLUSH(0)
+}
+
+template <int CIN>
+__global__ void __launch_bounds__(FW_NT, 4) rs_cnn_fwd_kernel(CnnIn in, const float* __restrict__ wt, float* __restrict__ a2,
+                                                            float* __restrict__ p1g, uint8_t* __restrict__ amax,
+                                                            uint16_t* __restrict__ relu_mask) {
+    cnn_fwd_rounds<CIN>(in, wt, a2, p1g, amax, relu_mask, blockIdx.x, gridDim.x);
+}
+
+// The actor trunk of every agent of a team in one launch, grid = (image rounds, agent): agent blockIdx.y runs K9's forward pass (the
+// same function, the same bits) on the shared maps with ITS prepared weights and ITS column of the heat maps' int32 cell fields, into
+// its own [S][2704] block of a2.  Evaluation only: no activations for a backward pass.
+__global__ void __launch_bounds__(FW_NT, 4) rs_cnn_team_fwd_kernel(CnnIn32 in, const float* __restrict__ wscratch, float* __restrict__ a2,
+                                                                 float* __restrict__ p1g, uint8_t* __restrict__ amax,
+                                                                 uint16_t* __restrict__ relu_mask) {
+    // K9's argument list on purpose (the three training outputs arrive as NULL at run time, not as constants): the body was tuned
+    // as K9 -- scalar weight streams, pinned accumulators, scheduling barriers -- and with its branches folded away hipcc lays it
+    // out 6 % slower
+    in.agent = blockIdx.y;
+    cnn_fwd_rounds<6>(in, wscratch + (size_t)in.agent * WT_TOTAL(6), a2 + (size_t)in.agent * in.S * FLAT, p1g, amax, relu_mask, blockIdx.x,
+                      gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -844,6 +878,21 @@ int rs_cnn_trunk_infer(const float* maps, const int64_t* cells, const int64_t* p
                                        in, wscratch, a2, (float*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr);
     else hipLaunchKernelGGL(rs_cnn_fwd_kernel<4>, dim3(cnn_grid(rs_cnn_fwd_kernel<4>, FW_NT, fwd_lds(4), rounds)), dim3(FW_NT), fwd_lds(4), s, in,
                             wscratch, a2, (float*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_cnn_team_trunk_infer(const float* maps, const int32_t* cells, const int32_t* pcells, int32_t num_agents, int64_t num_samples,
+                            const float* wscratch, float* a2, rs_stream_t stream) {
+    if (!maps || !cells || !pcells || !wscratch || !a2 || num_agents < 1 || num_agents > RS_MAX_AGENTS || num_samples < 0)
+        return RS_ERR_INVALID_ARG;
+    if (num_samples == 0) return RS_OK;
+    const long long rounds = (num_samples + FW_IMG - 1) / FW_IMG;
+    // the whole launch is one resident wave of workgroups: the agents share what K9's grid is for one of them
+    int gx = cnn_grid(rs_cnn_team_fwd_kernel, FW_NT, fwd_lds(6), rounds * num_agents) / num_agents;
+    if (gx < 1) gx = 1;
+    CnnIn32 in{maps, cells, pcells, num_agents, 0, (long long)num_samples};
+    hipLaunchKernelGGL(rs_cnn_team_fwd_kernel, dim3(gx, num_agents), dim3(FW_NT), fwd_lds(6), (hipStream_t)stream, in, wscratch, a2,
+                       (float*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -1,0 +1,193 @@
+// rs_cnn_eval.hip -- the policy heads of a RAD-TEAM (CNN) team in the Monte-Carlo evaluation's lock-step
+// (radiation_ppo_amd/evaluate.py: run_test_environments_cnn_team), one launch for every agent: grid = (64-image tiles, agent).
+//
+// rs_cnn_team_eval_head: a2 [A][N][2704] (the team trunk's output, rs_cnn.hip) -> Linear(2704, 32) -> ReLU -> Linear(32, 16) -> ReLU ->
+// Linear(16, 8) -> log-softmax -> inverse-CDF draw -> rs_step's action rows, 8 (idle) on the lanes whose episode has ended.
+//
+// The first layer is 173 kFLOP on 10.8 KB per image and agent, the only part with weight: y1 = a2 W1^T runs on v_mfma_f32_32x32x2_f32
+// (exact f32, an fmaf chain over k).  A = W1 (row = output neuron), B = a2 (column = image); both matrices are row-major over k and
+// both operands have the lane pattern (row l & 31, k-half l >> 5), so one loading scheme serves both: a lane reads float4s along ITS
+// row.  A workgroup is four waves on the same 64 images (two 32-image B tiles share every A fragment: W1 comes from L2 once per 64
+// images); wave w owns k in [676 w, 676 w + 676) = 21 pieces of 32 floats, of which its lane halves take 16 each (64 contiguous bytes
+// per lane and operand: the two halves of a row read one 128-byte piece), and a last float4 that the lower half takes while the upper
+// feeds zeros (2704 = 8 x 338, and 338 is no multiple of 4).  The four partial sums meet in LDS and are added in wave order, then the bias: no atomics, the
+// bits of an image's result depend on neither N nor the grid.  Wave 0 then runs rs_cnn_head_kernel<8>'s arithmetic (rs_cnn_loss.hip),
+// operation for operation, one image per lane, its weights through the scalar unit.
+//
+// Not fused into the trunk on purpose: a trunk workgroup holds 3 images, so W1 (346 KB per agent) would be re-read from L2 once per 3
+// images = 115 KB per image, where the a2 round trip it would save is 21.6 KB per image.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/radsearch.h"
+
+namespace {
+
+constexpr int FLAT = 2704, H1 = 32, H2 = 16, NACT = 8;
+constexpr int EH_WAVES = 4, EH_NT = 64 * EH_WAVES;
+constexpr int EH_TILE = 64;                         // images per workgroup: two MFMA column tiles
+constexpr int EH_KW = FLAT / EH_WAVES;              // 676 k per wave
+constexpr int EH_PIECES = EH_KW / 32;               // 21 pieces of 32 floats per wave (16 per lane half), then 4 floats
+constexpr int EH_ROW = H1 + 4;                      // LDS row of an image's 32 partial sums, padded (16-byte aligned rows, banks spread)
+static_assert(FLAT % (4 * EH_WAVES) == 0 && EH_KW == 32 * EH_PIECES + 4 && EH_PIECES % 2 == 1, "21 pieces and one float4 per wave");
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef const float __attribute__((address_space(4))) * eh_cmem_t;
+__device__ __forceinline__ eh_cmem_t eh_cmem(const float* p) { return (eh_cmem_t)(uintptr_t)p; }
+
+// every agent's head pointers travel in the kernel's argument block (8 agents x 6 pointers = 384 bytes)
+struct EhNets {
+    rs_cnn_head_params head[RS_MAX_AGENTS];
+};
+
+__global__ void __launch_bounds__(EH_NT) rs_cnn_team_eval_head_kernel(EhNets nets, int A, const float* __restrict__ a2,
+                                                                      const float* __restrict__ u, const uint8_t* __restrict__ alive,
+                                                                      int8_t* __restrict__ act8, int64_t* __restrict__ act,
+                                                                      float* __restrict__ logp, float* __restrict__ y1_out, int N) {
+    __shared__ __align__(16) float part[EH_WAVES][EH_TILE][EH_ROW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int ag = blockIdx.y;
+    const rs_cnn_head_params P = nets.head[ag];
+    const int n0 = blockIdx.x * EH_TILE;
+    // rows past the last image read the last image's (their sums are dropped)
+    const int na = n0 + r < N ? n0 + r : N - 1, nb = n0 + 32 + r < N ? n0 + 32 + r : N - 1;
+    const float* wp = P.w1 + (size_t)r * FLAT + wave * EH_KW + 16 * h;
+    const float* xa = a2 + ((size_t)ag * N + na) * FLAT + wave * EH_KW + 16 * h;
+    const float* xb = a2 + ((size_t)ag * N + nb) * FLAT + wave * EH_KW + 16 * h;
+    v16f acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
+    auto step = [&](const float4& w, const float4& a, const float4& b) {
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, a.x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, b.x, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, a.y, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, b.y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, a.z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, b.z, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, a.w, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, b.w, acc1, 0, 0, 0);
+    };
+    // a piece = 32 floats of the wave's k range: 16 per lane half, four float4s per operand and lane (64 contiguous bytes of its row).
+    // Two pieces live in registers: piece g + 2 is requested as soon as piece g has been issued to the matrix cores, so ~12 KB per
+    // wave are in flight under the 32 MFMAs (2048 cycles) of a piece -- one request per trip left the kernel waiting on HBM latency
+    struct Piece { float4 w[4], a[4], b[4]; };
+    auto fetch = [&](Piece& q, int g) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            q.w[i] = *reinterpret_cast<const float4*>(wp + 32 * g + 4 * i);
+            q.a[i] = *reinterpret_cast<const float4*>(xa + 32 * g + 4 * i);
+            q.b[i] = *reinterpret_cast<const float4*>(xb + 32 * g + 4 * i);
+        }
+    };
+    auto consume = [&](const Piece& q) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) step(q.w[i], q.a[i], q.b[i]);
+    };
+    Piece p0, p1;
+    fetch(p0, 0);
+    fetch(p1, 1);
+#pragma unroll 1
+    for (int g = 0; g < EH_PIECES - 1; g += 2) {                    // pieces 0 .. 19 in pairs, piece 20 behind the loop
+        consume(p0);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(p0, g + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        consume(p1);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(p1, g + 3 < EH_PIECES ? g + 3 : EH_PIECES - 1);       // (the last trip re-requests piece 20; it is dropped)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    consume(p0);
+    {   // the range's last four floats, 672 .. 675: on the lower half; the upper half re-reads floats of piece 20 and feeds zeros
+        const int o = 32 * EH_PIECES - 32 * h;
+        float4 w = *reinterpret_cast<const float4*>(wp + o);
+        float4 a = *reinterpret_cast<const float4*>(xa + o);
+        float4 b = *reinterpret_cast<const float4*>(xb + o);
+        if (h) { w = make_float4(0.f, 0.f, 0.f, 0.f); a = w; b = w; }
+        step(w, a, b);
+    }
+    // C layout: register i of lane (r, h) is neuron (i & 3) + 8 (i >> 2) + 4 h of image r
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        *reinterpret_cast<float4*>(&part[wave][r][8 * g + 4 * h]) = make_float4(acc0[4 * g], acc0[4 * g + 1], acc0[4 * g + 2], acc0[4 * g + 3]);
+        *reinterpret_cast<float4*>(&part[wave][32 + r][8 * g + 4 * h]) = make_float4(acc1[4 * g], acc1[4 * g + 1], acc1[4 * g + 2], acc1[4 * g + 3]);
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // ---- one image per lane: the four k-quarters in wave order, then the bias; behind it rs_cnn_head_kernel<8>
+    const int n = n0 + lane;
+    const bool live = n < N;
+    const int nc = live ? n : N - 1;
+    const eh_cmem_t b1 = eh_cmem(P.b1), w2 = eh_cmem(P.w2), b2 = eh_cmem(P.b2), w3 = eh_cmem(P.w3), b3 = eh_cmem(P.b3);
+    float h1[H1];
+#pragma unroll
+    for (int k = 0; k < H1; k += 4) {
+        float4 s = *reinterpret_cast<const float4*>(&part[0][lane][k]);
+#pragma unroll
+        for (int w = 1; w < EH_WAVES; ++w) {
+            const float4 q = *reinterpret_cast<const float4*>(&part[w][lane][k]);
+            s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
+        }
+        s.x += b1[k]; s.y += b1[k + 1]; s.z += b1[k + 2]; s.w += b1[k + 3];
+        if (y1_out && live) *reinterpret_cast<float4*>(y1_out + ((size_t)ag * N + n) * H1 + k) = s;
+        h1[k] = fmaxf(s.x, 0.0f); h1[k + 1] = fmaxf(s.y, 0.0f); h1[k + 2] = fmaxf(s.z, 0.0f); h1[k + 3] = fmaxf(s.w, 0.0f);
+    }
+    float h2[H2];
+#pragma unroll
+    for (int o = 0; o < H2; ++o) {
+        float s = b2[o];
+#pragma unroll
+        for (int k = 0; k < H1; ++k) s = __builtin_fmaf(w2[o * H1 + k], h1[k], s);
+        h2[o] = fmaxf(s, 0.0f);
+    }
+    float lg[NACT];
+#pragma unroll
+    for (int o = 0; o < NACT; ++o) {
+        float s = b3[o];
+#pragma unroll
+        for (int k = 0; k < H2; ++k) s = __builtin_fmaf(w3[o * H2 + k], h2[k], s);
+        lg[o] = s;
+    }
+    float mx = lg[0];
+#pragma unroll
+    for (int o = 1; o < NACT; ++o) mx = fmaxf(mx, lg[o]);
+    float se = 0.0f;
+#pragma unroll
+    for (int o = 0; o < NACT; ++o) se += expf(lg[o] - mx);
+    const float lse = logf(se);
+    const float uu = u[(size_t)nc * A + ag];
+    float cdf = 0.0f, lp_sel = (lg[0] - mx) - lse;
+    int a = 0;
+#pragma unroll
+    for (int o = 0; o < NACT; ++o) {
+        const float lp = (lg[o] - mx) - lse;
+        cdf += expf(lp);
+        if (o < NACT - 1 && cdf <= uu) a = o + 1;
+    }
+#pragma unroll
+    for (int o = 1; o < NACT; ++o) if (a == o) lp_sel = (lg[o] - mx) - lse;
+    if (live) {
+        if (act) act[(size_t)ag * N + n] = a;
+        if (logp) logp[(size_t)ag * N + n] = lp_sel;
+        act8[(size_t)n * A + ag] = alive[n] != 0 ? (int8_t)a : (int8_t)8;     // finished episodes idle in place
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int rs_cnn_team_eval_head(const rs_cnn_head_params* heads, int32_t num_agents, const float* a2, const float* u, const uint8_t* alive,
+                          int8_t* act8, int64_t* act, float* logp, float* y1_out, int32_t num_envs, rs_stream_t stream) {
+    if (!heads || !a2 || !u || !alive || !act8 || num_agents < 1 || num_agents > RS_MAX_AGENTS || num_envs < 1) return RS_ERR_INVALID_ARG;
+    for (int a = 0; a < num_agents; ++a)
+        if (!heads[a].w1 || !heads[a].b1 || !heads[a].w2 || !heads[a].b2 || !heads[a].w3 || !heads[a].b3) return RS_ERR_INVALID_ARG;
+    EhNets nets;
+    for (int a = 0; a < RS_MAX_AGENTS; ++a) nets.head[a] = heads[a < num_agents ? a : 0];     // the slots behind the team repeat agent 0 (never read)
+    hipLaunchKernelGGL(rs_cnn_team_eval_head_kernel, dim3((num_envs + EH_TILE - 1) / EH_TILE, num_agents), dim3(EH_NT), 0,
+                       static_cast<hipStream_t>(stream), nets, (int)num_agents, a2, u, alive, act8, act, logp, y1_out, (int)num_envs);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+}  // extern "C"

@@ -10,7 +10,8 @@ with its own Philox stream -- and the same per-environment records come out (`Mo
 Saved sets use the reference's layout `env_dict["env_<i>"] = (src_coords, det_coords, intensity, bkg[, obstacles])`
 (algos/test_environment/eval/test_env_gen.py:13-24).  `sample_test_environments` draws such a set from the
 environment's own spawn rules; the reference's own pickled sets are read by radiation_ppo_amd.testsets WITHOUT unpickling.
-`run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `run_test_environments_team` for feed-forward agents and
+`run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `run_test_environments_cnn_team` its HIP lock-step for teams
+of up to 8 on 27 x 27 maps (csrc/rs_cnn.hip, csrc/rs_cnn_eval.hip), `run_test_environments_team` for feed-forward agents and
 teams of up to 8, `run_test_environments_rnn` for the recurrent agent and `run_test_environments_rnn_team` for recurrent teams of up to 8 with
 their lock-steps in HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip), `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
@@ -592,6 +593,113 @@ def run_test_environments_cnn(agents: Dict[int, Any], env_sets: Dict[str, tuple]
 
 
 @torch.no_grad()
+def run_test_environments_cnn_team(agents: Dict[int, Any], env_sets: Dict[str, tuple], montecarlo_runs: int = 100,
+                                   steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
+                                   enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0",
+                                   use_predictor: bool = True, return_actions: bool = False, fused: bool = True):
+    """run_test_environments_cnn for RAD-TEAM teams of 1..8 agents on 27 x 27 maps (enforce_grid_boundaries=True, the size every CLI of
+    the reference trains with) with its lock-step in HIP: the same arguments, the same records.  agents: {id: CNNAgentPPO}, ids 0..A-1.
+    It needs a cuda device and the HIP predictor bank; another map side, another device or other ids raise ValueError -- those
+    configurations stay with run_test_environments_cnn.
+
+    fused=True: a lock-step is rs_action_uniforms, the PFGRU step of every owner (and the bank's call counter), rs_maps_update,
+    rs_maps_stack, rs_cnn_team_trunk_infer (every agent's actor trunk, straight from the heat maps' int32 cell fields),
+    rs_cnn_team_eval_head (Linear(2704, 32) on the matrix cores, heads, draw, idle rows for finished lanes), rs_step and
+    rs_eval_post_step -- nothing per agent, on one stream; the agents' convolution weights are re-arranged once before the loop and the
+    host reads the finished-lane count once every 16 lock-steps.  The trunk's output travels through ONE scratch tensor a2 [A, N, 2704],
+    allocated once: A * N * 10 816 bytes, about 8.7 GB at 100 000 lanes and 8 agents.
+    fused=False: the same loop and stopping rule composed from what the collector uses -- per agent rs_cnn_trunk_infer,
+    torch.nn.functional.linear, rs_cnn_head and the idle rule, shared torch bookkeeping and the observation copy: the A/B baseline.
+
+    Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log of rs_step's action rows
+    (8 where a lane had finished)."""
+    from .maps import HeatMaps
+    from .pfgru import PredictorBank
+    A = len(agents)
+    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
+        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}; run_test_environments_cnn takes any ids")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("run_test_environments_cnn_team needs a cuda device; run_test_environments_cnn runs elsewhere")
+    R, L = montecarlo_runs, steps_per_episode
+    N = len(env_sets) * R
+    lib = _lib.load()
+    vec, keys, saved, obs, _ = _open(env_sets, R, A, obstruction_count, enforce_grid_boundaries, seed, device, welford=False)
+    maps = HeatMaps(vec, L, enforce_boundaries=bool(enforce_grid_boundaries))
+    if tuple(maps.map_dimensions) != (27, 27) or any(tuple(agents[a].map_dim) != (27, 27) for a in range(A)):
+        raise ValueError(f"run_test_environments_cnn_team serves 27 x 27 heat maps, this configuration has {tuple(maps.map_dimensions)}; "
+                         "use run_test_environments_cnn")
+    bank = None
+    if use_predictor:
+        bank = PredictorBank(N, A, seed=seed, device=dev)
+        if bank.impl != "hip":
+            raise ValueError("run_test_environments_cnn_team needs PredictorBank(impl='hip'); use run_test_environments_cnn")
+        for a in range(A):
+            if getattr(agents[a], "model", None) is not None:         # the agent's own (saved) predictor weights
+                bank.load_state_dict(a, agents[a].model.state_dict())
+        bank.reset()
+    alive, ep_len, ep_ret, success = _lane_records(N, dev)
+    u = torch.empty(N, A, dtype=torch.float32, device=dev)
+    # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads
+    log = torch.full((L, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
+    act8 = None if return_actions else torch.empty(N, A, dtype=torch.int8, device=dev)
+    use_team = team_mode != "individual"
+    p = lambda t: t.data_ptr()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    actors = [agents[a].pi.actor for a in range(A)]
+    scratch = lib.rs_cnn_trunk_scratch_floats(6)
+    wt = torch.empty(A, scratch, dtype=torch.float32, device=dev)     # every agent's convolution weights in K9's layout, once per run
+    for a, m in enumerate(actors):
+        _lib.check(lib.rs_cnn_trunk_prepare(6, p(m[0].weight), p(m[0].bias), p(m[3].weight), p(m[3].bias), p(wt[a]), st), "rs_cnn_trunk_prepare")
+    cells, pcells = maps.field("cell"), maps.field("pred_cell")       # views of the heat maps' own state: [N, A] int32, -1 = none
+    assert cells.dtype == torch.int32 and pcells.dtype == torch.int32 and cells.shape == (N, A) and pcells.shape == (N, A)
+    if fused:
+        a2 = torch.empty(A, N, 2704, dtype=torch.float32, device=dev)
+        heads = (_lib.RsCnnHeadParams * A)(*[_lib.RsCnnHeadParams(p(m[6].weight), p(m[6].bias), p(m[8].weight), p(m[8].bias), p(m[10].weight),
+                                                                   p(m[10].bias)) for m in actors])
+        finished = torch.zeros(1, dtype=torch.int32, device=dev)
+        alive8, success8 = alive.view(torch.uint8), success.view(torch.uint8)
+        state = _lib.RsEvalState(N, A, 1 if use_team else 0, p(vec.obs), p(vec.reward), p(vec.team), p(vec.done), p(obs), None, None, None,
+                                 None, p(alive8), p(success8), p(ep_len), p(ep_ret), p(finished))
+    else:
+        a2 = torch.empty(N, 2704, dtype=torch.float32, device=dev)
+        k_act = torch.empty(A, N, dtype=torch.int64, device=dev)
+    it = 0
+    while it < L:
+        if it and it % 16 == 0:                                   # one host read per 16 lock-steps
+            if (int(finished.item()) if fused else N - int(alive.sum().item())) == N:
+                break
+        a8 = log[it] if return_actions else act8
+        vec.action_uniforms(u)
+        pred = None
+        if bank is not None:
+            pred = bank.predict_kernel(obs)                       # bank.predict without its copy of the prediction
+            bank.calls.add_(1)
+        maps.update(obs, pred=pred)
+        shared = maps.shared_maps()
+        if fused:
+            _lib.check(lib.rs_cnn_team_trunk_infer(p(shared), p(cells), p(pcells), A, N, p(wt), p(a2), st), "rs_cnn_team_trunk_infer")
+            _lib.check(lib.rs_cnn_team_eval_head(heads, A, p(a2), p(u), p(alive8), p(a8), None, None, None, N, st), "rs_cnn_team_eval_head")
+            vec.step(a8)
+            _lib.check(lib.rs_eval_post_step(C.byref(state), st), "rs_eval_post_step")
+        else:
+            cl, pl = cells.long(), pcells.long()
+            for a, m in enumerate(actors):
+                _lib.check(lib.rs_cnn_trunk_infer(p(shared), p(cl), p(pl), A, a, N, p(wt[a]), p(a2), st), "rs_cnn_trunk_infer")
+                y1 = torch.nn.functional.linear(a2, m[6].weight, m[6].bias)
+                _lib.check(lib.rs_cnn_head(p(y1), p(m[8].weight), p(m[8].bias), p(m[10].weight), p(m[10].bias), 8, p(u) + 4 * a, A, p(k_act[a]),
+                                           None, None, 1, None, 1, 0, None, N, st), "rs_cnn_head")
+                a8[:, a] = torch.where(alive, k_act[a], torch.full_like(k_act[a], 8)).to(torch.int8)    # finished episodes idle in place
+            obs_n, rew, team, done, _ = vec.step(a8)
+            _book_step(alive, ep_len, ep_ret, success, team if use_team else rew[:, 0], done.bool().any(dim=1))
+            obs.copy_(obs_n)
+        it += 1
+    # finished episodes idle on purpose; stacked agents may "stall"
+    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=log[:it] if return_actions else None,
+                  ignore_flags=_lib.ENVERR_IDLE_STALL)
+
+
+@torch.no_grad()
 def run_test_environments_team(agents: Dict[int, VecAgentPPO], env_sets: Dict[str, tuple], montecarlo_runs: int = 100,
                                steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
                                enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0", return_actions: bool = False,
@@ -783,7 +891,11 @@ class evaluate_PPO:
                 ag.model = PFGRUCell().to(dev)
                 ag.load(agent_dir(i))                                   # CNNBase.load (RADTEAM_core.py:1945-1953)
                 agents[i] = ag
-            self.results, self.summary = run_test_environments_cnn(agents, sets, team_mode=kw.get("team_mode", "individual"), **common)
+            # the HIP lock-step where it applies (27 x 27 maps, ids 0..A-1, a cuda device); elsewhere the composed runner
+            team = (bool(kw.get("enforce_boundaries", True)) and torch.device(dev).type == "cuda" and 1 <= A <= _lib.RS_MAX_AGENTS
+                    and all(tuple(ag.map_dim) == (27, 27) for ag in agents.values()))
+            runner = run_test_environments_cnn_team if team else run_test_environments_cnn
+            self.results, self.summary = runner(agents, sets, team_mode=kw.get("team_mode", "individual"), **common)
         elif arch == "rnn":
             from .rada2c import RNNAgentPPO
 

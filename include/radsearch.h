@@ -718,7 +718,10 @@ int rs_eval_post_step(const rs_eval_state* s, rs_stream_t stream);
  * keeps the reference's hidden-state lifetime (`hiddens` is created once per EpisodeRunner.run, :357), runs_per_lane = 1 on N = E R
  * lanes gives every run a lane of its own.  One lock-step is rs_action_uniforms, rs_pfgru_step (mask = active), rs_rnn_policy_step_rows
  * or rs_rnn_sized_step (mask = active, act8 = the step's action row), rs_step, rs_rnn_eval_post_step and, when runs_per_lane > 1,
- * rs_refresh(mask = again) and rs_rnn_eval_post_refresh, all on one stream (radiation_ppo_amd/evaluate.py: run_test_environments_rnn).
+ * rs_refresh(mask = again) and rs_rnn_eval_post_refresh, all on one stream.
+ * This section is the A = 1 case of the team section below it: rs_rnn_eval_state is rs_rnn_team_eval_state without the field A, and the
+ * two entries widen it on the host and launch the team's kernels, with the team entries' refusals.  The package's own runners
+ * (radiation_ppo_amd/evaluate.py: run_test_environments_rnn, a front to run_test_environments_rnn_team) use the team entries.
  *
  * rs_rnn_eval_post_step: one launch after rs_step, one thread per lane, in this order (a = active[n] on entry):
  *   where a: ret += env_reward (float32), steps += 1, pf_calls += 1; found = a and env_done, over = found or (a and steps ==

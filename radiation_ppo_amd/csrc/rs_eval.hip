@@ -11,14 +11,15 @@
 // terminal rule, the Welford update (rs_welford.hpp) on the lanes still running, the new current observation, and a
 // monotonic count of finished lanes that the host reads once every few lock-steps instead of reducing `alive` every step.
 //
-// rs_rnn_eval_post_step / rs_rnn_eval_post_refresh: the same place in the lock-step of the recurrent agent (RAD-A2C;
-// radiation_ppo_amd/evaluate.py: run_test_environments_rnn), where a lane works through `runs_per_lane` consecutive runs with its
-// hidden states carried (evaluate.py:357, :455-470): returns, step counts, the per-run records, the Welford update and restart, the
-// next observation raw and standardised, the predictor bank's call counter and the finished-lane count, one thread per lane.
+// rs_rnn_team_eval_post_step / rs_rnn_team_eval_post_refresh: the same place in the lock-step of RAD-A2C, a team of A >= 1 recurrent
+// agents per lane (radiation_ppo_amd/evaluate.py: run_test_environments_rnn_team), where a lane works through `runs_per_lane`
+// consecutive runs with its hidden states carried (evaluate.py:353, :455-470): agent 0's return, step counts, the per-run records under
+// the any-agent terminal rule, every agent's Welford update and restart, the next observation raw and standardised, the predictor
+// bank's call counter and the finished-lane count, one thread per lane.  The team's policy round, rs_rnn_team_eval_step, lives beside
+// K14 in rs_rnn_policy.hip.
 //
-// rs_rnn_team_eval_post_step / rs_rnn_team_eval_post_refresh: the same for a team of A recurrent agents per lane
-// (radiation_ppo_amd/evaluate.py: run_test_environments_rnn_team): every agent's own statistics and rows, the any-agent terminal rule,
-// agent 0's reward.  The team's policy round, rs_rnn_team_eval_step, lives beside K14 in rs_rnn_policy.hip.
+// rs_rnn_eval_post_step / rs_rnn_eval_post_refresh: the A = 1 case under its own struct (no field A); the host widens the struct and
+// launches the team kernels.
 //
 // The float64 arithmetic is the reference's, operation by operation (the build disables FMA contraction): the results equal
 // DeviceWelford's and the torch composition's bit for bit.
@@ -119,76 +120,10 @@ __global__ void __launch_bounds__(256) rs_eval_post_step_kernel(rs_eval_state s)
     if ((threadIdx.x & 63) == 0 && b != 0ull) atomicAdd(s.finished, (int)__popcll(b));
 }
 
-// ---- RAD-A2C (one recurrent agent per lane, `runs_per_lane` consecutive runs): the state machine between rs_step and the next
-// PFGRU / policy round.  cur_obs <- env_obs and x <- its form with the reading standardised by the lane's statistics
-__device__ __forceinline__ void re_rows(const rs_rnn_eval_state& s, int n, const float* __restrict__ src) {
-    float* cur = s.cur_obs + (size_t)n * RS_OBS_DIM;
-    float* x = s.x + (size_t)n * RS_OBS_DIM;
-#pragma unroll
-    for (int k = 0; k < RS_OBS_DIM; ++k) cur[k] = src[k];
-#pragma unroll
-    for (int k = 1; k < RS_OBS_DIM; ++k) x[k] = src[k];
-    x[0] = rs_welford_standardized(s.w_mean, s.w_std, n, src[0]);
-}
-
-__global__ void __launch_bounds__(256) rs_rnn_eval_post_step_kernel(rs_rnn_eval_state s) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    bool ended = false;
-    if (n < s.N) {
-        const int R = s.runs_per_lane;
-        const bool a = s.active[n] != 0;
-        int run = s.run[n], steps = s.steps[n];
-        float ret = s.ret[n];
-        if (a) {
-            ret += s.env_reward[n];
-            steps += 1;
-            if (s.pf_calls) s.pf_calls[n] += 1;
-        }
-        const bool found = a && s.env_done[n] != 0;
-        const bool over = found || (a && steps == s.steps_per_episode);
-        const float* src = s.env_obs + (size_t)n * RS_OBS_DIM;
-        if (a) rs_welford_push(s.w_count, s.w_mean, s.w_sq, s.w_std, n, (double)src[0]);      // before the episode-over test (evaluate.py:392-397)
-        if (over) {
-            if (run >= 0 && run < R) {                                  // an active lane has run < R; never write past the lane's records
-                const size_t slot = (size_t)n * R + run;
-                s.rec_len[slot] = steps;
-                s.rec_ret[slot] = ret;
-                s.rec_suc[slot] = found ? 1 : 0;
-            }
-            run += 1;
-            steps = 0;
-            ret = 0.0f;
-        }
-        s.again[n] = (over && run < R) ? 1 : 0;
-        if (over && run == R) {
-            s.active[n] = 0;
-            if (s.idle_act8) s.idle_act8[n] = 8;
-            ended = true;
-        }
-        if (a) {
-            s.run[n] = run;
-            s.steps[n] = steps;
-            s.ret[n] = ret;
-        }
-        re_rows(s, n, src);
-    }
-    // one ballot per wave, one atomic by one of its lanes (every lane of the wave is here: nothing returned early)
-    const unsigned long long b = __ballot(ended);
-    if ((threadIdx.x & 63) == 0 && b != 0ull) atomicAdd(s.finished, (int)__popcll(b));
-}
-
-// after rs_refresh(mask = again): the lanes that begin their next run restart their statistics on the refreshed reading
-// (evaluate.py:455-468: reset, then the first update, which sets the mean only); hidden states are not touched (:357)
-__global__ void __launch_bounds__(256) rs_rnn_eval_post_refresh_kernel(rs_rnn_eval_state s) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= s.N || s.again[n] == 0) return;
-    const float* src = s.env_obs + (size_t)n * RS_OBS_DIM;
-    rs_welford_restart(s.w_count, s.w_mean, s.w_sq, s.w_std, n, (double)src[0]);
-    re_rows(s, n, src);
-}
-
-// ---- RAD-A2C teams (A recurrent agents per lane): rs_rnn_eval_post_step / _post_refresh with every agent's own statistics and rows,
-// the any-agent terminal rule and agent 0's reward (evaluate.py:395-397, :411-423, :441-444)
+// ---- RAD-A2C (A recurrent agents per lane, `runs_per_lane` consecutive runs): the state machine between rs_step and the next PFGRU /
+// policy round, with every agent's own statistics and rows, the any-agent terminal rule and agent 0's reward (evaluate.py:395-397,
+// :411-423, :441-444).  The one-agent exports launch these kernels with A = 1.
+// cur_obs <- env_obs and x <- its form with the reading standardised by the (lane, agent)'s statistics
 __device__ __forceinline__ void rte_rows(const rs_rnn_team_eval_state& s, size_t i) {
     const float* src = s.env_obs + i * RS_OBS_DIM;
     float* cur = s.cur_obs + i * RS_OBS_DIM;
@@ -298,24 +233,6 @@ int rs_eval_post_step(const rs_eval_state* s, rs_stream_t stream) {
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 
-static bool rnn_eval_ok(const rs_rnn_eval_state* s) {
-    return s && s->N >= 1 && s->runs_per_lane >= 1 && s->steps_per_episode >= 1 && s->env_obs && s->env_reward && s->env_done && s->cur_obs &&
-           s->x && s->w_count && s->w_mean && s->w_sq && s->w_std && s->active && s->again && s->run && s->steps && s->ret && s->rec_len &&
-           s->rec_ret && s->rec_suc && s->finished;
-}
-
-int rs_rnn_eval_post_step(const rs_rnn_eval_state* s, rs_stream_t stream) {
-    if (!rnn_eval_ok(s)) return RS_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(rs_rnn_eval_post_step_kernel, dim3((s->N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *s);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
-}
-
-int rs_rnn_eval_post_refresh(const rs_rnn_eval_state* s, rs_stream_t stream) {
-    if (!rnn_eval_ok(s)) return RS_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(rs_rnn_eval_post_refresh_kernel, dim3((s->N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *s);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
-}
-
 static bool rnn_team_eval_ok(const rs_rnn_team_eval_state* s) {
     return s && s->N >= 1 && s->A >= 1 && s->A <= RS_MAX_AGENTS && s->runs_per_lane >= 1 && s->steps_per_episode >= 1 && s->env_obs &&
            s->env_reward && s->env_done && s->cur_obs && s->x && s->w_count && s->w_mean && s->w_sq && s->w_std && s->active && s->again &&
@@ -332,6 +249,26 @@ int rs_rnn_team_eval_post_refresh(const rs_rnn_team_eval_state* s, rs_stream_t s
     if (!rnn_team_eval_ok(s)) return RS_ERR_INVALID_ARG;
     hipLaunchKernelGGL(rs_rnn_team_post_refresh_kernel, dim3((s->N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *s);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+// the one-agent entries: rs_rnn_eval_state is rs_rnn_team_eval_state without A, so the struct is widened to a team of one and takes
+// the team entry's refusals and kernels
+static rs_rnn_team_eval_state team_of_one(const rs_rnn_eval_state& s) {
+    return rs_rnn_team_eval_state{s.N, 1, s.runs_per_lane, s.steps_per_episode, s.env_obs, s.env_reward, s.env_done, s.cur_obs, s.x,
+                                  s.w_count, s.w_mean, s.w_sq, s.w_std, s.active, s.again, s.run, s.steps, s.ret, s.rec_len, s.rec_ret,
+                                  s.rec_suc, s.pf_calls, s.idle_act8, s.finished};
+}
+
+int rs_rnn_eval_post_step(const rs_rnn_eval_state* s, rs_stream_t stream) {
+    if (!s) return RS_ERR_INVALID_ARG;
+    const rs_rnn_team_eval_state t = team_of_one(*s);
+    return rs_rnn_team_eval_post_step(&t, stream);
+}
+
+int rs_rnn_eval_post_refresh(const rs_rnn_eval_state* s, rs_stream_t stream) {
+    if (!s) return RS_ERR_INVALID_ARG;
+    const rs_rnn_team_eval_state t = team_of_one(*s);
+    return rs_rnn_team_eval_post_refresh(&t, stream);
 }
 
 }  // extern "C"

@@ -12,13 +12,15 @@ Saved sets use the reference's layout `env_dict["env_<i>"] = (src_coords, det_co
 environment's own spawn rules; the reference's own pickled sets are read by radiation_ppo_amd.testsets WITHOUT unpickling.
 `run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `run_test_environments_cnn_team` its HIP lock-step for teams
 of up to 8 on 27 x 27 maps (csrc/rs_cnn.hip, csrc/rs_cnn_eval.hip), `run_test_environments_team` for feed-forward agents and
-teams of up to 8, `run_test_environments_rnn` for the recurrent agent and `run_test_environments_rnn_team` for recurrent teams of up to 8 with
-their lock-steps in HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip), `summarize` the result statistics
+teams of up to 8, `run_test_environments_rnn_team` for recurrent (RAD-A2C) teams of 1 to 8 -- it holds the recurrent lock-step, fused in
+HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip) and composed; `run_test_environments_rnn` is its front for one agent, and
+`run_test_environments` sends a recurrent agent there --, `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
 """
 import ctypes as C
 import os
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Any, Dict, List
 
 import numpy as np
@@ -130,22 +132,11 @@ def _has_pfgru_kernel(ac, dev) -> bool:
     return ac.fused_pfgru or (ac.sized_pfgru and dev.type == "cuda")
 
 
-def recurrent_start(ac, N, seed, dev, impl):
-    """`hiddens` of N lanes of the recurrent agent `ac` as an evaluation creates them, once (evaluate.py:357): a one-agent PredictorBank
-    around the agent's own PFGRU with its particle sets drawn, and the GRU's initial state from the hash of the bank's lane keys.  The
-    composed and the fused runners start from this one definition, so their initial states cannot drift apart.  Returns (bank, hid)."""
-    from .pfgru import PredictorBank, hash_uniform
-    bank = PredictorBank(N, 1, hidden_size=ac.rec, seed=seed, carry_hidden=True, device=dev, impl=impl)
-    bank.cells[0] = ac.model
-    bank.reset()
-    gk = (bank._base[0] * 1000003 + 5).view(-1, 1) * 1048583 + torch.arange(ac.hid, dtype=torch.int64, device=dev).view(1, -1)
-    return bank, ac.gru_h0(hash_uniform(gk)).contiguous()
-
-
 def recurrent_team_start(agents, N, seed, dev, impl):
-    """recurrent_start for a team {id: RNNAgentPPO} of equal widths: ONE PredictorBank of A owners around the agents' own PFGRUs, its
-    particle sets drawn once, and every agent's GRU state from the hash of ITS row of the bank's lane keys (every agent has its own
-    `hiddens` entry, evaluate.py:353).  Returns (bank, hid [A, N, hid]); with one agent hid[0] is recurrent_start's."""
+    """`hiddens` of N lanes of a team {id: RNNAgentPPO} of equal widths as an evaluation creates them, once (evaluate.py:353, :357):
+    ONE PredictorBank of A owners around the agents' own PFGRUs with its particle sets drawn, and every agent's GRU state from the hash
+    of ITS row of the bank's lane keys (every agent has its own `hiddens` entry).  The composed and the fused runners start from this one
+    definition, so their initial states cannot drift apart.  Returns (bank, hid [A, N, hid])."""
     from .pfgru import PredictorBank, hash_uniform
     A = len(agents)
     ac0 = agents[0].agent
@@ -156,6 +147,12 @@ def recurrent_team_start(agents, N, seed, dev, impl):
     unit = torch.arange(ac0.hid, dtype=torch.int64, device=dev).view(1, -1)
     hid = torch.stack([agents[a].agent.gru_h0(hash_uniform((bank._base[a] * 1000003 + 5).view(-1, 1) * 1048583 + unit)) for a in range(A)])
     return bank, hid.contiguous()
+
+
+def recurrent_start(ac, N, seed, dev, impl):
+    """recurrent_team_start for the one actor-critic `ac` (an RNNModelActorCritic, not its RNNAgentPPO).  Returns (bank, hid [N, hid])."""
+    bank, hid = recurrent_team_start({0: SimpleNamespace(agent=ac)}, N, seed, dev, impl)
+    return bank, hid[0]
 
 
 def _lane_records(N, dev):
@@ -196,15 +193,19 @@ def run_test_environments(agent: VecAgentPPO, env_sets: Dict[str, tuple], montec
     """EpisodeRunner.run for every saved environment at once.  Returns (List[MonteCarloResults] in set order, summary
     dict with the statistics `evaluate.py:776-828` prints); with return_actions also the [steps, E*R] action log.
 
-    carry_hidden_across_runs (recurrent policies only): the reference creates `hiddens` ONCE per EpisodeRunner.run
-    (evaluate.py:357) and between Monte-Carlo runs resets only the statistics buffer (:455-470), so run k + 1 of an
-    environment starts from the GRU / PFGRU state run k ended in.  True reproduces that (one lane per saved environment, its
-    runs one after the other: `_run_sequential`); False gives every (environment, run) pair its own lane and a fresh hidden
-    state -- R times fewer lock-steps, a deviation from the reference for 'rnn' policies (none for 'ff': no hidden state).
-    `evaluate_PPO` uses True."""
-    if carry_hidden_across_runs and hasattr(agent.agent, "gru_cell"):
-        return _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruction_count, enforce_grid_boundaries, seed,
-                               device, falloff, return_actions)
+    A recurrent agent (RAD-A2C) goes to run_test_environments_rnn(fused=False), the composed lock-step of the team runner with one
+    agent, and carry_hidden_across_runs is that runner's: the reference creates `hiddens` ONCE per EpisodeRunner.run (evaluate.py:357)
+    and between Monte-Carlo runs resets only the statistics buffer (:455-470), so run k + 1 of an environment starts from the GRU /
+    PFGRU state run k ended in.  True reproduces that (one lane per saved environment, its runs one after the other); False gives
+    every (environment, run) pair its own lane and a fresh hidden state -- R times fewer lock-steps, a deviation from the reference.
+    `evaluate_PPO` uses True.  With return_actions the log of a recurrent agent is that runner's: int8 [lock-steps run, lanes], the
+    action rows the env received, 8 (idle) wherever a lane had no run going.  A feed-forward policy has no hidden state, the flag means
+    nothing to it, and its log is int64 and keeps the unused draws of finished lanes."""
+    if hasattr(agent.agent, "gru_cell"):
+        return run_test_environments_rnn(agent, env_sets, montecarlo_runs=montecarlo_runs, steps_per_episode=steps_per_episode,
+                                         obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries, seed=seed,
+                                         device=device, return_actions=return_actions, falloff=falloff,
+                                         carry_hidden_across_runs=carry_hidden_across_runs, fused=False)
     R, L = montecarlo_runs, steps_per_episode
     N = len(env_sets) * R
     dev = torch.device(device)
@@ -214,23 +215,11 @@ def run_test_environments(agent: VecAgentPPO, env_sets: Dict[str, tuple], montec
     u = torch.empty(N, 1, dtype=torch.float32, device=dev)
     act8 = torch.empty(N, 1, dtype=torch.int8, device=dev)
     log = []
-    recurrent = hasattr(ac, "gru_cell")                           # RAD-A2C: hidden = ac.reset_hidden() per episode (evaluate.py:357-360)
-    if recurrent:
-        bank, hid = recurrent_start(ac, N, seed, dev, "hip" if _has_pfgru_kernel(ac, dev) else "torch")
-        fused = _has_policy_kernel(ac, dev) and hasattr(agent, "policy_step_hip")
     for _ in range(L):
         x = obs.clone()
         stat.standardize(obs[..., 0], out=x[..., 0])
         vec.action_uniforms(u)
-        if recurrent and fused:
-            a = torch.empty(N, dtype=torch.int64, device=dev)             # K14 (or the sized step): GRU cell + heads + draw in one launch
-            agent.policy_step_hip(x[:, 0].contiguous(), bank.predict(x)[:, 0].contiguous(), hid, u=u[:, 0].contiguous(), h_out=hid, act=a)
-        elif recurrent:
-            logits, _, hid = ac.policy_step(x[:, 0], bank.predict(x)[:, 0], hid)
-            cdf = torch.cumsum(torch.softmax(logits, dim=-1), dim=-1)
-            a = (cdf[:, :-1] <= u[:, 0].unsqueeze(-1)).sum(dim=-1)
-        else:
-            a, _, _ = ac.act(x[:, 0], u[:, 0])                    # ac.step: sample from the policy (evaluate.py:373-383)
+        a, _, _ = ac.act(x[:, 0], u[:, 0])                        # ac.step: sample from the policy (evaluate.py:373-383)
         act8[:, 0] = torch.where(alive, a, torch.full_like(a, 8)).to(torch.int8)      # finished episodes idle in place
         if return_actions:
             log.append(a.clone())
@@ -243,159 +232,31 @@ def run_test_environments(agent: VecAgentPPO, env_sets: Dict[str, tuple], montec
     return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=torch.stack(log) if return_actions else None)
 
 
-@torch.no_grad()
-def _run_sequential(agent, env_sets, montecarlo_runs, steps_per_episode, obstruction_count, enforce_grid_boundaries, seed, device, falloff,
-                    return_actions=False):
-    """EpisodeRunner.run (evaluate.py:333-476) with the reference's hidden-state lifetime: one lane per saved environment, its
-    Monte-Carlo runs in sequence.  When a run ends (source found or steps_per_episode reached) the lane's env is refreshed
-    (:455), its statistics buffer restarts on the fresh observation (:462-468) -- and the GRU state and the PFGRU's particle
-    set are left as the finished run left them (`hiddens` is assigned once, :357).  With return_actions the third result is the
-    [lock-steps, E] action log with -1 where a lane had finished all its runs."""
-    E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
-    dev = torch.device(device)
-    ac = agent.agent
-    vec, keys, saved, obs, stat = _open(env_sets, 1, 1, obstruction_count, enforce_grid_boundaries, seed, device, falloff=falloff)
-    bank, hid = recurrent_start(ac, E, seed, dev, "hip" if _has_pfgru_kernel(ac, dev) else "torch")
-    fused = _has_policy_kernel(ac, dev) and hasattr(agent, "policy_step_hip")
-    run = torch.zeros(E, dtype=torch.int64, device=dev)
-    steps = torch.zeros(E, dtype=torch.int32, device=dev)
-    ret = torch.zeros(E, dtype=torch.float32, device=dev)
-    rec_len = torch.zeros(E, R, dtype=torch.int32, device=dev)
-    rec_ret = torch.zeros(E, R, dtype=torch.float32, device=dev)
-    rec_suc = torch.zeros(E, R, dtype=torch.bool, device=dev)
-    lane = torch.arange(E, device=dev)
-    u = torch.empty(E, 1, dtype=torch.float32, device=dev)
-    act8 = torch.empty(E, 1, dtype=torch.int8, device=dev)
-    a = torch.empty(E, dtype=torch.int64, device=dev)
-    it = 0
-    log = []
-    while True:
-        active = run < R
-        if it % 16 == 0 and not bool(active.any()):            # one host read per 16 lock-steps
-            break
-        it += 1
-        x = obs.clone()
-        stat.standardize(obs[..., 0], out=x[..., 0])
-        vec.action_uniforms(u)
-        if fused:
-            agent.policy_step_hip(x[:, 0].contiguous(), bank.predict(x, mask=active)[:, 0].contiguous(), hid, u=u[:, 0].contiguous(),
-                                  h_out=hid, act=a)
-        else:
-            logits, _, hid = ac.policy_step(x[:, 0], bank.predict(x, mask=active)[:, 0], hid)
-            cdf = torch.cumsum(torch.softmax(logits, dim=-1), dim=-1)
-            a = (cdf[:, :-1] <= u[:, 0].unsqueeze(-1)).sum(dim=-1)
-        act8[:, 0] = torch.where(active, a, torch.full_like(a, 8)).to(torch.int8)       # lanes with all runs done idle in place
-        if return_actions:
-            log.append(torch.where(active, a, torch.full_like(a, -1)))
-        obs_n, rew, _, done, _ = vec.step(act8)
-        ret += torch.where(active, rew[:, 0], torch.zeros_like(rew[:, 0]))
-        steps += active.int()
-        found = done[:, 0].bool() & active
-        over = found | ((steps == L) & active)
-        stat.update(obs_n[..., 0], mask=active)                                         # :392-397 (before the episode-over test)
-        slot = run.clamp(max=R - 1)
-        rec_len[lane, slot] = torch.where(over, steps, rec_len[lane, slot])
-        rec_ret[lane, slot] = torch.where(over, ret, rec_ret[lane, slot])
-        rec_suc[lane, slot] = torch.where(over, found, rec_suc[lane, slot])
-        run += over.long()
-        again = over & (run < R)                                                        # :455-468: refresh, statistics restart
-        obs_r = vec.refresh(*saved, mask=again.to(torch.uint8))[0]
-        stat.reset(again)
-        stat.update(obs_r[..., 0], mask=again)
-        obs = torch.where(again.view(E, 1, 1), obs_r, obs_n).clone()
-        steps.masked_fill_(over, 0)
-        ret.masked_fill_(over, 0.0)
-    return _close(vec, keys, saved, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1),
-                  log=torch.stack(log) if return_actions else None)
-
-
-@torch.no_grad()
 def run_test_environments_rnn(agent, env_sets: Dict[str, tuple], montecarlo_runs: int = 100, steps_per_episode: int = 120,
                               obstruction_count: int = 0, enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0",
                               return_actions: bool = False, falloff: str = "reference", carry_hidden_across_runs: bool = True,
                               fused=None):
-    """EpisodeRunner.run (evaluate.py:333-476) for the recurrent agent (RAD-A2C) with its lock-step in HIP.  carry_hidden_across_runs
-    as in run_test_environments: True = one lane per saved environment, its R runs one after the other on carried hidden states (the
-    reference's lifetime of `hiddens`, :357); False = one lane per (environment, run) pair with a fresh hidden state.
-
-    fused=True: a lock-step is rs_action_uniforms, the PFGRU step on the lanes with runs left, the policy step on the same lanes
-    (GRU cell, policy head and draw; its action goes straight into rs_step's row), rs_step, rs_rnn_eval_post_step (return, length, the
-    per-run records, Welford update, the next observation raw and standardised, the bank's call counter, finished-lane count) and, with
-    more than one run per lane, rs_refresh on the lanes that begin their next run and rs_rnn_eval_post_refresh (statistics restart) --
-    5 or 7 launches on one stream.  The host reads the finished-lane count once every 16 lock-steps; nothing else synchronises.  It
-    needs a cuda device and a kernel for both halves of the agent (fused_policy or sized_policy, fused_pfgru or sized_pfgru);
-    ValueError otherwise.  fused=False: today's run_test_environments, identical records.  fused=None: the fused form where it can run.
+    """EpisodeRunner.run (evaluate.py:333-476) for the recurrent agent (RAD-A2C): run_test_environments_rnn_team with the team
+    {0: agent} -- its lanes, its hidden-state lifetimes (carry_hidden_across_runs), its fused and composed lock-steps, its records.
+    fused=True needs a cuda device and a kernel for both halves of the agent (fused_policy or sized_policy, fused_pfgru or sized_pfgru);
+    ValueError otherwise.  fused=None: the fused form where it can run.
 
     Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N] int8 log of rs_step's action rows, 8
     (idle) where a lane had no run going -- N = E with carried hidden states, else E * R."""
-    E, R, L = len(env_sets), montecarlo_runs, steps_per_episode
     dev = torch.device(device)
     ac = getattr(agent, "agent", None)
-    can = (dev.type == "cuda" and hasattr(ac, "gru_cell") and hasattr(agent, "policy_step_masked")
+    can = (dev.type == "cuda" and hasattr(ac, "gru_cell") and hasattr(agent, "policy_step_masked_rows")
            and _has_policy_kernel(ac, dev) and _has_pfgru_kernel(ac, dev))
     if fused is None:
         fused = can
     if fused and not can:
         raise ValueError("the fused evaluation needs a cuda device, a GRU of 1..64 units with single-layer heads of 2..64 units and a "
                          "PFGRU of 8, 16, .., 64 hidden units")
-    if not fused:
-        res = run_test_environments(agent, env_sets, montecarlo_runs=R, steps_per_episode=L, obstruction_count=obstruction_count,
-                                    enforce_grid_boundaries=enforce_grid_boundaries, seed=seed, device=device, return_actions=return_actions,
-                                    falloff=falloff, carry_hidden_across_runs=carry_hidden_across_runs)
-        if not return_actions:
-            return res
-        out, summary, log = res
-        if carry_hidden_across_runs and hasattr(ac, "gru_cell"):
-            log = np.where(log < 0, 8, log)                       # _run_sequential marks a lane without a run with -1
-        else:                                                     # the lane-per-run log keeps the draws of finished lanes: idle past the end
-            lens = np.array([l for r in out for l in r.total_episode_length])
-            log = np.where(np.arange(log.shape[0]).reshape(-1, 1) >= lens.reshape(1, -1), 8, log)
-        return out, summary, log.astype(np.int8)
-    Rl = R if carry_hidden_across_runs else 1                     # runs per lane
-    N = E * R // Rl
-    lib = _lib.load()
-    vec, keys, saved, obs, stat = _open(env_sets, R // Rl, 1, obstruction_count, enforce_grid_boundaries, seed, device, falloff=falloff)
-    bank, hid = recurrent_start(ac, N, seed, dev, "hip")          # particle sets and h0 are drawn here only
-    x = obs.clone()
-    stat.standardize(obs[..., 0], out=x[..., 0])
-    active = torch.ones(N, dtype=torch.uint8, device=dev)
-    again = torch.zeros(N, dtype=torch.uint8, device=dev)
-    run = torch.zeros(N, dtype=torch.int32, device=dev)
-    steps = torch.zeros(N, dtype=torch.int32, device=dev)
-    ret = torch.zeros(N, dtype=torch.float32, device=dev)
-    rec_len = torch.zeros(N, Rl, dtype=torch.int32, device=dev)
-    rec_ret = torch.zeros(N, Rl, dtype=torch.float32, device=dev)
-    rec_suc = torch.zeros(N, Rl, dtype=torch.uint8, device=dev)
-    finished = torch.zeros(1, dtype=torch.int32, device=dev)
-    u = torch.empty(N, 1, dtype=torch.float32, device=dev)
-    act = torch.empty(N, dtype=torch.int64, device=dev)           # scratch: asking for it makes K14 evaluate the policy head
-    bound = L * Rl
-    # with return_actions the action row of lock-step t is written straight into row t of the log, which rs_step then reads; a lane
-    # that is masked out is never written and reads 8.  Otherwise one fixed row, where rs_rnn_eval_post_step parks a finished lane on 8
-    log = torch.full((bound, N), 8, dtype=torch.int8, device=dev) if return_actions else None
-    act8 = None if return_actions else torch.full((N,), 8, dtype=torch.int8, device=dev)
-    p = lambda t: t.data_ptr()
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    state = _lib.RsRnnEvalState(N, Rl, L, p(vec.obs), p(vec.reward), p(vec.done), p(obs), p(x), p(stat.count), p(stat.mean), p(stat.sq),
-                                p(stat.std), p(active), p(again), p(run), p(steps), p(ret), p(rec_len), p(rec_ret), p(rec_suc),
-                                p(bank.calls), None if return_actions else p(act8), p(finished))
-    it = 0
-    while it < bound:
-        if it and it % 16 == 0 and int(finished.item()) == N:     # one host read per 16 lock-steps
-            break
-        a8 = log[it] if return_actions else act8
-        vec.action_uniforms(u)
-        loc = bank.predict_kernel(x, mask8=active)                # the draw counters are rs_rnn_eval_post_step's
-        agent.policy_step_masked(x, loc, hid, u, act, a8, active)
-        vec.step(a8)
-        _lib.check(lib.rs_rnn_eval_post_step(C.byref(state), st), "rs_rnn_eval_post_step")
-        if Rl > 1:                                                # :455-468: the lanes that begin their next run
-            vec.refresh(*saved, mask=again)
-            _lib.check(lib.rs_rnn_eval_post_refresh(C.byref(state), st), "rs_rnn_eval_post_refresh")
-        it += 1
-    # no flag is masked: one agent's idle step is a move by (0, 0), it never stalls
-    return _close(vec, keys, saved, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1).bool(),
-                  log=log[:it] if return_actions else None)
+    res = run_test_environments_rnn_team({0: agent}, env_sets, montecarlo_runs=montecarlo_runs, steps_per_episode=steps_per_episode,
+                                         obstruction_count=obstruction_count, enforce_grid_boundaries=enforce_grid_boundaries, seed=seed,
+                                         device=device, return_actions=return_actions, falloff=falloff,
+                                         carry_hidden_across_runs=carry_hidden_across_runs, fused=fused)
+    return res[:2] + (res[2][:, :, 0],) if return_actions else res
 
 
 @torch.no_grad()
@@ -407,8 +268,8 @@ def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
     its lock-step in HIP.  agents: {id: RNNAgentPPO}, ids 0..A-1, all of the same widths.  Every agent has its own network (:305-318),
     its own GRU state and particle set, created once (:353), and its own statistics buffer (:361-364, :395-397, :461-466); a run ends
     when any agent's terminal flag rises (:411-423) or at `steps_per_episode`; agent 0's return is recorded (:441-444).
-    carry_hidden_across_runs as in run_test_environments_rnn: True = N = E lanes with R runs each on carried hidden states, False =
-    N = E R lanes with one run each.
+    carry_hidden_across_runs: True = N = E lanes with R runs each, one after the other on carried hidden states (the reference's
+    lifetime of `hiddens`, :353); False = N = E R lanes with one run each and a fresh hidden state.
 
     fused=True: a lock-step is rs_action_uniforms, the PFGRU step of every owner on the lanes with runs left (one launch), the policy
     round -- rs_rnn_team_eval_step at the default widths (one launch for the team), one rs_rnn_sized_step per agent at the others --,
@@ -416,7 +277,7 @@ def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
     rs_rnn_team_eval_post_refresh: 5 or 7 launches at the default widths, on one stream.  The host reads the finished-lane count once
     every 16 lock-steps; nothing else synchronises.  It needs a cuda device and kernels for both halves of the agents; ValueError
     otherwise.  fused=False: the same lock-step composed from DeviceWelford, PredictorBank.predict, one policy step per agent and
-    torch bookkeeping in _run_sequential's order, with the same stopping rule: the A/B baseline, identical records and log.
+    torch bookkeeping in the reference's order, with the same stopping rule: the A/B baseline, identical records and log.
     fused=None: the fused form where it can run.
 
     Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log of rs_step's action rows,
@@ -535,9 +396,9 @@ def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
             steps.masked_fill_(over, 0)
             ret.masked_fill_(over, 0.0)
             it += 1
-    # lanes whose runs are over idle on purpose; stacked agents may "stall"
+    # lanes whose runs are over idle on purpose; stacked agents may "stall".  One agent's idle step is a move by (0, 0): it never stalls
     return _close(vec, keys, saved, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1).bool(),
-                  log=log[:it] if return_actions else None, ignore_flags=_lib.ENVERR_IDLE_STALL)
+                  log=log[:it] if return_actions else None, ignore_flags=_lib.ENVERR_IDLE_STALL if A > 1 else 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -802,29 +802,11 @@ class RNNAgentPPO:
                                                        None if mask8 is None else mask8.data_ptr(), N,
                                                        C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "rs_rnn_policy_step_rows")
 
-    def policy_step_masked(self, x, loc, h, u, act, act8, mask8) -> None:
-        """K14 (or the sized step) as the evaluation lock-step uses it: packed rows x [N, 11], loc [N, 2], u [N]; only the lanes with
-        mask8 != 0 are evaluated, their h [N, hid] is updated in place and their action goes to act8 [N] int8 (rs_step's row) and to the
-        act [N] int64 scratch -- K14 evaluates the policy head for act / logp / logits, not for act8 alone.  No value."""
-        ac = self.agent
-        w = self.policy_weights()
-        for t in (x, loc, h, u, act, act8, mask8):
-            assert t.is_cuda and t.is_contiguous()
-        N = x.shape[0]
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        if not ac.fused_policy:
-            assert ac.sized_policy
-            _lib.check(_lib.load().rs_rnn_sized_step(w.data_ptr(), ac.hid, ac.pol[0], ac.val[0], x.data_ptr(), _lib.RS_OBS_DIM, loc.data_ptr(), 2,
-                                                     h.data_ptr(), u.data_ptr(), 1, h.data_ptr(), None, None, act.data_ptr(), None,
-                                                     act8.data_ptr(), 1, mask8.data_ptr(), N, st), "rs_rnn_sized_step")
-            return
-        _lib.check(_lib.load().rs_rnn_policy_step_rows(w.data_ptr(), x.data_ptr(), _lib.RS_OBS_DIM, loc.data_ptr(), 2, h.data_ptr(), u.data_ptr(), 1,
-                                                       h.data_ptr(), None, act.data_ptr(), None, act8.data_ptr(), 1, mask8.data_ptr(), N, st),
-                   "rs_rnn_policy_step_rows")
-
     def policy_step_masked_rows(self, x, loc, h, u, a: int, act, act8, mask8) -> None:
-        """policy_step_masked on agent a's rows of a team's [N, A, .] tensors (no contiguous copies): x [N, A, 11], loc [N, A, 2],
-        u [N, A], act8 [N, A] int8; h [N, hid] is agent a's own state, act [N] int64 scratch, mask8 [N] uint8."""
+        """K14 (or the sized step) as the evaluation lock-step uses it, on agent a's rows of a team's [N, A, .] tensors (no contiguous
+        copies): x [N, A, 11], loc [N, A, 2], u [N, A]; only the lanes with mask8 [N] uint8 != 0 are evaluated, their h [N, hid] (agent
+        a's own state) is updated in place and their action goes to act8 [N, A] int8 (rs_step's rows) and to the act [N] int64 scratch
+        -- K14 evaluates the policy head for act / logp / logits, not for act8 alone.  No value."""
         ac = self.agent
         w = self.policy_weights()
         for t in (x, loc, h, u, act, act8, mask8):

@@ -1,7 +1,8 @@
 """Monte-Carlo evaluation of the recurrent agent (RAD-A2C) at the reference's size: the cost of ONE lock-step of
-evaluate.run_test_environments_rnn with fused=True (rs_action_uniforms, the PFGRU step, the policy step, rs_step,
-rs_rnn_eval_post_step and, with carried hidden states, rs_refresh and rs_rnn_eval_post_refresh) against fused=False, which is
-evaluate.run_test_environments as it was before the fused form existed (the same three big kernels inside ~20-35 torch ops).
+evaluate.run_test_environments_rnn -- the team runner (run_test_environments_rnn_team) with one agent -- with fused=True
+(rs_action_uniforms, the PFGRU step, the policy round, rs_step, rs_rnn_team_eval_post_step and, with carried hidden states, rs_refresh
+and rs_rnn_team_eval_post_refresh) against fused=False, the team runner's composed lock-step, which is also what
+evaluate.run_test_environments runs for a recurrent agent (the same three big kernels inside ~20-35 torch ops).
 
 --envs saved environments x --runs Monte-Carlo runs of --steps-per-episode steps, at the default widths, in both modes -- sequential
 (carry_hidden_across_runs=True: one lane per environment, 1000 lanes, its runs one after the other) and lane-per-run (100 000 lanes)

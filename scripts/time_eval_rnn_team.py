@@ -12,8 +12,8 @@ text on stdout and in profiles/eval_rnn_team_timing.txt.
    in the wrapped RadSearchVec.action_uniforms, over a window of lock-steps behind --skip): --envs saved environments x --runs runs of
    --steps-per-episode steps, A = 2 and 4 untrained default-width agents, both hidden-state lifetimes, obstacle-free and with
    --obstructions obstructions.  Per configuration the fused form's slowest repeat against the composed form's fastest; and, with
-   carried hidden states, the A-agent fused median against A times the one-agent fused median (run_test_environments_rnn, timed here
-   the same way): evaluating the agents one by one is what was possible before."""
+   carried hidden states, the A-agent fused median against A times the one-agent fused median (run_test_environments_rnn, the same runner with
+   one agent, timed here the same way): evaluating the agents one by one is what was possible before."""
 import argparse
 import ctypes as C
 import os

@@ -1,128 +1,25 @@
-"""The HIP Monte-Carlo evaluation of the recurrent agent, RAD-A2C (csrc/rs_eval.hip, evaluate.run_test_environments_rnn):
-rs_rnn_eval_post_step and rs_rnn_eval_post_refresh against the torch composition, bit for bit; the fused run against the composed one
-(today's run_test_environments) with carried and with fresh hidden states, at the default and at sized widths; the fused sequential run
-replayed through the oracle; the early stop on the device-side finished-lane count; the guard and the evaluate_PPO driver."""
+"""The Monte-Carlo evaluation of the recurrent agent, RAD-A2C, as the one-agent case of the team's (csrc/rs_eval.hip,
+evaluate.run_test_environments_rnn, a front to run_test_environments_rnn_team): rs_rnn_eval_post_step and rs_rnn_eval_post_refresh --
+the entries that widen rs_rnn_eval_state to a team of one -- against the torch composition, bit for bit; the fused run against the
+composed one with carried and with fresh hidden states, at the default and at sized widths; the fused sequential run replayed through
+the oracle; the early stop on the device-side finished-lane count; the guard and the evaluate_PPO driver.  The shared pieces are in
+tests/_rnn_eval.py."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from oracle.radsearch_oracle import PhiloxDraws, RadSearchOracle
+sys.path.insert(0, os.path.dirname(__file__))
+import _rnn_eval as H  # noqa: E402
+from _rnn_eval import DEV, WIDTHS, _args  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
-
-
-def _args(hid, pol, val, rec):
-    return dict(hidden=((hid,),), hidden_sizes_pol=((pol,),), hidden_sizes_val=((val,),), hidden_sizes_rec=(rec,))
-
-
-WIDTHS = {"default": None, "sized": _args(32, 64, 64, 16)}          # K11 + K14; rs_pfgru_sized_step + rs_rnn_sized_step
-
-
-def _agent(widths="default", L=30, scale=4.0, seed=9):
-    """a decisive policy (policy-head weights x scale, as tests/test_evaluate_gpu.py) finds sources within 30 steps sometimes"""
-    from radiation_ppo_amd.rada2c import RNNAgentPPO
-    torch.manual_seed(seed)
-    agent = RNNAgentPPO(id=0, steps_per_episode=L, actor_critic_args=WIDTHS[widths])
-    with torch.no_grad():
-        for p in agent.agent.pi.parameters():
-            p.mul_(scale)
-    return agent
-
 
 # ------------------------------------------------------------------------------------------------------ the two kernels
-class _Lanes:
-    """The state rs_rnn_eval_state points at.  impl "hip": the kernels' side; "torch": the composition's side (same dtypes)."""
-
-    def __init__(self, N, Rl, impl):
-        from radiation_ppo_amd.ppo import DeviceWelford
-        n = torch.arange(N, device=DEV)
-        self.N, self.Rl = N, Rl
-        self.stat = DeviceWelford((N, 1), DEV, impl=impl)
-        started = (n % 3 != 1).view(N, 1)                           # lanes with n % 3 == 1 enter with Welford count 0
-        first = torch.floor(torch.rand(N, 1, device=DEV, generator=torch.Generator(device=DEV).manual_seed(5)) * 900.0).double()
-        self.stat.count.copy_(started.double())
-        self.stat.mean.copy_(torch.where(started, first, torch.zeros_like(first)))
-        self.done_before = n % 5 == 3                               # lanes that enter with every run behind them
-        self.late = (n % 7 == 5) & ~self.done_before                # lanes the caller starts late (see the test's docstring)
-        self.active = (~(self.done_before | self.late)).to(torch.uint8)
-        self.again = torch.full((N,), 3, dtype=torch.uint8, device=DEV)      # overwritten on every lane by the first step
-        self.run = torch.where(self.done_before, torch.full_like(n, Rl), torch.zeros_like(n)).int()
-        self.steps = torch.zeros(N, dtype=torch.int32, device=DEV)
-        self.ret = torch.zeros(N, dtype=torch.float32, device=DEV)
-        self.rec_len = torch.full((N, Rl), -5, dtype=torch.int32, device=DEV)
-        self.rec_ret = torch.full((N, Rl), -7.5, dtype=torch.float32, device=DEV)
-        self.rec_suc = torch.full((N, Rl), 9, dtype=torch.uint8, device=DEV)
-        self.calls = (n * 3).long()
-        self.idle = (n % 8).to(torch.int8)
-        self.finished = torch.tensor([int(self.done_before.sum())], dtype=torch.int32, device=DEV)   # monotonic from the caller's start value
-        self.cur = torch.full((N, 1, 11), -1.0, device=DEV)
-        self.x = torch.full((N, 1, 11), -2.0, device=DEV)
-
-    def arrays(self):
-        return dict(active=self.active, again=self.again, run=self.run, steps=self.steps, ret=self.ret, rec_len=self.rec_len,
-                    rec_ret=self.rec_ret, rec_suc=self.rec_suc, pf_calls=self.calls, idle_act8=self.idle, finished=self.finished,
-                    cur_obs=self.cur, x=self.x, count=self.stat.count, mean=self.stat.mean, sq=self.stat.sq, std=self.stat.std)
-
-    def struct(self, L, env_obs, env_rew, env_done, optional=True):
-        from radiation_ppo_amd import _lib
-        p = lambda t: t.data_ptr()
-        s = self.stat
-        return _lib.RsRnnEvalState(self.N, self.Rl, L, p(env_obs), p(env_rew), p(env_done), p(self.cur), p(self.x), p(s.count), p(s.mean),
-                                   p(s.sq), p(s.std), p(self.active), p(self.again), p(self.run), p(self.steps), p(self.ret),
-                                   p(self.rec_len), p(self.rec_ret), p(self.rec_suc), p(self.calls) if optional else None,
-                                   p(self.idle) if optional else None, p(self.finished))
-
-    # the torch composition, in the order include/radsearch.h lists
-    def post_step(self, L, obs, rew, done):
-        N, Rl = self.N, self.Rl
-        a = self.active.bool()
-        self.ret.copy_(torch.where(a, self.ret + rew, self.ret))
-        self.steps += a.int()
-        self.calls += a.long()
-        found = a & done.bool()
-        over = found | (a & (self.steps == L))
-        self.stat.update(obs[..., 0], mask=a)
-        lane, slot = torch.arange(N, device=DEV), self.run.long().clamp(max=Rl - 1)
-        self.rec_len[lane, slot] = torch.where(over, self.steps, self.rec_len[lane, slot])
-        self.rec_ret[lane, slot] = torch.where(over, self.ret, self.rec_ret[lane, slot])
-        self.rec_suc[lane, slot] = torch.where(over, found.to(torch.uint8), self.rec_suc[lane, slot])
-        self.run += over.int()
-        self.steps.masked_fill_(over, 0)
-        self.ret.masked_fill_(over, 0.0)
-        self.again.copy_((over & (self.run < Rl)).to(torch.uint8))
-        last = over & (self.run == Rl)
-        self.active.masked_fill_(last, 0)
-        self.idle.masked_fill_(last, 8)
-        self.finished += last.sum().int()
-        self.cur.copy_(obs)
-        self.x.copy_(obs)
-        self.stat.standardize(obs[..., 0], out=self.x[..., 0])
-        return found, over, last
-
-    def post_refresh(self, obs):
-        m = self.again.bool()
-        self.stat.reset(m)
-        self.stat.update(obs[..., 0], mask=m)
-        z = obs.clone()
-        self.stat.standardize(obs[..., 0], out=z[..., 0])
-        self.cur.copy_(torch.where(m.view(-1, 1, 1), obs, self.cur))
-        self.x.copy_(torch.where(m.view(-1, 1, 1), z, self.x))
-
-
-def _same(k, t, what=""):
-    for (name, a), b in zip(k.arrays().items(), t.arrays().values()):
-        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), (what, name, (a != b).nonzero()[:6].tolist())
-
-
 @pytest.mark.parametrize("optional", [True, False], ids=["counters", "no_counters"])
 @pytest.mark.parametrize("Rl", [1, 3])
 @pytest.mark.parametrize("N", [70, 300])
@@ -142,11 +39,11 @@ def test_rnn_eval_post_step_equals_the_torch_composition_bit_for_bit(N, Rl, opti
     env_obs[..., 0] = torch.floor(env_obs[..., 0] * 900.0)
     env_rew = (torch.rand(T, N, device=DEV, generator=g) - 0.7) * 3.0
     n = torch.arange(N, device=DEV)
-    k, t = _Lanes(N, Rl, "hip"), _Lanes(N, Rl, "torch")
+    k, t = H.Lanes(N, 1, Rl, "hip"), H.Lanes(N, 1, Rl, "torch")
     env_done = torch.stack([((n + 3 * i) % 11 == 0) & ~k.late for i in range(T)]).to(torch.uint8)
     assert bool((k.active == 0).any()) and bool((k.active != 0).any()) and bool((k.stat.count[k.active != 0] == 0).any())
     o, r, d = torch.zeros_like(env_obs[0]), torch.zeros_like(env_rew[0]), torch.zeros_like(env_done[0])
-    state = k.struct(L, o, r, d, optional)
+    state = k.struct(L, o, r, d, optional, single=True)
     calls0, idle0 = t.calls.clone(), t.idle.clone()
     by_done = by_limit = next_runs = 0
     for i in range(T):
@@ -154,12 +51,12 @@ def test_rnn_eval_post_step_equals_the_torch_composition_bit_for_bit(N, Rl, opti
             for s in (k, t):
                 s.active.masked_fill_(s.late, 1)
         o.copy_(env_obs[i]); r.copy_(env_rew[i]); d.copy_(env_done[i])
-        _lib.check(lib.rs_rnn_eval_post_step(C.byref(state), _stream()), "rs_rnn_eval_post_step")
+        _lib.check(lib.rs_rnn_eval_post_step(C.byref(state), H.stream()), "rs_rnn_eval_post_step")
         found, over, last = t.post_step(L, env_obs[i], env_rew[i], env_done[i])
         if not optional:
             t.calls.copy_(calls0); t.idle.copy_(idle0)
         torch.cuda.synchronize()
-        _same(k, t, i)
+        H.same(k, t, i)
         by_done += int(found.sum())
         by_limit += int((over & ~found).sum())
         next_runs += int(t.again.sum())
@@ -180,15 +77,15 @@ def test_rnn_eval_post_refresh_restarts_the_statistics_of_the_masked_lanes_only(
     obs = torch.rand(N, 1, 11, device=DEV, generator=g)
     obs[..., 0] = torch.floor(obs[..., 0] * 900.0)
     n = torch.arange(N, device=DEV)
-    k, t = _Lanes(N, Rl, "hip"), _Lanes(N, Rl, "torch")
+    k, t = H.Lanes(N, 1, Rl, "hip"), H.Lanes(N, 1, Rl, "torch")
     for s in (k, t):
         s.again.copy_((n % 3 == 0).to(torch.uint8))
         s.stat.count.fill_(7.0); s.stat.mean.fill_(123.5); s.stat.sq.fill_(9.25); s.stat.std.fill_(3.5)
     rew, done = torch.zeros(N, device=DEV), torch.zeros(N, dtype=torch.uint8, device=DEV)
-    _lib.check(lib.rs_rnn_eval_post_refresh(C.byref(k.struct(4, obs, rew, done)), _stream()), "rs_rnn_eval_post_refresh")
+    _lib.check(lib.rs_rnn_eval_post_refresh(C.byref(k.struct(4, obs, rew, done, single=True)), H.stream()), "rs_rnn_eval_post_refresh")
     t.post_refresh(obs)
     torch.cuda.synchronize()
-    _same(k, t)
+    H.same(k, t)
     m = n % 3 == 0
     assert torch.equal(k.stat.count[m], torch.ones(int(m.sum()), 1, dtype=torch.float64, device=DEV))
     assert torch.equal(k.stat.mean[m][:, 0], obs[m][:, 0, 0].double()) and torch.equal(k.cur[m], obs[m])
@@ -217,7 +114,7 @@ def _run(agent, sets, obst, seed, fused, carry, runs=R, steps=L):
 def test_fused_run_equals_the_composed_run(widths, carry, obst):
     from radiation_ppo_amd.evaluate import sample_test_environments
     sets = sample_test_environments(E, obstruction_count=obst, seed=SET_SEED)
-    agent = _agent(widths)
+    agent = H.agent(widths)
     assert agent.agent.fused_policy == (widths == "default") and agent.agent.fused_pfgru == (widths == "default")
     seed = SEEDS[widths, carry, obst]
     res_f, sum_f, act_f = _run(agent, sets, obst, seed, True, carry)
@@ -230,12 +127,7 @@ def test_fused_run_equals_the_composed_run(widths, carry, obst):
     assert (act_f[common:] == 8).all() and (act_c[common:] == 8).all()
     assert int(act_f.min()) >= 0 and (act_f < 8).any()
     assert len(res_f) == len(res_c) == E and sum_f["completed_runs"] == sum_c["completed_runs"] == E * R
-    for a, b in zip(res_f, res_c):
-        assert a.id == b.id and a.completed_runs == b.completed_runs == R and a.success_counter == b.success_counter
-        assert a.total_episode_length == b.total_episode_length
-        for x, y in ((a.successful, b.successful), (a.unsuccessful, b.unsuccessful)):
-            assert x.episode_length == y.episode_length and x.episode_return == y.episode_return
-            assert x.intensity == y.intensity and x.background_intensity == y.background_intensity
+    H.same_records(res_f, res_c, R)
     assert sum_f["success_rate"] == sum_c["success_rate"]
     n_success = sum(r.success_counter for r in res_f)
     timed_out = sum(l == L for r in res_f for l in r.unsuccessful.episode_length)
@@ -251,7 +143,7 @@ def test_fused_sequential_run_replays_through_the_oracle(monkeypatch):
     from radiation_ppo_amd.pfgru import PredictorBank
     seed, obst = SEEDS["default", True, 2], 2                    # a run with a found source among the 24
     sets = ev.sample_test_environments(E, obstruction_count=obst, seed=SET_SEED)
-    agent = _agent()
+    agent = H.agent()
     calls = {"h0": 0, "bank_reset": 0}
     h0, br = agent.agent.gru_h0, PredictorBank.reset
     monkeypatch.setattr(agent.agent, "gru_h0", lambda u: (calls.__setitem__("h0", calls["h0"] + 1), h0(u))[1])
@@ -259,32 +151,7 @@ def test_fused_sequential_run_replays_through_the_oracle(monkeypatch):
     results, summary, actions = _run(agent, sets, obst, seed, True, True)
     assert calls == {"h0": 1, "bank_reset": 1}
     assert summary["completed_runs"] == E * R and actions.shape[1] == E and 0 < sum(r.success_counter for r in results) < E * R
-    for e, res in enumerate(results):
-        s = sets[f"env_{e}"]
-        rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]]
-        ref = RadSearchOracle(PhiloxDraws(seed, e), number_agents=1, obstruction_count=obst, enforce_grid_boundaries=True)
-        ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-        lens, rets, sucs = [], [], []
-        ret, steps = np.float32(0.0), 0
-        t_end = actions.shape[0]
-        for t in range(actions.shape[0]):
-            if actions[t, e] == 8:
-                t_end = t
-                break
-            o, rew, done, _ = ref.step({0: int(actions[t, e])})
-            ret = np.float32(ret + np.float32(rew["individual_reward"][0]))
-            steps += 1
-            if done[0] or steps == L:
-                lens.append(steps); rets.append(float(ret)); sucs.append(bool(done[0]))
-                ret, steps = np.float32(0.0), 0
-                ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-        assert (actions[t_end:, e] == 8).all(), e                   # a lane with every run behind it idles to the end
-        assert len(lens) == R and res.total_episode_length == lens, (e, lens, res.total_episode_length)
-        assert res.success_counter == sum(sucs)
-        assert res.successful.episode_length == [l for l, k in zip(lens, sucs) if k]
-        assert res.unsuccessful.episode_length == [l for l, k in zip(lens, sucs) if not k]
-        assert np.allclose(res.successful.episode_return, [r for r, k in zip(rets, sucs) if k], atol=1e-4)
-        assert np.allclose(res.unsuccessful.episode_return, [r for r, k in zip(rets, sucs) if not k], atol=1e-4)
+    H.replays_through_the_oracle(sets, results, actions[:, :, None], seed, obst, R, L)
 
 
 def test_the_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
@@ -293,7 +160,7 @@ def test_the_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
     reads the finished-lane count every 16 lock-steps: 16 rows, idle (8) from there on."""
     Es, Rs = 3, 4
     sets = {f"env_{i}": (np.array([1350.0, 1350.0]), np.array([1353.0, 1354.0]), 2_000_000 + 1000 * i, 20 + i) for i in range(Es)}
-    agent = _agent()
+    agent = H.agent()
     for carry, busy in ((True, Rs), (False, 1)):
         results, summary, actions = _run(agent, sets, 0, 5, True, carry, runs=Rs, steps=40)
         assert actions.shape == (16, Es if carry else Es * Rs), (carry, actions.shape)
@@ -314,7 +181,7 @@ def test_the_fused_form_refuses_a_width_no_kernel_serves():
     with pytest.raises(ValueError):
         run_test_environments_rnn(wide, sets, montecarlo_runs=2, steps_per_episode=5, fused=True)
     with pytest.raises(ValueError):
-        run_test_environments_rnn(_agent(), sets, montecarlo_runs=2, steps_per_episode=5, fused=True, device="cpu")
+        run_test_environments_rnn(H.agent(), sets, montecarlo_runs=2, steps_per_episode=5, fused=True, device="cpu")
 
 
 def test_evaluate_ppo_driver_reaches_the_rnn_runner(tmp_path, monkeypatch):

@@ -1,46 +1,24 @@
-"""The HIP Monte-Carlo evaluation of RAD-A2C teams of 2 to 8 recurrent agents (csrc/rs_rnn_policy.hip: rs_rnn_team_eval_step;
+"""The HIP Monte-Carlo evaluation of RAD-A2C teams of 1 to 8 recurrent agents (csrc/rs_rnn_policy.hip: rs_rnn_team_eval_step;
 csrc/rs_eval.hip: rs_rnn_team_eval_post_step / _post_refresh; evaluate.run_test_environments_rnn_team): the team's policy round against
 one K14 launch per agent, bit for bit; the two bookkeeping kernels against the torch composition, bit for bit; the fused run against
-the composed one at the default and a sized width with both hidden-state lifetimes; one agent through the team runner against
-run_test_environments_rnn; a carried-hidden fused run of two agents replayed through the oracle; the early stop on the device-side
-count; the refusals and the evaluate_PPO driver."""
+the composed one at the default and a sized width with both hidden-state lifetimes; one agent through the team runner against the
+records of the commit that still had a one-agent lock-step (tests/golden/rnn_eval_parent.npz); a carried-hidden fused run of two
+agents replayed through the oracle; the early stop on the device-side count; the refusals and the evaluate_PPO driver.  The shared
+pieces are in tests/_rnn_eval.py."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from oracle.radsearch_oracle import PhiloxDraws, RadSearchOracle
+sys.path.insert(0, os.path.dirname(__file__))
+import _k7_bits as K  # noqa: E402
+import _rnn_eval as H  # noqa: E402
+from _rnn_eval import DEV, WIDTHS, _args  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
-
-
-def _args(hid, pol, val, rec):
-    return dict(hidden=((hid,),), hidden_sizes_pol=((pol,),), hidden_sizes_val=((val,),), hidden_sizes_rec=(rec,))
-
-
-WIDTHS = {"default": None, "sized": _args(32, 64, 64, 16)}          # K11 + rs_rnn_team_eval_step; rs_pfgru_sized_step + rs_rnn_sized_step
-
-
-def _team(A, widths="default", L=30, scale=4.0, seed=9):
-    """A agents with their own weights (one torch seed per agent) and decisive policies (policy-head weights x scale, as
-    tests/test_rnn_eval_gpu.py): sources are found within 30 steps sometimes"""
-    from radiation_ppo_amd.rada2c import RNNAgentPPO
-    team = {}
-    for a in range(A):
-        torch.manual_seed(seed + 101 * a)
-        team[a] = RNNAgentPPO(id=a, steps_per_episode=L, actor_critic_args=WIDTHS[widths])
-        with torch.no_grad():
-            for p in team[a].agent.pi.parameters():
-                p.mul_(scale)
-    return team
 
 
 # ------------------------------------------------------------------------------------------------------ the policy round
@@ -65,12 +43,12 @@ def test_team_step_equals_one_k14_launch_per_agent_bit_for_bit(N, A, mask):
     p = lambda t: t.data_ptr()
     h_k, act_k = h0.clone(), torch.full((N, A), -3, dtype=torch.int8, device=DEV)
     wp = (C.c_void_p * A)(*[p(w) for w in W])
-    _lib.check(lib.rs_rnn_team_eval_step(wp, A, p(x), p(loc), p(h_k), p(u), p(a8m), p(act_k), N, _stream()), "rs_rnn_team_eval_step")
+    _lib.check(lib.rs_rnn_team_eval_step(wp, A, p(x), p(loc), p(h_k), p(u), p(a8m), p(act_k), N, H.stream()), "rs_rnn_team_eval_step")
     h_r, act_r = h0.clone(), torch.full((N, A), -3, dtype=torch.int8, device=DEV)
     scratch = torch.empty(N, dtype=torch.int64, device=DEV)
     for a in range(A):
         _lib.check(lib.rs_rnn_policy_step_rows(p(W[a]), p(x) + 44 * a, 11 * A, p(loc) + 8 * a, 2 * A, p(h_r[a]), p(u) + 4 * a, A, p(h_r[a]), None,
-                                               p(scratch), None, p(act_r) + a, A, p(a8m), N, _stream()), "rs_rnn_policy_step_rows")
+                                               p(scratch), None, p(act_r) + a, A, p(a8m), N, H.stream()), "rs_rnn_policy_step_rows")
     torch.cuda.synchronize()
     assert torch.equal(h_k, h_r), (h_k != h_r).nonzero()[:6].tolist()
     assert torch.equal(act_k, act_r), (act_k != act_r).nonzero()[:6].tolist()
@@ -81,91 +59,6 @@ def test_team_step_equals_one_k14_launch_per_agent_bit_for_bit(N, A, mask):
 
 
 # ------------------------------------------------------------------------------------------------------ the two bookkeeping kernels
-class _Lanes:
-    """The state rs_rnn_team_eval_state points at (tests/test_rnn_eval_gpu.py's _Lanes with [N][A] rows).  impl "hip": the kernels'
-    side; "torch": the composition's side (same dtypes)."""
-
-    def __init__(self, N, A, Rl, impl):
-        from radiation_ppo_amd.ppo import DeviceWelford
-        n = torch.arange(N, device=DEV)
-        self.N, self.A, self.Rl = N, A, Rl
-        self.stat = DeviceWelford((N, A), DEV, impl=impl)
-        started = (n % 3 != 1).view(N, 1).expand(N, A)              # lanes with n % 3 == 1 enter with Welford count 0
-        first = torch.floor(torch.rand(N, A, device=DEV, generator=torch.Generator(device=DEV).manual_seed(5)) * 900.0).double()
-        self.stat.count.copy_(started.double())
-        self.stat.mean.copy_(torch.where(started, first, torch.zeros_like(first)))
-        self.done_before = n % 5 == 3                               # lanes that enter with every run behind them
-        self.late = (n % 7 == 5) & ~self.done_before                # lanes the caller starts late
-        self.active = (~(self.done_before | self.late)).to(torch.uint8)
-        self.again = torch.full((N,), 3, dtype=torch.uint8, device=DEV)      # overwritten on every lane by the first step
-        self.run = torch.where(self.done_before, torch.full_like(n, Rl), torch.zeros_like(n)).int()
-        self.steps = torch.zeros(N, dtype=torch.int32, device=DEV)
-        self.ret = torch.zeros(N, dtype=torch.float32, device=DEV)
-        self.rec_len = torch.full((N, Rl), -5, dtype=torch.int32, device=DEV)
-        self.rec_ret = torch.full((N, Rl), -7.5, dtype=torch.float32, device=DEV)
-        self.rec_suc = torch.full((N, Rl), 9, dtype=torch.uint8, device=DEV)
-        self.calls = (n * 3).long()
-        self.idle = ((n.view(N, 1) + torch.arange(A, device=DEV).view(1, A)) % 8).to(torch.int8).contiguous()
-        self.finished = torch.tensor([int(self.done_before.sum())], dtype=torch.int32, device=DEV)   # monotonic from the caller's start value
-        self.cur = torch.full((N, A, 11), -1.0, device=DEV)
-        self.x = torch.full((N, A, 11), -2.0, device=DEV)
-
-    def arrays(self):
-        return dict(active=self.active, again=self.again, run=self.run, steps=self.steps, ret=self.ret, rec_len=self.rec_len,
-                    rec_ret=self.rec_ret, rec_suc=self.rec_suc, pf_calls=self.calls, idle_act8=self.idle, finished=self.finished,
-                    cur_obs=self.cur, x=self.x, count=self.stat.count, mean=self.stat.mean, sq=self.stat.sq, std=self.stat.std)
-
-    def struct(self, L, env_obs, env_rew, env_done, optional=True):
-        from radiation_ppo_amd import _lib
-        p = lambda t: t.data_ptr()
-        s = self.stat
-        return _lib.RsRnnTeamEvalState(self.N, self.A, self.Rl, L, p(env_obs), p(env_rew), p(env_done), p(self.cur), p(self.x), p(s.count),
-                                       p(s.mean), p(s.sq), p(s.std), p(self.active), p(self.again), p(self.run), p(self.steps), p(self.ret),
-                                       p(self.rec_len), p(self.rec_ret), p(self.rec_suc), p(self.calls) if optional else None,
-                                       p(self.idle) if optional else None, p(self.finished))
-
-    # the torch composition, in the order include/radsearch.h lists
-    def post_step(self, L, obs, rew, done):
-        N, Rl = self.N, self.Rl
-        a = self.active.bool()
-        self.ret.copy_(torch.where(a, self.ret + rew[:, 0], self.ret))
-        self.steps += a.int()
-        self.calls += a.long()
-        found = a & done.bool().any(dim=1)
-        over = found | (a & (self.steps == L))
-        self.stat.update(obs[..., 0], mask=a)
-        lane, slot = torch.arange(N, device=DEV), self.run.long().clamp(max=Rl - 1)
-        self.rec_len[lane, slot] = torch.where(over, self.steps, self.rec_len[lane, slot])
-        self.rec_ret[lane, slot] = torch.where(over, self.ret, self.rec_ret[lane, slot])
-        self.rec_suc[lane, slot] = torch.where(over, found.to(torch.uint8), self.rec_suc[lane, slot])
-        self.run += over.int()
-        self.steps.masked_fill_(over, 0)
-        self.ret.masked_fill_(over, 0.0)
-        self.again.copy_((over & (self.run < Rl)).to(torch.uint8))
-        last = over & (self.run == Rl)
-        self.active.masked_fill_(last, 0)
-        self.idle.masked_fill_(last.view(N, 1), 8)
-        self.finished += last.sum().int()
-        self.cur.copy_(obs)
-        self.x.copy_(obs)
-        self.stat.standardize(obs[..., 0], out=self.x[..., 0])
-        return found, over, last
-
-    def post_refresh(self, obs):
-        m = self.again.bool()
-        self.stat.reset(m)
-        self.stat.update(obs[..., 0], mask=m)
-        z = obs.clone()
-        self.stat.standardize(obs[..., 0], out=z[..., 0])
-        self.cur.copy_(torch.where(m.view(-1, 1, 1), obs, self.cur))
-        self.x.copy_(torch.where(m.view(-1, 1, 1), z, self.x))
-
-
-def _same(k, t, what=""):
-    for (name, a), b in zip(k.arrays().items(), t.arrays().values()):
-        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), (what, name, (a != b).nonzero()[:6].tolist())
-
-
 @pytest.mark.parametrize("optional", [True, False], ids=["counters", "no_counters"])
 @pytest.mark.parametrize("Rl", [1, 3])
 @pytest.mark.parametrize("A", [2, 3])
@@ -187,7 +80,7 @@ def test_team_post_step_equals_the_torch_composition_bit_for_bit(N, A, Rl, optio
     env_rew = (torch.rand(T, N, A, device=DEV, generator=g) - 0.7) * 3.0
     assert bool((env_rew[..., 1] != env_rew[..., 0]).all())
     n = torch.arange(N, device=DEV)
-    k, t = _Lanes(N, A, Rl, "hip"), _Lanes(N, A, Rl, "torch")
+    k, t = H.Lanes(N, A, Rl, "hip"), H.Lanes(N, A, Rl, "torch")
     ag = torch.arange(A, device=DEV).view(1, A)
     who = torch.where((n % 2 == 0).view(N, 1), ag == 1, torch.where((n % 4 == 1).view(N, 1), ag == 0, torch.ones_like(ag, dtype=torch.bool)))
     env_done = torch.stack([(((n + 3 * i) % 11 == 0) & ~k.late).view(N, 1) & who for i in range(T)]).to(torch.uint8)
@@ -202,12 +95,12 @@ def test_team_post_step_equals_the_torch_composition_bit_for_bit(N, A, Rl, optio
             for s in (k, t):
                 s.active.masked_fill_(s.late, 1)
         o.copy_(env_obs[i]); r.copy_(env_rew[i]); d.copy_(env_done[i])
-        _lib.check(lib.rs_rnn_team_eval_post_step(C.byref(state), _stream()), "rs_rnn_team_eval_post_step")
+        _lib.check(lib.rs_rnn_team_eval_post_step(C.byref(state), H.stream()), "rs_rnn_team_eval_post_step")
         found, over, last = t.post_step(L, env_obs[i], env_rew[i], env_done[i])
         if not optional:
             t.calls.copy_(calls0); t.idle.copy_(idle0)
         torch.cuda.synchronize()
-        _same(k, t, i)
+        H.same(k, t, i)
         by_done += int(found.sum())
         by_one += int((found & (env_done[i, :, 0] == 0)).sum())
         by_limit += int((over & ~found).sum())
@@ -231,15 +124,15 @@ def test_team_post_refresh_restarts_the_statistics_of_the_masked_lanes_only():
     obs = torch.rand(N, A, 11, device=DEV, generator=g)
     obs[..., 0] = torch.floor(obs[..., 0] * 900.0)
     n = torch.arange(N, device=DEV)
-    k, t = _Lanes(N, A, Rl, "hip"), _Lanes(N, A, Rl, "torch")
+    k, t = H.Lanes(N, A, Rl, "hip"), H.Lanes(N, A, Rl, "torch")
     for s in (k, t):
         s.again.copy_((n % 3 == 0).to(torch.uint8))
         s.stat.count.fill_(7.0); s.stat.mean.fill_(123.5); s.stat.sq.fill_(9.25); s.stat.std.fill_(3.5)
     rew, done = torch.zeros(N, A, device=DEV), torch.zeros(N, A, dtype=torch.uint8, device=DEV)
-    _lib.check(lib.rs_rnn_team_eval_post_refresh(C.byref(k.struct(4, obs, rew, done)), _stream()), "rs_rnn_team_eval_post_refresh")
+    _lib.check(lib.rs_rnn_team_eval_post_refresh(C.byref(k.struct(4, obs, rew, done)), H.stream()), "rs_rnn_team_eval_post_refresh")
     t.post_refresh(obs)
     torch.cuda.synchronize()
-    _same(k, t)
+    H.same(k, t)
     m = n % 3 == 0
     assert torch.equal(k.stat.count[m], torch.ones(int(m.sum()), A, dtype=torch.float64, device=DEV))
     assert torch.equal(k.stat.mean[m], obs[m][..., 0].double()) and torch.equal(k.cur[m], obs[m])
@@ -263,21 +156,11 @@ def _run(team, sets, obst, seed, fused, carry, runs=R, steps=L):
                                           return_actions=True, carry_hidden_across_runs=carry, fused=fused)
 
 
-def _same_records(res_a, res_b, runs=R):
-    assert len(res_a) == len(res_b)
-    for a, b in zip(res_a, res_b):
-        assert a.id == b.id and a.completed_runs == b.completed_runs == runs and a.success_counter == b.success_counter
-        assert a.total_episode_length == b.total_episode_length
-        for x, y in ((a.successful, b.successful), (a.unsuccessful, b.unsuccessful)):
-            assert x.episode_length == y.episode_length and x.episode_return == y.episode_return
-            assert x.intensity == y.intensity and x.background_intensity == y.background_intensity
-
-
 @pytest.mark.parametrize("A,widths,carry,obst", list(SEEDS), ids=[f"A{a}-{w}-{'carried' if c else 'lane_per_run'}-obst{o}" for a, w, c, o in SEEDS])
 def test_fused_run_equals_the_composed_run(A, widths, carry, obst):
     from radiation_ppo_amd.evaluate import sample_test_environments
     sets = sample_test_environments(E, obstruction_count=obst, seed=SET_SEED)
-    team = _team(A, widths)
+    team = H.team(A, widths)
     assert all(ag.agent.fused_policy == (widths == "default") and ag.agent.fused_pfgru == (widths == "default") for ag in team.values())
     seed = SEEDS[A, widths, carry, obst]
     res_f, sum_f, act_f = _run(team, sets, obst, seed, True, carry)
@@ -291,32 +174,41 @@ def test_fused_run_equals_the_composed_run(A, widths, carry, obst):
     assert int(act_f.min()) >= 0 and (act_f < 8).any()
     assert ((act_f == 8).all(axis=2) | (act_f < 8).all(axis=2)).all()                     # a lane's agents idle together
     assert sum_f["completed_runs"] == sum_c["completed_runs"] == E * R and len(res_f) == E
-    _same_records(res_f, res_c)
+    H.same_records(res_f, res_c, R)
     assert sum_f["success_rate"] == sum_c["success_rate"]
     n_success = sum(r.success_counter for r in res_f)
     timed_out = sum(l == L for r in res_f for l in r.unsuccessful.episode_length)
     assert 0 < n_success < E * R and timed_out > 0, (n_success, timed_out)
 
 
-@pytest.mark.parametrize("carry", [True, False], ids=["carried", "lane_per_run"])
-def test_one_agent_through_the_team_runner_equals_the_rnn_runner(carry):
-    """A = 1: recurrent_team_start is recurrent_start (same bank, same h0, bit for bit) and the team runner's fused run equals
-    run_test_environments_rnn's, records and log."""
+def test_recurrent_team_start_with_one_agent_is_recurrent_start():
+    """A = 1: recurrent_team_start is recurrent_start -- same bank, same h0, bit for bit"""
     from radiation_ppo_amd import evaluate as ev
-    team = _team(1)
+    team = H.team(1)
     dev = torch.device(DEV)
     bank1, hid1 = ev.recurrent_start(team[0].agent, 50, 3, dev, "hip")
     bankt, hidt = ev.recurrent_team_start(team, 50, 3, dev, "hip")
     assert hidt.shape == (1, 50, 24) and torch.equal(hidt[0], hid1) and torch.equal(bankt.h, bank1.h) and torch.equal(bankt.p, bank1.p)
     assert torch.equal(bankt._base, bank1._base) and torch.equal(bankt.episode, bank1.episode) and bankt.cells[0] is team[0].agent.model
-    obst, seed = 2, 20
-    sets = ev.sample_test_environments(E, obstruction_count=obst, seed=SET_SEED)
-    res_t, sum_t, act_t = _run(team, sets, obst, seed, True, carry)
-    res_1, sum_1, act_1 = ev.run_test_environments_rnn(team[0], sets, montecarlo_runs=R, steps_per_episode=L, obstruction_count=obst, seed=seed,
-                                                       return_actions=True, carry_hidden_across_runs=carry, fused=True)
-    assert act_t.shape == act_1.shape + (1,) and np.array_equal(act_t[:, :, 0], act_1) and (act_1 < 8).any()
-    _same_records(res_t, res_1)
-    assert sum_t["success_rate"] == sum_1["success_rate"] and sum_t["completed_runs"] == E * R
+
+
+PARENT = K.maker("make_rnn_eval_parent")         # the recorder: its cases, its run() and its encoding
+
+
+@pytest.mark.parametrize("case", list(PARENT.CASES), ids=[PARENT.name(*c) for c in PARENT.CASES])
+def test_one_agent_runs_equal_the_parent_commits(case):
+    """tests/golden/rnn_eval_parent.npz holds what run_test_environments_rnn (fused and composed) and run_test_environments computed
+    for one recurrent agent before they became fronts to the team runner: today's results equal it member by member -- keys, dtype,
+    shape, bytes: every field of the records, the returns as float32 bits, the fused run's action log."""
+    want = np.load(PARENT.OUT)
+    tag = "." + PARENT.name(*case) + "."
+    keys = sorted(k for k in want.files if tag in k)
+    got = PARENT.run(case)
+    assert sorted(got) == keys and "rnn_fused" + tag + "log" in keys and "rnn_composed" + tag + "id" in keys
+    assert ("plain" + tag + "id" in keys) == (case in PARENT.PLAIN)
+    for k in keys:
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and got[k].tobytes() == want[k].tobytes(), k
+    assert (got["rnn_fused" + tag + "log"] < 8).any()
 
 
 def test_fused_sequential_team_run_replays_through_the_oracle(monkeypatch):
@@ -329,7 +221,7 @@ def test_fused_sequential_team_run_replays_through_the_oracle(monkeypatch):
     A, obst = 2, 2
     seed = SEEDS[A, "default", True, obst]
     sets = ev.sample_test_environments(E, obstruction_count=obst, seed=SET_SEED)
-    team = _team(A)
+    team = H.team(A)
     calls = {"h0": 0, "bank_reset": 0}
     br = PredictorBank.reset
     for ag in team.values():
@@ -339,33 +231,7 @@ def test_fused_sequential_team_run_replays_through_the_oracle(monkeypatch):
     results, summary, actions = _run(team, sets, obst, seed, True, True)
     assert calls == {"h0": A, "bank_reset": 1}
     assert summary["completed_runs"] == E * R and actions.shape[1:] == (E, A) and 0 < sum(r.success_counter for r in results) < E * R
-    for e, res in enumerate(results):
-        s = sets[f"env_{e}"]
-        rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]]
-        ref = RadSearchOracle(PhiloxDraws(seed, e), number_agents=A, obstruction_count=obst, enforce_grid_boundaries=True)
-        ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-        lens, rets, sucs = [], [], []
-        ret, steps = np.float32(0.0), 0
-        t_end = actions.shape[0]
-        for t in range(actions.shape[0]):
-            if actions[t, e, 0] == 8:
-                t_end = t
-                break
-            o, rew, done, _ = ref.step({a: int(actions[t, e, a]) for a in range(A)})
-            ret = np.float32(ret + np.float32(rew["individual_reward"][0]))
-            steps += 1
-            found = any(done[a] for a in range(A))
-            if found or steps == L:
-                lens.append(steps); rets.append(float(ret)); sucs.append(bool(found))
-                ret, steps = np.float32(0.0), 0
-                ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-        assert (actions[t_end:, e] == 8).all(), e                   # a lane with every run behind it idles to the end
-        assert len(lens) == R and res.total_episode_length == lens, (e, lens, res.total_episode_length)
-        assert res.success_counter == sum(sucs)
-        assert res.successful.episode_length == [l for l, k in zip(lens, sucs) if k]
-        assert res.unsuccessful.episode_length == [l for l, k in zip(lens, sucs) if not k]
-        assert np.allclose(res.successful.episode_return, [r for r, k in zip(rets, sucs) if k], atol=1e-4)
-        assert np.allclose(res.unsuccessful.episode_return, [r for r, k in zip(rets, sucs) if not k], atol=1e-4)
+    H.replays_through_the_oracle(sets, results, actions, seed, obst, R, L)
 
 
 def test_the_team_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
@@ -376,7 +242,7 @@ def test_the_team_run_stops_on_the_device_side_count_at_the_next_sixteenth_step(
     its runs took, then 8; the host reads the finished-lane count every 16 lock-steps: 16 rows."""
     Es, Rs, A = 3, 4, 2
     sets = {f"env_{i}": (np.array([1350.0, 1350.0]), np.array([1353.0, 1354.0]), 2_000_000 + 1000 * i, 20 + i) for i in range(Es)}
-    team = _team(A)
+    team = H.team(A)
     for carry in (True, False):
         results, summary, actions = _run(team, sets, 0, 5, True, carry, runs=Rs, steps=40)
         assert actions.shape == (16, Es if carry else Es * Rs, A), (carry, actions.shape)
@@ -395,7 +261,7 @@ def test_the_team_runner_refuses_what_it_cannot_serve():
     from radiation_ppo_amd.rada2c import RNNAgentPPO
     sets = {"env_0": (np.array([1350.0, 1350.0]), np.array([400.0, 400.0]), 2_000_000, 20)}
     kw = dict(montecarlo_runs=2, steps_per_episode=5)
-    team = _team(2)
+    team = H.team(2)
     with pytest.raises(ValueError):
         run_test_environments_rnn_team({1: team[0], 2: team[1]}, sets, **kw)                                  # ids must be 0..A-1
     with pytest.raises(ValueError):
@@ -403,7 +269,7 @@ def test_the_team_runner_refuses_what_it_cannot_serve():
     with pytest.raises(ValueError):
         run_test_environments_rnn_team({i: team[0] for i in range(9)}, sets, **kw)                            # more than RS_MAX_AGENTS
     with pytest.raises(ValueError):
-        run_test_environments_rnn_team({0: team[0], 1: _team(1, "sized")[0]}, sets, **kw)                     # mixed widths
+        run_test_environments_rnn_team({0: team[0], 1: H.team(1, "sized")[0]}, sets, **kw)                     # mixed widths
     wide = {i: RNNAgentPPO(id=i, actor_critic_args=_args(80, 32, 32, 24)) for i in range(2)}                  # the sized step serves 1..64 units
     assert not wide[0].agent.fused_policy and not wide[0].agent.sized_policy
     with pytest.raises(ValueError):
@@ -450,5 +316,7 @@ def test_evaluate_ppo_driver_reaches_the_team_runner(tmp_path, monkeypatch):
     with pytest.raises(ValueError):
         ev_mod.evaluate_PPO(dict(kw, team_mode="team")).evaluate()
     del seen[:]
-    results, summary = ev_mod.evaluate_PPO(dict(kw, number_of_agents=1)).evaluate()                           # one agent: today's path
-    assert not seen and len(seen_one) == 1 and hasattr(seen_one[0][0].agent, "gru_cell") and summary["completed_runs"] == 3 * 4
+    results, summary = ev_mod.evaluate_PPO(dict(kw, number_of_agents=1)).evaluate()                           # one agent: through the front
+    assert len(seen_one) == 1 and hasattr(seen_one[0][0].agent, "gru_cell") and summary["completed_runs"] == 3 * 4
+    (agents, k), = seen                                         # the front's own call of the team runner, and no other
+    assert list(agents) == [0] and agents[0] is seen_one[0][0] and k["fused"] is True and k["carry_hidden_across_runs"] is True

@@ -845,6 +845,39 @@ typedef struct { const float *w1, *b1, *w2, *b2, *w3, *b3; } rs_cnn_head_params;
 int rs_cnn_team_eval_head(const rs_cnn_head_params* heads, int32_t num_agents, const float* a2, const float* u, const uint8_t* alive,
                           int8_t* act8, int64_t* act, float* logp, float* y1_out, int32_t num_envs, rs_stream_t stream);
 
+/* ---- The same evaluation for square maps of any side 8 <= map_side (M) <= 256: the maps without enforced walls, 147 x 147 for 120-step
+ * episodes (radiation_ppo_amd/evaluate.py: run_test_environments_cnn_team_sized).  One lock-step is rs_action_uniforms, rs_pfgru_step
+ * (every owner), rs_maps_update, rs_maps_stack, then per chunk of lanes rs_cnn_sized_team_infer and rs_cnn_sized_team_eval_head (the
+ * chunk bounds the a2 scratch: 16 P P floats per lane and agent, P = M / 2), rs_step, rs_eval_post_step on one stream.
+ *
+ * rs_cnn_sized_team_infer: every agent's actor trunk in one launch of the tiled trunk (rs_cnn_sized.hip), a persistent grid over the
+ * (agent, image, tile) units; the arithmetic is rs_cnn_sized_infer's: the result equals num_agents calls of it (agent = a, a's weights)
+ * bit for bit.  A unit whose staged 38 x 38 x 4 input window holds nothing but zeros (every element == 0.0f) and neither of the agent's
+ * two cells does not evaluate conv1: its pooled cells are max(0 + b1, 0), which is what conv1 gives there, bit for bit.
+ *   maps [S][4][M*M]          the shared maps (rs_maps_stack's critic stack)
+ *   cells, pcells [S][A]      int32: the heat maps' own "cell" / "pred_cell" fields (rs_maps_field), -1 = none
+ *   convs [A]                 host array (device pointers inside), torch layouts: w1 [8][6][3][3], b1 [8], w2 [16][8][3][3], b2 [16]
+ *   a2 [A][S][16*P*P]         every agent's flattened trunk output
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL pointer (those inside the first num_agents convs included), num_agents outside
+ * 1..RS_MAX_AGENTS, num_samples < 0; a side outside [8, 256] returns RS_ERR_UNSUPPORTED; num_samples == 0 returns RS_OK and launches
+ * nothing. */
+typedef struct { const float *w1, *b1, *w2, *b2; } rs_cnn_conv_params;
+int rs_cnn_sized_team_infer(const float* maps, const int32_t* cells, const int32_t* pcells, int32_t num_agents, int64_t num_samples,
+                            int32_t map_side, const rs_cnn_conv_params* convs, float* a2, rs_stream_t stream);
+
+/* rs_cnn_sized_team_eval_head: rs_cnn_team_eval_head with the first layer's depth as an argument, Linear(flat, 32) with flat = 16 p p for
+ * an integer p in 4..128: grid = (64-image tiles, agent), four waves on a quarter of k each, exact f32 matrix cores, the four partial
+ * sums added in wave order, then the bias (no atomics; an image's bits depend on neither num_envs nor the grid), then rs_cnn_head's
+ * arithmetic (out_dim 8) operation for operation and the evaluation's idle rule.
+ *   heads [A]             as rs_cnn_team_eval_head's, w1 [32][flat]
+ *   a2 [A][N][flat]       rs_cnn_sized_team_infer's output (N = num_envs)
+ *   u [N][A], alive [N], act8 [N][A], act [A][N], logp [A][N], y1_out [A][N][32]   as rs_cnn_team_eval_head's; a caller that walks its
+ *                         lanes in chunks passes each chunk's own rows (u, alive, act8 offset by the chunk's first lane)
+ * RS_ERR_INVALID_ARG, before anything is launched: flat not 16 p p with p in 4..128, and what rs_cnn_team_eval_head refuses. */
+int rs_cnn_sized_team_eval_head(const rs_cnn_head_params* heads, int32_t num_agents, int32_t flat, const float* a2, const float* u,
+                                const uint8_t* alive, int8_t* act8, int64_t* act, float* logp, float* y1_out, int32_t num_envs,
+                                rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

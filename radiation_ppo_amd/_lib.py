@@ -73,6 +73,11 @@ class RsCnnHeadParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
 
+class RsCnnConvParams(C.Structure):
+    """rs_cnn_conv_params (include/radsearch.h): a CNN actor's two convolutions in torch's layouts."""
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2")]
+
+
 class RsRolloutArgs(C.Structure):
     _fields_ = [("steps_per_epoch", C.c_int32), ("steps_per_episode", C.c_int32)] + [
         (n, C.c_void_p) for n in ("obs", "act", "logp", "val", "rew", "last_val", "cut", "source_tar", "cur_obs", "w_count",
@@ -204,6 +209,10 @@ SYMBOLS = [
     # the RAD-TEAM (CNN) evaluation's two entries (the header lists them last; this list's order binds nothing)
     ("rs_cnn_team_trunk_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rs_cnn_team_eval_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]),
+    # ... and their forms for maps of any side (walls off)
+    ("rs_cnn_sized_team_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.POINTER(RsCnnConvParams),
+                                          C.c_void_p, C.c_void_p]),
+    ("rs_cnn_sized_team_eval_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]),
     ("rs_rnn_team_eval_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
     ("rs_rnn_team_eval_post_step", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),
     ("rs_rnn_team_eval_post_refresh", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),

@@ -16,6 +16,9 @@
 //
 // Not fused into the trunk on purpose: a trunk workgroup holds 3 images, so W1 (346 KB per agent) would be re-read from L2 once per 3
 // images = 115 KB per image, where the a2 round trip it would save is 21.6 KB per image.
+//
+// rs_cnn_sized_team_eval_head (run_test_environments_cnn_team_sized): the same scheme at a run-time depth 16 p p for the tiled trunk's
+// maps of any side; it shares the MFMA step and everything behind the k loop (eh_step, eh_finish) and has a kernel of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -40,73 +43,26 @@ struct EhNets {
     rs_cnn_head_params head[RS_MAX_AGENTS];
 };
 
-__global__ void __launch_bounds__(EH_NT) rs_cnn_team_eval_head_kernel(EhNets nets, int A, const float* __restrict__ a2,
-                                                                      const float* __restrict__ u, const uint8_t* __restrict__ alive,
-                                                                      int8_t* __restrict__ act8, int64_t* __restrict__ act,
-                                                                      float* __restrict__ logp, float* __restrict__ y1_out, int N) {
-    __shared__ __align__(16) float part[EH_WAVES][EH_TILE][EH_ROW];
+// eight MFMAs: one float4 of W1 (A operand) against the same float4 of the two 32-image tiles (B operands)
+__device__ __forceinline__ void eh_step(v16f& acc0, v16f& acc1, const float4& w, const float4& a, const float4& b) {
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, a.x, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, b.x, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, a.y, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, b.y, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, a.z, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, b.z, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, a.w, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, b.w, acc1, 0, 0, 0);
+}
+
+// Behind the k loop, the same for every depth: the waves' partial sums meet in LDS; wave 0 adds them in wave order, then the bias, and
+// runs rs_cnn_head_kernel<8>'s arithmetic, the draw and the idle rule, one image per lane.
+__device__ __forceinline__ void eh_finish(float (*part)[EH_TILE][EH_ROW], const v16f& acc0, const v16f& acc1, const rs_cnn_head_params& P,
+                                          int ag, int A, int n0, const float* __restrict__ u, const uint8_t* __restrict__ alive,
+                                          int8_t* __restrict__ act8, int64_t* __restrict__ act, float* __restrict__ logp,
+                                          float* __restrict__ y1_out, int N) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const int ag = blockIdx.y;
-    const rs_cnn_head_params P = nets.head[ag];
-    const int n0 = blockIdx.x * EH_TILE;
-    // rows past the last image read the last image's (their sums are dropped)
-    const int na = n0 + r < N ? n0 + r : N - 1, nb = n0 + 32 + r < N ? n0 + 32 + r : N - 1;
-    const float* wp = P.w1 + (size_t)r * FLAT + wave * EH_KW + 16 * h;
-    const float* xa = a2 + ((size_t)ag * N + na) * FLAT + wave * EH_KW + 16 * h;
-    const float* xb = a2 + ((size_t)ag * N + nb) * FLAT + wave * EH_KW + 16 * h;
-    v16f acc0, acc1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
-    auto step = [&](const float4& w, const float4& a, const float4& b) {
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, a.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, b.x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, a.y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, b.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, a.z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, b.z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, a.w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, b.w, acc1, 0, 0, 0);
-    };
-    // a piece = 32 floats of the wave's k range: 16 per lane half, four float4s per operand and lane (64 contiguous bytes of its row).
-    // Two pieces live in registers: piece g + 2 is requested as soon as piece g has been issued to the matrix cores, so ~12 KB per
-    // wave are in flight under the 32 MFMAs (2048 cycles) of a piece -- one request per trip left the kernel waiting on HBM latency
-    struct Piece { float4 w[4], a[4], b[4]; };
-    auto fetch = [&](Piece& q, int g) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            q.w[i] = *reinterpret_cast<const float4*>(wp + 32 * g + 4 * i);
-            q.a[i] = *reinterpret_cast<const float4*>(xa + 32 * g + 4 * i);
-            q.b[i] = *reinterpret_cast<const float4*>(xb + 32 * g + 4 * i);
-        }
-    };
-    auto consume = [&](const Piece& q) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) step(q.w[i], q.a[i], q.b[i]);
-    };
-    Piece p0, p1;
-    fetch(p0, 0);
-    fetch(p1, 1);
-#pragma unroll 1
-    for (int g = 0; g < EH_PIECES - 1; g += 2) {                    // pieces 0 .. 19 in pairs, piece 20 behind the loop
-        consume(p0);
-        __builtin_amdgcn_sched_barrier(0);
-        fetch(p0, g + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        consume(p1);
-        __builtin_amdgcn_sched_barrier(0);
-        fetch(p1, g + 3 < EH_PIECES ? g + 3 : EH_PIECES - 1);       // (the last trip re-requests piece 20; it is dropped)
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    consume(p0);
-    {   // the range's last four floats, 672 .. 675: on the lower half; the upper half re-reads floats of piece 20 and feeds zeros
-        const int o = 32 * EH_PIECES - 32 * h;
-        float4 w = *reinterpret_cast<const float4*>(wp + o);
-        float4 a = *reinterpret_cast<const float4*>(xa + o);
-        float4 b = *reinterpret_cast<const float4*>(xb + o);
-        if (h) { w = make_float4(0.f, 0.f, 0.f, 0.f); a = w; b = w; }
-        step(w, a, b);
-    }
     // C layout: register i of lane (r, h) is neuron (i & 3) + 8 (i >> 2) + 4 h of image r
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -174,6 +130,144 @@ __global__ void __launch_bounds__(EH_NT) rs_cnn_team_eval_head_kernel(EhNets net
     }
 }
 
+__global__ void __launch_bounds__(EH_NT) rs_cnn_team_eval_head_kernel(EhNets nets, int A, const float* __restrict__ a2,
+                                                                      const float* __restrict__ u, const uint8_t* __restrict__ alive,
+                                                                      int8_t* __restrict__ act8, int64_t* __restrict__ act,
+                                                                      float* __restrict__ logp, float* __restrict__ y1_out, int N) {
+    __shared__ __align__(16) float part[EH_WAVES][EH_TILE][EH_ROW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int ag = blockIdx.y;
+    const rs_cnn_head_params P = nets.head[ag];
+    const int n0 = blockIdx.x * EH_TILE;
+    // rows past the last image read the last image's (their sums are dropped)
+    const int na = n0 + r < N ? n0 + r : N - 1, nb = n0 + 32 + r < N ? n0 + 32 + r : N - 1;
+    const float* wp = P.w1 + (size_t)r * FLAT + wave * EH_KW + 16 * h;
+    const float* xa = a2 + ((size_t)ag * N + na) * FLAT + wave * EH_KW + 16 * h;
+    const float* xb = a2 + ((size_t)ag * N + nb) * FLAT + wave * EH_KW + 16 * h;
+    v16f acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
+    auto step = [&](const float4& w, const float4& a, const float4& b) { eh_step(acc0, acc1, w, a, b); };
+    // a piece = 32 floats of the wave's k range: 16 per lane half, four float4s per operand and lane (64 contiguous bytes of its row).
+    // Two pieces live in registers: piece g + 2 is requested as soon as piece g has been issued to the matrix cores, so ~12 KB per
+    // wave are in flight under the 32 MFMAs (2048 cycles) of a piece -- one request per trip left the kernel waiting on HBM latency
+    struct Piece { float4 w[4], a[4], b[4]; };
+    auto fetch = [&](Piece& q, int g) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            q.w[i] = *reinterpret_cast<const float4*>(wp + 32 * g + 4 * i);
+            q.a[i] = *reinterpret_cast<const float4*>(xa + 32 * g + 4 * i);
+            q.b[i] = *reinterpret_cast<const float4*>(xb + 32 * g + 4 * i);
+        }
+    };
+    auto consume = [&](const Piece& q) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) step(q.w[i], q.a[i], q.b[i]);
+    };
+    Piece p0, p1;
+    fetch(p0, 0);
+    fetch(p1, 1);
+#pragma unroll 1
+    for (int g = 0; g < EH_PIECES - 1; g += 2) {                    // pieces 0 .. 19 in pairs, piece 20 behind the loop
+        consume(p0);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(p0, g + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        consume(p1);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(p1, g + 3 < EH_PIECES ? g + 3 : EH_PIECES - 1);       // (the last trip re-requests piece 20; it is dropped)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    consume(p0);
+    {   // the range's last four floats, 672 .. 675: on the lower half; the upper half re-reads floats of piece 20 and feeds zeros
+        const int o = 32 * EH_PIECES - 32 * h;
+        float4 w = *reinterpret_cast<const float4*>(wp + o);
+        float4 a = *reinterpret_cast<const float4*>(xa + o);
+        float4 b = *reinterpret_cast<const float4*>(xb + o);
+        if (h) { w = make_float4(0.f, 0.f, 0.f, 0.f); a = w; b = w; }
+        step(w, a, b);
+    }
+    eh_finish(part, acc0, acc1, P, ag, A, n0, u, alive, act8, act, logp, y1_out, N);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rs_cnn_sized_team_eval_head: the same scheme with the depth as an argument, flat = 16 p p (p = 4..128: the tiled trunk's output,
+// rs_cnn_sized.hip; 85 264 at 147 x 147 maps).  Wave w owns k in [kw w, kw w + kw), kw = flat / 4 = 4 p p: np = kw / 32 whole pieces
+// (at least 2: p = 4 gives 2, p = 5 gives 3, p = 73 gives 666), which the two-pieces-in-flight loop takes in pairs with the odd one
+// behind it, and a tail of kw % 32 floats: 0 (p % 4 == 0), 16 (p % 4 == 2: two float4 steps, floats 0..7 on the lower lane half and 8..15
+// on the upper) or 4 (p odd: one float4 step on the lower half while the upper feeds zeros, as the 2704 kernel's).  Every row of a2 and
+// W1 is 64-byte aligned and every wave's range 16-byte aligned, so all loads are float4s.  A kernel of its own: the 2704 kernel keeps
+// its compile-time trip counts and its measured numbers.  No scratch; 196 VGPRs with the accumulators (two waves per SIMD, <= 256);
+// 4 x 64 x 36 floats of LDS.
+__global__ void __launch_bounds__(EH_NT) rs_cnn_sized_team_eval_head_kernel(EhNets nets, int A, int flat, const float* __restrict__ a2,
+                                                                            const float* __restrict__ u, const uint8_t* __restrict__ alive,
+                                                                            int8_t* __restrict__ act8, int64_t* __restrict__ act,
+                                                                            float* __restrict__ logp, float* __restrict__ y1_out, int N) {
+    __shared__ __align__(16) float part[EH_WAVES][EH_TILE][EH_ROW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int ag = blockIdx.y;
+    const rs_cnn_head_params P = nets.head[ag];
+    const int n0 = blockIdx.x * EH_TILE;
+    const int kw = flat / EH_WAVES, np = kw / 32, tail = kw - 32 * np;
+    // rows past the last image read the last image's (their sums are dropped)
+    const int na = n0 + r < N ? n0 + r : N - 1, nb = n0 + 32 + r < N ? n0 + 32 + r : N - 1;
+    const float* wp = P.w1 + (size_t)r * flat + (size_t)wave * kw;
+    const float* xa = a2 + ((size_t)ag * N + na) * flat + (size_t)wave * kw;
+    const float* xb = a2 + ((size_t)ag * N + nb) * flat + (size_t)wave * kw;
+    v16f acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
+    struct Piece { float4 w[4], a[4], b[4]; };
+    auto fetch = [&](Piece& q, int g) {                               // the lane half's 16 floats of piece g
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int o = 32 * g + 16 * h + 4 * i;
+            q.w[i] = *reinterpret_cast<const float4*>(wp + o);
+            q.a[i] = *reinterpret_cast<const float4*>(xa + o);
+            q.b[i] = *reinterpret_cast<const float4*>(xb + o);
+        }
+    };
+    auto consume = [&](const Piece& q) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) eh_step(acc0, acc1, q.w[i], q.a[i], q.b[i]);
+    };
+    Piece p0, p1;
+    fetch(p0, 0);
+    fetch(p1, 1);
+    int g = 0;
+#pragma unroll 1
+    for (; g + 2 < np; g += 2) {                                      // p0 holds piece g, p1 piece g + 1, both with a successor
+        consume(p0);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(p0, g + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        consume(p1);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(p1, g + 3 < np ? g + 3 : np - 1);                       // (an odd np re-requests its last piece; it is dropped)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    consume(p0);                                                      // the last two pieces, or the last one
+    if (g + 1 < np) consume(p1);
+    if (tail == 16) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int o = 32 * np + 8 * h + 4 * i;
+            eh_step(acc0, acc1, *reinterpret_cast<const float4*>(wp + o), *reinterpret_cast<const float4*>(xa + o),
+                    *reinterpret_cast<const float4*>(xb + o));
+        }
+    } else if (tail == 4) {                                           // both halves read the float4; the upper half feeds zeros
+        const int o = 32 * np;
+        float4 w = *reinterpret_cast<const float4*>(wp + o);
+        float4 a = *reinterpret_cast<const float4*>(xa + o);
+        float4 b = *reinterpret_cast<const float4*>(xb + o);
+        if (h) { w = make_float4(0.f, 0.f, 0.f, 0.f); a = w; b = w; }
+        eh_step(acc0, acc1, w, a, b);
+    }
+    eh_finish(part, acc0, acc1, P, ag, A, n0, u, alive, act8, act, logp, y1_out, N);
+}
+
 }  // namespace
 
 extern "C" {
@@ -187,6 +281,22 @@ int rs_cnn_team_eval_head(const rs_cnn_head_params* heads, int32_t num_agents, c
     for (int a = 0; a < RS_MAX_AGENTS; ++a) nets.head[a] = heads[a < num_agents ? a : 0];     // the slots behind the team repeat agent 0 (never read)
     hipLaunchKernelGGL(rs_cnn_team_eval_head_kernel, dim3((num_envs + EH_TILE - 1) / EH_TILE, num_agents), dim3(EH_NT), 0,
                        static_cast<hipStream_t>(stream), nets, (int)num_agents, a2, u, alive, act8, act, logp, y1_out, (int)num_envs);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_cnn_sized_team_eval_head(const rs_cnn_head_params* heads, int32_t num_agents, int32_t flat, const float* a2, const float* u,
+                                const uint8_t* alive, int8_t* act8, int64_t* act, float* logp, float* y1_out, int32_t num_envs,
+                                rs_stream_t stream) {
+    if (!heads || !a2 || !u || !alive || !act8 || num_agents < 1 || num_agents > RS_MAX_AGENTS || num_envs < 1) return RS_ERR_INVALID_ARG;
+    for (int a = 0; a < num_agents; ++a)
+        if (!heads[a].w1 || !heads[a].b1 || !heads[a].w2 || !heads[a].b2 || !heads[a].w3 || !heads[a].b3) return RS_ERR_INVALID_ARG;
+    int p = 4;
+    while (p < 128 && 16 * p * p < flat) ++p;
+    if (16 * p * p != flat) return RS_ERR_INVALID_ARG;                // the tiled trunk's output: 16 p p, p = 4..128
+    EhNets nets;
+    for (int a = 0; a < RS_MAX_AGENTS; ++a) nets.head[a] = heads[a < num_agents ? a : 0];     // the slots behind the team repeat agent 0 (never read)
+    hipLaunchKernelGGL(rs_cnn_sized_team_eval_head_kernel, dim3((num_envs + EH_TILE - 1) / EH_TILE, num_agents), dim3(EH_NT), 0,
+                       static_cast<hipStream_t>(stream), nets, (int)num_agents, (int)flat, a2, u, alive, act8, act, logp, y1_out, (int)num_envs);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -16,7 +16,9 @@
 //   * backward: dW2 = dZ2 x patches(P1) and db2 on threads (output channel, input channel, half tile), dP1 = conv2^T(dZ2) per pooled cell, gated by
 //     P1 > 0, dW1 through the pool's arg-max (one of the four conv1 pixels of a cell carries gradient) on threads (output channel,
 //     plane pair, tile row).  Accumulators stay in registers across all tiles of a workgroup, which writes one slab row at the end
-//     (fixed-order reduction, no atomics: bit-identical from one run to the next).
+//     (fixed-order reduction, no atomics: bit-identical from one run to the next);
+//   * the Monte-Carlo evaluation's team forward (rs_sized_team_fwd, rs_cnn_sized_team_infer): every agent's actor trunk in one launch
+//     over (image, tile, agent) units, the same unit function, conv1 skipped over empty input windows (bit for bit: fwd_unit).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -46,10 +48,13 @@ struct SzIn {
 
 // the four dense planes of image s over the window [r0, r0 + W) x [c0, c0 + W) into LDS (zero outside the map), BATCH loads in flight
 // per thread at a time (all ~20 at once held their 64-bit addresses too and pushed the forward kernel past its VGPR budget)
+// Returns whether any staged element compares unequal to 0.0f (a NaN does, -0.0f does not): the team kernel's empty-window test; the
+// other kernels drop the value and the compiler the comparisons.
 template <int W>
-__device__ __forceinline__ void stage_window(const SzIn& in, long long s, int r0, int c0, float* xs) {
+__device__ __forceinline__ bool stage_window(const SzIn& in, long long s, int r0, int c0, float* xs) {
     constexpr int N = DP * W * W, PER = (N + NT - 1) / NT, BATCH = 8;
     const float* src = in.maps + (size_t)s * DP * in.M * in.M;
+    bool nz = false;
 #pragma unroll
     for (int i0 = 0; i0 < PER; i0 += BATCH) {
         float v[BATCH];
@@ -64,8 +69,10 @@ __device__ __forceinline__ void stage_window(const SzIn& in, long long s, int r0
         for (int i = 0; i < BATCH; ++i) {
             const int e = threadIdx.x + (i0 + i) * NT;
             if (i0 + i < PER && e < N) xs[e] = v[i];
+            nz |= v[i] != 0.0f;
         }
     }
+    return nz;
 }
 
 __device__ __forceinline__ void owner_cells(const SzIn& in, long long s, int& loc, int& pc) {
@@ -79,147 +86,219 @@ __device__ __forceinline__ void owner_cells(const SzIn& in, long long s, int& lo
 // ------------------------------------------------------------------------------------------------
 // Forward: maps -> a2 [S][16 P P] (torch Flatten order c P P + y P + x); TRAIN also writes p1 [S][P P][8], amax [S][P P][8] (0..3,
 // row-major, first maximum) and relu_mask [S][P P] (bit c = a2 channel c > 0), the schema of K9 with P P in place of 169.
+
+// The LDS of a forward workgroup; stl [which][tap][co] holds the actor's one-hot stamps: prediction, location - others.
+struct FwdLds {
+    __align__(16) float xs[DP * FWS * FWS];                   // input window, [plane][38][38]
+    float ps[C1 * HC];                                        // P1 with halo, [ci][18][18]
+    float stl[2 * 9 * C1];
+};
+
+__device__ __forceinline__ void fwd_stamps(const float* __restrict__ w1, float* stl) {
+    const int tid = threadIdx.x;
+    if (tid < 2 * 9 * C1) {
+        const int which = tid / (9 * C1), kk = (tid % (9 * C1)) / C1, co = tid % C1;
+        stl[tid] = which == 0 ? w1[(co * 6 + 0) * 9 + kk] : w1[(co * 6 + 1) * 9 + kk] - w1[(co * 6 + 2) * 9 + kk];
+    }
+}
+
+// One (image, tile) unit of the forward pass, by the whole workgroup; loc / pc: the owner's cells (-1: none), stl: its stamps.
+// SKIP (the evaluation's team kernel): a unit whose staged window holds nothing but zeros and neither cell does not evaluate conv1.
+// There every conv1 accumulator is +0 (they start at +0 and fmaf(w, +-0, +0) = +0), so every pooled cell inside the map is
+// max(0 + b1, 0), the maximum of four equal values: the same bits.  One block-wide OR decides, uniform over the workgroup.
+template <int CIN, bool TRAIN, bool SKIP>
+__device__ __forceinline__ void fwd_unit(const SzIn& in, long long s, int tile, int loc, int pc, const float* __restrict__ w1,
+                                         const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+                                         float* __restrict__ a2, float* __restrict__ p1g, uint8_t* __restrict__ amax,
+                                         uint16_t* __restrict__ relu_mask, FwdLds& lds) {
+    float* xs = lds.xs;
+    float* ps = lds.ps;
+    const float* stl = lds.stl;
+    constexpr int CH0 = (CIN == 6) ? 2 : 0;                   // logical channel of dense plane 0 (actor: `others`, convolved as `combined`)
+    const int tid = threadIdx.x, M = in.M, P = in.P, PP = P * P;
+    const int ty0 = (tile / in.ntile) * TS, tx0 = (tile % in.ntile) * TS;
+    // the weight addresses as values of this iteration: loop-invariant, hipcc hoisted the scalar weight loads out of the tile loop
+    cmem_t w1c = as_cmem(w1), b1c = as_cmem(b1), w2c = as_cmem(w2), b2c = as_cmem(b2);
+    asm volatile("" : "+s"(w1c), "+s"(b1c), "+s"(w2c), "+s"(b2c));
+    const bool nz = stage_window<FWS>(in, s, 2 * ty0 - 3, 2 * tx0 - 3, xs);
+    bool dense = true;
+    if (SKIP) {
+        auto inside = [&](int at) {
+            const int r = at / M - (2 * ty0 - 3), c = at % M - (2 * tx0 - 3);
+            return at >= 0 && r >= 0 && r < FWS && c >= 0 && c < FWS;
+        };
+        dense = __syncthreads_or(nz || inside(loc) || inside(pc)) != 0;
+    } else {
+        __syncthreads();
+    }
+    if (!dense) {
+        for (int h = tid; h < HC; h += NT) {
+            const int hy = h / HS, hx = h - hy * HS, gy = ty0 - 1 + hy, gx = tx0 - 1 + hx;
+            const bool in_map = gy >= 0 && gy < P && gx >= 0 && gx < P;
+#pragma unroll
+            for (int co = 0; co < C1; ++co) ps[co * HC + h] = in_map ? fmaxf(0.0f + b1c[co], 0.0f) : 0.0f;
+        }
+    }
+    // ---- conv1 + bias + ReLU + max-pool for the 18 x 18 halo cells (two passes of the 256 threads)
+#pragma unroll 1
+    for (int h = tid; dense && h < HC; h += NT) {
+        const int hy = h / HS, hx = h - hy * HS, gy = ty0 - 1 + hy, gx = tx0 - 1 + hx;
+        if (gy < 0 || gy >= P || gx < 0 || gx >= P) {
+#pragma unroll
+            for (int co = 0; co < C1; ++co) ps[co * HC + h] = 0.0f;      // conv2's zero padding
+            continue;
+        }
+        float acc[4][C1];
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int co = 0; co < C1; ++co) acc[p][co] = 0.0f;
+        // rolled over (plane, ky): each trip needs 24 weights (3 kx x 8 co) in SGPRs; unrolled, hipcc issued all 288 scalar loads
+        // up front and spilled them
+        const float* xw = xs + 2 * hy * FWS + 2 * hx;
+#pragma unroll 1
+        for (int q = 0; q < DP * 3; ++q) {
+            const int d = q / 3, ky = q - d * 3;
+            float win[2][4];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const float2 a = *reinterpret_cast<const float2*>(&xw[d * FWS * FWS + (i + ky) * FWS]);
+                const float2 c = *reinterpret_cast<const float2*>(&xw[d * FWS * FWS + (i + ky) * FWS + 2]);
+                win[i][0] = a.x; win[i][1] = a.y; win[i][2] = c.x; win[i][3] = c.y;
+            }
+            const cmem_t wq = w1c + (CH0 + d) * 9 + ky * 3;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+                for (int co = 0; co < C1; ++co) {
+                    const float w = wq[co * CIN * 9 + kx];
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) acc[i * 2 + j][co] = __builtin_fmaf(w, win[i][j + kx], acc[i * 2 + j][co]);
+                }
+        }
+        if (CIN == 6) {
+            // a 1 at input (r, c) adds w[ky][kx] to conv pixel (r - ky + 1, c - kx + 1)
+            auto stamp = [&](int at, const float* ws) {
+                const int r = at / M, c = at - r * M, dy = r - 2 * gy, dx = c - 2 * gx;
+                if (dy >= -1 && dy <= 2 && dx >= -1 && dx <= 2) {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const int ky = dy - i + 1, kx = dx - j + 1;
+                            if (ky >= 0 && ky < 3 && kx >= 0 && kx < 3)
+#pragma unroll
+                                for (int co = 0; co < C1; ++co) acc[i * 2 + j][co] += ws[(ky * 3 + kx) * C1 + co];
+                        }
+                }
+            };
+            if (loc >= 0) stamp(loc, stl + 9 * C1);       // -1: no position recorded yet (fresh maps), an empty one-hot
+            if (pc >= 0) stamp(pc, stl);
+        }
+        const bool own = hy >= 1 && hy <= TS && hx >= 1 && hx <= TS;
+        float best[C1];
+        uint32_t pidx[2] = {0u, 0u};
+#pragma unroll
+        for (int co = 0; co < C1; ++co) {
+            const float bb = b1c[co];
+            float bv = fmaxf(acc[0][co] + bb, 0.0f);
+            int idx = 0;
+#pragma unroll
+            for (int p = 1; p < 4; ++p) {
+                const float v = fmaxf(acc[p][co] + bb, 0.0f);
+                if (v > bv) { bv = v; idx = p; }
+            }
+            ps[co * HC + h] = bv;
+            best[co] = bv;
+            pidx[co >> 2] |= (uint32_t)idx << (8 * (co & 3));
+        }
+        if (TRAIN && own) {
+            const size_t cell = (size_t)s * PP + gy * P + gx;
+            float4* dst = reinterpret_cast<float4*>(p1g + cell * C1);
+            dst[0] = make_float4(best[0], best[1], best[2], best[3]);
+            dst[1] = make_float4(best[4], best[5], best[6], best[7]);
+            *reinterpret_cast<uint2*>(amax + cell * C1) = make_uint2(pidx[0], pidx[1]);
+        }
+    }
+    __syncthreads();
+    // ---- conv2 + bias + ReLU: thread = output pixel
+    {
+        const int ly = tid / TS, lx = tid - ly * TS, oy = ty0 + ly, ox = tx0 + lx;
+        if (oy < P && ox < P) {
+            float acc2[C2];
+#pragma unroll
+            for (int co = 0; co < C2; ++co) acc2[co] = b2c[co];
+            const float* pq = ps + ly * HS + lx;
+#pragma unroll 1
+            for (int q = 0; q < C1 * 3; ++q) {           // rolled over (ci, ky): 48 weights per trip
+                const int ci = q / 3, ky = q - ci * 3;
+                const cmem_t wq = w2c + ci * 9 + ky * 3;
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const float v = pq[ci * HC + ky * HS + kx];
+#pragma unroll
+                    for (int co = 0; co < C2; ++co) acc2[co] = __builtin_fmaf(wq[co * 72 + kx], v, acc2[co]);
+                }
+            }
+            uint32_t live = 0u;
+            float* dst = a2 + (size_t)s * C2 * PP + oy * P + ox;
+#pragma unroll
+            for (int co = 0; co < C2; ++co) {
+                const float o = fmaxf(acc2[co], 0.0f);
+                dst[(size_t)co * PP] = o;
+                live |= (o > 0.0f ? 1u : 0u) << co;
+            }
+            if (TRAIN) relu_mask[(size_t)s * PP + oy * P + ox] = (uint16_t)live;
+        }
+    }
+    // the next unit's staging writes xs (and the team kernel stl) only; ps is rewritten after the barrier behind that staging
+}
+
 template <int CIN, bool TRAIN>
 __global__ void __launch_bounds__(NT, 3) rs_sized_trunk_fwd(SzIn in, const float* __restrict__ w1, const float* __restrict__ b1,
                                                            const float* __restrict__ w2, const float* __restrict__ b2,
                                                            float* __restrict__ a2, float* __restrict__ p1g, uint8_t* __restrict__ amax,
                                                            uint16_t* __restrict__ relu_mask) {
-    __shared__ __align__(16) float xs[DP * FWS * FWS];        // input window, [plane][38][38]
-    __shared__ float ps[C1 * HC];                             // P1 with halo, [ci][18][18]
-    __shared__ float stl[2 * 9 * C1];                         // actor: one-hot stamps [which][tap][co]: prediction, location - others
-    constexpr int CH0 = (CIN == 6) ? 2 : 0;                   // logical channel of dense plane 0 (actor: `others`, convolved as `combined`)
-    const int tid = threadIdx.x, M = in.M, P = in.P, PP = P * P;
-    if (CIN == 6 && tid < 2 * 9 * C1) {
-        const int which = tid / (9 * C1), kk = (tid % (9 * C1)) / C1, co = tid % C1;
-        stl[tid] = which == 0 ? w1[(co * 6 + 0) * 9 + kk] : w1[(co * 6 + 1) * 9 + kk] - w1[(co * 6 + 2) * 9 + kk];
-    }
+    __shared__ FwdLds lds;
+    if (CIN == 6) fwd_stamps(w1, lds.stl);
     const int nt2 = in.ntile * in.ntile;
     const long long units = in.S * nt2;
     for (long long u = blockIdx.x; u < units; u += gridDim.x) {
         const long long s = u / nt2;
-        const int tile = (int)(u - s * nt2), ty0 = (tile / in.ntile) * TS, tx0 = (tile % in.ntile) * TS;
         int loc, pc;
         owner_cells(in, s, loc, pc);
-        // the weight addresses as values of this iteration: loop-invariant, hipcc hoisted the scalar weight loads out of the tile loop
-        cmem_t w1c = as_cmem(w1), b1c = as_cmem(b1), w2c = as_cmem(w2), b2c = as_cmem(b2);
-        asm volatile("" : "+s"(w1c), "+s"(b1c), "+s"(w2c), "+s"(b2c));
-        stage_window<FWS>(in, s, 2 * ty0 - 3, 2 * tx0 - 3, xs);
-        __syncthreads();
-        // ---- conv1 + bias + ReLU + max-pool for the 18 x 18 halo cells (two passes of the 256 threads)
-#pragma unroll 1
-        for (int h = tid; h < HC; h += NT) {
-            const int hy = h / HS, hx = h - hy * HS, gy = ty0 - 1 + hy, gx = tx0 - 1 + hx;
-            if (gy < 0 || gy >= P || gx < 0 || gx >= P) {
-#pragma unroll
-                for (int co = 0; co < C1; ++co) ps[co * HC + h] = 0.0f;      // conv2's zero padding
-                continue;
-            }
-            float acc[4][C1];
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int co = 0; co < C1; ++co) acc[p][co] = 0.0f;
-            // rolled over (plane, ky): each trip needs 24 weights (3 kx x 8 co) in SGPRs; unrolled, hipcc issued all 288 scalar loads
-            // up front and spilled them
-            const float* xw = xs + 2 * hy * FWS + 2 * hx;
-#pragma unroll 1
-            for (int q = 0; q < DP * 3; ++q) {
-                const int d = q / 3, ky = q - d * 3;
-                float win[2][4];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const float2 a = *reinterpret_cast<const float2*>(&xw[d * FWS * FWS + (i + ky) * FWS]);
-                    const float2 c = *reinterpret_cast<const float2*>(&xw[d * FWS * FWS + (i + ky) * FWS + 2]);
-                    win[i][0] = a.x; win[i][1] = a.y; win[i][2] = c.x; win[i][3] = c.y;
-                }
-                const cmem_t wq = w1c + (CH0 + d) * 9 + ky * 3;
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-                    for (int co = 0; co < C1; ++co) {
-                        const float w = wq[co * CIN * 9 + kx];
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) acc[i * 2 + j][co] = __builtin_fmaf(w, win[i][j + kx], acc[i * 2 + j][co]);
-                    }
-            }
-            if (CIN == 6) {
-                // a 1 at input (r, c) adds w[ky][kx] to conv pixel (r - ky + 1, c - kx + 1)
-                auto stamp = [&](int at, const float* ws) {
-                    const int r = at / M, c = at - r * M, dy = r - 2 * gy, dx = c - 2 * gx;
-                    if (dy >= -1 && dy <= 2 && dx >= -1 && dx <= 2) {
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) {
-                                const int ky = dy - i + 1, kx = dx - j + 1;
-                                if (ky >= 0 && ky < 3 && kx >= 0 && kx < 3)
-#pragma unroll
-                                    for (int co = 0; co < C1; ++co) acc[i * 2 + j][co] += ws[(ky * 3 + kx) * C1 + co];
-                            }
-                    }
-                };
-                if (loc >= 0) stamp(loc, stl + 9 * C1);       // -1: no position recorded yet (fresh maps), an empty one-hot
-                if (pc >= 0) stamp(pc, stl);
-            }
-            const bool own = hy >= 1 && hy <= TS && hx >= 1 && hx <= TS;
-            float best[C1];
-            uint32_t pidx[2] = {0u, 0u};
-#pragma unroll
-            for (int co = 0; co < C1; ++co) {
-                const float bb = b1c[co];
-                float bv = fmaxf(acc[0][co] + bb, 0.0f);
-                int idx = 0;
-#pragma unroll
-                for (int p = 1; p < 4; ++p) {
-                    const float v = fmaxf(acc[p][co] + bb, 0.0f);
-                    if (v > bv) { bv = v; idx = p; }
-                }
-                ps[co * HC + h] = bv;
-                best[co] = bv;
-                pidx[co >> 2] |= (uint32_t)idx << (8 * (co & 3));
-            }
-            if (TRAIN && own) {
-                const size_t cell = (size_t)s * PP + gy * P + gx;
-                float4* dst = reinterpret_cast<float4*>(p1g + cell * C1);
-                dst[0] = make_float4(best[0], best[1], best[2], best[3]);
-                dst[1] = make_float4(best[4], best[5], best[6], best[7]);
-                *reinterpret_cast<uint2*>(amax + cell * C1) = make_uint2(pidx[0], pidx[1]);
-            }
-        }
-        __syncthreads();
-        // ---- conv2 + bias + ReLU: thread = output pixel
-        {
-            const int ly = tid / TS, lx = tid - ly * TS, oy = ty0 + ly, ox = tx0 + lx;
-            if (oy < P && ox < P) {
-                float acc2[C2];
-#pragma unroll
-                for (int co = 0; co < C2; ++co) acc2[co] = b2c[co];
-                const float* pq = ps + ly * HS + lx;
-#pragma unroll 1
-                for (int q = 0; q < C1 * 3; ++q) {           // rolled over (ci, ky): 48 weights per trip
-                    const int ci = q / 3, ky = q - ci * 3;
-                    const cmem_t wq = w2c + ci * 9 + ky * 3;
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const float v = pq[ci * HC + ky * HS + kx];
-#pragma unroll
-                        for (int co = 0; co < C2; ++co) acc2[co] = __builtin_fmaf(wq[co * 72 + kx], v, acc2[co]);
-                    }
-                }
-                uint32_t live = 0u;
-                float* dst = a2 + (size_t)s * C2 * PP + oy * P + ox;
-#pragma unroll
-                for (int co = 0; co < C2; ++co) {
-                    const float o = fmaxf(acc2[co], 0.0f);
-                    dst[(size_t)co * PP] = o;
-                    live |= (o > 0.0f ? 1u : 0u) << co;
-                }
-                if (TRAIN) relu_mask[(size_t)s * PP + oy * P + ox] = (uint16_t)live;
-            }
-        }
-        // the next tile's staging writes xs only; ps is rewritten after the barrier behind that staging
+        fwd_unit<CIN, TRAIN, false>(in, s, (int)(u - s * nt2), loc, pc, w1, b1, w2, b2, a2, p1g, amax, relu_mask, lds);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The evaluation's team forward: every agent's actor trunk in one launch.  A persistent grid strides over the (image, tile, agent)
+// units, the agent fastest: the workgroups that are resident together stage the same windows, which then come from L2.  The unit is
+// fwd_unit's, so the bits are rs_sized_trunk_fwd<6, false>'s with the agent's weights; the cells come from the heat maps' own int32
+// fields.  168 VGPRs (three workgroups per CU, as the forward kernel), 34 KB of LDS.
+struct SzTeam {
+    rs_cnn_conv_params conv[RS_MAX_AGENTS];   // in the kernel's argument block (8 agents x 4 pointers = 256 bytes)
+    const int32_t* cells;                     // [S][A]
+    const int32_t* pcells;                    // [S][A]
+};
+
+__global__ void __launch_bounds__(NT, 3) rs_sized_team_fwd(SzIn in, SzTeam team, float* __restrict__ a2) {
+    __shared__ FwdLds lds;
+    const int nt2 = in.ntile * in.ntile, A = in.A;
+    const long long units = in.S * nt2 * A;
+    const size_t per_agent = (size_t)in.S * C2 * in.P * in.P;
+    int stamped = -1;                          // the agent whose stamps stl holds
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const long long it = u / A, s = it / nt2;
+        const int a = (int)(u - it * A);
+        const rs_cnn_conv_params cv = team.conv[a];
+        const int loc = team.cells[(size_t)s * A + a], pc = team.pcells[(size_t)s * A + a];
+        if (a != stamped) fwd_stamps(cv.w1, lds.stl);      // the last unit's conv1 has read its stamps: a barrier lies behind every conv1
+        stamped = a;
+        fwd_unit<6, false, true>(in, s, (int)(it - s * nt2), loc, pc, cv.w1, cv.b1, cv.w2, cv.b2, a2 + (size_t)a * per_agent, nullptr, nullptr,
+                                 nullptr, lds);
     }
 }
 
@@ -455,6 +534,23 @@ int rs_cnn_sized_infer(const float* maps, const int64_t* cells, const int64_t* p
                        int32_t map_side, const float* w1, const float* b1, const float* w2, const float* b2, float* a2, rs_stream_t stream) {
     return sized_forward(maps, cells, pcells, num_agents, agent, num_samples, map_side, w1, b1, w2, b2, a2, nullptr, nullptr, nullptr,
                          stream);
+}
+
+int rs_cnn_sized_team_infer(const float* maps, const int32_t* cells, const int32_t* pcells, int32_t num_agents, int64_t num_samples,
+                            int32_t map_side, const rs_cnn_conv_params* convs, float* a2, rs_stream_t stream) {
+    if (!maps || !cells || !pcells || !convs || !a2 || num_agents < 1 || num_agents > RS_MAX_AGENTS || num_samples < 0) return RS_ERR_INVALID_ARG;
+    for (int a = 0; a < num_agents; ++a)
+        if (!convs[a].w1 || !convs[a].b1 || !convs[a].w2 || !convs[a].b2) return RS_ERR_INVALID_ARG;
+    if (!side_ok(map_side)) return RS_ERR_UNSUPPORTED;
+    if (num_samples == 0) return RS_OK;
+    SzIn in{maps, nullptr, nullptr, num_agents, 0, map_side, map_side / 2, tiles(map_side), (long long)num_samples};
+    SzTeam team;
+    for (int a = 0; a < RS_MAX_AGENTS; ++a) team.conv[a] = convs[a < num_agents ? a : 0];     // the slots behind the team repeat agent 0 (never read)
+    team.cells = cells;
+    team.pcells = pcells;
+    const long long units = (long long)num_samples * in.ntile * in.ntile * num_agents;
+    hipLaunchKernelGGL(rs_sized_team_fwd, dim3(sized_grid(rs_sized_team_fwd, units)), dim3(NT), 0, (hipStream_t)stream, in, team, a2);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 
 int rs_cnn_sized_backward(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,

@@ -11,13 +11,15 @@ Saved sets use the reference's layout `env_dict["env_<i>"] = (src_coords, det_co
 (algos/test_environment/eval/test_env_gen.py:13-24).  `sample_test_environments` draws such a set from the
 environment's own spawn rules; the reference's own pickled sets are read by radiation_ppo_amd.testsets WITHOUT unpickling.
 `run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `run_test_environments_cnn_team` its HIP lock-step for teams
-of up to 8 on 27 x 27 maps (csrc/rs_cnn.hip, csrc/rs_cnn_eval.hip), `run_test_environments_team` for feed-forward agents and
+of up to 8 on 27 x 27 maps (csrc/rs_cnn.hip, csrc/rs_cnn_eval.hip), `run_test_environments_cnn_team_sized` the same for square maps of
+any side 8..256 (walls off: 147 x 147; csrc/rs_cnn_sized.hip, csrc/rs_cnn_eval.hip), `run_test_environments_team` for feed-forward agents and
 teams of up to 8, `run_test_environments_rnn_team` for recurrent (RAD-A2C) teams of 1 to 8 -- it holds the recurrent lock-step, fused in
 HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip) and composed; `run_test_environments_rnn` is its front for one agent, and
 `run_test_environments` sends a recurrent agent there --, `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
 """
 import ctypes as C
+import inspect
 import os
 from dataclasses import dataclass, field
 from types import SimpleNamespace
@@ -561,6 +563,124 @@ def run_test_environments_cnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
 
 
 @torch.no_grad()
+def run_test_environments_cnn_team_sized(agents: Dict[int, Any], env_sets: Dict[str, tuple], montecarlo_runs: int = 100,
+                                         steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
+                                         enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0",
+                                         use_predictor: bool = True, return_actions: bool = False, fused: bool = True,
+                                         a2_bytes: int = 4 << 30):
+    """run_test_environments_cnn_team for square heat maps of any side 8..256 that every agent was built for (agent.map_dim): the maps
+    without enforced walls are 27 + steps_per_episode cells a side, 147 x 147 for 120-step episodes.  The same arguments, the same
+    records; ids 0..A-1, a cuda device and the HIP predictor bank, anything else raises ValueError -- those configurations stay with
+    run_test_environments_cnn.
+
+    fused=True: a lock-step is rs_action_uniforms, the PFGRU step of every owner, rs_maps_update, rs_maps_stack, then per chunk of lanes
+    rs_cnn_sized_team_infer (every agent's trunk from the heat maps' int32 cell fields; conv1 is not evaluated over empty input
+    windows) and rs_cnn_sized_team_eval_head (Linear(16 P P, 32) on the matrix cores, heads, draw, idle rows), then rs_step and
+    rs_eval_post_step, on one stream; the host reads the finished-lane count once every 16 lock-steps.  The trunk's output is 16 P P
+    floats per lane and agent (341 KB at 147), so it travels through ONE scratch tensor of at most a2_bytes (never less than 64 lanes'):
+    chunk = max(64, a2_bytes // (4 A 16 P P) // 64 * 64) lanes at a time.  The head's bits depend on neither the lane count nor the
+    grid, so the records do not depend on a2_bytes.
+    fused=False: the same loop and stopping rule composed per agent from rs_cnn_sized_infer, torch.nn.functional.linear, rs_cnn_head
+    and the idle rule with the torch bookkeeping (the A/B baseline), chunked in the same way.
+
+    Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log of rs_step's action rows
+    (8 where a lane had finished)."""
+    from .maps import HeatMaps
+    from .pfgru import PredictorBank
+    A = len(agents)
+    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
+        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}; run_test_environments_cnn takes any ids")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("run_test_environments_cnn_team_sized needs a cuda device; run_test_environments_cnn runs elsewhere")
+    R, L = montecarlo_runs, steps_per_episode
+    N = len(env_sets) * R
+    lib = _lib.load()
+    vec, keys, saved, obs, _ = _open(env_sets, R, A, obstruction_count, enforce_grid_boundaries, seed, device, welford=False)
+    maps = HeatMaps(vec, L, enforce_boundaries=bool(enforce_grid_boundaries))
+    X, Y = maps.map_dimensions
+    if X != Y or not 8 <= X <= 256 or any(tuple(agents[a].map_dim) != (X, Y) for a in range(A)):
+        raise ValueError(f"run_test_environments_cnn_team_sized serves square heat maps of side 8..256 that every agent was built for; "
+                         f"this configuration has {(X, Y)} maps and agents for {[tuple(agents[a].map_dim) for a in range(A)]}; "
+                         "use run_test_environments_cnn")
+    M, flat = X, 16 * (X // 2) ** 2
+    bank = None
+    if use_predictor:
+        bank = PredictorBank(N, A, seed=seed, device=dev)
+        if bank.impl != "hip":
+            raise ValueError("run_test_environments_cnn_team_sized needs PredictorBank(impl='hip'); use run_test_environments_cnn")
+        for a in range(A):
+            if getattr(agents[a], "model", None) is not None:         # the agent's own (saved) predictor weights
+                bank.load_state_dict(a, agents[a].model.state_dict())
+        bank.reset()
+    alive, ep_len, ep_ret, success = _lane_records(N, dev)
+    u = torch.empty(N, A, dtype=torch.float32, device=dev)
+    # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads
+    log = torch.full((L, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
+    act8 = None if return_actions else torch.empty(N, A, dtype=torch.int8, device=dev)
+    use_team = team_mode != "individual"
+    p = lambda t: t.data_ptr()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    actors = [agents[a].pi.actor for a in range(A)]
+    cells, pcells = maps.field("cell"), maps.field("pred_cell")       # views of the heat maps' own state: [N, A] int32, -1 = none
+    assert cells.dtype == torch.int32 and pcells.dtype == torch.int32 and cells.shape == (N, A) and pcells.shape == (N, A)
+    chunk = min(max(64, int(a2_bytes) // (4 * A * flat) // 64 * 64), N)
+    if fused:
+        a2 = torch.empty(A * chunk * flat, dtype=torch.float32, device=dev)
+        convs = (_lib.RsCnnConvParams * A)(*[_lib.RsCnnConvParams(p(m[0].weight), p(m[0].bias), p(m[3].weight), p(m[3].bias)) for m in actors])
+        heads = (_lib.RsCnnHeadParams * A)(*[_lib.RsCnnHeadParams(p(m[6].weight), p(m[6].bias), p(m[8].weight), p(m[8].bias), p(m[10].weight),
+                                                                   p(m[10].bias)) for m in actors])
+        finished = torch.zeros(1, dtype=torch.int32, device=dev)
+        alive8, success8 = alive.view(torch.uint8), success.view(torch.uint8)
+        state = _lib.RsEvalState(N, A, 1 if use_team else 0, p(vec.obs), p(vec.reward), p(vec.team), p(vec.done), p(obs), None, None, None,
+                                 None, p(alive8), p(success8), p(ep_len), p(ep_ret), p(finished))
+    else:
+        a2 = torch.empty(chunk * flat, dtype=torch.float32, device=dev)
+        k_act = torch.empty(A, N, dtype=torch.int64, device=dev)
+    it = 0
+    while it < L:
+        if it and it % 16 == 0:                                   # one host read per 16 lock-steps
+            if (int(finished.item()) if fused else N - int(alive.sum().item())) == N:
+                break
+        a8 = log[it] if return_actions else act8
+        vec.action_uniforms(u)
+        pred = None
+        if bank is not None:
+            pred = bank.predict_kernel(obs)                       # bank.predict without its copy of the prediction
+            bank.calls.add_(1)
+        maps.update(obs, pred=pred)
+        shared = maps.shared_maps()
+        if fused:
+            for lo in range(0, N, chunk):                         # the same scratch for every chunk: one stream keeps them in order
+                n = min(chunk, N - lo)
+                _lib.check(lib.rs_cnn_sized_team_infer(p(shared) + 16 * M * M * lo, p(cells) + 4 * A * lo, p(pcells) + 4 * A * lo, A, n, M, convs,
+                                                       p(a2), st), "rs_cnn_sized_team_infer")
+                _lib.check(lib.rs_cnn_sized_team_eval_head(heads, A, flat, p(a2), p(u) + 4 * A * lo, p(alive8) + lo, p(a8) + A * lo, None, None,
+                                                           None, n, st), "rs_cnn_sized_team_eval_head")
+            vec.step(a8)
+            _lib.check(lib.rs_eval_post_step(C.byref(state), st), "rs_eval_post_step")
+        else:
+            cl, pl = cells.long(), pcells.long()
+            for a, m in enumerate(actors):
+                for lo in range(0, N, chunk):
+                    n = min(chunk, N - lo)
+                    x = a2[:n * flat].view(n, flat)
+                    _lib.check(lib.rs_cnn_sized_infer(p(shared) + 16 * M * M * lo, p(cl) + 8 * A * lo, p(pl) + 8 * A * lo, A, a, n, M, p(m[0].weight),
+                                                      p(m[0].bias), p(m[3].weight), p(m[3].bias), p(x), st), "rs_cnn_sized_infer")
+                    y1 = torch.nn.functional.linear(x, m[6].weight, m[6].bias)
+                    _lib.check(lib.rs_cnn_head(p(y1), p(m[8].weight), p(m[8].bias), p(m[10].weight), p(m[10].bias), 8, p(u) + 4 * (A * lo + a), A,
+                                               p(k_act[a]) + 8 * lo, None, None, 1, None, 1, 0, None, n, st), "rs_cnn_head")
+                a8[:, a] = torch.where(alive, k_act[a], torch.full_like(k_act[a], 8)).to(torch.int8)    # finished episodes idle in place
+            obs_n, rew, team, done, _ = vec.step(a8)
+            _book_step(alive, ep_len, ep_ret, success, team if use_team else rew[:, 0], done.bool().any(dim=1))
+            obs.copy_(obs_n)
+        it += 1
+    # finished episodes idle on purpose; stacked agents may "stall"
+    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=log[:it] if return_actions else None,
+                  ignore_flags=_lib.ENVERR_IDLE_STALL)
+
+
+@torch.no_grad()
 def run_test_environments_team(agents: Dict[int, VecAgentPPO], env_sets: Dict[str, tuple], montecarlo_runs: int = 100,
                                steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
                                enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0", return_actions: bool = False,
@@ -746,16 +866,29 @@ class evaluate_PPO:
             from .maps import CNNCritic
             from .pfgru import PFGRUCell
             from .ppo_cnn import CNNAgentPPO
+            from .maps import heat_map_geometry
+            # the maps' side as the environment and train_PPO derive it: 27 with enforced walls, 27 + steps_per_episode without; the env's
+            # bbox and observation area are RadSearchVec's defaults here, as in the runners
+            d = inspect.signature(RadSearchVec.__init__).parameters
+            bb, oa = d["bbox"].default, d["observation_area"].default
+            env_cfg = SimpleNamespace(cfg=SimpleNamespace(bbox=(min(q[0] for q in bb), min(q[1] for q in bb), max(q[0] for q in bb),
+                                                                max(q[1] for q in bb)), observation_area=oa))
+            map_dim = tuple(heat_map_geometry(env_cfg, common["steps_per_episode"], common["enforce_grid_boundaries"])[2])
             agents = {}
             for i in range(A):
-                ag = CNNAgentPPO(id=i, device=dev)
+                ag = CNNAgentPPO(id=i, map_dim=map_dim, device=dev)
                 ag.model = PFGRUCell().to(dev)
                 ag.load(agent_dir(i))                                   # CNNBase.load (RADTEAM_core.py:1945-1953)
                 agents[i] = ag
-            # the HIP lock-step where it applies (27 x 27 maps, ids 0..A-1, a cuda device); elsewhere the composed runner
-            team = (bool(kw.get("enforce_boundaries", True)) and torch.device(dev).type == "cuda" and 1 <= A <= _lib.RS_MAX_AGENTS
-                    and all(tuple(ag.map_dim) == (27, 27) for ag in agents.values()))
-            runner = run_test_environments_cnn_team if team else run_test_environments_cnn
+            # the HIP lock-steps where they apply (ids 0..A-1, a cuda device; 27 x 27 maps, or square maps of another side 8..256);
+            # elsewhere the composed runner
+            hip = torch.device(dev).type == "cuda" and 1 <= A <= _lib.RS_MAX_AGENTS
+            if hip and map_dim == (27, 27):
+                runner = run_test_environments_cnn_team
+            elif hip and map_dim[0] == map_dim[1] and 8 <= map_dim[0] <= 256:
+                runner = run_test_environments_cnn_team_sized
+            else:
+                runner = run_test_environments_cnn
             self.results, self.summary = runner(agents, sets, team_mode=kw.get("team_mode", "individual"), **common)
         elif arch == "rnn":
             from .rada2c import RNNAgentPPO

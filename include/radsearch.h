@@ -136,6 +136,14 @@ int rs_step(rs_handle* h, const int8_t* actions, float* obs, float* reward, floa
  * (seed, env id, policy).  Replaces Categorical(probs).sample() (FF_core.py:101-104). */
 int rs_action_uniforms(rs_handle* h, float* u, rs_stream_t stream);
 
+/* Test probe of the measurement draw: draw d = Poisson(lam[d]) with key (seed, env_id[d]) and counter (candidate, t[d], episode[d],
+ * 1), as agent 0's measurement in rs_step.  serial[d]: the serial sampler every kernel but the fused rollout uses; group3[d] /
+ * group4[d]: the fused rollout's grouped sampler with 3 / 4 candidates evaluated side by side (the rollout uses 3); candidates[d]:
+ * how many candidates the serial rejection loop consumed (0 for lam < 10, which has no such loop).  The three values must agree.
+ * Rates outside [0, 1e12] are drawn as 0.  All arrays [count], on the device. */
+int rs_poisson_probe(const double* lam, const uint32_t* t, const uint32_t* episode, const uint32_t* env_id, int64_t count, uint32_t seed,
+                     int64_t* serial, int64_t* group3, int64_t* group4, int32_t* candidates, rs_stream_t stream);
+
 /* host copy of the OR of all per-env error bits (synchronises `stream`; debugging/adapters only) */
 int rs_error_flags(rs_handle* h, rs_stream_t stream, uint32_t* flags_out);
 

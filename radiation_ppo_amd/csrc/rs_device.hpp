@@ -171,6 +171,70 @@ __device__ __forceinline__ int64_t rs_poisson(double lam, uint32_t t, uint32_t e
     }
 }
 
+// ---- the grouped form of the same draw (K6, rs_rollout16.hpp).  Candidate i of a draw is a pure function of (i, t, episode, stream,
+// key, lam) and the result is the first candidate that passes, so the candidates may be evaluated side by side.  A lone wave pays
+// the instruction stream of a loop trip once however many lanes run it, and the serial loop runs until the slowest env of the wave
+// has accepted (2.1 trips on average for 16 envs, each with the slow path); the lanes of an env that would idle evaluate the next
+// candidates in the same trip instead.
+struct RsPtrs { double a, b, vr; };
+__device__ __forceinline__ RsPtrs rs_ptrs_setup(double lam) {
+    double slam = sqrt(lam);
+    double b = 0.931 + 2.53 * slam;
+    double a = -0.059 + 0.02483 * b;
+    double vr = 0.9277 - 3.6224 / (b - 2.0);
+    return RsPtrs{a, b, vr};
+}
+// One candidate of rs_poisson's loop, operation for operation: true = accepted with the value k; o = its Philox block.
+__device__ __forceinline__ bool rs_ptrs_try(const u32x4& o, double lam, const RsPtrs& c, double& k) {
+    double u = u53(o.x, o.y) - 0.5;
+    double v = u53(o.z, o.w);
+    double us = 0.5 - fabs(u);
+    if (!(us > 0.0)) return false;
+    k = floor((2.0 * c.a / us + c.b) * u + lam + 0.43);
+    if (us >= 0.07 && v <= c.vr) return true;
+    if (k < 0.0 || (us < 0.013 && v > us)) return false;
+    return rs_ptrs_slow_accept(v, us, k, lam, c.a, c.b);
+}
+// rs_poisson(lam, t, episode, stream, k0, k1) for the envs of a wave in the layout lane = (j = lane & 15, g = lane >> 4), env slot j
+// in its four lanes (j, 0..3).  All 64 lanes call it, the lanes of an env with the same arguments except o: lane (j, g), g >= FIRST,
+// passes philox4x32_10(g - FIRST, t, episode, stream, k0, k1), the block of candidate g - FIRST (lanes g < FIRST: anything).
+// Every such lane evaluates its candidate completely, the slow test included where the candidate is undecided, the env takes the
+// accepted candidate of the lowest index, and every lane of the env returns its value.  An env whose 4 - FIRST candidates were all
+// rejected (0.2 % of the draws at FIRST = 1) goes on with the serial loop from index 4 - FIRST.  lam == 0 and lam < 10 take
+// rs_poisson's paths.
+template <int FIRST>
+__device__ __forceinline__ int64_t rs_poisson_group(double lam, const u32x4& o, uint32_t t, uint32_t episode, uint32_t stream, uint32_t k0, uint32_t k1) {
+    static_assert(FIRST >= 0 && FIRST < 4, "candidates sit in the lanes g = FIRST..3");
+    const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+    const bool ptrs = !(lam == 0.0) && !(lam < 10.0);
+    const RsPtrs c = rs_ptrs_setup(lam);
+    double k = 0.0;
+    const bool acc = ptrs && g >= FIRST && rs_ptrs_try(o, lam, c, k);
+    const unsigned long long won = __ballot(acc) >> j;          // bit 16 q: candidate q - FIRST of this env passed
+    int src = -1;
+#pragma unroll
+    for (int q = 3; q >= FIRST; --q) src = ((won >> (16 * q)) & 1ull) ? q : src;
+    const int64_t first = __shfl((long long)k, j + 16 * (src < 0 ? 0 : src));
+    if (lam == 0.0) return 0;
+    if (lam < 10.0) return rs_poisson_small(lam, t, episode, stream, k0, k1);
+    if (src >= 0) return first;
+    for (uint32_t i = 4 - FIRST;; ++i) {
+        u32x4 oi = philox4x32_10(i, t, episode, stream, k0, k1);
+        if (rs_ptrs_try(oi, lam, c, k)) return (int64_t)k;
+    }
+}
+// How many candidates rs_poisson's PTRS loop consumes for this draw (0 where it does not reach the loop): for the probe
+// (rs_poisson_probe) and the diagnostic builds.
+__device__ __forceinline__ int rs_poisson_count(double lam, uint32_t t, uint32_t episode, uint32_t stream, uint32_t k0, uint32_t k1) {
+    if (lam == 0.0 || lam < 10.0) return 0;
+    const RsPtrs c = rs_ptrs_setup(lam);
+    double k;
+    for (uint32_t i = 0;; ++i) {
+        u32x4 oi = philox4x32_10(i, t, episode, stream, k0, k1);
+        if (rs_ptrs_try(oi, lam, c, k)) return (int)(i + 1);
+    }
+}
+
 // round(x, 2) of a Python float (rad_search_env.py:613): correctly rounded, ties-to-even on the EXACT
 // binary value.  x = m * 2^e exactly, so x*100 = (100 m) / 2^s is classified with integer arithmetic.
 __device__ __forceinline__ double rs_round2(double x) {
@@ -610,6 +674,12 @@ struct RsEnvRegs {
         if (err) P.err[n] |= err;
         err = 0;
     }
+    // every lane takes the copy lane src of its wave holds
+    __device__ __forceinline__ void from_lane(int src) {
+        sx = __shfl(sx, src); sy = __shfl(sy, src); intensity = __shfl(intensity, src); bkg = __shfl(bkg, src);
+        iter_count = __shfl(iter_count, src); episode = __shfl(episode, src); tstep = __shfl(tstep, src); err = __shfl(err, src);
+        done = __shfl((int)done, src) != 0;
+    }
 };
 struct RsAgentRegs {
     int x, y, oobc;
@@ -621,11 +691,36 @@ struct RsAgentRegs {
     __device__ __forceinline__ void store(const RsParams& P, size_t ia) const {
         P.ax[ia] = x; P.ay[ia] = y; P.sp[ia] = sp; P.prev[ia] = prev; P.oobc[ia] = oobc; P.aflags[ia] = fl;
     }
+    __device__ __forceinline__ void from_lane(int src) {
+        x = __shfl(x, src); y = __shfl(y, src); oobc = __shfl(oobc, src); sp = __shfl(sp, src); prev = __shfl(prev, src);
+        fl = (uint8_t)__shfl((int)fl, src);
+    }
 };
 
 #ifdef RS_STEP_STAMPS
 #define RS_ESTAMP_PARAM , unsigned long long& es_last
 #define RS_ESTAMP_ARG , es_last
+#elif defined(RS_K6_STAMPS)
+// Diagnostic build only (-DRS_K6_STAMPS, scripts/k6_stamps.py): the measurement draw inside K6's env step.  k6p[0]: its wave
+// cycles, summed; k6p[1]: the candidates rs_poisson's loop needs for this lane's draw of this step (the wave's largest is the trips
+// of the serial loop; K6 reduces it); k6p[2]: the cycles spent counting, summed, which the script takes out of "env step".  The
+// other callers of the step core pass a dummy.
+#undef RS_ESTAMP_DECL
+#define RS_ESTAMP_DECL unsigned long long k6p[3] = {0, 0, 0};
+#define RS_ESTAMP_PARAM , unsigned long long (&k6p)[3]
+#define RS_ESTAMP_ARG , k6p
+__device__ __forceinline__ unsigned long long rs_k6p_now() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+__device__ __forceinline__ int rs_k6p_wave_max(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+    return v;
+}
 #else
 #define RS_ESTAMP_PARAM
 #define RS_ESTAMP_ARG
@@ -634,9 +729,12 @@ struct RsAgentRegs {
 // Agent a's part of RadSearch.step on values: take_action, distances, measurement, reward, observation row and the lock-step's
 // outputs.  E is read (done is also set); S is the agent's state before and after.  No env array is touched.
 // CN > 1: the cooperative form (see rs_grp_any): lanes cj = 0..CN-1 of a group call this with the same arguments.
+// cand (K6's wave 0, all 64 lanes in the call, a == 0): the lane's candidate block of the measurement draw for rs_poisson_group<1>;
+// null: the serial rs_poisson.
 template <bool HAS_OBS, int CN = 1>
 __device__ __forceinline__ void rs_agent_step_core(const RsParams& P, const RsGeo& g, int n, int a, int act, bool collided, RsEnvRegs& E,
-                                                   RsAgentRegs& S, const RsOut& O, double& max_reward, bool& have_max, int cj RS_ESTAMP_PARAM) {
+                                                   RsAgentRegs& S, const RsOut& O, double& max_reward, bool& have_max, int cj RS_ESTAMP_PARAM,
+                                                   const u32x4* cand = nullptr) {
     const int N = P.N, A = P.A;
     const int sx = E.sx, sy = E.sy, intensity = E.intensity, bkg = E.bkg;
     const uint32_t episode = E.episode, t = E.tstep;
@@ -694,7 +792,19 @@ __device__ __forceinline__ void rs_agent_step_core(const RsParams& P, const RsGe
         if (r == 0.0) { err |= RS_ENVERR_ZERO_DIST; r = 1.0; }
         lam = (P.falloff ? ((double)intensity / (r * r)) : ((double)intensity / r)) + (double)bkg;
     }
-    int64_t meas = rs_poisson(lam, t, episode, RS_STREAM_STEP + (uint32_t)a, k0, k1);
+#if defined(RS_K6_STAMPS) && !defined(RS_STEP_STAMPS)
+    const unsigned long long k6p_t0 = rs_k6p_now();
+#endif
+    int64_t meas = cand ? rs_poisson_group<1>(lam, *cand, t, episode, RS_STREAM_STEP + (uint32_t)a, k0, k1)
+                        : rs_poisson(lam, t, episode, RS_STREAM_STEP + (uint32_t)a, k0, k1);
+#if defined(RS_K6_STAMPS) && !defined(RS_STEP_STAMPS)
+    {
+        const unsigned long long t1 = rs_k6p_now();
+        k6p[0] += t1 - k6p_t0;
+        k6p[1] = (unsigned long long)rs_poisson_count(lam, t, episode, RS_STREAM_STEP + (uint32_t)a, k0, k1);
+        k6p[2] += rs_k6p_now() - t1;
+    }
+#endif
     RS_ESTAMP(4);                                            // Poisson measurement
     if (moved) {
         if (sp < 110.0) { reward = 0.1; done = true; }

@@ -205,6 +205,26 @@ __global__ void __launch_bounds__(64) rs_action_uniform_kernel(RsParams P, float
     }
 }
 
+// rs_poisson_probe: the serial sampler and the grouped one (rs_poisson_group, K6's) on the same draws.  A wave takes 16 draws in
+// K6's layout, draw 16 block + j in the lanes (j, 0..3); rates the env cannot produce (negative, NaN, above 1e12) are drawn as 0.
+__global__ void __launch_bounds__(64) rs_poisson_probe_kernel(const double* __restrict__ lam_in, const uint32_t* __restrict__ t_in,
+                                                              const uint32_t* __restrict__ ep_in, const uint32_t* __restrict__ id_in,
+                                                              long long count, uint32_t seed, int64_t* __restrict__ serial,
+                                                              int64_t* __restrict__ group3, int64_t* __restrict__ group4,
+                                                              int32_t* __restrict__ candidates) {
+    const int lane = threadIdx.x & 63, g = lane >> 4;
+    const long long d = (long long)blockIdx.x * 16 + (lane & 15);
+    const bool live = d < count;
+    double lam = live ? lam_in[d] : 0.0;
+    if (!(lam >= 0.0 && lam <= 1e12)) lam = 0.0;
+    const uint32_t t = live ? t_in[d] : 0u, ep = live ? ep_in[d] : 0u, k1 = live ? id_in[d] : 0u;
+    const int64_t s = rs_poisson(lam, t, ep, RS_STREAM_STEP, seed, k1);
+    const int c = rs_poisson_count(lam, t, ep, RS_STREAM_STEP, seed, k1);
+    const int64_t g3 = rs_poisson_group<1>(lam, philox4x32_10(g ? (uint32_t)(g - 1) : 0u, t, ep, RS_STREAM_STEP, seed, k1), t, ep, RS_STREAM_STEP, seed, k1);
+    const int64_t g4 = rs_poisson_group<0>(lam, philox4x32_10((uint32_t)g, t, ep, RS_STREAM_STEP, seed, k1), t, ep, RS_STREAM_STEP, seed, k1);
+    if (live && g == 0) { serial[d] = s; group3[d] = g3; group4[d] = g4; candidates[d] = c; }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K4: GAE(lambda) + rewards-to-go, PPOBuffer.GAE_advantage_and_rewardsToGO (ppo.py:391-423) for the
 // whole time-major buffer.  One column (env x agent trajectory stream) per lane; a reverse scan in
@@ -613,6 +633,15 @@ int rs_error_flags(rs_handle* h, rs_stream_t stream, uint32_t* flags_out) {
     delete[] host;
     *flags_out = acc;
     return rc;
+}
+
+int rs_poisson_probe(const double* lam, const uint32_t* t, const uint32_t* episode, const uint32_t* env_id, int64_t count, uint32_t seed,
+                     int64_t* serial, int64_t* group3, int64_t* group4, int32_t* candidates, rs_stream_t stream) {
+    if (!lam || !t || !episode || !env_id || !serial || !group3 || !group4 || !candidates || count < 1 || count > (int64_t)1 << 34)
+        return RS_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(rs_poisson_probe_kernel, dim3((unsigned)((count + 15) / 16)), dim3(64), 0, static_cast<hipStream_t>(stream), lam, t,
+                       episode, env_id, (long long)count, seed, serial, group3, group4, candidates);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 
 int rs_gae(const float* rew, const float* val, const uint8_t* cut, const float* last_val, float* adv, float* ret,

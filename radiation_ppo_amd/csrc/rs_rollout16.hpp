@@ -24,6 +24,14 @@
 // has the registers), its output layer runs as two 4x4x1 MFMA chains like K7's, and the env state stays in registers between the
 // lock-steps (RsEnvRegs / RsAgentRegs, rs_agent_step_core); the env arrays are written and re-read around a reset only.  Buffers,
 // env arrays and carried state keep their bits (tests/test_k6_chain_bits_gpu.py).
+//
+// The draws (round 14).  The env step's measurement was a serial rejection loop that ran until the slowest of the wave's 16 envs had
+// accepted (2.1 trips per lock-step) while 48 of wave 0's lanes idled, and the action draw hashed a Philox block of its own once the
+// logits were there.  Now one philox4x32_10 call ahead of the forward pass serves both: lane (j, 0) hashes the action uniform's block,
+// lanes (j, 1..3) the blocks of candidates 0..2 of the measurement draw, which rs_poisson_group<1> (rs_device.hpp) evaluates side by
+// side in the env step; the serial loop is left for an env with three rejections (0.03 trips per lock-step).  For that all four lanes
+// of an env run the step core in both templates, with identical values.  Without obstacles the critic's wave also writes the buffer's
+// observation rows from the messages it reads.  Same bits (tests/test_k6_poisson_group_gpu.py).
 #pragma once
 #include "rs_mlp.hpp"
 
@@ -198,15 +206,36 @@ constexpr bool RS_K6_SHORT = false;
 #else
 constexpr bool RS_K6_SHORT = true;
 #endif
+// A/B switches of round 14 (profiles/r14_k6_poisson_ab.txt).  RS_K6_SERIAL_DRAW: the serial rs_poisson, the action draw's own Philox call
+// inside the softmax and the observation rows from wave 0, as before; -DRS_K6_OBS_BY_WAVE1=false: the observation rows alone as before.
+#ifdef RS_K6_SERIAL_DRAW
+constexpr bool RS_K6_GROUP = false;
+#else
+constexpr bool RS_K6_GROUP = true;
+#endif
+#ifndef RS_K6_OBS_BY_WAVE1
+#define RS_K6_OBS_BY_WAVE1 true
+#endif
 template <bool HAS_OBS> struct RsK6Cfg {
     static constexpr bool reg_weights = RS_K6_SHORT && !HAS_OBS;     // actor operands in registers for the launch (RsMlp16::Regs)
     static constexpr bool mfma_out = RS_K6_SHORT;                    // actor output layer on 4x4x1 MFMA chains
     static constexpr bool reg_state = RS_K6_SHORT;                   // env state in registers across the lock-steps (RsEnvRegs / RsAgentRegs)
+    // one Philox call per lock-step, ahead of the forward pass: lane group 0 hashes the action uniform's block, groups 1..3 the
+    // candidates 0..2 of the measurement draw, which rs_poisson_group<1> then evaluates side by side
+    static constexpr bool group_draw = RS_K6_GROUP && reg_state;
+    // the buffer's observation row t + 1 is the row of message t (the post-reset one where the env was cut): the critic's wave, which
+    // reads the message anyway and is off the chain, writes it; wave 0's eleven tile stores and its copy-out loop go.  Not with
+    // obstacles: that template then spills 270 registers instead of 18.
+    static constexpr bool obs_by_wave1 = RS_K6_SHORT && RS_K6_GROUP && RS_K6_OBS_BY_WAVE1 && !HAS_OBS;
 };
 
 // Diagnostic build only (-DRS_K6_STAMPS, scripts/k6_stamps.py): s_memtime stamps at the phase boundaries of wave 0's lock-step,
 // summed per wave in scalar registers and added (lane 0, plain vector atomics) to a table no other code reads.  Slot 14 holds the
-// launch's 100 MHz ticks, slot 15 the lock-steps counted.  The product build contains none of it.
+// launch's 100 MHz ticks, slot 15 the lock-steps counted.  Slots 8..12 look into the draws: 8 the cycles of the measurement draw inside
+// "env step", 9 the trips rs_poisson's serial loop needs per lock-step (the candidates of the wave's slowest env), summed, 10 the same
+// beyond three (the serial trips the grouped sampler has left), 11 the cycles spent counting them (inside "env step": the script takes
+// them out), 12 the cycles of the Philox call of the action draw (group_draw: of the lock-step's one call).  The product build
+// contains none of it.  Slot 13 is a phase of its own: that one call ("draw blocks"), kept out of "hidden layers".
 #ifdef RS_K6_STAMPS
 #define RS_K6_NPH 16
 __device__ unsigned long long rs_k6_stamp_table[2][RS_K6_NPH];
@@ -216,14 +245,18 @@ __device__ __forceinline__ unsigned long long rs_k6_now() {
     return t;
 }
 #define RS_K6STAMP_DECL unsigned long long k6_acc[RS_K6_NPH] = {0}; const unsigned long long k6_rt0 = __builtin_amdgcn_s_memrealtime(); \
-                        unsigned long long k6_last = rs_k6_now();
+                        unsigned long long k6_last = rs_k6_now(); unsigned long long k6p[3] = {0, 0, 0};
 #define RS_K6STAMP(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = rs_k6_now(); k6_acc[i] += t_ - k6_last; k6_last = t_; \
                            __builtin_amdgcn_sched_barrier(0); } while (0)
-#define RS_K6STAMP_EXIT(tmpl, steps) do { if ((threadIdx.x & 63) == 0) { k6_acc[14] = __builtin_amdgcn_s_memrealtime() - k6_rt0; k6_acc[15] = (steps); \
+#define RS_K6STAMP_TRIPS(active) do { const int m_ = rs_k6p_wave_max((active) ? (int)k6p[1] : 0); k6_acc[9] += m_; k6_acc[10] += m_ > 3 ? m_ - 3 : 0; } while (0)
+#define RS_K6STAMP_PHILOX(t0) do { k6_acc[12] += rs_k6p_now() - (t0); } while (0)
+#define RS_K6STAMP_EXIT(tmpl, steps) do { if ((threadIdx.x & 63) == 0) { k6_acc[8] = k6p[0]; k6_acc[11] = k6p[2]; k6_acc[14] = __builtin_amdgcn_s_memrealtime() - k6_rt0; k6_acc[15] = (steps); \
                            for (int q = 0; q < RS_K6_NPH; ++q) atomicAdd(&rs_k6_stamp_table[tmpl][q], k6_acc[q]); } } while (0)
 #else
 #define RS_K6STAMP_DECL
 #define RS_K6STAMP(i) do {} while (0)
+#define RS_K6STAMP_TRIPS(active) do {} while (0)
+#define RS_K6STAMP_PHILOX(t0) do {} while (0)
 #define RS_K6STAMP_EXIT(tmpl, steps) do {} while (0)
 #endif
 
@@ -267,6 +300,16 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
         for (int t = -1; t < T; ++t) {
             __syncthreads();
             const float* M = mbox + (t & 1) * RS_MB_SLOT;
+            if constexpr (RsK6Cfg<HAS_OBS>::obs_by_wave1) {
+                if (t + 1 < T) {                                  // the 16 rows of lock-step t + 1, 704 contiguous bytes
+                    float* dst = R.obs + ((size_t)(t + 1) * N + (size_t)blockIdx.x * 16) * RS_OBS_DIM;
+                    const int* F = reinterpret_cast<const int*>(M + RS_MB_FLAGS);
+                    for (int i = lane; i < 16 * RS_OBS_DIM; i += RS_WAVE) {
+                        const int e = i / RS_OBS_DIM, k = i - e * RS_OBS_DIM;
+                        dst[i] = M[((F[e] & 1) ? RS_MB_POST : RS_MB_PRE) + e * RS_IN_PAD + k];
+                    }
+                }
+            }
             float xs[RS_IN_PAD];
 #pragma unroll
             for (int k = 0; k < RS_IN_PAD; ++k) xs[k] = M[RS_MB_PRE + j * RS_IN_PAD + k];
@@ -342,6 +385,15 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
         const size_t row = (size_t)t * N + n;
         float* M = mbox + (t & 1) * RS_MB_SLOT;
         float lg[8];
+        u32x4 ph{0u, 0u, 0u, 0u};
+        if constexpr (Cfg::group_draw) {                          // the counters are known before the logits are
+#ifdef RS_K6_STAMPS
+            const unsigned long long p0 = rs_k6p_now();
+#endif
+            ph = philox4x32_10(cj ? (uint32_t)(cj - 1) : 0u, E.tstep, E.episode, cj ? RS_STREAM_STEP : RS_STREAM_ACT, k0, k1);
+            RS_K6STAMP_PHILOX(p0);
+            RS_K6STAMP(13);                                      // (kept out of "hidden layers")
+        }
         {
             f32x4 H2[4];
             ACT.template hidden<Cfg::reg_weights>(xs, H2, AR);
@@ -361,8 +413,13 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
 #pragma unroll
             for (int q = 0; q < 8; ++q) se += __expf(lg[q] - mx);
             const float lse = __logf(se);
-            const uint32_t episode = E.episode, tenv = E.tstep;
-            u32x4 ph = philox4x32_10(0u, tenv, episode, RS_STREAM_ACT, k0, k1);
+            if constexpr (!Cfg::group_draw) {
+#ifdef RS_K6_STAMPS
+                const unsigned long long p0 = rs_k6p_now();
+#endif
+                ph = philox4x32_10(0u, E.tstep, E.episode, RS_STREAM_ACT, k0, k1);
+                RS_K6STAMP_PHILOX(p0);
+            }
             const float u = (float)(ph.x >> 8) * (1.0f / 16777216.0f);
             float cdf = 0.0f;
 #pragma unroll
@@ -373,12 +430,14 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
             }
 #pragma unroll
             for (int q = 0; q < 8; ++q) logp = (a == q) ? ((lg[q] - mx) - lse) : logp;
+            if constexpr (!Cfg::obs_by_wave1) {
 #pragma unroll
-            for (int k = 0; k < RS_OBS_DIM; ++k) tile[lane * RS_OBS_DIM + k] = xo[k];
+                for (int k = 0; k < RS_OBS_DIM; ++k) tile[lane * RS_OBS_DIM + k] = xo[k];
+            }
         }
         __builtin_amdgcn_wave_barrier();                         // (one wave: its LDS operations are ordered; this only pins the compiler)
         RS_K6STAMP(2);                                           // softmax + draw
-        {
+        if constexpr (!Cfg::obs_by_wave1) {
             float* dst = R.obs + ((size_t)t * N + (size_t)blockIdx.x * 16) * RS_OBS_DIM;
             for (int i = lane; i < 16 * RS_OBS_DIM; i += RS_WAVE) dst[i] = tile[i];
         }
@@ -392,21 +451,26 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
             R.source_tar[row * 2 + 1] = (float)E.sy;
         }
         RS_K6STAMP(3);                                           // buffer stores
-        if (HAS_OBS || own) {
-            const int a_env = HAS_OBS ? __shfl(a, j) : a;
+        // group_draw: all four lanes of an env step it, with identical values (the LDS outputs are duplicate addresses, as with
+        // obstacles), so that lanes 1..3 hold the rate and their candidates of the measurement draw
+        constexpr bool STEP_ALL = HAS_OBS || Cfg::group_draw;
+        if (STEP_ALL || own) {
+            const int a_env = STEP_ALL ? __shfl(a, j) : a;
             if constexpr (Cfg::reg_state) {
                 double max_reward = 0.0;
                 bool have_max = false;
 #ifdef RS_STEP_STAMPS
                 RS_ESTAMP_DECL
 #endif
-                rs_agent_step_core<HAS_OBS, HAS_OBS ? 4 : 1>(P, g, n, 0, a_env, false, E, S, O, max_reward, have_max, cj RS_ESTAMP_ARG);
+                rs_agent_step_core<HAS_OBS, HAS_OBS ? 4 : 1>(P, g, n, 0, a_env, false, E, S, O, max_reward, have_max, cj RS_ESTAMP_ARG,
+                                                             Cfg::group_draw ? &ph : nullptr);
             } else {
                 rs_env_step_lane<HAS_OBS, HAS_OBS ? 4 : 1>(P, g, n, [&](int) -> int { return a_env; }, O, false, cj);
             }
             E.iter_count += 1;
             E.tstep += 1;                                        // the env advanced its step counter
         }
+        RS_K6STAMP_TRIPS(STEP_ALL || own);
         RS_K6STAMP(4);                                           // env step
         if (own) {
             const float r = lds_rew[lane];
@@ -445,6 +509,9 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
             else rs_env_reset_lane<false>(P, g, n, lds_geo, lds_adj, lds_d, tile + lane * RS_OBS_DIM, O);
             E.load(P, n);                                        // new episode: new source, new Philox counters
             if constexpr (Cfg::reg_state) S.load(P, (size_t)n);
+        }
+        if constexpr (Cfg::group_draw && !HAS_OBS) {             // the reset ran in lane (j, 0) alone: its new state to the env's other lanes
+            if (__ballot(cut) != 0ull) { E.from_lane(j); S.from_lane(j); }
         }
         if (own) {
             if (cut) {

@@ -3,9 +3,13 @@ stamps at the phase boundaries of wave 0's loop:
 
     python -c "from radiation_ppo_amd.build import build; build(defines=['RS_K6_STAMPS'], suffix='_k6stamps')"
     python -c "from radiation_ppo_amd.build import build; build(defines=['RS_K6_STAMPS', 'RS_K6_PARENT_CHAIN'], suffix='_k6stamps_parent')"
+    python -c "from radiation_ppo_amd.build import build; build(defines=['RS_K6_STAMPS', 'RS_K6_SERIAL_DRAW'], suffix='_k6stamps_serial')"
     python scripts/k6_stamps.py [N] [obstruction_count]            # RS_STAMPS_LIB selects the library (default: lib/librs_hip_k6stamps.so)
 
 RS_K6_PARENT_CHAIN compiles the chain as it was before the weights, the output layer and the env state left it: the 'before' column.
+RS_K6_SERIAL_DRAW compiles the serial measurement draw (rs_poisson) and the action draw's own Philox call inside the softmax: the
+'before' column of the grouped draw.  Below the phase table: the measurement draw's cycles inside "env step", the trips of the
+serial loop per lock-step (the candidates the wave's slowest env needs) and the cycles of the action draw's Philox call.
 Read the SHARES, not the run time: every stamp waits for the wave's outstanding LDS and scalar-memory operations, which forbids
 overlaps the product kernel has."""
 import ctypes as C
@@ -46,6 +50,10 @@ torch.cuda.synchronize()
 lib.rs_debug_k6_stamps(buf, 0)
 row = 16 * (1 if OBST != 0 else 0)
 cyc = [buf[row + q] for q in range(8)]
+cyc[4] -= buf[row + 11]                     # counting the candidates is the diagnostic's own work inside "env step"
+if buf[row + 13]:
+    PH.append("draw blocks (one Philox call)")
+    cyc.append(buf[row + 13])
 ticks, steps = buf[row + 14], buf[row + 15]
 tot = sum(cyc)
 print(f"{os.path.basename(os.environ['RS_LIB_PATH'])}: N = {N}, obstruction_count = {OBST}, {R} launches of {T} lock-steps")
@@ -53,3 +61,9 @@ print(f"stamped build: {e0.elapsed_time(e1) / R:.3f} ms per collect() (slower th
 print(f"in-kernel clock {tot / max(ticks, 1) * 100:.0f} MHz; {tot / max(steps, 1):.0f} wave-cycles per lock-step (mean over {N // 16} waves)")
 for q, c in enumerate(cyc):
     print(f"   {PH[q]:28s} {c / max(steps, 1):8.0f} cyc  {100.0 * c / max(tot, 1):5.1f} %")
+poi, trips, left, phx = (buf[row + q] / max(steps, 1) for q in (8, 9, 10, 12))
+print(f"   inside env step: measurement draw {poi:.0f} cyc ({100.0 * poi * steps / max(tot, 1):.1f} %); a serial loop needs {trips:.3f} trips per lock-step, "
+      f"{left:.3f} of them beyond candidate 3; Philox call of the action draw {phx:.0f} cyc")
+if not buf[row + 13]:
+    print(f"   predicted saving of the grouped draw: (trips - 1) / trips x draw + 2 Philox calls = {(trips - 1) / max(trips, 1e-9) * poi + 2 * phx:.0f} cyc "
+          f"= {100.0 * ((trips - 1) / max(trips, 1e-9) * poi + 2 * phx) * steps / max(tot, 1):.1f} % of the lock-step")

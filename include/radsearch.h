@@ -558,6 +558,29 @@ int rs_a2c_sized_heads_loss(const float* weights, int32_t hid, int32_t pol, int3
 int rs_gru_h0_reset_sized(float* h, const int64_t* base_key, const int64_t* episodes_begun, const uint8_t* mask, double scale, int32_t hid,
                           int32_t num_envs, int32_t num_agents, rs_stream_t stream);
 
+/* ---- RAD-A2C teams: one policy round of every agent in one launch (csrc/rs_rnn_policy.hip, csrc/rs_rnn_sized.hip) -------------------
+ * rs_rnn_team_step (GRU 24, heads 32 / 32) and rs_rnn_sized_team_step (hid 1..64, pol / val 2..64): grid = (64-lane groups, agent),
+ * each agent with its own weights on its own rows of the collectors' tensors.  Every output equals num_agents calls of
+ * rs_rnn_policy_step_rows (rs_rnn_sized_step) on agent a's rows, h_out = h in the step round, bit for bit.
+ *   weights [A]             host array of device pointers, copied into the launch's arguments (a captured graph holds them by value);
+ *                           each to RS_RNN_POLICY_WEIGHT_FLOATS, or rs_rnn_sized_weight_floats(hid, pol, val), packed floats
+ *   x [N][A][11], loc [N][A][2], h [A][N][hid], u [N][A] or NULL, mask [N] or NULL (NULL: every env)
+ *   act [A][N] int64 or NULL, logp_val_boot [A][3][N] or NULL, act8 [N][A] or NULL
+ * Step round (u != NULL), on the envs with mask != 0: agent a's h row is updated in place (a lane reads its row before it stores);
+ *   act8 and act, each if given, receive #{j < 7 : cdf_j <= u}; logp_val_boot, if given, receives the log-softmax at the action in
+ *   slot 0 and the value in slot 1 -- without it the value head is not evaluated (an evaluation's use).
+ * Bootstrap round (u == NULL): slot 2 of logp_val_boot receives the value of the GRU's next state on the masked envs; h is not
+ *   written, nor anything else.
+ * A masked-out env writes nothing in either round; a wave without a live env leaves at once.
+ * RS_ERR_INVALID_ARG, before anything is launched: NULL weights / x / loc / h, a NULL entry among the first num_agents weights,
+ * num_agents outside 1..RS_MAX_AGENTS, num_envs < 1, a step round with neither act nor act8, a bootstrap round without
+ * logp_val_boot.  rs_rnn_sized_team_step: RS_ERR_UNSUPPORTED for widths outside the ranges above, as rs_rnn_sized_step. */
+int rs_rnn_team_step(const float* const* weights, int32_t num_agents, const float* x, const float* loc, float* h, const float* u, int64_t* act,
+                     float* logp_val_boot, int8_t* act8, const uint8_t* mask, int32_t num_envs, rs_stream_t stream);
+int rs_rnn_sized_team_step(const float* const* weights, int32_t num_agents, int32_t hid, int32_t pol, int32_t val, const float* x,
+                           const float* loc, float* h, const float* u, int64_t* act, float* logp_val_boot, int8_t* act8, const uint8_t* mask,
+                           int32_t num_envs, rs_stream_t stream);
+
 /* The forward trunk as the collectors use it: rs_cnn_trunk_prepare re-arranges a network's convolution weights into wscratch
  * (rs_cnn_trunk_scratch_floats floats) once per epoch, rs_cnn_trunk_infer is then ONE launch per select_action round (a2 only). */
 int rs_cnn_trunk_prepare(int32_t in_channels, const float* w1, const float* b1, const float* w2, const float* b2, float* wscratch,
@@ -769,7 +792,7 @@ int rs_rnn_eval_post_refresh(const rs_rnn_eval_state* s, rs_stream_t stream);
  * buffer (:361-364, :395-397, :461-466); an episode ends when any agent's terminal flag rises (:411-423) or at steps_per_episode, and
  * agent 0's return is recorded (`episode_return[0]`, :441-444).  A lane is one team working through runs_per_lane consecutive runs of one
  * saved environment, as for the single agent above.  One lock-step is rs_action_uniforms, rs_pfgru_step (every owner, mask = active),
- * rs_rnn_team_eval_step (or, at other widths, one rs_rnn_sized_step per agent on its rows), rs_step, rs_rnn_team_eval_post_step and,
+ * rs_rnn_team_eval_step (or, at other widths, rs_rnn_sized_team_step without act and logp_val_boot), rs_step, rs_rnn_team_eval_post_step and,
  * when runs_per_lane > 1, rs_refresh(mask = again) and rs_rnn_team_eval_post_refresh, all on one stream
  * (radiation_ppo_amd/evaluate.py: run_test_environments_rnn_team).
  *

@@ -204,6 +204,10 @@ SYMBOLS = [
     ("rs_a2c_sized_heads_loss", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10
      + [C.c_int64, C.c_double, C.c_double, C.c_void_p]),
     ("rs_gru_h0_reset_sized", C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    # a recurrent team's policy round in one launch (the collectors' step and bootstrap rounds, the evaluation at sized widths)
+    ("rs_rnn_team_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_void_p]),
+    ("rs_rnn_sized_team_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8
+     + [C.c_int32, C.c_void_p]),
     ("rs_ff_eval_step", C.c_int, [C.POINTER(RsMlpParams), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
     ("rs_eval_post_step", C.c_int, [C.POINTER(RsEvalState), C.c_void_p]),
     ("rs_rnn_eval_post_step", C.c_int, [C.POINTER(RsRnnEvalState), C.c_void_p]),

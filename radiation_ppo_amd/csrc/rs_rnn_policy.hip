@@ -231,6 +231,116 @@ __global__ void __launch_bounds__(64) rs_rnn_team_step_kernel(TeamArgs t) {
     if (keep) *arow = (int8_t)act;
 }
 
+// The policy round of a whole team as a collector runs it, step round (u given) or bootstrap round (u null), in one launch: the grid,
+// the rows and the in-place h of rs_rnn_team_step_kernel, with K14's value head and log-probability and an optional mask.  The step
+// round stores h, the action (act [A][N] int64 and / or act8 [N][A]) and, when f = logp_val_boot [A][3][N] is given, the log-
+// probability (slot 0) and the value (slot 1); the bootstrap round stores the value of the GRU's next state (slot 2) and nothing else.
+// K14's arithmetic, operation by operation and in K14's order; a body of its own for the reason given above.  Every address a lane
+// stores through is in vector registers before the products; the two round switches are re-read from the argument block.
+struct CollectArgs {
+    const float* w[RS_MAX_AGENTS];
+    const float* x;
+    const float* loc;
+    float* h;
+    const float* u;        // [N][A] or null: the bootstrap round
+    int64_t* act;          // [A][N] or null
+    float* f;              // [A][3][N] (logp, value, bootstrap value) or null
+    int8_t* act8;          // [N][A] or null
+    const uint8_t* mask;   // [N] or null
+    int N, A;
+};
+
+__global__ void __launch_bounds__(64) rs_rnn_team_collect_kernel(CollectArgs t) {
+    const int e = blockIdx.x * 64 + threadIdx.x, a = blockIdx.y;
+    const bool live = e < t.N && (t.mask == nullptr || t.mask[e] != 0);
+    if (!__any(live)) return;
+    const int ec = e < t.N ? e : t.N - 1;                  // idle lanes shadow a real lane, store nothing
+    const cmem_t W = as_cmem(t.w[a]);
+    const size_t i = (size_t)ec * t.A + a;
+    const bool step = t.u != nullptr;
+    float* hrow = t.h + ((size_t)a * t.N + ec) * GH;
+    float* frow = t.f ? t.f + (size_t)a * 3 * t.N + ec : nullptr;          // slot s of this lane: frow[s N]
+    float* vrow = frow ? frow + (size_t)(step ? 1 : 2) * t.N : nullptr;
+    int8_t* arow = t.act8 ? t.act8 + i : nullptr;
+    int64_t* krow = t.act ? t.act + (size_t)a * t.N + ec : nullptr;
+    const float uu = step ? t.u[i] : 0.0f;
+    int keep = live ? 1 : 0;
+    asm volatile("" : "+v"(keep), "+v"(frow), "+v"(vrow), "+v"(arow), "+v"(krow));
+    float x[NX], h[GH];
+#pragma unroll
+    for (int k = 0; k < RS_OBS_DIM; ++k) x[k] = t.x[i * RS_OBS_DIM + k];
+    x[RS_OBS_DIM] = t.loc[i * 2]; x[RS_OBS_DIM + 1] = t.loc[i * 2 + 1];
+#pragma unroll
+    for (int u = 0; u < GH; u += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(hrow + u);
+        h[u] = v.x; h[u + 1] = v.y; h[u + 2] = v.z; h[u + 3] = v.w;
+    }
+    float gi[80], gh[80];
+#pragma unroll
+    for (int o = 0; o < 80; ++o) { gi[o] = W[P_BIH + o]; gh[o] = W[P_BHH + o]; }
+    mv<NX, 80, 72>(W + P_IH, [&](int k) -> float { return x[k]; }, gi);
+    mv<GH, 80, 72>(W + P_HH, [&](int k) -> float { return h[k]; }, gh);
+#pragma unroll
+    for (int j = 0; j < GH; ++j) {
+        const float r = rs_sigmoid(gi[j] + gh[j]);
+        const float z = rs_sigmoid(gi[GH + j] + gh[GH + j]);
+        const float n = rs_tanh(gi[2 * GH + j] + r * gh[2 * GH + j]);
+        h[j] = (1.0f - z) * n + z * h[j];
+    }
+    if (t.u != nullptr && keep) {
+#pragma unroll
+        for (int u = 0; u < GH; u += 4) *reinterpret_cast<float4*>(hrow + u) = make_float4(h[u], h[u + 1], h[u + 2], h[u + 3]);
+    }
+    // ---- value head
+    if (t.f != nullptr) {
+        float tv[HD];
+#pragma unroll
+        for (int o = 0; o < HD; ++o) tv[o] = W[P_VB1 + o];
+        mv<GH, HD>(W + P_V1, [&](int k) -> float { return h[k]; }, tv);
+        float v0 = W[P_V2 + HD], v1 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < HD; k += 2) {
+            v0 = fmaf(W[P_V2 + k], rs_tanh(tv[k]), v0);
+            v1 = fmaf(W[P_V2 + k + 1], rs_tanh(tv[k + 1]), v1);
+        }
+        if (keep) *vrow = v0 + v1;
+    }
+    if (t.u == nullptr) return;
+    // ---- policy head, log-softmax, inverse-CDF draw
+    float tt[HD];
+#pragma unroll
+    for (int o = 0; o < HD; ++o) tt[o] = W[P_B1 + o];
+    mv<GH, HD>(W + P_W1, [&](int k) -> float { return h[k]; }, tt);
+#pragma unroll
+    for (int o = 0; o < HD; ++o) tt[o] = rs_tanh(tt[o]);
+    float lg[16];
+#pragma unroll
+    for (int o = 0; o < 16; ++o) lg[o] = W[P_B2 + o];
+    mv<HD, 16>(W + P_W2, [&](int k) -> float { return tt[k]; }, lg);
+    float mx = lg[0];
+#pragma unroll
+    for (int o = 1; o < NA; ++o) mx = fmaxf(mx, lg[o]);
+    float se = 0.0f;
+#pragma unroll
+    for (int o = 0; o < NA; ++o) se += expf(lg[o] - mx);
+    const float lse = logf(se);
+    float cdf = 0.0f, lp_sel = (lg[0] - mx) - lse;
+    int act = 0;
+#pragma unroll
+    for (int o = 0; o < NA; ++o) {
+        const float lp = (lg[o] - mx) - lse;
+        cdf += expf(lp);
+        if (o < NA - 1 && cdf <= uu) { act = o + 1; }
+    }
+#pragma unroll
+    for (int o = 1; o < NA; ++o) if (act == o) lp_sel = (lg[o] - mx) - lse;
+    if (keep) {
+        if (krow) *krow = act;
+        if (arow) *arow = (int8_t)act;
+        if (frow) *frow = lp_sel;
+    }
+}
+
 // out[k] += sum_o W[k][o] c(o) on a k-major [K][OUTP] block (the transposed product: a dot product along each row)
 template <int K, int OUTP, typename F>
 __device__ __forceinline__ void mvt(cmem_t W, F cval, float (&out)[K]) { rs_ss_mvt<K, OUTP>(W, cval, out); }
@@ -411,6 +521,20 @@ int rs_rnn_team_eval_step(const float* const* weights, int32_t num_agents, const
     }
     t.x = x; t.loc = loc; t.h = h; t.u = u; t.active = active; t.act8 = act8; t.N = num_envs; t.A = num_agents;
     hipLaunchKernelGGL(rs_rnn_team_step_kernel, dim3((num_envs + 63) / 64, num_agents), dim3(64), 0, static_cast<hipStream_t>(stream), t);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_rnn_team_step(const float* const* weights, int32_t num_agents, const float* x, const float* loc, float* h, const float* u, int64_t* act,
+                     float* logp_val_boot, int8_t* act8, const uint8_t* mask, int32_t num_envs, rs_stream_t stream) {
+    if (!weights || !x || !loc || !h || num_agents < 1 || num_agents > RS_MAX_AGENTS || num_envs < 1) return RS_ERR_INVALID_ARG;
+    if (u ? (!act && !act8) : !logp_val_boot) return RS_ERR_INVALID_ARG;       // a step round draws an action, a bootstrap round a value
+    CollectArgs t{};
+    for (int a = 0; a < RS_MAX_AGENTS; ++a) {
+        if (a < num_agents && !weights[a]) return RS_ERR_INVALID_ARG;
+        t.w[a] = weights[a < num_agents ? a : 0];                  // the slots behind the team repeat agent 0 (never read)
+    }
+    t.x = x; t.loc = loc; t.h = h; t.u = u; t.act = act; t.f = logp_val_boot; t.act8 = act8; t.mask = mask; t.N = num_envs; t.A = num_agents;
+    hipLaunchKernelGGL(rs_rnn_team_collect_kernel, dim3((num_envs + 63) / 64, num_agents), dim3(64), 0, static_cast<hipStream_t>(stream), t);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -226,6 +226,76 @@ __global__ void __launch_bounds__(64) rs_rnn_sized_step_kernel(StepArgs a_) {
     }
 }
 
+// the policy round of a whole team in one launch (rs_rnn_team_step's contract, csrc/rs_rnn_policy.hip): grid = (64-lane groups,
+// agent), blockIdx.y's agent on its rows of x [N][A][11], loc [N][A][2], u [N][A], act8 [N][A], with its own weights and its own slab
+// of h [A][N][hid], updated in place (a lane has its row in registers before it stores).  u given: the step round -- h, the action
+// (act [A][N], act8) and, when f = logp_val_boot [A][3][N] is given, the log-probability (slot 0) and the value (slot 1); u null: the
+// bootstrap round -- the value of the GRU's next state (slot 2) and nothing else.  The pieces are rs_rnn_sized_step_kernel's.
+struct TeamStepArgs {
+    const float* w[RS_MAX_AGENTS];   // the weight pointers travel in the argument block
+    const float* x; const float* loc; float* h; const float* u;
+    int64_t* act; float* f; int8_t* act8;
+    const uint8_t* mask;
+    int N, A, hid;
+    Layout l;
+};
+
+template <int HT>
+__global__ void __launch_bounds__(64) rs_rnn_sized_team_kernel(TeamStepArgs t) {
+    const int e = blockIdx.x * 64 + threadIdx.x, a = blockIdx.y;
+    const bool live = e < t.N && (t.mask == nullptr || t.mask[e] != 0);
+    if (!__any(live)) return;
+    const int ec = e < t.N ? e : t.N - 1;                  // idle lanes shadow a real env, store nothing
+    const float* w = t.w[a];
+    const size_t i = (size_t)ec * t.A + a;
+    const bool step = t.u != nullptr;
+    float x[NX], h[HT], hn[HT];
+#pragma unroll
+    for (int k = 0; k < RS_OBS_DIM; ++k) x[k] = t.x[i * RS_OBS_DIM + k];
+    x[RS_OBS_DIM] = t.loc[i * 2]; x[RS_OBS_DIM + 1] = t.loc[i * 2 + 1];
+    float* hrow = t.h + ((size_t)a * t.N + ec) * t.hid;
+#pragma unroll
+    for (int b = 0; b < HT / 8; ++b) {
+        float v[8];
+        ld8(hrow, 8 * b, t.hid, v);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) h[8 * b + k] = v[k];
+    }
+    gru_cell<HT>(rs_as_cmem(w), x, h, hn);
+    if (step && live) {
+#pragma unroll
+        for (int b = 0; b < HT / 8; ++b) st8(hrow, 8 * b, t.hid, hn + 8 * b);
+    }
+    float lg[8], val;
+    heads_fwd<HT>(w, t.l.pol_at, t.l.npb, t.l.val_at, t.l.nvb, t.l.tail_at, hn, lg, val, step, t.f != nullptr);
+    float* frow = t.f ? t.f + (size_t)a * 3 * t.N + ec : nullptr;          // slot s of this lane: frow[s N]
+    if (frow && live) frow[(size_t)(step ? 1 : 2) * t.N] = val;
+    if (!step) return;
+    float mx = lg[0];
+#pragma unroll
+    for (int o = 1; o < NA; ++o) mx = fmaxf(mx, lg[o]);
+    float se = 0.0f;
+#pragma unroll
+    for (int o = 0; o < NA; ++o) se += expf(lg[o] - mx);
+    const float lse = logf(se);
+    const float uu = t.u[i];
+    float cdf = 0.0f, lp_sel = (lg[0] - mx) - lse;
+    int act = 0;
+#pragma unroll
+    for (int o = 0; o < NA; ++o) {
+        const float lp = (lg[o] - mx) - lse;
+        cdf += expf(lp);
+        if (o < NA - 1 && cdf <= uu) { act = o + 1; }
+    }
+#pragma unroll
+    for (int o = 1; o < NA; ++o) if (act == o) lp_sel = (lg[o] - mx) - lse;
+    if (live) {
+        if (t.act) t.act[(size_t)a * t.N + e] = act;
+        if (t.act8) t.act8[i] = (int8_t)act;
+        if (frow) *frow = lp_sel;
+    }
+}
+
 // ---- GRU sequence (K12's contract at any width): gi [L][E][3 hid], h0 [E][hid] -> hs [L][E][hid], gates [L][E][4 HT]
 //      (per 8-unit block: r | z | n | W_hn h + b_hn, 32 floats)
 template <int HT>
@@ -526,6 +596,23 @@ int rs_rnn_sized_step(const float* weights, int32_t hid, int32_t pol, int32_t va
     StepArgs a{weights, x, loc, h, u, h_out, logits, value, act, logp, act8, mask, num_envs, hid, x_stride, loc_stride, u_stride, act8_stride,
                layout_rt(hid, pol, val)};
     RS_TIER_SWITCH(hid, rs_rnn_sized_step_kernel, dim3((num_envs + 63) / 64), dim3(64), a);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_rnn_sized_team_step(const float* const* weights, int32_t num_agents, int32_t hid, int32_t pol, int32_t val, const float* x,
+                           const float* loc, float* h, const float* u, int64_t* act, float* logp_val_boot, int8_t* act8, const uint8_t* mask,
+                           int32_t num_envs, rs_stream_t stream) {
+    if (!widths_ok(hid, pol, val)) return RS_ERR_UNSUPPORTED;
+    if (!weights || !x || !loc || !h || num_agents < 1 || num_agents > RS_MAX_AGENTS || num_envs < 1) return RS_ERR_INVALID_ARG;
+    if (u ? (!act && !act8) : !logp_val_boot) return RS_ERR_INVALID_ARG;       // a step round draws an action, a bootstrap round a value
+    TeamStepArgs t{};
+    for (int a = 0; a < RS_MAX_AGENTS; ++a) {
+        if (a < num_agents && !weights[a]) return RS_ERR_INVALID_ARG;
+        t.w[a] = weights[a < num_agents ? a : 0];                  // the slots behind the team repeat agent 0 (never read)
+    }
+    t.x = x; t.loc = loc; t.h = h; t.u = u; t.act = act; t.f = logp_val_boot; t.act8 = act8; t.mask = mask;
+    t.N = num_envs; t.A = num_agents; t.hid = hid; t.l = layout_rt(hid, pol, val);
+    RS_TIER_SWITCH(hid, rs_rnn_sized_team_kernel, dim3((num_envs + 63) / 64, num_agents), dim3(64), t);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

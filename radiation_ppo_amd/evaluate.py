@@ -247,7 +247,7 @@ def run_test_environments_rnn(agent, env_sets: Dict[str, tuple], montecarlo_runs
     (idle) where a lane had no run going -- N = E with carried hidden states, else E * R."""
     dev = torch.device(device)
     ac = getattr(agent, "agent", None)
-    can = (dev.type == "cuda" and hasattr(ac, "gru_cell") and hasattr(agent, "policy_step_masked_rows")
+    can = (dev.type == "cuda" and hasattr(ac, "gru_cell") and hasattr(agent, "policy_weights")
            and _has_policy_kernel(ac, dev) and _has_pfgru_kernel(ac, dev))
     if fused is None:
         fused = can
@@ -274,9 +274,9 @@ def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
     lifetime of `hiddens`, :353); False = N = E R lanes with one run each and a fresh hidden state.
 
     fused=True: a lock-step is rs_action_uniforms, the PFGRU step of every owner on the lanes with runs left (one launch), the policy
-    round -- rs_rnn_team_eval_step at the default widths (one launch for the team), one rs_rnn_sized_step per agent at the others --,
+    round -- one launch for the team: rs_rnn_team_eval_step at the default widths, rs_rnn_sized_team_step at the others --,
     rs_step, rs_rnn_team_eval_post_step and, with more than one run per lane, rs_refresh on the lanes that begin their next run and
-    rs_rnn_team_eval_post_refresh: 5 or 7 launches at the default widths, on one stream.  The host reads the finished-lane count once
+    rs_rnn_team_eval_post_refresh: 5 or 7 launches, on one stream.  The host reads the finished-lane count once
     every 16 lock-steps; nothing else synchronises.  It needs a cuda device and kernels for both halves of the agents; ValueError
     otherwise.  fused=False: the same lock-step composed from DeviceWelford, PredictorBank.predict, one policy step per agent and
     torch bookkeeping in the reference's order, with the same stopping rule: the A/B baseline, identical records and log.
@@ -296,7 +296,7 @@ def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
     dev = torch.device(device)
     pol_kernel = all(_has_policy_kernel(ac, dev) for ac in acs)
     pf_kernel = all(_has_pfgru_kernel(ac, dev) for ac in acs)
-    can = dev.type == "cuda" and pol_kernel and pf_kernel and all(hasattr(agents[a], "policy_step_masked_rows") for a in range(A))
+    can = dev.type == "cuda" and pol_kernel and pf_kernel and all(hasattr(agents[a], "policy_weights") for a in range(A))
     if fused is None:
         fused = can
     if fused and not can:
@@ -313,7 +313,6 @@ def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
     rec_ret = torch.zeros(N, Rl, dtype=torch.float32, device=dev)
     rec_suc = torch.zeros(N, Rl, dtype=torch.uint8, device=dev)
     u = torch.empty(N, A, dtype=torch.float32, device=dev)
-    act = torch.empty(N, dtype=torch.int64, device=dev)           # scratch: asking for it makes the per-agent steps evaluate the policy head
     bound = L * Rl
     # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads; a lane
     # that is masked out is never written and reads 8.  Otherwise one fixed buffer, where the post-step parks a finished lane on 8
@@ -332,21 +331,20 @@ def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
         state = _lib.RsRnnTeamEvalState(N, A, Rl, L, p(vec.obs), p(vec.reward), p(vec.done), p(obs), p(x), p(stat.count), p(stat.mean),
                                         p(stat.sq), p(stat.std), p(active), p(again), p(run), p(steps), p(ret), p(rec_len), p(rec_ret),
                                         p(rec_suc), p(bank.calls), None if return_actions else p(act8), p(finished))
-        one_launch = all(ac.fused_policy for ac in acs)
-        if one_launch:
-            wts = [agents[a].policy_weights() for a in range(A)]  # kept alive for the run: the kernel reads them by address
-            wp = (C.c_void_p * A)(*[p(w) for w in wts])
+        default = all(ac.fused_policy for ac in acs)
+        wts = [agents[a].policy_weights() for a in range(A)]      # kept alive for the run: the kernel reads them by address
+        wp = (C.c_void_p * A)(*[p(w) for w in wts])
         while it < bound:
             if it and it % 16 == 0 and int(finished.item()) == N: # one host read per 16 lock-steps
                 break
             a8 = log[it] if return_actions else act8
             vec.action_uniforms(u)
             loc = bank.predict_kernel(x, mask8=active)            # every owner in one launch; the draw counters are the post-step's
-            if one_launch:
+            if default:
                 _lib.check(lib.rs_rnn_team_eval_step(wp, A, p(x), p(loc), p(hid), p(u), p(active), p(a8), N, st), "rs_rnn_team_eval_step")
-            else:
-                for a in range(A):
-                    agents[a].policy_step_masked_rows(x, loc, hid[a], u, a, act, a8, active)
+            else:                                                 # the same round at the other widths: no value, no log-probability
+                _lib.check(lib.rs_rnn_sized_team_step(wp, A, acs[0].hid, acs[0].pol[0], acs[0].val[0], p(x), p(loc), p(hid), p(u), None, None,
+                                                      p(a8), p(active), N, st), "rs_rnn_sized_team_step")
             vec.step(a8)
             _lib.check(lib.rs_rnn_team_eval_post_step(C.byref(state), st), "rs_rnn_team_eval_post_step")
             if Rl > 1:                                            # :455-466: the lanes that begin their next run

@@ -802,28 +802,6 @@ class RNNAgentPPO:
                                                        None if mask8 is None else mask8.data_ptr(), N,
                                                        C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "rs_rnn_policy_step_rows")
 
-    def policy_step_masked_rows(self, x, loc, h, u, a: int, act, act8, mask8) -> None:
-        """K14 (or the sized step) as the evaluation lock-step uses it, on agent a's rows of a team's [N, A, .] tensors (no contiguous
-        copies): x [N, A, 11], loc [N, A, 2], u [N, A]; only the lanes with mask8 [N] uint8 != 0 are evaluated, their h [N, hid] (agent
-        a's own state) is updated in place and their action goes to act8 [N, A] int8 (rs_step's rows) and to the act [N] int64 scratch
-        -- K14 evaluates the policy head for act / logp / logits, not for act8 alone.  No value."""
-        ac = self.agent
-        w = self.policy_weights()
-        for t in (x, loc, h, u, act, act8, mask8):
-            assert t.is_cuda and t.is_contiguous()
-        N, A = x.shape[0], x.shape[1]
-        assert 0 <= a < A and loc.shape[1] == A and u.shape[1] == A and act8.shape[1] == A
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        xa, la, ua, a8 = x.data_ptr() + 4 * a * _lib.RS_OBS_DIM, loc.data_ptr() + 4 * a * 2, u.data_ptr() + 4 * a, act8.data_ptr() + a
-        if not ac.fused_policy:
-            assert ac.sized_policy
-            _lib.check(_lib.load().rs_rnn_sized_step(w.data_ptr(), ac.hid, ac.pol[0], ac.val[0], xa, A * _lib.RS_OBS_DIM, la, 2 * A, h.data_ptr(),
-                                                     ua, A, h.data_ptr(), None, None, act.data_ptr(), None, a8, A, mask8.data_ptr(), N, st),
-                       "rs_rnn_sized_step")
-            return
-        _lib.check(_lib.load().rs_rnn_policy_step_rows(w.data_ptr(), xa, A * _lib.RS_OBS_DIM, la, 2 * A, h.data_ptr(), ua, A, h.data_ptr(), None,
-                                                       act.data_ptr(), None, a8, A, mask8.data_ptr(), N, st), "rs_rnn_policy_step_rows")
-
     def reduce_pfgru_training(self) -> None:
         """ppo.py:685-689."""
         if self.reduce_pfgru_iters:
@@ -1321,6 +1299,10 @@ class RNNCollector:
         # the lock-step's element-wise bookkeeping as three launches (rs_collect_*; ~30 torch launches before): needs K14 and the fused bank
         self.use_glue = (self.use_k14 or self.use_sized) and fused_pf
         self._cs = None
+        # teams: each policy round of the glued lock-step as one launch for all agents (rs_rnn_team_step / rs_rnn_sized_team_step) in
+        # place of one K14 / sized-step launch per agent; one agent keeps its launch.  Like use_glue, settable before the first collect()
+        self.use_team_step = bool(self.A >= 2 and self.use_glue
+                                  and len({(ag.agent.hid, tuple(ag.agent.pol), tuple(ag.agent.val)) for ag in agents.values()}) == 1)
 
     @property
     def _kstep(self) -> bool:
@@ -1347,11 +1329,27 @@ class RNNCollector:
                                            p(env.state("src_y")), p(self._done_oob[0]), p(self._done_oob[1]), p(self._src_copy), None)
         return self._cs
 
+    def _team_round(self, x, loc, u, act, act8, mask8) -> None:
+        """One policy round of every agent in one launch (rs_rnn_team_step, or rs_rnn_sized_team_step at the other widths) on the
+        collector's [N, A, .] rows: u given = the step round (h in place, act / act8, logp and value into _k_f slots 0 and 1), u None =
+        the bootstrap round (the value into slot 2 on the envs of mask8).  The pointer array is rebuilt from policy_weights() on every
+        call, as the per-agent calls do: the buffers are re-packed in place, so a captured launch keeps reading the right addresses."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        wp = (C.c_void_p * self.A)(*[self.agents[a].policy_weights().data_ptr() for a in range(self.A)])
+        st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        tail = (ptr(x), ptr(loc), ptr(self.h), ptr(u), ptr(act), ptr(self._k_f), ptr(act8), ptr(mask8), self.N, st)
+        if self.use_k14:
+            _lib.check(_lib.load().rs_rnn_team_step(wp, self.A, *tail), "rs_rnn_team_step")
+        else:
+            ac = self.agents[0].agent
+            _lib.check(_lib.load().rs_rnn_sized_team_step(wp, self.A, ac.hid, ac.pol[0], ac.val[0], *tail), "rs_rnn_sized_team_step")
+
     @torch.no_grad()
     def _step_glued(self, epoch_ended: bool) -> None:
         """_step with the bookkeeping between the library calls in rs_collect_pre / _post_step / _post_reset: 15 launches per lock-step
         (pre, uniforms, K11, K14, env step, post_step, K11 + K14 of the bootstrap round, store_rows, epoch_stats, env reset, post_reset,
-        particle-set and GRU-state resets) where the torch composition took ~45.  Same arithmetic, operation by operation."""
+        particle-set and GRU-state resets) where the torch composition took ~45.  Same arithmetic, operation by operation.  A team's
+        two K14 rounds are one launch each for all agents (use_team_step; one K14 launch per agent and round without it)."""
         env, buf, N, A = self.env, self.buf, self.N, self.A
         lib, cs = _lib.load(), self._glue_state()
         st = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
@@ -1360,8 +1358,11 @@ class RNNCollector:
         x = self._x_buf
         env.action_uniforms(self._u)
         loc = self.bank.predict_kernel(x)                                                      # PFGRU (K11), carried particle sets
-        for a, ag in self.agents.items():
-            ag.policy_step_rows(x, loc, self.h[a], self._u, a, value=self._k_f[a, 1], act=self._k_act[a], logp=self._k_f[a, 0], act8=self._act8)
+        if self.use_team_step:
+            self._team_round(x, loc, self._u, self._k_act, self._act8, None)
+        else:
+            for a, ag in self.agents.items():
+                ag.policy_step_rows(x, loc, self.h[a], self._u, a, value=self._k_f[a, 1], act=self._k_act[a], logp=self._k_f[a, 0], act8=self._act8)
         env.step(self._act8)
         _lib.check(lib.rs_collect_post_step(C.byref(cs), 1 if epoch_ended else 0, st), "rs_collect_post_step")
         # the env's reset (a latency-bound ~50 us: one env's spawn is a 15 k-instruction chain on four lanes) runs on a side stream
@@ -1374,8 +1375,11 @@ class RNNCollector:
                 env.set_epoch_end()
             env.reset(cut)
         locb = self.bank.predict_kernel(self._xb_buf, mask8=boot)                              # train.py:462-487: one more ac.step for the value
-        for a, ag in self.agents.items():
-            ag.policy_step_rows(self._xb_buf, locb, self.h[a], None, a, value=self._k_f[a, 2], mask8=boot)
+        if self.use_team_step:
+            self._team_round(self._xb_buf, locb, None, None, None, boot)
+        else:
+            for a, ag in self.agents.items():
+                ag.policy_step_rows(self._xb_buf, locb, self.h[a], None, a, value=self._k_f[a, 2], mask8=boot)
         _lib.check(lib.rs_store_rows(self._t.data_ptr(), self._k_act.data_ptr(), self._k_f.data_ptr(), x.data_ptr(),
                                      self._src_copy[0].data_ptr(), self._src_copy[1].data_ptr(), self._rew_used.data_ptr(), cut.data_ptr(),
                                      boot.data_ptr(), buf.act.data_ptr(), buf.logp.data_ptr(), buf.val.data_ptr(), buf.last_val.data_ptr(),

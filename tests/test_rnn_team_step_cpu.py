@@ -1,0 +1,69 @@
+"""rs_rnn_team_step and rs_rnn_sized_team_step at the C boundary, without a GPU: the built library exports both under ABI version 4,
+the header declares them, the binding lists them, and every invalid argument is refused -- RS_ERR_INVALID_ARG (1) or, for widths the
+sized kernels do not serve, RS_ERR_UNSUPPORTED (4).  This machine has no device, so a refusal here proves that the validation runs
+before any HIP call: a launch would have come back as RS_ERR_HIP."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RS_ERR_INVALID_ARG, RS_ERR_UNSUPPORTED = 1, 4
+ENTRIES = ("rs_rnn_team_step", "rs_rnn_sized_team_step")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from radiation_ppo_amd import build
+    build.build(verbose=False)
+    from radiation_ppo_amd import _lib
+    return _lib.load()
+
+
+def test_symbols_are_exported_declared_and_bound_and_the_abi_version_stays_4(lib):
+    from radiation_ppo_amd import _lib
+    names = [s[0] for s in _lib.SYMBOLS]
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "radsearch.h")).read(), flags=re.S)
+    for sym in ENTRIES:
+        assert hasattr(lib, sym) and names.count(sym) == 1
+        assert getattr(lib, sym).argtypes is not None                # bound by _lib.load()
+        assert re.search(r"\bint " + sym + r"\(const float\* const\* weights, int32_t num_agents,", src), sym
+    assert len(lib.rs_rnn_team_step.argtypes) == 12 and len(lib.rs_rnn_sized_team_step.argtypes) == 15
+    assert lib.rs_abi_version() == 4
+
+
+def _weights(A, null_at=None):
+    return (C.c_void_p * 8)(*[None if a == null_at or a >= A else 0x100000 * (a + 1) for a in range(8)])
+
+
+# non-NULL stand-ins that are never dereferenced; one argument spoilt per case
+GOOD = dict(weights=_weights(3), A=3, x=0x1000, loc=0x2000, h=0x3000, u=0x4000, act=0x5000, f=0x6000, act8=0x7000, mask=0x8000, N=70)
+CASES = ([(f"{k} NULL", {k: None}) for k in ("weights", "x", "loc", "h")]
+         + [(f"weight {a} of 3 NULL", dict(weights=_weights(3, null_at=a))) for a in range(3)]
+         + [("no agent", dict(A=0)), ("nine agents", dict(A=9, weights=(C.c_void_p * 9)(*[0x100000] * 9))), ("negative agents", dict(A=-2)),
+            ("no env", dict(N=0)), ("negative envs", dict(N=-64)),
+            ("step round with neither act nor act8", dict(act=None, act8=None)),
+            ("step round with neither act nor act8, no value either", dict(act=None, act8=None, f=None)),
+            ("bootstrap round without logp_val_boot", dict(u=None, f=None)),
+            ("bootstrap round without logp_val_boot or actions", dict(u=None, f=None, act=None, act8=None))])
+
+
+def _call(lib, entry, a, widths=(32, 64, 64)):
+    tail = (a["x"], a["loc"], a["h"], a["u"], a["act"], a["f"], a["act8"], a["mask"], a["N"], None)
+    if entry == "rs_rnn_team_step":
+        return lib.rs_rnn_team_step(a["weights"], a["A"], *tail)
+    return lib.rs_rnn_sized_team_step(a["weights"], a["A"], *widths, *tail)
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("name,spoil", CASES, ids=[c[0] for c in CASES])
+def test_invalid_arguments_are_refused_before_any_hip_call(lib, entry, name, spoil):
+    assert _call(lib, entry, dict(GOOD, **spoil)) == RS_ERR_INVALID_ARG, name
+
+
+@pytest.mark.parametrize("widths", [(0, 32, 32), (65, 32, 32), (32, 1, 32), (32, 65, 32), (32, 32, 1), (32, 32, 65), (-1, -1, -1)])
+def test_the_sized_entry_refuses_widths_it_does_not_serve(lib, widths):
+    """as rs_rnn_sized_step: the widths are looked at first, so the answer is 4 with valid and with invalid other arguments"""
+    assert _call(lib, "rs_rnn_sized_team_step", GOOD, widths) == RS_ERR_UNSUPPORTED
+    assert _call(lib, "rs_rnn_sized_team_step", dict(GOOD, x=None), widths) == RS_ERR_UNSUPPORTED

@@ -909,6 +909,42 @@ int rs_cnn_sized_team_eval_head(const rs_cnn_head_params* heads, int32_t num_age
                                 const uint8_t* alive, int8_t* act8, int64_t* act, float* logp, float* y1_out, int32_t num_envs,
                                 rs_stream_t stream);
 
+/* ---- The policy round of a RAD-TEAM (CNN) team in TRAINING on 27 x 27 maps (radiation_ppo_amd/ppo_cnn.py: CNNCollector._step_glued):
+ * at most three launches whatever the team size and the critic mode -- rs_cnn_team_trunk_infer (the actors), rs_cnn_trunk_infer(agent = -1)
+ * for a global critic or rs_cnn_team_critic_trunk_infer for one critic per agent, rs_cnn_team_step_head; a bootstrap round is the critic
+ * trunk(s) and the heads.
+ *
+ * rs_cnn_team_critic_trunk_infer: every critic's trunk (4 input channels) in one launch, grid = (image rounds, critic); the result equals
+ * num_critics calls of rs_cnn_trunk_infer(agent = -1) with critic c's prepared weights, bit for bit.
+ *   maps [S][4][729]; wscratch [C][rs_cnn_trunk_scratch_floats(4)] (rs_cnn_trunk_prepare(4, ...) per critic); a2 [C][S][2704]
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL pointer, num_critics outside 1..RS_MAX_AGENTS, num_samples < 0; num_samples == 0
+ * returns RS_OK and launches nothing. */
+int rs_cnn_team_critic_trunk_infer(const float* maps, int32_t num_critics, int64_t num_samples, const float* wscratch, float* a2,
+                                   rs_stream_t stream);
+
+/* rs_cnn_team_step_head: every actor's and every critic's head behind the trunks in one launch, grid = (64-image tiles, A + C): rows
+ * y < A are the actors, rows y >= A the critics.  Every row runs rs_cnn_team_eval_head's first layer, Linear(2704, 32) on the f32 matrix
+ * cores, four k-quarters added in wave order, then the bias (no atomics: an env's bits depend on neither num_envs nor the grid).  Behind
+ * it an actor row runs rs_cnn_head's out_dim = 8 arithmetic operation for operation -- its y1, action and log-probability are
+ * rs_cnn_team_eval_head's bits -- and a critic row rs_cnn_head's out_dim = 1 arithmetic.
+ *   actors [A], critics [C]   host arrays (device pointers inside, passed to the kernel by value: a captured graph holds them), torch
+ *                             layouts: w1 [32][2704], b1 [32], w2 [16][32], b2 [16], w3 [8][16] / [1][16], b3 [8] / [1]
+ *   num_critics               1: a global critic, its value goes to every agent's row; num_agents: critic c serves agent c
+ *   a2_actor [A][N][2704], a2_critic [C][N][2704]   the trunks' outputs (N = num_envs)
+ *   u [N][A]                  the uniforms of rs_action_uniforms.  Not NULL = a STEP round: the actor rows write act [A][N], slot 0 of
+ *                             logp_val_boot [A][3][N] (the row layout rs_store_rows reads) and act8 [N][A] (the drawn action: no idle
+ *                             rule), the critic rows slot 1.  NULL = a BOOTSTRAP round: only the critic rows are launched; they write slot 2
+ *                             (actors, a2_actor, act and act8 may be NULL)
+ *   mask [N] or NULL          an env with mask[n] == 0 writes nothing; a workgroup whose 64 envs are all masked out returns before its k
+ *                             loop.  Required in a bootstrap round
+ *   y1_out [A + C][N][32]     or NULL: the first layer's pre-activation output of every row (for tests)
+ * RS_ERR_INVALID_ARG, before anything is launched: num_agents outside 1..RS_MAX_AGENTS, num_critics neither 1 nor num_agents,
+ * num_envs < 1, NULL critics / a2_critic / logp_val_boot or a NULL pointer inside the first num_critics critics; a step round with NULL
+ * actors / a2_actor / act / act8 or a NULL pointer inside the first num_agents actors; a bootstrap round without mask. */
+int rs_cnn_team_step_head(const rs_cnn_head_params* actors, int32_t num_agents, const rs_cnn_head_params* critics, int32_t num_critics,
+                          const float* a2_actor, const float* a2_critic, const float* u, int64_t* act, float* logp_val_boot, int8_t* act8,
+                          const uint8_t* mask, float* y1_out, int32_t num_envs, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,10 @@ SYMBOLS = [
     ("rs_cnn_sized_team_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.POINTER(RsCnnConvParams),
                                           C.c_void_p, C.c_void_p]),
     ("rs_cnn_sized_team_eval_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]),
+    # the RAD-TEAM (CNN) training round: every critic's trunk, every actor's and critic's head
+    ("rs_cnn_team_critic_trunk_infer", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rs_cnn_team_step_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32, C.POINTER(RsCnnHeadParams), C.c_int32] + [C.c_void_p] * 8
+     + [C.c_int32, C.c_void_p]),
     ("rs_rnn_team_eval_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
     ("rs_rnn_team_eval_post_step", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),
     ("rs_rnn_team_eval_post_refresh", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),

@@ -476,6 +476,16 @@ __global__ void __launch_bounds__(FW_NT, 4) rs_cnn_team_fwd_kernel(CnnIn32 in, c
                       gridDim.x);
 }
 
+// Every critic's trunk of a team without a global critic in one launch, grid = (image rounds, critic): critic blockIdx.y runs K9's
+// 4-channel forward pass (the same function, the same bits; no cell columns) with ITS prepared weights into its own [S][2704] block of
+// a2.  K9's argument list, as the team kernel above and for its reason.
+__global__ void __launch_bounds__(FW_NT, 4) rs_cnn_team_critic_fwd_kernel(CnnIn in, const float* __restrict__ wscratch, float* __restrict__ a2,
+                                                                        float* __restrict__ p1g, uint8_t* __restrict__ amax,
+                                                                        uint16_t* __restrict__ relu_mask) {
+    const size_t c = blockIdx.y;
+    cnn_fwd_rounds<4>(in, wscratch + c * WT_TOTAL(4), a2 + c * in.S * FLAT, p1g, amax, relu_mask, blockIdx.x, gridDim.x);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K10 backward: dL/d(a2) -> per-workgroup partial sums of dW1, db1, dW2, db2 (slab row layout:
 // [dW1 8*CIN*9 | db1 8 | dW2 16*72 | db2 16], torch weight order).
@@ -892,6 +902,20 @@ int rs_cnn_team_trunk_infer(const float* maps, const int32_t* cells, const int32
     if (gx < 1) gx = 1;
     CnnIn32 in{maps, cells, pcells, num_agents, 0, (long long)num_samples};
     hipLaunchKernelGGL(rs_cnn_team_fwd_kernel, dim3(gx, num_agents), dim3(FW_NT), fwd_lds(6), (hipStream_t)stream, in, wscratch, a2,
+                       (float*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_cnn_team_critic_trunk_infer(const float* maps, int32_t num_critics, int64_t num_samples, const float* wscratch, float* a2,
+                                   rs_stream_t stream) {
+    if (!maps || !wscratch || !a2 || num_critics < 1 || num_critics > RS_MAX_AGENTS || num_samples < 0) return RS_ERR_INVALID_ARG;
+    if (num_samples == 0) return RS_OK;
+    const long long rounds = (num_samples + FW_IMG - 1) / FW_IMG;
+    // one resident wave of workgroups for the whole launch, as rs_cnn_team_trunk_infer
+    int gx = cnn_grid(rs_cnn_team_critic_fwd_kernel, FW_NT, fwd_lds(4), rounds * num_critics) / num_critics;
+    if (gx < 1) gx = 1;
+    CnnIn in{maps, nullptr, nullptr, 0, -1, (long long)num_samples};
+    hipLaunchKernelGGL(rs_cnn_team_critic_fwd_kernel, dim3(gx, num_critics), dim3(FW_NT), fwd_lds(4), (hipStream_t)stream, in, wscratch, a2,
                        (float*)nullptr, (uint8_t*)nullptr, (uint16_t*)nullptr);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }

@@ -19,6 +19,9 @@
 //
 // rs_cnn_sized_team_eval_head (run_test_environments_cnn_team_sized): the same scheme at a run-time depth 16 p p for the tiled trunk's
 // maps of any side; it shares the MFMA step and everything behind the k loop (eh_step, eh_finish) and has a kernel of its own.
+//
+// rs_cnn_team_step_head (CNNCollector._step_glued, radiation_ppo_amd/ppo_cnn.py): the same first layer for every actor AND every critic
+// of a team in training, one launch per policy round; at the end of this file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -268,6 +271,184 @@ __global__ void __launch_bounds__(EH_NT) rs_cnn_sized_team_eval_head_kernel(EhNe
     eh_finish(part, acc0, acc1, P, ag, A, n0, u, alive, act8, act, logp, y1_out, N);
 }
 
+// ------------------------------------------------------------------------------------------------
+// rs_cnn_team_step_head: the heads of a team's TRAINING round (CNNCollector._step_glued), one launch for every actor and every critic:
+// grid = (64-image tiles, row), rows 0 .. A - 1 the actors, rows A .. A + C - 1 the critics (C = 1: a global critic, its value goes to every
+// agent's row; C = A: critic c serves agent c).  Every row runs the evaluation kernel's first layer -- the same k ranges, pieces and MFMA
+// order, the four k-quarters added in wave order, then the bias: an actor row's y1, action and log-probability are
+// rs_cnn_team_eval_head's bits -- and behind it rs_cnn_head_kernel's arithmetic: <8> with the draw on the actor rows (no idle rule: act8 is
+// the drawn action), <1> on the critic rows.  Results go to the collector's row buffer f [A][3][N] = {logp, value, bootstrap value}
+// (what rs_store_rows reads).  The bootstrap round launches the critic rows alone (row0 = A) under a mask that is empty on most
+// lock-steps: a workgroup whose 64 envs are all masked out returns before it has requested a byte of W1 or a2.
+// The k loop and the pieces behind it are copies of the evaluation kernel's (the lambdas above, eh_finish) and not shared with it:
+// called from a common inline function the evaluation kernel keeps its registers but comes out in another instruction order, and its
+// measured numbers are the ones DESIGN.md quotes.  eh_step and the constants are shared.
+struct TsNets {
+    rs_cnn_head_params net[2 * RS_MAX_AGENTS];      // [0, A): the actors; [A, A + C): the critics (768 bytes of the argument block)
+};
+
+__device__ __forceinline__ void ts_meet(float (*part)[EH_TILE][EH_ROW], const v16f& acc0, const v16f& acc1) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    // C layout: register i of lane (r, h) is neuron (i & 3) + 8 (i >> 2) + 4 h of image r
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        *reinterpret_cast<float4*>(&part[wave][r][8 * g + 4 * h]) = make_float4(acc0[4 * g], acc0[4 * g + 1], acc0[4 * g + 2], acc0[4 * g + 3]);
+        *reinterpret_cast<float4*>(&part[wave][32 + r][8 * g + 4 * h]) = make_float4(acc1[4 * g], acc1[4 * g + 1], acc1[4 * g + 2], acc1[4 * g + 3]);
+    }
+    __syncthreads();
+}
+
+// y1 of the lane's image: the four k-quarters in wave order, then the bias (y1_row: where to keep it, or NULL); ReLU -> Linear(32, 16) -> ReLU
+__device__ __forceinline__ void ts_hidden(float (*part)[EH_TILE][EH_ROW], const rs_cnn_head_params& P, int lane, float* __restrict__ y1_row,
+                                          float (&h2)[H2]) {
+    const eh_cmem_t b1 = eh_cmem(P.b1), w2 = eh_cmem(P.w2), b2 = eh_cmem(P.b2);
+    float h1[H1];
+#pragma unroll
+    for (int k = 0; k < H1; k += 4) {
+        float4 s = *reinterpret_cast<const float4*>(&part[0][lane][k]);
+#pragma unroll
+        for (int w = 1; w < EH_WAVES; ++w) {
+            const float4 q = *reinterpret_cast<const float4*>(&part[w][lane][k]);
+            s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
+        }
+        s.x += b1[k]; s.y += b1[k + 1]; s.z += b1[k + 2]; s.w += b1[k + 3];
+        if (y1_row) *reinterpret_cast<float4*>(y1_row + k) = s;
+        h1[k] = fmaxf(s.x, 0.0f); h1[k + 1] = fmaxf(s.y, 0.0f); h1[k + 2] = fmaxf(s.z, 0.0f); h1[k + 3] = fmaxf(s.w, 0.0f);
+    }
+#pragma unroll
+    for (int o = 0; o < H2; ++o) {
+        float s = b2[o];
+#pragma unroll
+        for (int k = 0; k < H1; ++k) s = __builtin_fmaf(w2[o * H1 + k], h1[k], s);
+        h2[o] = fmaxf(s, 0.0f);
+    }
+}
+
+// Linear(16, 8) -> log-softmax -> the inverse-CDF draw on uu: the action and its log-probability
+__device__ __forceinline__ void ts_draw(const rs_cnn_head_params& P, const float (&h2)[H2], float uu, int& a, float& lp_sel) {
+    const eh_cmem_t w3 = eh_cmem(P.w3), b3 = eh_cmem(P.b3);
+    float lg[NACT];
+#pragma unroll
+    for (int o = 0; o < NACT; ++o) {
+        float s = b3[o];
+#pragma unroll
+        for (int k = 0; k < H2; ++k) s = __builtin_fmaf(w3[o * H2 + k], h2[k], s);
+        lg[o] = s;
+    }
+    float mx = lg[0];
+#pragma unroll
+    for (int o = 1; o < NACT; ++o) mx = fmaxf(mx, lg[o]);
+    float se = 0.0f;
+#pragma unroll
+    for (int o = 0; o < NACT; ++o) se += expf(lg[o] - mx);
+    const float lse = logf(se);
+    float cdf = 0.0f;
+    lp_sel = (lg[0] - mx) - lse;
+    a = 0;
+#pragma unroll
+    for (int o = 0; o < NACT; ++o) {
+        const float lp = (lg[o] - mx) - lse;
+        cdf += expf(lp);
+        if (o < NACT - 1 && cdf <= uu) a = o + 1;
+    }
+#pragma unroll
+    for (int o = 1; o < NACT; ++o) if (a == o) lp_sel = (lg[o] - mx) - lse;
+}
+
+// one wave's quarter of the 2704-deep first layer: rs_cnn_team_eval_head_kernel's loop (see there), two pieces in flight
+__device__ __forceinline__ void ts_k2704(const float* wp, const float* xa, const float* xb, int h, v16f& acc0, v16f& acc1) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
+    struct Piece { float4 w[4], a[4], b[4]; };
+    auto fetch = [&](Piece& q, int g) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            q.w[i] = *reinterpret_cast<const float4*>(wp + 32 * g + 4 * i);
+            q.a[i] = *reinterpret_cast<const float4*>(xa + 32 * g + 4 * i);
+            q.b[i] = *reinterpret_cast<const float4*>(xb + 32 * g + 4 * i);
+        }
+    };
+    auto consume = [&](const Piece& q) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) eh_step(acc0, acc1, q.w[i], q.a[i], q.b[i]);
+    };
+    Piece p0, p1;
+    fetch(p0, 0);
+    fetch(p1, 1);
+#pragma unroll 1
+    for (int g = 0; g < EH_PIECES - 1; g += 2) {                    // pieces 0 .. 19 in pairs, piece 20 behind the loop
+        consume(p0);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(p0, g + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        consume(p1);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(p1, g + 3 < EH_PIECES ? g + 3 : EH_PIECES - 1);       // (the last trip re-requests piece 20; it is dropped)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    consume(p0);
+    {   // the range's last four floats, 672 .. 675: on the lower half; the upper half re-reads floats of piece 20 and feeds zeros
+        const int o = 32 * EH_PIECES - 32 * h;
+        float4 w = *reinterpret_cast<const float4*>(wp + o);
+        float4 a = *reinterpret_cast<const float4*>(xa + o);
+        float4 b = *reinterpret_cast<const float4*>(xb + o);
+        if (h) { w = make_float4(0.f, 0.f, 0.f, 0.f); a = w; b = w; }
+        eh_step(acc0, acc1, w, a, b);
+    }
+}
+
+__global__ void __launch_bounds__(EH_NT) rs_cnn_team_step_head_kernel(TsNets nets, int A, int C, int row0, int slot,
+                                                                      const float* __restrict__ a2_actor, const float* __restrict__ a2_critic,
+                                                                      const float* __restrict__ u, int64_t* __restrict__ act,
+                                                                      float* __restrict__ f, int8_t* __restrict__ act8,
+                                                                      const uint8_t* __restrict__ mask, float* __restrict__ y1_out, int N) {
+    __shared__ __align__(16) float part[EH_WAVES][EH_TILE][EH_ROW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int y = row0 + blockIdx.y;
+    const int n0 = blockIdx.x * EH_TILE;
+    const int n = n0 + lane;
+    // every wave looks at the same 64 flags, so the four of them agree: nothing to do for this tile -> all leave before the barrier
+    const bool on = n < N && (mask == nullptr || mask[n] != 0);
+    if (!__any(on)) return;
+    const bool actor = y < A;
+    const rs_cnn_head_params P = nets.net[y];
+    const float* a2 = actor ? a2_actor + (size_t)y * N * FLAT : a2_critic + (size_t)(y - A) * N * FLAT;
+    // rows past the last image read the last image's (their sums are dropped)
+    const int na = n0 + r < N ? n0 + r : N - 1, nb = n0 + 32 + r < N ? n0 + 32 + r : N - 1;
+    const float* wp = P.w1 + (size_t)r * FLAT + wave * EH_KW + 16 * h;
+    const float* xa = a2 + (size_t)na * FLAT + wave * EH_KW + 16 * h;
+    const float* xb = a2 + (size_t)nb * FLAT + wave * EH_KW + 16 * h;
+    v16f acc0, acc1;
+    ts_k2704(wp, xa, xb, h, acc0, acc1);
+    ts_meet(part, acc0, acc1);
+    if (wave != 0) return;
+    const int nc = n < N ? n : N - 1;
+    float h2[H2];
+    ts_hidden(part, P, lane, y1_out && on ? y1_out + ((size_t)y * N + n) * H1 : nullptr, h2);
+    if (actor) {
+        int a;
+        float lp_sel;
+        ts_draw(P, h2, u[(size_t)nc * A + y], a, lp_sel);
+        if (on) {
+            act[(size_t)y * N + n] = a;
+            f[(size_t)y * 3 * N + n] = lp_sel;
+            act8[(size_t)n * A + y] = (int8_t)a;
+        }
+    } else {
+        // rs_cnn_head_kernel<1>: the state value, to its owner's row or (global critic) to every agent's
+        const eh_cmem_t w3 = eh_cmem(P.w3), b3 = eh_cmem(P.b3);
+        float v = b3[0];
+#pragma unroll
+        for (int k = 0; k < H2; ++k) v = __builtin_fmaf(w3[k], h2[k], v);
+        if (on) {
+            if (C == 1) for (int a = 0; a < A; ++a) f[((size_t)a * 3 + slot) * N + n] = v;
+            else f[((size_t)(y - A) * 3 + slot) * N + n] = v;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -297,6 +478,29 @@ int rs_cnn_sized_team_eval_head(const rs_cnn_head_params* heads, int32_t num_age
     for (int a = 0; a < RS_MAX_AGENTS; ++a) nets.head[a] = heads[a < num_agents ? a : 0];     // the slots behind the team repeat agent 0 (never read)
     hipLaunchKernelGGL(rs_cnn_sized_team_eval_head_kernel, dim3((num_envs + EH_TILE - 1) / EH_TILE, num_agents), dim3(EH_NT), 0,
                        static_cast<hipStream_t>(stream), nets, (int)num_agents, (int)flat, a2, u, alive, act8, act, logp, y1_out, (int)num_envs);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_cnn_team_step_head(const rs_cnn_head_params* actors, int32_t num_agents, const rs_cnn_head_params* critics, int32_t num_critics,
+                          const float* a2_actor, const float* a2_critic, const float* u, int64_t* act, float* logp_val_boot, int8_t* act8,
+                          const uint8_t* mask, float* y1_out, int32_t num_envs, rs_stream_t stream) {
+    const bool step = u != nullptr;
+    if (num_agents < 1 || num_agents > RS_MAX_AGENTS || (num_critics != 1 && num_critics != num_agents) || num_envs < 1) return RS_ERR_INVALID_ARG;
+    if (!critics || !a2_critic || !logp_val_boot) return RS_ERR_INVALID_ARG;
+    if (step ? (!actors || !a2_actor || !act || !act8) : !mask) return RS_ERR_INVALID_ARG;
+    auto whole = [](const rs_cnn_head_params& p) { return p.w1 && p.b1 && p.w2 && p.b2 && p.w3 && p.b3; };
+    for (int c = 0; c < num_critics; ++c)
+        if (!whole(critics[c])) return RS_ERR_INVALID_ARG;
+    for (int a = 0; step && a < num_agents; ++a)
+        if (!whole(actors[a])) return RS_ERR_INVALID_ARG;
+    TsNets nets;
+    for (int i = 0; i < 2 * RS_MAX_AGENTS; ++i) nets.net[i] = critics[0];                       // the slots no row reads
+    for (int a = 0; step && a < num_agents; ++a) nets.net[a] = actors[a];
+    for (int c = 0; c < num_critics; ++c) nets.net[num_agents + c] = critics[c];
+    const int rows = step ? num_agents + num_critics : num_critics;                              // the bootstrap round: the critic rows alone
+    hipLaunchKernelGGL(rs_cnn_team_step_head_kernel, dim3((num_envs + EH_TILE - 1) / EH_TILE, rows), dim3(EH_NT), 0,
+                       static_cast<hipStream_t>(stream), nets, (int)num_agents, (int)num_critics, step ? 0 : (int)num_agents, step ? 1 : 2,
+                       a2_actor, a2_critic, u, act, logp_val_boot, act8, mask, y1_out, (int)num_envs);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -319,11 +319,14 @@ class CNNCollector:
         return self._cs
 
     @torch.no_grad()
-    def _round_glued(self, mask8: Optional[torch.Tensor] = None):
+    def _round_glued(self, mask8: Optional[torch.Tensor] = None, cells: bool = True):
+        """cells=False: without the int64 copies of the owners' cells (the team round reads the heat maps' own int32 fields)."""
         pred = None
         if self.predictor is not None:
             pred = self.predictor.predict_kernel(self.obs, mask8=mask8)
         self.maps.update(self.obs, pred=pred, mask=mask8)
+        if not cells:
+            return self.maps.shared_maps(), None, None
         return self.maps.shared_maps(), self.maps.field("cell").long(), self.maps.field("pred_cell").long()
 
     @property
@@ -332,14 +335,32 @@ class CNNCollector:
         rs_store_rows; any map size (K9 at 27 x 27, the tiled trunk elsewhere)."""
         return self.use_glue and getattr(self, "heads", True)
 
+    @property
+    def use_team_round(self) -> bool:
+        """The fused round in at most three launches whatever the team size (27 x 27 maps, agents 0..A-1, one shared critic or one per
+        agent): rs_cnn_team_trunk_infer, the critic trunk(s), rs_cnn_team_step_head; the bootstrap round in two.  `team_round = False`
+        selects the per-agent round (the A/B form); on by default for every team size, one agent included: it measured faster
+        for 1, 2, 4 and 8 agents in both critic modes (profiles/cnn_team_collect_timing.txt)."""
+        if not (self.use_heads and getattr(self, "team_round", True)):
+            return False
+        if tuple(self.maps.map_dimensions) != (27, 27) or sorted(self.agents) != list(range(self.A)):
+            return False
+        ags = [self.agents[a] for a in range(self.A)]
+        shared = all(ag.global_critic and ag.critic is ags[0].critic for ag in ags)
+        own = not any(ag.global_critic for ag in ags) and len({id(ag.critic) for ag in ags}) == self.A
+        return shared or own
+
     def _prepare_heads(self) -> None:
         """Once per epoch (the networks do not change during collection): every agent's convolution weights in the trunk kernel's
         layout (27 x 27; the tiled trunk reads torch's layout); the fixed-address buffers of the fused round."""
         lib, dev, N, A = _lib.load(), self.env.device, self.N, self.A
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         if getattr(self, "_wt", None) is None:
-            self._wt = {a: torch.empty(lib.rs_cnn_trunk_scratch_floats(6), dtype=torch.float32, device=dev) for a in self.agents}
-            self._wt_c = {a: torch.empty(lib.rs_cnn_trunk_scratch_floats(4), dtype=torch.float32, device=dev) for a in self.agents}
+            # [A][scratch] / [C][scratch], what the team launches read; agent a's rows are at its place in the sorted ids
+            self._wt_all = torch.empty(A, lib.rs_cnn_trunk_scratch_floats(6), dtype=torch.float32, device=dev)
+            self._wt_c_all = torch.empty(A, lib.rs_cnn_trunk_scratch_floats(4), dtype=torch.float32, device=dev)
+            self._wt = {a: self._wt_all[i] for i, a in enumerate(sorted(self.agents))}
+            self._wt_c = {a: self._wt_c_all[i] for i, a in enumerate(sorted(self.agents))}
             P = self.maps.map_dimensions[0] // 2
             self._a2 = torch.empty(N, 16 * P * P, dtype=torch.float32, device=dev)
             self._k_act = torch.zeros(A, N, dtype=torch.int64, device=dev)
@@ -355,6 +376,38 @@ class CNNCollector:
                 c = ag.critic.critic
                 _lib.check(lib.rs_cnn_trunk_prepare(4, c[0].weight.data_ptr(), c[0].bias.data_ptr(), c[3].weight.data_ptr(), c[3].bias.data_ptr(),
                                                     self._wt_c[a].data_ptr(), st), "rs_cnn_trunk_prepare")
+        if self.use_team_round:
+            ags = [self.agents[a] for a in range(A)]
+            nc = 1 if ags[0].global_critic else A
+            if getattr(self, "_a2_act", None) is None or self._a2_cri.shape[0] != nc:
+                self._a2_act = torch.empty(A, N, 2704, dtype=torch.float32, device=dev)             # one a2 scratch per role
+                self._a2_cri = torch.empty(nc, N, 2704, dtype=torch.float32, device=dev)
+                self._cell32, self._pcell32 = self.maps.field("cell"), self.maps.field("pred_cell")     # views of the heat maps' own state
+                assert self._cell32.dtype == torch.int32 and self._pcell32.dtype == torch.int32 and self._cell32.shape == (N, A)
+            hp = lambda m: _lib.RsCnnHeadParams(m[6].weight.data_ptr(), m[6].bias.data_ptr(), m[8].weight.data_ptr(), m[8].bias.data_ptr(),
+                                                m[10].weight.data_ptr(), m[10].bias.data_ptr())
+            self._hp_act = (_lib.RsCnnHeadParams * A)(*[hp(ag.pi.actor) for ag in ags])
+            self._hp_cri = (_lib.RsCnnHeadParams * nc)(*[hp(ag.critic.critic) for ag in ags[:nc]])
+
+    def _team_round(self, maps, mask8=None) -> None:
+        """The step round (mask8 None: every agent's action, log-probability and value into self._k_act / _k_f[:, 0] / _k_f[:, 1] /
+        self._act8) or the bootstrap round (the values of the envs in mask8 into self._k_f[:, 2]) in three / two launches."""
+        lib, N, A = _lib.load(), self.N, self.A
+        st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        p = lambda t: t.data_ptr()
+        step = mask8 is None
+        nc = self._a2_cri.shape[0]
+        if step:
+            _lib.check(lib.rs_cnn_team_trunk_infer(p(maps), p(self._cell32), p(self._pcell32), A, N, p(self._wt_all), p(self._a2_act), st),
+                       "rs_cnn_team_trunk_infer")
+        if nc == 1:
+            _lib.check(lib.rs_cnn_trunk_infer(p(maps), None, None, 0, -1, N, p(self._wt_c_all), p(self._a2_cri), st), "rs_cnn_trunk_infer")
+        else:
+            _lib.check(lib.rs_cnn_team_critic_trunk_infer(p(maps), nc, N, p(self._wt_c_all), p(self._a2_cri), st),
+                       "rs_cnn_team_critic_trunk_infer")
+        o = (p(self._u), p(self._k_act), p(self._k_f), p(self._act8), None) if step else (None, None, p(self._k_f), None, p(mask8))
+        _lib.check(lib.rs_cnn_team_step_head(self._hp_act, A, self._hp_cri, nc, p(self._a2_act), p(self._a2_cri), *o, None, N, st),
+                   "rs_cnn_team_step_head")
 
     def _values_fused(self, critic_maps, slot: int, mask8=None) -> None:
         """V(s) of every env into self._k_f[:, slot] (slot 1: the step's value, 2: the bootstrap value): one evaluation serves every
@@ -392,18 +445,21 @@ class CNNCollector:
     def _step_glued(self, epoch_ended: bool) -> None:
         """_step with the element-wise bookkeeping between the library calls in rs_collect_post_step / _post_reset and (27 x 27 maps) every
         agent's select_action as trunk + Linear + rs_cnn_head, the buffer rows by rs_store_rows: ~40 launches per lock-step where the
-        torch composition took ~110."""
+        torch composition took ~110; with use_team_round the policy round is three launches and the bootstrap round two (_team_round)."""
         env, buf, N, A = self.env, self.buf, self.N, self.A
         acc, ti = self._acc, self._t
         lib, cs = _lib.load(), self._glue_state()
         st = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
         over, cut, boot = self._flags[0], self._flags[1], self._flags[2]
         put = lambda dst, row: dst.index_copy_(0, ti, row.unsqueeze(0))
-        heads = self.use_heads
+        heads, team = self.use_heads, self.use_team_round
         critic, cells, pcells = self._round_glued()
         put(self.shared, critic); put(self.cells, cells); put(self.pcells, pcells)
         env.action_uniforms(self._u)
-        if heads:
+        if team:
+            self._x_buf.copy_(self.obs)
+            self._team_round(critic)
+        elif heads:
             self._x_buf.copy_(self.obs)
             for a, ag in self.agents.items():
                 m = ag.pi.actor
@@ -429,7 +485,7 @@ class CNNCollector:
         _lib.check(lib.rs_collect_post_step(C.byref(cs), 1 if epoch_ended else 0, st), "rs_collect_post_step")
         done, oob_now = self._done_oob[0], self._done_oob[1]           # post_step's copies: the env's own rows are rewritten by the reset
         # bootstrap: ac.step(observations) once more for the envs that time out / are cut (train.py:462-480)
-        critic_b, _, _ = self._round_glued(mask8=boot)
+        critic_b, _, _ = self._round_glued(mask8=boot, cells=not team)
         # the heat maps have seen the agents' last positions: from here the env's reset (latency bound, ~110 us) runs on the side stream
         # beside the critic's bootstrap evaluation, the buffer rows and the statistics (which read post_step's copies)
         main = torch.cuda.current_stream(env.device)
@@ -440,7 +496,10 @@ class CNNCollector:
                 env.set_epoch_end()
             env.reset(cut)
         if heads:
-            self._values_fused(critic_b, 2, mask8=boot)
+            if team:
+                self._team_round(critic_b, mask8=boot)
+            else:
+                self._values_fused(critic_b, 2, mask8=boot)
             _lib.check(lib.rs_store_rows(ti.data_ptr(), self._k_act.data_ptr(), self._k_f.data_ptr(), self._x_buf.data_ptr(),
                                          self._src_copy[0].data_ptr(), self._src_copy[1].data_ptr(), self._rew_used.data_ptr(), cut.data_ptr(),
                                          boot.data_ptr(), buf.act.data_ptr(), buf.logp.data_ptr(), buf.val.data_ptr(), buf.last_val.data_ptr(),
@@ -551,8 +610,9 @@ class CNNCollector:
             with torch.cuda.stream(side):
                 critic = self.maps.shared_maps()
                 cells, pcells = self.maps.field("cell").long(), self.maps.field("pred_cell").long()
-                for a, ag in self.agents.items():
-                    ag.act((critic, cells, pcells, a), self._u[:, a]); ag._values((critic,))
+                if not (self.use_glue and getattr(self, "glue", True) and self.use_team_round):     # the team round calls no library GEMM
+                    for a, ag in self.agents.items():
+                        ag.act((critic, cells, pcells, a), self._u[:, a]); ag._values((critic,))
                 if self.predictor is not None:
                     self.predictor._packed()
             torch.cuda.current_stream(self.env.device).wait_stream(side)

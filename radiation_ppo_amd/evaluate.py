@@ -13,7 +13,7 @@ environment's own spawn rules; the reference's own pickled sets are read by radi
 `run_test_environments_cnn` is the same runner for RAD-TEAM (CNN) policies, `run_test_environments_cnn_team` its HIP lock-step for teams
 of up to 8 on 27 x 27 maps (csrc/rs_cnn.hip, csrc/rs_cnn_eval.hip), `run_test_environments_cnn_team_sized` the same for square maps of
 any side 8..256 (walls off: 147 x 147; csrc/rs_cnn_sized.hip, csrc/rs_cnn_eval.hip), `run_test_environments_team` for feed-forward agents and
-teams of up to 8, `run_test_environments_rnn_team` for recurrent (RAD-A2C) teams of 1 to 8 -- it holds the recurrent lock-step, fused in
+teams of up to 8 -- these three are fronts to one lock-step loop, `_run_lane_per_run_team` --, `run_test_environments_rnn_team` for recurrent (RAD-A2C) teams of 1 to 8 -- it holds the recurrent lock-step, fused in
 HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip) and composed; `run_test_environments_rnn` is its front for one agent, and
 `run_test_environments` sends a recurrent agent there --, `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
@@ -454,6 +454,202 @@ def run_test_environments_cnn(agents: Dict[int, Any], env_sets: Dict[str, tuple]
 
 
 @torch.no_grad()
+def _run_lane_per_run_team(rounds, agents, env_sets, montecarlo_runs, steps_per_episode, team_mode, obstruction_count,
+                           enforce_grid_boundaries, seed, device, return_actions, fused, welford, id_hint="", cuda_front="", setup=None,
+                           **vec_kwargs):
+    """The loop under run_test_environments_team, run_test_environments_cnn_team and run_test_environments_cnn_team_sized: E * R lanes
+    of one episode each; a lane ends when any agent's terminal flag rises or at steps_per_episode and then idles (rows of 8), its
+    records frozen.  Ids other than 0..A-1 (id_hint ends that message) and, for the front named in cuda_front, a device that is not
+    cuda are refused before the library is loaded or an environment is built.  setup(run), where given, runs right after the opening
+    and returns what the architecture keeps for the run; rounds(run, fused, *that) -- run.obs [N, A, 11] holds the current observation
+    throughout, run.stat is None without welford, run.alive8 is run.alive as bytes --, called once, returns (before, policy_round):
+    before(), or None, is the same in both forms; policy_round(a8) writes every lane's action row into a8 [N, A] int8, 8 on finished
+    lanes -- by the kernel's own rule in the fused form, by the torch idle rule in the composed one.
+    A lock-step is rs_action_uniforms, before(), policy_round(a8), rs_step and then, fused, rs_eval_post_step (returns, lengths, the
+    terminal rule, the Welford update where there are statistics, the new observation, the finished-lane count) on the same stream;
+    composed, the same in torch.  The host reads the finished-lane count at every 16th lock-step and nowhere else."""
+    A = len(agents)
+    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
+        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}{id_hint}")
+    dev = torch.device(device)
+    if cuda_front and dev.type != "cuda":
+        raise ValueError(f"{cuda_front} needs a cuda device; run_test_environments_cnn runs elsewhere")
+    R, L, N = montecarlo_runs, steps_per_episode, len(env_sets) * montecarlo_runs
+    lib = _lib.load()
+    vec, keys, saved, obs, stat = _open(env_sets, R, A, obstruction_count, enforce_grid_boundaries, seed, device, welford=welford, **vec_kwargs)
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    run = SimpleNamespace(lib=lib, vec=vec, obs=obs, stat=stat, N=N, A=A, L=L, seed=seed, dev=dev, st=st)
+    own = setup(run) if setup else ()                             # before the records: device memory is laid out as it always was
+    alive, ep_len, ep_ret, success = _lane_records(N, dev)
+    u = torch.empty(N, A, dtype=torch.float32, device=dev)
+    # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads
+    log = torch.full((L, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
+    act8 = None if return_actions else torch.empty(N, A, dtype=torch.int8, device=dev)
+    use_team, p = team_mode != "individual", lambda t: t.data_ptr()
+    run.u, run.alive, run.alive8 = u, alive, alive.view(torch.uint8)
+    before, policy_round = rounds(run, fused, *own)
+    if fused:
+        finished = torch.zeros(1, dtype=torch.int32, device=dev)
+        w = [None] * 4 if stat is None else [p(t) for t in (stat.count, stat.mean, stat.sq, stat.std)]
+        state = _lib.RsEvalState(N, A, 1 if use_team else 0, p(vec.obs), p(vec.reward), p(vec.team), p(vec.done), p(obs), *w,
+                                 p(run.alive8), p(success.view(torch.uint8)), p(ep_len), p(ep_ret), p(finished))
+        post_step, state_ref = lib.rs_eval_post_step, C.byref(state)      # once, not per lock-step: it pays for the policy round's call
+    it = 0
+    while it < L:
+        if it and it % 16 == 0:                                   # one host read per 16 lock-steps
+            if (int(finished.item()) if fused else N - int(alive.sum().item())) == N:
+                break
+        a8 = log[it] if return_actions else act8
+        vec.action_uniforms(u)
+        if before is not None:
+            before()
+        policy_round(a8)
+        if fused:
+            vec.step(a8)
+            _lib.check(post_step(state_ref, st), "rs_eval_post_step")
+        else:
+            obs_n, rew, team, done, _ = vec.step(a8)
+            _book_step(alive, ep_len, ep_ret, success, team if use_team else rew[:, 0], done.bool().any(dim=1))
+            if stat is not None:
+                stat.update(obs_n[..., 0], mask=alive)            # after _book_step: the lanes that have just finished are out
+            obs.copy_(obs_n)
+        it += 1
+    # finished episodes idle on purpose; stacked agents may "stall"
+    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=log[:it] if return_actions else None,
+                  ignore_flags=_lib.ENVERR_IDLE_STALL)
+
+
+def _ff_rounds(run, fused, agents):
+    """The feed-forward policy round.  fused: rs_ff_eval_step (standardisation, every agent's actor, the draw, idle rows).  composed:
+    DeviceWelford.standardize, rs_ff_team_step's step round (value and log-probability dropped) and the idle rule."""
+    lib, obs, stat, N, A, u, alive, alive8, st = run.lib, run.obs, run.stat, run.N, run.A, run.u, run.alive, run.alive8, run.st
+    p = lambda t: t.data_ptr()
+    arr = _lib.RsMlpParams * A
+    pa = arr(*[mlp_params(agents[a].agent.actor) for a in range(A)])
+    if fused:
+        step, fixed = lib.rs_ff_eval_step, (A, p(obs), p(stat.mean), p(stat.std), p(u), p(alive8))     # buffers that stay where they are
+
+        def policy_round(a8):
+            _lib.check(step(pa, *fixed, p(a8), N, st), "rs_ff_eval_step")
+    else:
+        pc = arr(*[mlp_params(agents[a].agent.critic) for a in range(A)])
+        x = torch.empty_like(obs)
+        k_act = torch.empty(A, N, dtype=torch.int64, device=run.dev)
+        k_f = torch.empty(A, 3, N, dtype=torch.float32, device=run.dev)
+
+        def policy_round(a8):
+            x.copy_(obs)
+            stat.standardize(obs[..., 0], out=x[..., 0])
+            _lib.check(lib.rs_ff_team_step(pa, pc, A, p(x), p(u), p(k_act), p(k_f), None, None, N, st), "rs_ff_team_step")
+            a8.copy_(torch.where(alive.view(N, 1), k_act.t(), torch.full_like(k_act.t(), 8)).to(torch.int8))   # finished episodes idle
+    return None, policy_round
+
+
+def _cnn_team_setup(run, front, agents, use_predictor, refuse_sides):
+    """What the two RAD-TEAM rounds share, for the runner `front`: the HeatMaps -- refuse_sides(map dimensions) raises the front's own
+    message about sides it does not serve --, the HIP PredictorBank with the agents' saved predictor weights, the views of the maps'
+    cell fields, the actors, and the step before either round: the PFGRU step of every owner with the bank's call counter,
+    rs_maps_update, rs_maps_stack.  Returns (shared, cells, pcells, actors, before); shared [N, 4, X, Y] is what rs_maps_stack fills."""
+    from .maps import HeatMaps
+    from .pfgru import PredictorBank
+    obs, N, A = run.obs, run.N, run.A
+    maps = HeatMaps(run.vec, run.L, enforce_boundaries=bool(run.vec.cfg.enforce_grid_boundaries))
+    refuse_sides(tuple(maps.map_dimensions))
+    bank = None
+    if use_predictor:
+        bank = PredictorBank(N, A, seed=run.seed, device=run.dev)
+        if bank.impl != "hip":
+            raise ValueError(f"{front} needs PredictorBank(impl='hip'); use run_test_environments_cnn")
+        for a in range(A):
+            if getattr(agents[a], "model", None) is not None:         # the agent's own (saved) predictor weights
+                bank.load_state_dict(a, agents[a].model.state_dict())
+        bank.reset()
+    cells, pcells = maps.field("cell"), maps.field("pred_cell")       # views of the heat maps' own state: [N, A] int32, -1 = none
+    assert cells.dtype == torch.int32 and pcells.dtype == torch.int32 and cells.shape == (N, A) and pcells.shape == (N, A)
+
+    def before():
+        pred = None
+        if bank is not None:
+            pred = bank.predict_kernel(obs)                       # bank.predict without its copy of the prediction
+            bank.calls.add_(1)
+        maps.update(obs, pred=pred)
+        maps.shared_maps()                                        # fills maps.critic_stack in place and returns it: `shared` below
+    return maps.critic_stack, cells, pcells, [agents[a].pi.actor for a in range(A)], before
+
+
+def _cnn_rounds(run, fused, shared, cells, pcells, actors, before):
+    """The RAD-TEAM policy round on 27 x 27 maps behind _cnn_team_setup; the agents' convolution weights are re-arranged
+    once.  fused: rs_cnn_team_trunk_infer and rs_cnn_team_eval_head over one a2 [A, N, 2704].  composed: per agent
+    rs_cnn_trunk_infer, torch.nn.functional.linear, rs_cnn_head and the idle rule."""
+    from .maps import cnn_head_params, cnn_trunk_prepare
+    lib, N, A, dev, u, alive, alive8, st = run.lib, run.N, run.A, run.dev, run.u, run.alive, run.alive8, run.st
+    p = lambda t: t.data_ptr()
+    wt = torch.empty(A, lib.rs_cnn_trunk_scratch_floats(6), dtype=torch.float32, device=dev)     # in K9's layout, once per run
+    for a, m in enumerate(actors):
+        cnn_trunk_prepare(m, 6, wt[a], st)
+    if fused:
+        a2 = torch.empty(A, N, 2704, dtype=torch.float32, device=dev)
+        heads = (_lib.RsCnnHeadParams * A)(*[cnn_head_params(m) for m in actors])
+
+        def policy_round(a8):
+            _lib.check(lib.rs_cnn_team_trunk_infer(p(shared), p(cells), p(pcells), A, N, p(wt), p(a2), st), "rs_cnn_team_trunk_infer")
+            _lib.check(lib.rs_cnn_team_eval_head(heads, A, p(a2), p(u), p(alive8), p(a8), None, None, None, N, st), "rs_cnn_team_eval_head")
+    else:
+        a2 = torch.empty(N, 2704, dtype=torch.float32, device=dev)
+        k_act = torch.empty(A, N, dtype=torch.int64, device=dev)
+
+        def policy_round(a8):
+            cl, pl = cells.long(), pcells.long()
+            for a, m in enumerate(actors):
+                _lib.check(lib.rs_cnn_trunk_infer(p(shared), p(cl), p(pl), A, a, N, p(wt[a]), p(a2), st), "rs_cnn_trunk_infer")
+                y1 = torch.nn.functional.linear(a2, m[6].weight, m[6].bias)
+                _lib.check(lib.rs_cnn_head(p(y1), p(m[8].weight), p(m[8].bias), p(m[10].weight), p(m[10].bias), 8, p(u) + 4 * a, A, p(k_act[a]),
+                                           None, None, 1, None, 1, 0, None, N, st), "rs_cnn_head")
+                a8[:, a] = torch.where(alive, k_act[a], torch.full_like(k_act[a], 8)).to(torch.int8)    # finished episodes idle in place
+    return before, policy_round
+
+
+def _cnn_sized_rounds(run, fused, a2_bytes, shared, cells, pcells, actors, before):
+    """The RAD-TEAM policy round on square maps of side M behind _cnn_team_setup, chunk lanes at a time through one scratch
+    a2 of at most a2_bytes (never less than 64 lanes').  fused: rs_cnn_sized_team_infer and rs_cnn_sized_team_eval_head per chunk.
+    composed: per agent and chunk rs_cnn_sized_infer, torch.nn.functional.linear and rs_cnn_head, then the idle rule."""
+    from .maps import cnn_conv_params, cnn_head_params
+    lib, N, A, dev, u, alive, alive8, st = run.lib, run.N, run.A, run.dev, run.u, run.alive, run.alive8, run.st
+    p = lambda t: t.data_ptr()
+    M = shared.shape[-1]
+    flat = 16 * (M // 2) ** 2
+    chunk = min(max(64, int(a2_bytes) // (4 * A * flat) // 64 * 64), N)
+    if fused:
+        a2 = torch.empty(A * chunk * flat, dtype=torch.float32, device=dev)
+        convs = (_lib.RsCnnConvParams * A)(*[cnn_conv_params(m) for m in actors])
+        heads = (_lib.RsCnnHeadParams * A)(*[cnn_head_params(m) for m in actors])
+
+        def policy_round(a8):
+            for lo in range(0, N, chunk):                         # the same scratch for every chunk: one stream keeps them in order
+                n = min(chunk, N - lo)
+                _lib.check(lib.rs_cnn_sized_team_infer(p(shared) + 16 * M * M * lo, p(cells) + 4 * A * lo, p(pcells) + 4 * A * lo, A, n, M, convs,
+                                                       p(a2), st), "rs_cnn_sized_team_infer")
+                _lib.check(lib.rs_cnn_sized_team_eval_head(heads, A, flat, p(a2), p(u) + 4 * A * lo, p(alive8) + lo, p(a8) + A * lo, None, None,
+                                                           None, n, st), "rs_cnn_sized_team_eval_head")
+    else:
+        a2 = torch.empty(chunk * flat, dtype=torch.float32, device=dev)
+        k_act = torch.empty(A, N, dtype=torch.int64, device=dev)
+
+        def policy_round(a8):
+            cl, pl = cells.long(), pcells.long()
+            for a, m in enumerate(actors):
+                for lo in range(0, N, chunk):
+                    n = min(chunk, N - lo)
+                    x = a2[:n * flat].view(n, flat)
+                    _lib.check(lib.rs_cnn_sized_infer(p(shared) + 16 * M * M * lo, p(cl) + 8 * A * lo, p(pl) + 8 * A * lo, A, a, n, M, p(m[0].weight),
+                                                      p(m[0].bias), p(m[3].weight), p(m[3].bias), p(x), st), "rs_cnn_sized_infer")
+                    y1 = torch.nn.functional.linear(x, m[6].weight, m[6].bias)
+                    _lib.check(lib.rs_cnn_head(p(y1), p(m[8].weight), p(m[8].bias), p(m[10].weight), p(m[10].bias), 8, p(u) + 4 * (A * lo + a), A,
+                                               p(k_act[a]) + 8 * lo, None, None, 1, None, 1, 0, None, n, st), "rs_cnn_head")
+                a8[:, a] = torch.where(alive, k_act[a], torch.full_like(k_act[a], 8)).to(torch.int8)    # finished episodes idle in place
+    return before, policy_round
+
+
 def run_test_environments_cnn_team(agents: Dict[int, Any], env_sets: Dict[str, tuple], montecarlo_runs: int = 100,
                                    steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
                                    enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0",
@@ -474,93 +670,17 @@ def run_test_environments_cnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
 
     Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log of rs_step's action rows
     (8 where a lane had finished)."""
-    from .maps import HeatMaps
-    from .pfgru import PredictorBank
-    A = len(agents)
-    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
-        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}; run_test_environments_cnn takes any ids")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("run_test_environments_cnn_team needs a cuda device; run_test_environments_cnn runs elsewhere")
-    R, L = montecarlo_runs, steps_per_episode
-    N = len(env_sets) * R
-    lib = _lib.load()
-    vec, keys, saved, obs, _ = _open(env_sets, R, A, obstruction_count, enforce_grid_boundaries, seed, device, welford=False)
-    maps = HeatMaps(vec, L, enforce_boundaries=bool(enforce_grid_boundaries))
-    if tuple(maps.map_dimensions) != (27, 27) or any(tuple(agents[a].map_dim) != (27, 27) for a in range(A)):
-        raise ValueError(f"run_test_environments_cnn_team serves 27 x 27 heat maps, this configuration has {tuple(maps.map_dimensions)}; "
-                         "use run_test_environments_cnn")
-    bank = None
-    if use_predictor:
-        bank = PredictorBank(N, A, seed=seed, device=dev)
-        if bank.impl != "hip":
-            raise ValueError("run_test_environments_cnn_team needs PredictorBank(impl='hip'); use run_test_environments_cnn")
-        for a in range(A):
-            if getattr(agents[a], "model", None) is not None:         # the agent's own (saved) predictor weights
-                bank.load_state_dict(a, agents[a].model.state_dict())
-        bank.reset()
-    alive, ep_len, ep_ret, success = _lane_records(N, dev)
-    u = torch.empty(N, A, dtype=torch.float32, device=dev)
-    # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads
-    log = torch.full((L, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
-    act8 = None if return_actions else torch.empty(N, A, dtype=torch.int8, device=dev)
-    use_team = team_mode != "individual"
-    p = lambda t: t.data_ptr()
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    actors = [agents[a].pi.actor for a in range(A)]
-    scratch = lib.rs_cnn_trunk_scratch_floats(6)
-    wt = torch.empty(A, scratch, dtype=torch.float32, device=dev)     # every agent's convolution weights in K9's layout, once per run
-    for a, m in enumerate(actors):
-        _lib.check(lib.rs_cnn_trunk_prepare(6, p(m[0].weight), p(m[0].bias), p(m[3].weight), p(m[3].bias), p(wt[a]), st), "rs_cnn_trunk_prepare")
-    cells, pcells = maps.field("cell"), maps.field("pred_cell")       # views of the heat maps' own state: [N, A] int32, -1 = none
-    assert cells.dtype == torch.int32 and pcells.dtype == torch.int32 and cells.shape == (N, A) and pcells.shape == (N, A)
-    if fused:
-        a2 = torch.empty(A, N, 2704, dtype=torch.float32, device=dev)
-        heads = (_lib.RsCnnHeadParams * A)(*[_lib.RsCnnHeadParams(p(m[6].weight), p(m[6].bias), p(m[8].weight), p(m[8].bias), p(m[10].weight),
-                                                                   p(m[10].bias)) for m in actors])
-        finished = torch.zeros(1, dtype=torch.int32, device=dev)
-        alive8, success8 = alive.view(torch.uint8), success.view(torch.uint8)
-        state = _lib.RsEvalState(N, A, 1 if use_team else 0, p(vec.obs), p(vec.reward), p(vec.team), p(vec.done), p(obs), None, None, None,
-                                 None, p(alive8), p(success8), p(ep_len), p(ep_ret), p(finished))
-    else:
-        a2 = torch.empty(N, 2704, dtype=torch.float32, device=dev)
-        k_act = torch.empty(A, N, dtype=torch.int64, device=dev)
-    it = 0
-    while it < L:
-        if it and it % 16 == 0:                                   # one host read per 16 lock-steps
-            if (int(finished.item()) if fused else N - int(alive.sum().item())) == N:
-                break
-        a8 = log[it] if return_actions else act8
-        vec.action_uniforms(u)
-        pred = None
-        if bank is not None:
-            pred = bank.predict_kernel(obs)                       # bank.predict without its copy of the prediction
-            bank.calls.add_(1)
-        maps.update(obs, pred=pred)
-        shared = maps.shared_maps()
-        if fused:
-            _lib.check(lib.rs_cnn_team_trunk_infer(p(shared), p(cells), p(pcells), A, N, p(wt), p(a2), st), "rs_cnn_team_trunk_infer")
-            _lib.check(lib.rs_cnn_team_eval_head(heads, A, p(a2), p(u), p(alive8), p(a8), None, None, None, N, st), "rs_cnn_team_eval_head")
-            vec.step(a8)
-            _lib.check(lib.rs_eval_post_step(C.byref(state), st), "rs_eval_post_step")
-        else:
-            cl, pl = cells.long(), pcells.long()
-            for a, m in enumerate(actors):
-                _lib.check(lib.rs_cnn_trunk_infer(p(shared), p(cl), p(pl), A, a, N, p(wt[a]), p(a2), st), "rs_cnn_trunk_infer")
-                y1 = torch.nn.functional.linear(a2, m[6].weight, m[6].bias)
-                _lib.check(lib.rs_cnn_head(p(y1), p(m[8].weight), p(m[8].bias), p(m[10].weight), p(m[10].bias), 8, p(u) + 4 * a, A, p(k_act[a]),
-                                           None, None, 1, None, 1, 0, None, N, st), "rs_cnn_head")
-                a8[:, a] = torch.where(alive, k_act[a], torch.full_like(k_act[a], 8)).to(torch.int8)    # finished episodes idle in place
-            obs_n, rew, team, done, _ = vec.step(a8)
-            _book_step(alive, ep_len, ep_ret, success, team if use_team else rew[:, 0], done.bool().any(dim=1))
-            obs.copy_(obs_n)
-        it += 1
-    # finished episodes idle on purpose; stacked agents may "stall"
-    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=log[:it] if return_actions else None,
-                  ignore_flags=_lib.ENVERR_IDLE_STALL)
+    front = "run_test_environments_cnn_team"
+
+    def refuse_sides(dims):
+        if dims != (27, 27) or any(tuple(ag.map_dim) != (27, 27) for ag in agents.values()):
+            raise ValueError(f"{front} serves 27 x 27 heat maps, this configuration has {dims}; use run_test_environments_cnn")
+    return _run_lane_per_run_team(
+        _cnn_rounds, agents, env_sets, montecarlo_runs, steps_per_episode, team_mode, obstruction_count, enforce_grid_boundaries, seed,
+        device, return_actions, fused, welford=False, id_hint="; run_test_environments_cnn takes any ids", cuda_front=front,
+        setup=lambda run: _cnn_team_setup(run, front, agents, use_predictor, refuse_sides))
 
 
-@torch.no_grad()
 def run_test_environments_cnn_team_sized(agents: Dict[int, Any], env_sets: Dict[str, tuple], montecarlo_runs: int = 100,
                                          steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
                                          enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0",
@@ -583,102 +703,21 @@ def run_test_environments_cnn_team_sized(agents: Dict[int, Any], env_sets: Dict[
 
     Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log of rs_step's action rows
     (8 where a lane had finished)."""
-    from .maps import HeatMaps
-    from .pfgru import PredictorBank
-    A = len(agents)
-    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
-        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}; run_test_environments_cnn takes any ids")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("run_test_environments_cnn_team_sized needs a cuda device; run_test_environments_cnn runs elsewhere")
-    R, L = montecarlo_runs, steps_per_episode
-    N = len(env_sets) * R
-    lib = _lib.load()
-    vec, keys, saved, obs, _ = _open(env_sets, R, A, obstruction_count, enforce_grid_boundaries, seed, device, welford=False)
-    maps = HeatMaps(vec, L, enforce_boundaries=bool(enforce_grid_boundaries))
-    X, Y = maps.map_dimensions
-    if X != Y or not 8 <= X <= 256 or any(tuple(agents[a].map_dim) != (X, Y) for a in range(A)):
-        raise ValueError(f"run_test_environments_cnn_team_sized serves square heat maps of side 8..256 that every agent was built for; "
-                         f"this configuration has {(X, Y)} maps and agents for {[tuple(agents[a].map_dim) for a in range(A)]}; "
-                         "use run_test_environments_cnn")
-    M, flat = X, 16 * (X // 2) ** 2
-    bank = None
-    if use_predictor:
-        bank = PredictorBank(N, A, seed=seed, device=dev)
-        if bank.impl != "hip":
-            raise ValueError("run_test_environments_cnn_team_sized needs PredictorBank(impl='hip'); use run_test_environments_cnn")
-        for a in range(A):
-            if getattr(agents[a], "model", None) is not None:         # the agent's own (saved) predictor weights
-                bank.load_state_dict(a, agents[a].model.state_dict())
-        bank.reset()
-    alive, ep_len, ep_ret, success = _lane_records(N, dev)
-    u = torch.empty(N, A, dtype=torch.float32, device=dev)
-    # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads
-    log = torch.full((L, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
-    act8 = None if return_actions else torch.empty(N, A, dtype=torch.int8, device=dev)
-    use_team = team_mode != "individual"
-    p = lambda t: t.data_ptr()
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    actors = [agents[a].pi.actor for a in range(A)]
-    cells, pcells = maps.field("cell"), maps.field("pred_cell")       # views of the heat maps' own state: [N, A] int32, -1 = none
-    assert cells.dtype == torch.int32 and pcells.dtype == torch.int32 and cells.shape == (N, A) and pcells.shape == (N, A)
-    chunk = min(max(64, int(a2_bytes) // (4 * A * flat) // 64 * 64), N)
-    if fused:
-        a2 = torch.empty(A * chunk * flat, dtype=torch.float32, device=dev)
-        convs = (_lib.RsCnnConvParams * A)(*[_lib.RsCnnConvParams(p(m[0].weight), p(m[0].bias), p(m[3].weight), p(m[3].bias)) for m in actors])
-        heads = (_lib.RsCnnHeadParams * A)(*[_lib.RsCnnHeadParams(p(m[6].weight), p(m[6].bias), p(m[8].weight), p(m[8].bias), p(m[10].weight),
-                                                                   p(m[10].bias)) for m in actors])
-        finished = torch.zeros(1, dtype=torch.int32, device=dev)
-        alive8, success8 = alive.view(torch.uint8), success.view(torch.uint8)
-        state = _lib.RsEvalState(N, A, 1 if use_team else 0, p(vec.obs), p(vec.reward), p(vec.team), p(vec.done), p(obs), None, None, None,
-                                 None, p(alive8), p(success8), p(ep_len), p(ep_ret), p(finished))
-    else:
-        a2 = torch.empty(chunk * flat, dtype=torch.float32, device=dev)
-        k_act = torch.empty(A, N, dtype=torch.int64, device=dev)
-    it = 0
-    while it < L:
-        if it and it % 16 == 0:                                   # one host read per 16 lock-steps
-            if (int(finished.item()) if fused else N - int(alive.sum().item())) == N:
-                break
-        a8 = log[it] if return_actions else act8
-        vec.action_uniforms(u)
-        pred = None
-        if bank is not None:
-            pred = bank.predict_kernel(obs)                       # bank.predict without its copy of the prediction
-            bank.calls.add_(1)
-        maps.update(obs, pred=pred)
-        shared = maps.shared_maps()
-        if fused:
-            for lo in range(0, N, chunk):                         # the same scratch for every chunk: one stream keeps them in order
-                n = min(chunk, N - lo)
-                _lib.check(lib.rs_cnn_sized_team_infer(p(shared) + 16 * M * M * lo, p(cells) + 4 * A * lo, p(pcells) + 4 * A * lo, A, n, M, convs,
-                                                       p(a2), st), "rs_cnn_sized_team_infer")
-                _lib.check(lib.rs_cnn_sized_team_eval_head(heads, A, flat, p(a2), p(u) + 4 * A * lo, p(alive8) + lo, p(a8) + A * lo, None, None,
-                                                           None, n, st), "rs_cnn_sized_team_eval_head")
-            vec.step(a8)
-            _lib.check(lib.rs_eval_post_step(C.byref(state), st), "rs_eval_post_step")
-        else:
-            cl, pl = cells.long(), pcells.long()
-            for a, m in enumerate(actors):
-                for lo in range(0, N, chunk):
-                    n = min(chunk, N - lo)
-                    x = a2[:n * flat].view(n, flat)
-                    _lib.check(lib.rs_cnn_sized_infer(p(shared) + 16 * M * M * lo, p(cl) + 8 * A * lo, p(pl) + 8 * A * lo, A, a, n, M, p(m[0].weight),
-                                                      p(m[0].bias), p(m[3].weight), p(m[3].bias), p(x), st), "rs_cnn_sized_infer")
-                    y1 = torch.nn.functional.linear(x, m[6].weight, m[6].bias)
-                    _lib.check(lib.rs_cnn_head(p(y1), p(m[8].weight), p(m[8].bias), p(m[10].weight), p(m[10].bias), 8, p(u) + 4 * (A * lo + a), A,
-                                               p(k_act[a]) + 8 * lo, None, None, 1, None, 1, 0, None, n, st), "rs_cnn_head")
-                a8[:, a] = torch.where(alive, k_act[a], torch.full_like(k_act[a], 8)).to(torch.int8)    # finished episodes idle in place
-            obs_n, rew, team, done, _ = vec.step(a8)
-            _book_step(alive, ep_len, ep_ret, success, team if use_team else rew[:, 0], done.bool().any(dim=1))
-            obs.copy_(obs_n)
-        it += 1
-    # finished episodes idle on purpose; stacked agents may "stall"
-    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=log[:it] if return_actions else None,
-                  ignore_flags=_lib.ENVERR_IDLE_STALL)
+    front = "run_test_environments_cnn_team_sized"
+
+    def refuse_sides(dims):
+        X, Y = dims
+        if X != Y or not 8 <= X <= 256 or any(tuple(ag.map_dim) != (X, Y) for ag in agents.values()):
+            raise ValueError(f"{front} serves square heat maps of side 8..256 that every agent was built for; this configuration has "
+                             f"{(X, Y)} maps and agents for {[tuple(agents[a].map_dim) for a in range(len(agents))]}; "
+                             "use run_test_environments_cnn")
+    return _run_lane_per_run_team(
+        lambda run, f, *cnn: _cnn_sized_rounds(run, f, a2_bytes, *cnn), agents, env_sets, montecarlo_runs, steps_per_episode, team_mode,
+        obstruction_count, enforce_grid_boundaries, seed, device, return_actions, fused, welford=False,
+        id_hint="; run_test_environments_cnn takes any ids", cuda_front=front,
+        setup=lambda run: _cnn_team_setup(run, front, agents, use_predictor, refuse_sides))
 
 
-@torch.no_grad()
 def run_test_environments_team(agents: Dict[int, VecAgentPPO], env_sets: Dict[str, tuple], montecarlo_runs: int = 100,
                                steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
                                enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0", return_actions: bool = False,
@@ -697,58 +736,9 @@ def run_test_environments_team(agents: Dict[int, VecAgentPPO], env_sets: Dict[st
 
     Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log of rs_step's action rows
     (8 where a lane had finished)."""
-    A = len(agents)
-    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
-        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}")
-    R, L = montecarlo_runs, steps_per_episode
-    N = len(env_sets) * R
-    dev = torch.device(device)
-    lib = _lib.load()
-    vec, keys, saved, obs, stat = _open(env_sets, R, A, obstruction_count, enforce_grid_boundaries, seed, device, falloff=falloff)
-    alive, ep_len, ep_ret, success = _lane_records(N, dev)
-    u = torch.empty(N, A, dtype=torch.float32, device=dev)
-    # with return_actions the action rows of lock-step t are written straight into row t of the log, which rs_step then reads
-    log = torch.full((L, N, A), 8, dtype=torch.int8, device=dev) if return_actions else None
-    act8 = None if return_actions else torch.empty(N, A, dtype=torch.int8, device=dev)
-    arr = _lib.RsMlpParams * A
-    pa = arr(*[mlp_params(agents[a].agent.actor) for a in range(A)])
-    use_team = team_mode != "individual"
-    p = lambda t: t.data_ptr()
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    if fused:
-        finished = torch.zeros(1, dtype=torch.int32, device=dev)
-        alive8, success8 = alive.view(torch.uint8), success.view(torch.uint8)
-        state = _lib.RsEvalState(N, A, 1 if use_team else 0, p(vec.obs), p(vec.reward), p(vec.team), p(vec.done), p(obs), p(stat.count),
-                                 p(stat.mean), p(stat.sq), p(stat.std), p(alive8), p(success8), p(ep_len), p(ep_ret), p(finished))
-    else:
-        pc = arr(*[mlp_params(agents[a].agent.critic) for a in range(A)])
-        x = torch.empty_like(obs)
-        k_act = torch.empty(A, N, dtype=torch.int64, device=dev)
-        k_f = torch.empty(A, 3, N, dtype=torch.float32, device=dev)
-    it = 0
-    while it < L:
-        if it and it % 16 == 0:                                   # one host read per 16 lock-steps
-            if (int(finished.item()) if fused else N - int(alive.sum().item())) == N:
-                break
-        a8 = log[it] if return_actions else act8
-        vec.action_uniforms(u)
-        if fused:
-            _lib.check(lib.rs_ff_eval_step(pa, A, p(obs), p(stat.mean), p(stat.std), p(u), p(alive8), p(a8), N, st), "rs_ff_eval_step")
-            vec.step(a8)
-            _lib.check(lib.rs_eval_post_step(C.byref(state), st), "rs_eval_post_step")
-        else:
-            x.copy_(obs)
-            stat.standardize(obs[..., 0], out=x[..., 0])
-            _lib.check(lib.rs_ff_team_step(pa, pc, A, p(x), p(u), p(k_act), p(k_f), None, None, N, st), "rs_ff_team_step")
-            a8.copy_(torch.where(alive.view(N, 1), k_act.t(), torch.full_like(k_act.t(), 8)).to(torch.int8))   # finished episodes idle
-            obs_n, rew, team, done, _ = vec.step(a8)
-            _book_step(alive, ep_len, ep_ret, success, team if use_team else rew[:, 0], done.bool().any(dim=1))
-            stat.update(obs_n[..., 0], mask=alive)
-            obs.copy_(obs_n)
-        it += 1
-    # finished episodes idle on purpose; stacked agents may "stall"
-    return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=log[:it] if return_actions else None,
-                  ignore_flags=_lib.ENVERR_IDLE_STALL)
+    return _run_lane_per_run_team(lambda run, f: _ff_rounds(run, f, agents), agents, env_sets, montecarlo_runs, steps_per_episode,
+                                  team_mode, obstruction_count, enforce_grid_boundaries, seed, device, return_actions, fused, welford=True,
+                                  falloff=falloff)
 
 
 def _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg) -> List[MonteCarloResults]:

@@ -367,3 +367,20 @@ class CNNCritic(nn.Module):
         for layer in list(c)[6:]:
             x = _head(layer, x)
         return x.squeeze(-1)
+
+
+def cnn_conv_params(seq: nn.Sequential) -> "_lib.RsCnnConvParams":
+    """C-ABI view (rs_cnn_conv_params) of a CNNActor.actor / CNNCritic.critic Sequential's convolutions, at indices 0 and 3."""
+    return _lib.RsCnnConvParams(*[t.data_ptr() for i in (0, 3) for t in (seq[i].weight, seq[i].bias)])
+
+
+def cnn_head_params(seq: nn.Sequential) -> "_lib.RsCnnHeadParams":
+    """The same (rs_cnn_head_params) of its Linear layers, at indices 6, 8 and 10."""
+    return _lib.RsCnnHeadParams(*[t.data_ptr() for i in (6, 8, 10) for t in (seq[i].weight, seq[i].bias)])
+
+
+def cnn_trunk_prepare(seq: nn.Sequential, cin: int, out: torch.Tensor, stream) -> None:
+    """Its convolutions (cin channels: 6 for an actor, 4 for a critic) in the 27 x 27 trunk kernels' layout into `out`, one scratch row.
+    Once per run or per epoch; not for a lock-step."""
+    c = cnn_conv_params(seq)
+    _lib.check(_lib.load().rs_cnn_trunk_prepare(cin, c.w1, c.b1, c.w2, c.b2, out.data_ptr(), stream), "rs_cnn_trunk_prepare")

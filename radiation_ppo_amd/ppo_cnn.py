@@ -21,7 +21,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .envs import RadSearchVec
-from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from, sized_trunk_sample_bytes
+from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from, cnn_head_params, cnn_trunk_prepare, sized_trunk_sample_bytes
 from .pfgru import PredictorBank, hash_bits, hash_uniform
 from .ppo import (EpochStats, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
                   reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
@@ -369,13 +369,9 @@ class CNNCollector:
         if tuple(self.maps.map_dimensions) != (27, 27):
             return
         for a, ag in self.agents.items():
-            m = ag.pi.actor
-            _lib.check(lib.rs_cnn_trunk_prepare(6, m[0].weight.data_ptr(), m[0].bias.data_ptr(), m[3].weight.data_ptr(), m[3].bias.data_ptr(),
-                                                self._wt[a].data_ptr(), st), "rs_cnn_trunk_prepare")
+            cnn_trunk_prepare(ag.pi.actor, 6, self._wt[a], st)
             if not ag.global_critic or a == min(self.agents):
-                c = ag.critic.critic
-                _lib.check(lib.rs_cnn_trunk_prepare(4, c[0].weight.data_ptr(), c[0].bias.data_ptr(), c[3].weight.data_ptr(), c[3].bias.data_ptr(),
-                                                    self._wt_c[a].data_ptr(), st), "rs_cnn_trunk_prepare")
+                cnn_trunk_prepare(ag.critic.critic, 4, self._wt_c[a], st)
         if self.use_team_round:
             ags = [self.agents[a] for a in range(A)]
             nc = 1 if ags[0].global_critic else A
@@ -384,10 +380,8 @@ class CNNCollector:
                 self._a2_cri = torch.empty(nc, N, 2704, dtype=torch.float32, device=dev)
                 self._cell32, self._pcell32 = self.maps.field("cell"), self.maps.field("pred_cell")     # views of the heat maps' own state
                 assert self._cell32.dtype == torch.int32 and self._pcell32.dtype == torch.int32 and self._cell32.shape == (N, A)
-            hp = lambda m: _lib.RsCnnHeadParams(m[6].weight.data_ptr(), m[6].bias.data_ptr(), m[8].weight.data_ptr(), m[8].bias.data_ptr(),
-                                                m[10].weight.data_ptr(), m[10].bias.data_ptr())
-            self._hp_act = (_lib.RsCnnHeadParams * A)(*[hp(ag.pi.actor) for ag in ags])
-            self._hp_cri = (_lib.RsCnnHeadParams * nc)(*[hp(ag.critic.critic) for ag in ags[:nc]])
+            self._hp_act = (_lib.RsCnnHeadParams * A)(*[cnn_head_params(ag.pi.actor) for ag in ags])
+            self._hp_cri = (_lib.RsCnnHeadParams * nc)(*[cnn_head_params(ag.critic.critic) for ag in ags[:nc]])
 
     def _team_round(self, maps, mask8=None) -> None:
         """The step round (mask8 None: every agent's action, log-probability and value into self._k_act / _k_f[:, 0] / _k_f[:, 1] /

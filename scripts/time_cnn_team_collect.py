@@ -54,7 +54,7 @@ def ab(forms, rounds, warmup, repeats):
 def kernels_ab(N, A, nc, boot_every, rounds, warmup, repeats):
     """{(what, form): [wall ms per call]} for the step heads, the bootstrap heads and the critic trunks of A agents and nc critics"""
     from radiation_ppo_amd import _lib
-    from radiation_ppo_amd.maps import CNNActor, CNNCritic
+    from radiation_ppo_amd.maps import CNNActor, CNNCritic, cnn_head_params, cnn_trunk_prepare
     lib = _lib.load()
     dev = torch.device("cuda:0")
     torch.manual_seed(N + 10 * A + nc)
@@ -62,8 +62,7 @@ def kernels_ab(N, A, nc, boot_every, rounds, warmup, repeats):
     critics = [CNNCritic().to(dev).critic for _ in range(nc)]
     p = lambda t: t.data_ptr()
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    hp = lambda m: _lib.RsCnnHeadParams(p(m[6].weight), p(m[6].bias), p(m[8].weight), p(m[8].bias), p(m[10].weight), p(m[10].bias))
-    hpa, hpc = (_lib.RsCnnHeadParams * A)(*[hp(m) for m in actors]), (_lib.RsCnnHeadParams * nc)(*[hp(m) for m in critics])
+    hpa, hpc = (_lib.RsCnnHeadParams * A)(*map(cnn_head_params, actors)), (_lib.RsCnnHeadParams * nc)(*map(cnn_head_params, critics))
     sparse = lambda *s: torch.rand(*s, device=dev) * (torch.rand(*s, device=dev) < 0.3)            # a trunk's output: non-negative, sparse
     a2a, a2c, u = sparse(A, N, FLAT), sparse(nc, N, FLAT), torch.rand(N, A, device=dev)
     maps = torch.rand(N, 4, 729, device=dev) * (torch.rand(N, 4, 729, device=dev) < 0.1)
@@ -71,7 +70,7 @@ def kernels_ab(N, A, nc, boot_every, rounds, warmup, repeats):
     act, f, act8 = torch.zeros(A, N, dtype=torch.int64, device=dev), torch.zeros(A, 3, N, device=dev), torch.zeros(N, A, dtype=torch.int8, device=dev)
     wt_c = torch.empty(nc, lib.rs_cnn_trunk_scratch_floats(4), device=dev)
     for c, m in enumerate(critics):
-        _lib.check(lib.rs_cnn_trunk_prepare(4, p(m[0].weight), p(m[0].bias), p(m[3].weight), p(m[3].bias), p(wt_c[c]), st), "rs_cnn_trunk_prepare")
+        cnn_trunk_prepare(m, 4, wt_c[c], st)
     copies = A if nc == 1 else 1
 
     def value(c, slot, mask):

@@ -46,7 +46,7 @@ def event_ms(fn, reps):
 def kernels_alone(N, A, reps, say):
     """the policy round's two kernels on random maps, N lanes, A agents"""
     from radiation_ppo_amd import _lib
-    from radiation_ppo_amd.maps import CNNActor
+    from radiation_ppo_amd.maps import CNNActor, cnn_head_params, cnn_trunk_prepare
     lib = _lib.load()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: t.data_ptr()
@@ -61,10 +61,9 @@ def kernels_alone(N, A, reps, say):
     act8 = torch.empty(N, A, dtype=torch.int8, device="cuda")
     wt = torch.empty(A, lib.rs_cnn_trunk_scratch_floats(6), dtype=torch.float32, device="cuda")
     for a, s in enumerate(seqs):
-        _lib.check(lib.rs_cnn_trunk_prepare(6, p(s[0].weight), p(s[0].bias), p(s[3].weight), p(s[3].bias), p(wt[a]), st), "rs_cnn_trunk_prepare")
+        cnn_trunk_prepare(s, 6, wt[a], st)
     a2 = torch.empty(A, N, 2704, device="cuda")
-    heads = (_lib.RsCnnHeadParams * A)(*[_lib.RsCnnHeadParams(p(s[6].weight), p(s[6].bias), p(s[8].weight), p(s[8].bias), p(s[10].weight),
-                                                               p(s[10].bias)) for s in seqs])
+    heads = (_lib.RsCnnHeadParams * A)(*[cnn_head_params(s) for s in seqs])
 
     def team_trunk():
         _lib.check(lib.rs_cnn_team_trunk_infer(p(maps), p(c32), p(p32), A, N, p(wt), p(a2), st), "rs_cnn_team_trunk_infer")

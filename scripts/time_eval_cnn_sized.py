@@ -79,7 +79,7 @@ def run_maps(N, A, L, obst, seed, at_steps):
 
 def trunk_alone(A, snaps, reps, say):
     from radiation_ppo_amd import _lib
-    from radiation_ppo_amd.maps import CNNActor
+    from radiation_ppo_amd.maps import CNNActor, cnn_conv_params
     lib = _lib.load()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: t.data_ptr()
@@ -87,7 +87,7 @@ def trunk_alone(A, snaps, reps, say):
     for name, (maps, c32, p32) in snaps.items():
         N, _, M, _ = maps.shape
         seqs = [CNNActor(map_dim=(M, M)).cuda().actor for _ in range(A)]
-        convs = (_lib.RsCnnConvParams * A)(*[_lib.RsCnnConvParams(p(s[0].weight), p(s[0].bias), p(s[3].weight), p(s[3].bias)) for s in seqs])
+        convs = (_lib.RsCnnConvParams * A)(*[cnn_conv_params(s) for s in seqs])
         c64, p64 = c32.long().contiguous(), p32.long().contiguous()
         a2 = torch.empty(A, N, 16 * (M // 2) ** 2, device="cuda")
 
@@ -109,15 +109,14 @@ def trunk_alone(A, snaps, reps, say):
 
 def head_alone(N, A, M, reps, say):
     from radiation_ppo_amd import _lib
-    from radiation_ppo_amd.maps import CNNActor
+    from radiation_ppo_amd.maps import CNNActor, cnn_head_params
     lib = _lib.load()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: t.data_ptr()
     torch.manual_seed(A)
     flat = 16 * (M // 2) ** 2
     seqs = [CNNActor(map_dim=(M, M)).cuda().actor for _ in range(A)]
-    heads = (_lib.RsCnnHeadParams * A)(*[_lib.RsCnnHeadParams(p(s[6].weight), p(s[6].bias), p(s[8].weight), p(s[8].bias), p(s[10].weight),
-                                                               p(s[10].bias)) for s in seqs])
+    heads = (_lib.RsCnnHeadParams * A)(*[cnn_head_params(s) for s in seqs])
     a2 = torch.rand(A, N, flat, device="cuda") * (torch.rand(A, N, flat, device="cuda") < 0.3)
     u = torch.rand(N, A, device="cuda")
     alive = torch.ones(N, dtype=torch.uint8, device="cuda")

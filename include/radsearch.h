@@ -945,6 +945,48 @@ int rs_cnn_team_step_head(const rs_cnn_head_params* actors, int32_t num_agents, 
                           const float* a2_actor, const float* a2_critic, const float* u, int64_t* act, float* logp_val_boot, int8_t* act8,
                           const uint8_t* mask, float* y1_out, int32_t num_envs, rs_stream_t stream);
 
+/* ---- The same round for square maps of any side 8 <= map_side <= 256 (walls off: 147 x 147, Linear(85 264, 32) behind the trunk), where
+ * the workload is a few hundred envs and a grid of 64-env tiles alone would leave most of the device idle: rs_cnn_sized_team_infer (the
+ * actors), rs_cnn_sized_infer(agent = -1) for a global critic or rs_cnn_sized_team_critic_infer for one critic per agent,
+ * rs_cnn_sized_team_step_head; a bootstrap round is the critic trunk(s) and the heads.
+ *
+ * rs_cnn_sized_team_critic_infer: every critic's tiled trunk (4 input channels, no cell planes) in one launch, a persistent grid over the
+ * (image, tile, critic) units with rs_cnn_sized_team_infer's empty-window shortcut; the result equals num_critics calls of
+ * rs_cnn_sized_infer(agent = -1) with critic c's weights, bit for bit.
+ *   maps [S][4][M*M]; convs [C] host array (device pointers inside), torch layouts: w1 [8][4][3][3], b1 [8], w2 [16][8][3][3], b2 [16];
+ *   a2 [C][S][16*P*P], P = M / 2
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL pointer (those inside the first num_critics convs included), num_critics outside
+ * 1..RS_MAX_AGENTS, num_samples < 0; a side outside [8, 256] returns RS_ERR_UNSUPPORTED; num_samples == 0 returns RS_OK and launches
+ * nothing. */
+int rs_cnn_sized_team_critic_infer(const float* maps, int32_t num_critics, int64_t num_samples, int32_t map_side,
+                                   const rs_cnn_conv_params* convs, float* a2, rs_stream_t stream);
+
+/* rs_cnn_sized_team_step_head: rs_cnn_team_step_head at the depth flat = 16 p p (p in 4..128), in two launches.
+ * Stage 1, grid = (64-env tiles, k slices, rows): Linear(flat, 32) split over k.  A slice is rs_cnn_sized_team_head_slice_floats()
+ * floats (a compile-time constant, a multiple of 128; the last slice is shorter, a multiple of 16), S = ceil(flat / slice) slices: S
+ * depends on flat alone.  Within a workgroup four waves take a quarter of the slice each on the f32 matrix cores (exact f32) and their
+ * partial sums are added in wave order; the 64 x 32 sums go to scratch [rows][S][N][32].
+ * Stage 2, grid = (64-env tiles, rows), one env per lane: the S partial sums in slice order, then the bias, then rs_cnn_head's arithmetic
+ * operation for operation (out_dim 8 with the inverse-CDF draw and no idle rule on an actor row, out_dim 1 on a critic row).  No atomics:
+ * an env's bits depend on neither num_envs nor the grid.
+ *   actors, critics, num_critics, u, act, logp_val_boot, act8, mask, y1_out   as rs_cnn_team_step_head's, w1 [32][flat]; a step round
+ *                             (u not NULL) launches the A + C rows, a bootstrap round (u NULL, mask required) the C critic rows, which
+ *                             write slot 2
+ *   a2_actor [A][N][flat], a2_critic [C][N][flat]   the trunks' outputs (N = num_envs)
+ *   scratch, scratch_floats   at least rs_cnn_sized_team_head_scratch_floats(flat, rows launched, num_envs) floats; its contents before the
+ *                             call do not matter and it holds nothing of use after it.  A masked-out env writes nothing and reads no
+ *                             scratch; a workgroup of stage 1 whose 64 envs are all masked out returns before its k loop
+ * rs_cnn_sized_team_head_scratch_floats: num_rows x S x num_envs x 32, or 0 for a flat that is not 16 p p with p in 4..128 (or num_rows
+ * or num_envs < 1).
+ * RS_ERR_INVALID_ARG, before anything is launched: what rs_cnn_team_step_head refuses, such a flat, a NULL scratch, scratch_floats below
+ * the size function's value. */
+int32_t rs_cnn_sized_team_head_slice_floats(void);
+int64_t rs_cnn_sized_team_head_scratch_floats(int32_t flat, int32_t num_rows, int32_t num_envs); /* 0 for a bad flat */
+int rs_cnn_sized_team_step_head(const rs_cnn_head_params* actors, int32_t num_agents, const rs_cnn_head_params* critics,
+                                int32_t num_critics, int32_t flat, const float* a2_actor, const float* a2_critic, const float* u,
+                                int64_t* act, float* logp_val_boot, int8_t* act8, const uint8_t* mask, float* y1_out,
+                                float* scratch, int64_t scratch_floats, int32_t num_envs, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

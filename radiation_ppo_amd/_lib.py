@@ -223,6 +223,12 @@ SYMBOLS = [
     ("rs_cnn_team_critic_trunk_infer", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rs_cnn_team_step_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32, C.POINTER(RsCnnHeadParams), C.c_int32] + [C.c_void_p] * 8
      + [C.c_int32, C.c_void_p]),
+    # the same round on maps of any side: every critic's tiled trunk, the k-split first layer and the heads behind it
+    ("rs_cnn_sized_team_head_slice_floats", C.c_int32, []),
+    ("rs_cnn_sized_team_head_scratch_floats", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    ("rs_cnn_sized_team_critic_infer", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.POINTER(RsCnnConvParams), C.c_void_p, C.c_void_p]),
+    ("rs_cnn_sized_team_step_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32, C.POINTER(RsCnnHeadParams), C.c_int32, C.c_int32]
+     + [C.c_void_p] * 9 + [C.c_int64, C.c_int32, C.c_void_p]),
     ("rs_rnn_team_eval_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
     ("rs_rnn_team_eval_post_step", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),
     ("rs_rnn_team_eval_post_refresh", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),

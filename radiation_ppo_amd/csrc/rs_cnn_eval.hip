@@ -21,7 +21,10 @@
 // maps of any side; it shares the MFMA step and everything behind the k loop (eh_step, eh_finish) and has a kernel of its own.
 //
 // rs_cnn_team_step_head (CNNCollector._step_glued, radiation_ppo_amd/ppo_cnn.py): the same first layer for every actor AND every critic
-// of a team in training, one launch per policy round; at the end of this file.
+// of a team in training, one launch per policy round; behind the evaluation kernels.
+//
+// rs_cnn_sized_team_step_head: that round at a run-time depth (walls-off maps), the first layer split over k across workgroups with a
+// fixed-order second stage; at the end of this file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -449,9 +452,248 @@ __global__ void __launch_bounds__(EH_NT) rs_cnn_team_step_head_kernel(TsNets net
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// rs_cnn_sized_team_step_head: the heads of a team's TRAINING round at a run-time depth flat = 16 p p (the tiled trunk's maps of any
+// side; 85 264 at 147 x 147), in two launches.  The walls-off workload is 512 envs: rs_cnn_sized_team_eval_head's grid of 64-image tiles
+// would be 8 workgroups per row on 256 CUs, each walking the whole depth.  So the first layer is split over k as well.
+//
+// Stage 1 (sk_first_layer_kernel), grid = (64-env tiles, k slices, rows): a workgroup takes slice s = floats [SK_SLICE s, SK_SLICE (s + 1))
+// of k, cut at flat (the last slice is shorter, a multiple of 16 floats).  Its four waves own the slice's quarters
+// [SK_QUARTER w, SK_QUARTER (w + 1)), cut at the slice's end -- a wave's share is a multiple of 16 floats, whole 32-float pieces and
+// possibly a tail of 16 (floats 0..7 on the lower lane half, 8..15 on the upper); a wave behind the end adds nothing.  The pieces go
+// through eh_step two in flight as in the kernels above; the four partial sums meet in LDS (ts_meet) and are added in wave order; the
+// workgroup's 64 x 32 sums go to scratch [row][S][N][32] as float4s.  S = ceil(flat / SK_SLICE) depends on flat alone, so the terms of
+// an env's sum and their order depend on neither N nor the grid.  A workgroup whose 64 envs are all masked out returns before the k loop.
+//
+// Stage 2 (sk_heads_kernel), grid = (64-env tiles, rows), one env per lane: wave w adds the S partial sums of neurons 8 w .. 8 w + 7 in
+// slice order, then the bias; wave 0 then runs ts_hidden's / ts_draw's arithmetic (rs_cnn_head's, operation for operation) and writes
+// rs_cnn_team_step_head_kernel's outputs.  A masked-out env reads no scratch and writes nothing: the scratch of a masked-in env was
+// written by stage 1 in the same call (its tile had that env on).
+//
+// SK_SLICE: see DESIGN.md section 3 for the lengths tried.
+#ifndef RS_SK_SLICE
+#define RS_SK_SLICE 4096                            // (-DRS_SK_SLICE=n: an A/B build for scripts/time_cnn_sized_team_collect.py)
+#endif
+constexpr int SK_SLICE = RS_SK_SLICE;               // floats of k per stage-1 workgroup
+constexpr int SK_QUARTER = SK_SLICE / EH_WAVES;     // 1024 per wave: 32 pieces of 32 floats
+static_assert(SK_SLICE % 128 == 0 && SK_QUARTER % 32 == 0, "whole pieces per wave in a full slice");
+
+struct SkRows {
+    const float* w1[2 * RS_MAX_AGENTS];             // the launched rows' first-layer weights [32][flat]
+    const float* a2[2 * RS_MAX_AGENTS];             // and their trunk outputs [N][flat]
+};
+
+__global__ void __launch_bounds__(EH_NT) sk_first_layer_kernel(SkRows rows, int flat, const uint8_t* __restrict__ mask,
+                                                               float* __restrict__ scratch, int N) {
+    __shared__ __align__(16) float part[EH_WAVES][EH_TILE][EH_ROW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int y = blockIdx.z, sl = blockIdx.y, S = gridDim.y;
+    const int n0 = blockIdx.x * EH_TILE;
+    {   // every wave looks at the same 64 flags, so the four of them agree: nothing to do for this tile -> all leave before the barrier
+        const int n = n0 + lane;
+        const bool on = n < N && (mask == nullptr || mask[n] != 0);
+        if (!__any(on)) return;
+    }
+    const int len = min(SK_SLICE, flat - sl * SK_SLICE);                        // the slice's floats: a multiple of 16
+    const int lw = max(0, min(SK_QUARTER, len - wave * SK_QUARTER));            // the wave's: a multiple of 16
+    const int np = lw / 32, tail = lw - 32 * np;                                // tail: 0 or 16
+    const size_t k0 = (size_t)sl * SK_SLICE + (size_t)wave * SK_QUARTER;
+    // rows past the last image read the last image's (their sums are dropped)
+    const int na = n0 + r < N ? n0 + r : N - 1, nb = n0 + 32 + r < N ? n0 + 32 + r : N - 1;
+    const float* wp = rows.w1[y] + (size_t)r * flat + k0;
+    const float* xa = rows.a2[y] + (size_t)na * flat + k0;
+    const float* xb = rows.a2[y] + (size_t)nb * flat + k0;
+    v16f acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc0[i] = 0.0f; acc1[i] = 0.0f; }
+    struct Piece { float4 w[4], a[4], b[4]; };
+    auto fetch = [&](Piece& q, int g) {                               // the lane half's 16 floats of piece g
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int o = 32 * g + 16 * h + 4 * i;
+            q.w[i] = *reinterpret_cast<const float4*>(wp + o);
+            q.a[i] = *reinterpret_cast<const float4*>(xa + o);
+            q.b[i] = *reinterpret_cast<const float4*>(xb + o);
+        }
+    };
+    auto consume = [&](const Piece& q) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) eh_step(acc0, acc1, q.w[i], q.a[i], q.b[i]);
+    };
+    if (np > 0) {                                                     // (np is wave-uniform)
+        Piece p0, p1;
+        fetch(p0, 0);
+        fetch(p1, np > 1 ? 1 : 0);                                    // (a single piece is requested twice; the copy is dropped)
+        int g = 0;
+#pragma unroll 1
+        for (; g + 2 < np; g += 2) {                                  // p0 holds piece g, p1 piece g + 1, both with a successor
+            consume(p0);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch(p0, g + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            consume(p1);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch(p1, g + 3 < np ? g + 3 : np - 1);                   // (an odd np re-requests its last piece; it is dropped)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        consume(p0);                                                  // the last two pieces, or the last one
+        if (g + 1 < np) consume(p1);
+    }
+    if (tail == 16) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int o = 32 * np + 8 * h + 4 * i;
+            eh_step(acc0, acc1, *reinterpret_cast<const float4*>(wp + o), *reinterpret_cast<const float4*>(xa + o),
+                    *reinterpret_cast<const float4*>(xb + o));
+        }
+    }
+    ts_meet(part, acc0, acc1);
+    // thread -> (env tid / 4, neurons 8 (tid % 4) .. + 7): the four quarters in wave order, two float4 stores
+    const int e = tid >> 2, j0 = 8 * (tid & 3);
+    if (n0 + e < N) {
+        float* dst = scratch + (((size_t)y * S + sl) * N + n0 + e) * H1 + j0;
+#pragma unroll
+        for (int k = 0; k < 8; k += 4) {
+            float4 s = *reinterpret_cast<const float4*>(&part[0][e][j0 + k]);
+#pragma unroll
+            for (int w = 1; w < EH_WAVES; ++w) {
+                const float4 q = *reinterpret_cast<const float4*>(&part[w][e][j0 + k]);
+                s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
+            }
+            *reinterpret_cast<float4*>(dst + k) = s;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(EH_NT) sk_heads_kernel(TsNets nets, int A, int C, int row0, int slot, int S,
+                                                         const float* __restrict__ scratch, const float* __restrict__ u,
+                                                         int64_t* __restrict__ act, float* __restrict__ f, int8_t* __restrict__ act8,
+                                                         const uint8_t* __restrict__ mask, float* __restrict__ y1_out, int N) {
+    __shared__ __align__(16) float y1s[EH_TILE][EH_ROW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int y = row0 + blockIdx.y;                                  // the network; blockIdx.y is its row of the scratch
+    const int n = blockIdx.x * EH_TILE + lane;
+    const bool on = n < N && (mask == nullptr || mask[n] != 0);
+    if (!__any(on)) return;                                           // the four waves agree (the same 64 flags)
+    const rs_cnn_head_params P = nets.net[y];
+    {   // wave w: neurons 8 w .. 8 w + 7 of the lane's env, the slices in order 0 .. S - 1, then the bias
+        const int j0 = 8 * wave;
+        float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+        if (on) {
+            const float* src = scratch + (((size_t)blockIdx.y * S) * N + n) * H1 + j0;
+            const size_t stride = (size_t)N * H1;
+            s0 = *reinterpret_cast<const float4*>(src);
+            s1 = *reinterpret_cast<const float4*>(src + 4);
+#pragma unroll 8
+            for (int sl = 1; sl < S; ++sl) {
+                const float4 q0 = *reinterpret_cast<const float4*>(src + sl * stride);
+                const float4 q1 = *reinterpret_cast<const float4*>(src + sl * stride + 4);
+                s0.x += q0.x; s0.y += q0.y; s0.z += q0.z; s0.w += q0.w;
+                s1.x += q1.x; s1.y += q1.y; s1.z += q1.z; s1.w += q1.w;
+            }
+        }
+        const eh_cmem_t b1 = eh_cmem(P.b1);
+        s0.x += b1[j0]; s0.y += b1[j0 + 1]; s0.z += b1[j0 + 2]; s0.w += b1[j0 + 3];
+        s1.x += b1[j0 + 4]; s1.y += b1[j0 + 5]; s1.z += b1[j0 + 6]; s1.w += b1[j0 + 7];
+        if (y1_out && on) {
+            float* dst = y1_out + ((size_t)y * N + n) * H1 + j0;
+            *reinterpret_cast<float4*>(dst) = s0;
+            *reinterpret_cast<float4*>(dst + 4) = s1;
+        }
+        *reinterpret_cast<float4*>(&y1s[lane][j0]) = s0;
+        *reinterpret_cast<float4*>(&y1s[lane][j0 + 4]) = s1;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // ---- ts_hidden behind y1: ReLU -> Linear(32, 16) -> ReLU
+    const eh_cmem_t w2 = eh_cmem(P.w2), b2 = eh_cmem(P.b2);
+    float h1[H1], h2[H2];
+#pragma unroll
+    for (int k = 0; k < H1; k += 4) {
+        const float4 s = *reinterpret_cast<const float4*>(&y1s[lane][k]);
+        h1[k] = fmaxf(s.x, 0.0f); h1[k + 1] = fmaxf(s.y, 0.0f); h1[k + 2] = fmaxf(s.z, 0.0f); h1[k + 3] = fmaxf(s.w, 0.0f);
+    }
+#pragma unroll
+    for (int o = 0; o < H2; ++o) {
+        float s = b2[o];
+#pragma unroll
+        for (int k = 0; k < H1; ++k) s = __builtin_fmaf(w2[o * H1 + k], h1[k], s);
+        h2[o] = fmaxf(s, 0.0f);
+    }
+    const int nc = n < N ? n : N - 1;
+    if (y < A) {
+        int a;
+        float lp_sel;
+        ts_draw(P, h2, u[(size_t)nc * A + y], a, lp_sel);
+        if (on) {
+            act[(size_t)y * N + n] = a;
+            f[(size_t)y * 3 * N + n] = lp_sel;
+            act8[(size_t)n * A + y] = (int8_t)a;
+        }
+    } else {
+        // rs_cnn_head_kernel<1>: the state value, to its owner's row or (global critic) to every agent's
+        const eh_cmem_t w3 = eh_cmem(P.w3), b3 = eh_cmem(P.b3);
+        float v = b3[0];
+#pragma unroll
+        for (int k = 0; k < H2; ++k) v = __builtin_fmaf(w3[k], h2[k], v);
+        if (on) {
+            if (C == 1) for (int a = 0; a < A; ++a) f[((size_t)a * 3 + slot) * N + n] = v;
+            else f[((size_t)(y - A) * 3 + slot) * N + n] = v;
+        }
+    }
+}
+
+inline int sk_depth_ok(int32_t flat) {
+    int p = 4;
+    while (p < 128 && 16 * p * p < flat) ++p;
+    return 16 * p * p == flat;                                        // the tiled trunk's output: 16 p p, p = 4..128
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t rs_cnn_sized_team_head_slice_floats(void) { return SK_SLICE; }
+
+int64_t rs_cnn_sized_team_head_scratch_floats(int32_t flat, int32_t num_rows, int32_t num_envs) {
+    if (!sk_depth_ok(flat) || num_rows < 1 || num_envs < 1) return 0;
+    return (int64_t)num_rows * ((flat + SK_SLICE - 1) / SK_SLICE) * num_envs * H1;
+}
+
+int rs_cnn_sized_team_step_head(const rs_cnn_head_params* actors, int32_t num_agents, const rs_cnn_head_params* critics,
+                                int32_t num_critics, int32_t flat, const float* a2_actor, const float* a2_critic, const float* u,
+                                int64_t* act, float* logp_val_boot, int8_t* act8, const uint8_t* mask, float* y1_out, float* scratch,
+                                int64_t scratch_floats, int32_t num_envs, rs_stream_t stream) {
+    const bool step = u != nullptr;
+    if (num_agents < 1 || num_agents > RS_MAX_AGENTS || (num_critics != 1 && num_critics != num_agents) || num_envs < 1) return RS_ERR_INVALID_ARG;
+    if (!critics || !a2_critic || !logp_val_boot) return RS_ERR_INVALID_ARG;
+    if (step ? (!actors || !a2_actor || !act || !act8) : !mask) return RS_ERR_INVALID_ARG;
+    auto whole = [](const rs_cnn_head_params& p) { return p.w1 && p.b1 && p.w2 && p.b2 && p.w3 && p.b3; };
+    for (int c = 0; c < num_critics; ++c)
+        if (!whole(critics[c])) return RS_ERR_INVALID_ARG;
+    for (int a = 0; step && a < num_agents; ++a)
+        if (!whole(actors[a])) return RS_ERR_INVALID_ARG;
+    const int rows = step ? num_agents + num_critics : num_critics;                              // the bootstrap round: the critic rows alone
+    if (!sk_depth_ok(flat) || !scratch || scratch_floats < rs_cnn_sized_team_head_scratch_floats(flat, rows, num_envs)) return RS_ERR_INVALID_ARG;
+    const int row0 = step ? 0 : (int)num_agents;
+    TsNets nets;
+    for (int i = 0; i < 2 * RS_MAX_AGENTS; ++i) nets.net[i] = critics[0];                       // the slots no row reads
+    for (int a = 0; step && a < num_agents; ++a) nets.net[a] = actors[a];
+    for (int c = 0; c < num_critics; ++c) nets.net[num_agents + c] = critics[c];
+    SkRows rw;
+    for (int i = 0; i < 2 * RS_MAX_AGENTS; ++i) {                                               // launched row i is network row0 + i
+        const int y = row0 + (i < rows ? i : 0);
+        rw.w1[i] = nets.net[y].w1;
+        rw.a2[i] = y < num_agents ? a2_actor + (size_t)y * num_envs * flat : a2_critic + (size_t)(y - num_agents) * num_envs * flat;
+    }
+    const int tiles = (num_envs + EH_TILE - 1) / EH_TILE, S = (flat + SK_SLICE - 1) / SK_SLICE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(sk_first_layer_kernel, dim3(tiles, S, rows), dim3(EH_NT), 0, s, rw, (int)flat, mask, scratch, (int)num_envs);
+    hipLaunchKernelGGL(sk_heads_kernel, dim3(tiles, rows), dim3(EH_NT), 0, s, nets, (int)num_agents, (int)num_critics, row0, step ? 1 : 2, S,
+                       (const float*)scratch, u, act, logp_val_boot, act8, mask, y1_out, (int)num_envs);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
 
 int rs_cnn_team_eval_head(const rs_cnn_head_params* heads, int32_t num_agents, const float* a2, const float* u, const uint8_t* alive,
                           int8_t* act8, int64_t* act, float* logp, float* y1_out, int32_t num_envs, rs_stream_t stream) {

@@ -302,6 +302,27 @@ __global__ void __launch_bounds__(NT, 3) rs_sized_team_fwd(SzIn in, SzTeam team,
     }
 }
 
+// The training round's critic team forward (rs_cnn_sized_team_critic_infer): every critic's trunk in one launch, the Cin = 4 form of the
+// kernel above -- no cell planes, no stamps -- over (image, tile, critic) units, the critic fastest.  The unit is fwd_unit's with the
+// empty-window shortcut, so the bits are rs_sized_trunk_fwd<4, false>'s with the critic's weights.
+struct SzCritics {
+    rs_cnn_conv_params conv[RS_MAX_AGENTS];
+};
+
+__global__ void __launch_bounds__(NT, 3) rs_sized_critics_fwd(SzIn in, SzCritics team, float* __restrict__ a2) {
+    __shared__ FwdLds lds;
+    const int nt2 = in.ntile * in.ntile, C = in.A;                   // in.A: the number of critics
+    const long long units = in.S * nt2 * C;
+    const size_t per_critic = (size_t)in.S * C2 * in.P * in.P;
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const long long it = u / C, s = it / nt2;
+        const int c = (int)(u - it * C);
+        const rs_cnn_conv_params cv = team.conv[c];
+        fwd_unit<4, false, true>(in, s, (int)(it - s * nt2), -1, -1, cv.w1, cv.b1, cv.w2, cv.b2, a2 + (size_t)c * per_critic, nullptr, nullptr,
+                                 nullptr, lds);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Backward: dL/d(a2) -> per-workgroup partial sums, slab row {dW1 8*CIN*9 | db1 8 | dW2 16*72 | db2 16} in torch weight order.
 template <int CIN>
@@ -550,6 +571,21 @@ int rs_cnn_sized_team_infer(const float* maps, const int32_t* cells, const int32
     team.pcells = pcells;
     const long long units = (long long)num_samples * in.ntile * in.ntile * num_agents;
     hipLaunchKernelGGL(rs_sized_team_fwd, dim3(sized_grid(rs_sized_team_fwd, units)), dim3(NT), 0, (hipStream_t)stream, in, team, a2);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_cnn_sized_team_critic_infer(const float* maps, int32_t num_critics, int64_t num_samples, int32_t map_side,
+                                   const rs_cnn_conv_params* convs, float* a2, rs_stream_t stream) {
+    if (!maps || !convs || !a2 || num_critics < 1 || num_critics > RS_MAX_AGENTS || num_samples < 0) return RS_ERR_INVALID_ARG;
+    for (int c = 0; c < num_critics; ++c)
+        if (!convs[c].w1 || !convs[c].b1 || !convs[c].w2 || !convs[c].b2) return RS_ERR_INVALID_ARG;
+    if (!side_ok(map_side)) return RS_ERR_UNSUPPORTED;
+    if (num_samples == 0) return RS_OK;
+    SzIn in{maps, nullptr, nullptr, num_critics, -1, map_side, map_side / 2, tiles(map_side), (long long)num_samples};
+    SzCritics team;
+    for (int c = 0; c < RS_MAX_AGENTS; ++c) team.conv[c] = convs[c < num_critics ? c : 0];    // the slots behind the critics repeat critic 0 (never read)
+    const long long units = (long long)num_samples * in.ntile * in.ntile * num_critics;
+    hipLaunchKernelGGL(rs_sized_critics_fwd, dim3(sized_grid(rs_sized_critics_fwd, units)), dim3(NT), 0, (hipStream_t)stream, in, team, a2);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

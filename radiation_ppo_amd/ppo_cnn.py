@@ -21,7 +21,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .envs import RadSearchVec
-from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from, cnn_head_params, cnn_trunk_prepare, sized_trunk_sample_bytes
+from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from, cnn_conv_params, cnn_head_params, cnn_trunk_prepare, sized_trunk_sample_bytes
 from .pfgru import PredictorBank, hash_bits, hash_uniform
 from .ppo import (EpochStats, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
                   reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
@@ -350,6 +350,29 @@ class CNNCollector:
         own = not any(ag.global_critic for ag in ags) and len({id(ag.critic) for ag in ags}) == self.A
         return shared or own
 
+    SIZED_TEAM_BYTES = 16 << 30                      # the sized team round's a2 rows and scratch stay below this; above it, the per-agent round
+
+    @property
+    def use_sized_team_round(self) -> bool:
+        """The same round on square maps of any other side in 8..256 (walls off: 147 x 147): rs_cnn_sized_team_infer, the critic trunk(s)
+        (rs_cnn_sized_infer(agent = -1) / rs_cnn_sized_team_critic_infer) and rs_cnn_sized_team_step_head, whose first layer is split over
+        k across workgroups; the bootstrap round is the critic trunk(s) and the head.  `sized_team_round = False` selects the per-agent
+        round (the A/B form).  The a2 rows [A + C][N][16 P P] and the head's scratch must fit SIZED_TEAM_BYTES; the measured epochs are
+        in profiles/cnn_sized_team_collect_timing.txt."""
+        if not (self.use_heads and getattr(self, "sized_team_round", True)):
+            return False
+        X, Y = self.maps.map_dimensions
+        if X != Y or (X, Y) == (27, 27) or not 8 <= X <= 256 or sorted(self.agents) != list(range(self.A)):
+            return False
+        ags = [self.agents[a] for a in range(self.A)]
+        shared = all(ag.global_critic and ag.critic is ags[0].critic for ag in ags)
+        own = not any(ag.global_critic for ag in ags) and len({id(ag.critic) for ag in ags}) == self.A
+        if not (shared or own):
+            return False
+        rows, flat = self.A + (1 if shared else self.A), 16 * (X // 2) ** 2
+        scratch = _lib.load().rs_cnn_sized_team_head_scratch_floats(flat, rows, self.N)
+        return scratch > 0 and 4 * (rows * self.N * flat + scratch) <= self.SIZED_TEAM_BYTES
+
     def _prepare_heads(self) -> None:
         """Once per epoch (the networks do not change during collection): every agent's convolution weights in the trunk kernel's
         layout (27 x 27; the tiled trunk reads torch's layout); the fixed-address buffers of the fused round."""
@@ -367,6 +390,20 @@ class CNNCollector:
             self._k_f = torch.zeros(A, 3, N, dtype=torch.float32, device=dev)                   # logp, value, bootstrap value
             self._x_buf = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)   # the step's observation (buffer row)
         if tuple(self.maps.map_dimensions) != (27, 27):
+            if self.use_sized_team_round:
+                ags = [self.agents[a] for a in range(A)]
+                nc = 1 if ags[0].global_critic else A
+                flat = 16 * (self.maps.map_dimensions[0] // 2) ** 2
+                if getattr(self, "_sz_a2_act", None) is None or self._sz_a2_cri.shape[0] != nc:
+                    self._sz_a2_act = torch.empty(A, N, flat, dtype=torch.float32, device=dev)      # one a2 buffer per role
+                    self._sz_a2_cri = torch.empty(nc, N, flat, dtype=torch.float32, device=dev)
+                    self._sz_scratch = torch.empty(lib.rs_cnn_sized_team_head_scratch_floats(flat, A + nc, N), dtype=torch.float32, device=dev)
+                    self._cell32, self._pcell32 = self.maps.field("cell"), self.maps.field("pred_cell")     # views of the heat maps' own state
+                    assert self._cell32.dtype == torch.int32 and self._pcell32.dtype == torch.int32 and self._cell32.shape == (N, A)
+                self._cv_act = (_lib.RsCnnConvParams * A)(*[cnn_conv_params(ag.pi.actor) for ag in ags])
+                self._cv_cri = (_lib.RsCnnConvParams * nc)(*[cnn_conv_params(ag.critic.critic) for ag in ags[:nc]])
+                self._hp_act = (_lib.RsCnnHeadParams * A)(*[cnn_head_params(ag.pi.actor) for ag in ags])
+                self._hp_cri = (_lib.RsCnnHeadParams * nc)(*[cnn_head_params(ag.critic.critic) for ag in ags[:nc]])
             return
         for a, ag in self.agents.items():
             cnn_trunk_prepare(ag.pi.actor, 6, self._wt[a], st)
@@ -402,6 +439,28 @@ class CNNCollector:
         o = (p(self._u), p(self._k_act), p(self._k_f), p(self._act8), None) if step else (None, None, p(self._k_f), None, p(mask8))
         _lib.check(lib.rs_cnn_team_step_head(self._hp_act, A, self._hp_cri, nc, p(self._a2_act), p(self._a2_cri), *o, None, N, st),
                    "rs_cnn_team_step_head")
+
+    def _sized_team_round(self, maps, mask8=None) -> None:
+        """_team_round on maps of any side (use_sized_team_round): the actors' tiled trunks in one launch, the critic trunk(s) in one,
+        the k-split first layer and the heads in two; the bootstrap round without the first of them."""
+        lib, N, A = _lib.load(), self.N, self.A
+        st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        p = lambda t: t.data_ptr()
+        step = mask8 is None
+        nc, flat, M = self._sz_a2_cri.shape[0], self._sz_a2_cri.shape[2], self.maps.map_dimensions[0]
+        if step:
+            _lib.check(lib.rs_cnn_sized_team_infer(p(maps), p(self._cell32), p(self._pcell32), A, N, M, self._cv_act, p(self._sz_a2_act), st),
+                       "rs_cnn_sized_team_infer")
+        if nc == 1:
+            cv = self._cv_cri[0]
+            _lib.check(lib.rs_cnn_sized_infer(p(maps), None, None, 0, -1, N, M, cv.w1, cv.b1, cv.w2, cv.b2, p(self._sz_a2_cri), st),
+                       "rs_cnn_sized_infer")
+        else:
+            _lib.check(lib.rs_cnn_sized_team_critic_infer(p(maps), nc, N, M, self._cv_cri, p(self._sz_a2_cri), st),
+                       "rs_cnn_sized_team_critic_infer")
+        o = (p(self._u), p(self._k_act), p(self._k_f), p(self._act8), None) if step else (None, None, p(self._k_f), None, p(mask8))
+        _lib.check(lib.rs_cnn_sized_team_step_head(self._hp_act, A, self._hp_cri, nc, flat, p(self._sz_a2_act), p(self._sz_a2_cri), *o, None,
+                                                   p(self._sz_scratch), self._sz_scratch.numel(), N, st), "rs_cnn_sized_team_step_head")
 
     def _values_fused(self, critic_maps, slot: int, mask8=None) -> None:
         """V(s) of every env into self._k_f[:, slot] (slot 1: the step's value, 2: the bootstrap value): one evaluation serves every
@@ -439,20 +498,23 @@ class CNNCollector:
     def _step_glued(self, epoch_ended: bool) -> None:
         """_step with the element-wise bookkeeping between the library calls in rs_collect_post_step / _post_reset and (27 x 27 maps) every
         agent's select_action as trunk + Linear + rs_cnn_head, the buffer rows by rs_store_rows: ~40 launches per lock-step where the
-        torch composition took ~110; with use_team_round the policy round is three launches and the bootstrap round two (_team_round)."""
+        torch composition took ~110; with use_team_round the policy round is three launches and the bootstrap round two (_team_round), with
+        use_sized_team_round (any other map side) four and three (_sized_team_round)."""
         env, buf, N, A = self.env, self.buf, self.N, self.A
         acc, ti = self._acc, self._t
         lib, cs = _lib.load(), self._glue_state()
         st = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
         over, cut, boot = self._flags[0], self._flags[1], self._flags[2]
         put = lambda dst, row: dst.index_copy_(0, ti, row.unsqueeze(0))
-        heads, team = self.use_heads, self.use_team_round
+        heads, sized = self.use_heads, self.use_sized_team_round
+        team = self.use_team_round or sized
+        team_round = self._sized_team_round if sized else self._team_round
         critic, cells, pcells = self._round_glued()
         put(self.shared, critic); put(self.cells, cells); put(self.pcells, pcells)
         env.action_uniforms(self._u)
         if team:
             self._x_buf.copy_(self.obs)
-            self._team_round(critic)
+            team_round(critic)
         elif heads:
             self._x_buf.copy_(self.obs)
             for a, ag in self.agents.items():
@@ -491,7 +553,7 @@ class CNNCollector:
             env.reset(cut)
         if heads:
             if team:
-                self._team_round(critic_b, mask8=boot)
+                team_round(critic_b, mask8=boot)
             else:
                 self._values_fused(critic_b, 2, mask8=boot)
             _lib.check(lib.rs_store_rows(ti.data_ptr(), self._k_act.data_ptr(), self._k_f.data_ptr(), self._x_buf.data_ptr(),
@@ -604,7 +666,7 @@ class CNNCollector:
             with torch.cuda.stream(side):
                 critic = self.maps.shared_maps()
                 cells, pcells = self.maps.field("cell").long(), self.maps.field("pred_cell").long()
-                if not (self.use_glue and getattr(self, "glue", True) and self.use_team_round):     # the team round calls no library GEMM
+                if not (self.use_glue and getattr(self, "glue", True) and (self.use_team_round or self.use_sized_team_round)):     # the team rounds call no library GEMM
                     for a, ag in self.agents.items():
                         ag.act((critic, cells, pcells, a), self._u[:, a]); ag._values((critic,))
                 if self.predictor is not None:

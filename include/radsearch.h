@@ -236,6 +236,8 @@ typedef struct rs_rollout_args {
 
 int rs_rollout(rs_handle* h, const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_rollout_args* args,
                rs_stream_t stream);
+/* the dynamic LDS bytes rs_rollout gives a workgroup of its kernel (has_obs != 0: the obstacle template); no device needed */
+size_t rs_rollout_lds_bytes(int has_obs);
 
 /* ---- fused PPO loss + gradients ------------------------------------------------------------------
  * One pass over the whole batch (M samples) computes the loss of AgentPPO.update_rada2c

@@ -120,6 +120,7 @@ SYMBOLS = [
     ("rs_ff_team_step", C.c_int, [C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("rs_rollout", C.c_int, [C.c_void_p, C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.POINTER(RsRolloutArgs), C.c_void_p]),
+    ("rs_rollout_lds_bytes", C.c_size_t, [C.c_int]),
     ("rs_ppo_grad_workspace_bytes", C.c_size_t, []),
     ("rs_ppo_grad", C.c_int, [C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.POINTER(RsPpoBatch), C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),

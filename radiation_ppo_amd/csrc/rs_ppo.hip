@@ -259,6 +259,14 @@ __global__ void __launch_bounds__(1024) rs_ppo_tail_kernel(const float* __restri
 
 extern "C" {
 
+size_t rs_rollout_lds_bytes(int has_obs) {
+    size_t lds = sizeof(float) * (size_t)(rs_mlp16_lds_floats(8) + rs_mlp16_lds_floats(1)) + 16;
+    lds += (has_obs ? (2 * RS_MAX_VERT * RS_WAVE * 4 + RS_MAX_VERT * RS_WAVE * 8) : 0);
+    lds += RS_WAVE * RS_OBS_DIM * 4 + RS_WAVE * 4 + 2 * RS_WAVE + rs_rollout16_mailbox_bytes();
+    lds += has_obs ? rs_rollout16_exchange_bytes<true>() : rs_rollout16_exchange_bytes<false>();
+    return lds;
+}
+
 int rs_rollout(rs_handle* h, const rs_mlp_params* actor, const rs_mlp_params* critic, const rs_rollout_args* args,
                rs_stream_t stream) {
     if (!h || !actor || !critic || !args) return RS_ERR_INVALID_ARG;
@@ -267,12 +275,17 @@ int rs_rollout(rs_handle* h, const rs_mlp_params* actor, const rs_mlp_params* cr
     const bool has_obs = P.obstruction_count != 0;
     if (has_obs && P.group != 1) return RS_ERR_UNSUPPORTED;
     if (args->steps_per_epoch < 1 || args->steps_per_episode < 1) return RS_ERR_INVALID_ARG;
-    size_t lds = sizeof(float) * (size_t)(rs_mlp16_lds_floats(8) + rs_mlp16_lds_floats(1)) + 16;
-    lds += (has_obs ? (2 * RS_MAX_VERT * RS_WAVE * 4 + RS_MAX_VERT * RS_WAVE * 8) : 0);
-    lds += RS_WAVE * RS_OBS_DIM * 4 + RS_WAVE * 4 + 2 * RS_WAVE + rs_rollout16_mailbox_bytes();
+    const size_t lds = rs_rollout_lds_bytes(has_obs ? 1 : 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (has_obs) hipLaunchKernelGGL(rs_rollout16_kernel<true>, dim3(P.N / 16), dim3(2 * RS_WAVE), lds, s, P, to_dev(actor), to_dev(critic), *args);
-    else hipLaunchKernelGGL(rs_rollout16_kernel<false>, dim3(P.N / 16), dim3(2 * RS_WAVE), lds, s, P, to_dev(actor), to_dev(critic), *args);
+    // tile waves (four waves, a CU per workgroup) while every workgroup gets a CU at once; beyond that the two-wave workgroup, two per CU
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+    }
+    if (has_obs) hipLaunchKernelGGL(rs_rollout16_kernel<true>, dim3(P.N / 16), dim3(RsK6Cfg<true>::waves * RS_WAVE), lds, s, P, to_dev(actor), to_dev(critic), *args);
+    else if (P.N / 16 <= cus) hipLaunchKernelGGL(rs_rollout16_kernel<false>, dim3(P.N / 16), dim3(RsK6Cfg<false>::waves * RS_WAVE), lds, s, P, to_dev(actor), to_dev(critic), *args);
+    else hipLaunchKernelGGL(rs_rollout16_wide_kernel, dim3(P.N / 16), dim3(2 * RS_WAVE), lds, s, P, to_dev(actor), to_dev(critic), *args);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 
@@ -409,7 +422,7 @@ int rs_debug_k7_skew(unsigned long long* out, int clear) {
 #endif
 
 #ifdef RS_K6_STAMPS
-// diagnostic build only: read (and optionally clear) the phase-cycle table of rs_rollout16_kernel; out[2][16], row 1 = obstacle template
+// diagnostic build only: read (and optionally clear) the phase-cycle table of rs_rollout16_kernel; out[2][RS_K6_NPH], row 1 = obstacle template
 int rs_debug_k6_stamps(unsigned long long* out, int clear) {
     if (hipDeviceSynchronize() != hipSuccess) return RS_ERR_HIP;
     if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(rs_k6_stamp_table), sizeof(unsigned long long) * 2 * RS_K6_NPH) != hipSuccess) return RS_ERR_HIP;

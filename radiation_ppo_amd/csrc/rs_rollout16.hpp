@@ -32,6 +32,26 @@
 // side in the env step; the serial loop is left for an env with three rejections (0.03 trips per lock-step).  For that all four lanes
 // of an env run the step core in both templates, with identical values.  Without obstacles the critic's wave also writes the buffer's
 // observation rows from the messages it reads.  Same bits (tests/test_k6_poisson_group_gpu.py).
+//
+// Tile waves (round 15; the template without obstacles).  The actor's two hidden layers were 76 MFMAs and 32 tanh back to back in wave
+// 0 although their four output tiles are independent accumulator chains.  The workgroup now has four waves, one per SIMD (at 400
+// registers no two share one), and each computes ONE tile: wave 0 tile 0, wave 1 tile 3 (ahead of its critic work), waves 2 and 3
+// tiles 1 and 2 (RsMlp16::tile_layer1 / tile_layer2, operands parked per wave).  Waves 1..3 take the observation from the mailbox
+// message wave 0 completes before the lock-step's barrier: the post-reset row where flag bit 0 (cut) is set, else the pre-reset row,
+// which is what wave 0 goes on with.  Three workgroup barriers per lock-step t, executed by every wave, nothing else is waited on:
+//   obs(t - 1)  message t - 1 complete (the barrier there was before; obs(-1) in the prologue)
+//   H1(t)       every wave has stored its layer-1 tile to xch1; behind it every wave loads all four
+//   H2(t)       waves 1..3 have stored their layer-2 tiles to xch2; behind it wave 0 loads them, runs the output layer and the chain
+// Counts: wave 0 executes obs(-1) and then H1, H2, obs in each of its T lock-steps; waves 1..3 loop over t = -1 .. T - 1, execute
+// obs(t) and then, if lock-step t + 1 exists, H1(t + 1) and H2(t + 1): 3 T + 1 in every wave for every T >= 1, in the same order.
+// The exchange arrays are single-buffered: xch1 is read between H1(t) and H2(t) (a __syncthreads waits for the wave's LDS loads
+// before the barrier) and rewritten after obs(t); xch2 is read by wave 0 between H2(t) and obs(t) and rewritten after H1(t + 1).  A
+// tile is rewritten only after every reader has passed a later barrier.  The mailbox stays double buffered: wave 1 reads message t
+// for the critic while wave 0 writes message t + 1.  The order of every sum is the one of RsMlp16::hidden, so the buffers keep their
+// bits (tests/test_k6_tile_waves_gpu.py).  -DRS_K6_TILE_WAVES=2: waves 2 and 3 with two interleaved tiles each; =0: as before.
+// A four-wave workgroup has a CU to itself where two two-wave workgroups shared one, so the tile waves pay while there are no more
+// workgroups than CUs (4096 envs on 256 CUs: the SIMDs they use were idle).  Beyond that rs_rollout launches rs_rollout16_wide_kernel,
+// the same body with two waves; the obstacle template (config 3: 512 workgroups) stays on two waves for the same reason.
 #pragma once
 #include "rs_mlp.hpp"
 
@@ -135,6 +155,57 @@ struct RsMlp16 {
 #pragma unroll
             for (int q = 0; q < 4; ++q) H2[it][q] = rs_tanh_scaled(H2[it][q]);
     }
+    // The same two layers, NT of the four output tiles per wave (K6's tile waves): the tiles it0 .. it0 + NT - 1 are independent
+    // accumulator chains, so a wave that owns them computes what hidden() computes for them, instruction for instruction: layer 1 from
+    // 0.0f over s = 0..2, layer 2 from b2 over ks = 0..15, rs_tanh_scaled on the same values.  The operands of its tiles are parked in
+    // accumulation registers once per launch, as in Regs (19 per tile).  D of tile ut in lane l is exactly the B operand lane l needs
+    // for the k-steps ks = 4 ut + q of the next layer in every wave, so the waves exchange whole accumulators through LDS
+    // ([4 tiles][64 lanes] f32x4, one 16-byte store and four 16-byte loads per lane) without moving a value between lanes.
+    template <int NT> struct TileRegs { float w1[NT * 3], w2[NT * 16], b2[NT * 4]; };
+    template <int NT>
+    __device__ __forceinline__ void load_tiles(TileRegs<NT>& r, int it0) const {
+        const int lane = threadIdx.x & 63, g = lane >> 4;
+#pragma unroll
+        for (int i = 0; i < NT * 3; ++i) r.w1[i] = park(w1f[(it0 * 3 + i) * 64 + lane]);
+#pragma unroll
+        for (int i = 0; i < NT * 16; ++i) r.w2[i] = park(w2f[(it0 * 16 + i) * 64 + lane]);
+#pragma unroll
+        for (int i = 0; i < NT * 4; ++i) r.b2[i] = b2[16 * (it0 + (i >> 2)) + 4 * g + (i & 3)];
+    }
+    // b[s] = input 4 s + (lane >> 4) of sample lane & 15
+    template <int NT>
+    __device__ __forceinline__ void tile_layer1(const float (&b)[3], const TileRegs<NT>& r, f32x4 (&H1)[NT]) const {
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) H1[n][q] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) H1[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(r.w1[n * 3 + s], b[s], H1[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) H1[n][q] = rs_tanh_scaled(H1[n][q]);
+    }
+    // H1: all four tiles of layer 1 (after the exchange)
+    template <int NT>
+    __device__ __forceinline__ void tile_layer2(const f32x4 (&H1)[4], const TileRegs<NT>& r, f32x4 (&H2)[NT]) const {
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) H2[n][q] = r.b2[4 * n + q];
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) {
+            const float b = H1[ks >> 2][ks & 3];
+#pragma unroll
+            for (int n = 0; n < NT; ++n) H2[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(r.w2[n * 16 + ks], b, H2[n], 0, 0, 0);
+        }
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) H2[n][q] = rs_tanh_scaled(H2[n][q]);
+    }
     // fixed-order tree over the four lanes of the sample: (g0 + g1) + (g2 + g3) in every lane, then the bias
     __device__ __forceinline__ float combine(float p, int o) const {
         const int g = (threadIdx.x & 63) >> 4;
@@ -216,7 +287,25 @@ constexpr bool RS_K6_GROUP = true;
 #ifndef RS_K6_OBS_BY_WAVE1
 #define RS_K6_OBS_BY_WAVE1 true
 #endif
-template <bool HAS_OBS> struct RsK6Cfg {
+// A/B switch of round 15 (profiles/r15_k6_tile_waves_ab.txt): how many waves share the actor's hidden layers.  4: one output tile per
+// wave of a four-wave workgroup; 2: waves 2 and 3 with two interleaved tiles each, wave 0 only waits; 0: all four tiles in wave 0 of a
+// two-wave workgroup, as before.
+#ifndef RS_K6_TILE_WAVES
+#define RS_K6_TILE_WAVES 4
+#endif
+static_assert(RS_K6_TILE_WAVES == 0 || RS_K6_TILE_WAVES == 2 || RS_K6_TILE_WAVES == 4, "RS_K6_TILE_WAVES: 0, 2 or 4");
+#ifndef RS_K6_TILE_WAVES_OBS                 // the same for the obstacle template, which is left as it was
+#define RS_K6_TILE_WAVES_OBS 0
+#endif
+static_assert(RS_K6_TILE_WAVES_OBS == 0 || RS_K6_TILE_WAVES_OBS == 2 || RS_K6_TILE_WAVES_OBS == 4, "RS_K6_TILE_WAVES_OBS: 0, 2 or 4");
+template <bool HAS_OBS> constexpr int rs_k6_tile_waves = (RS_K6_SHORT && RS_K6_GROUP && RS_K6_OBS_BY_WAVE1) ? (HAS_OBS ? RS_K6_TILE_WAVES_OBS : RS_K6_TILE_WAVES) : 0;
+// TW: the tile waves of the kernel body; rs_rollout16_kernel<HAS_OBS> has the default, rs_rollout16_wide_kernel none
+template <bool HAS_OBS, int TW = rs_k6_tile_waves<HAS_OBS>> struct RsK6Cfg {
+    // the actor's hidden layers on tile waves (0: none), see "Tile waves" in the header.  Not with obstacles: a four-wave workgroup has a
+    // CU to itself, and config 3's 512 workgroups (8192 envs) then run in two rounds: its collect took 30.4 ms instead of 16.7
+    static constexpr int tile_waves = TW;
+    static constexpr int tiles_per_wave = tile_waves ? 4 / tile_waves : 4;
+    static constexpr int waves = tile_waves ? 4 : 2;                 // of the workgroup (each on a SIMD of its own: the registers allow no two)
     static constexpr bool reg_weights = RS_K6_SHORT && !HAS_OBS;     // actor operands in registers for the launch (RsMlp16::Regs)
     static constexpr bool mfma_out = RS_K6_SHORT;                    // actor output layer on 4x4x1 MFMA chains
     static constexpr bool reg_state = RS_K6_SHORT;                   // env state in registers across the lock-steps (RsEnvRegs / RsAgentRegs)
@@ -229,15 +318,21 @@ template <bool HAS_OBS> struct RsK6Cfg {
     static constexpr bool obs_by_wave1 = RS_K6_SHORT && RS_K6_GROUP && RS_K6_OBS_BY_WAVE1 && !HAS_OBS;
 };
 
+// the two exchange arrays of the tile waves, [4 tiles][64 lanes] f32x4 each, behind the mailbox (whose size keeps them 16-byte aligned)
+template <bool HAS_OBS> __host__ __device__ constexpr int rs_rollout16_exchange_bytes() { return RsK6Cfg<HAS_OBS>::tile_waves ? 2 * 4 * 64 * 16 : 0; }
+static_assert(rs_rollout16_mailbox_bytes() % 16 == 0 && (RS_WAVE * RS_OBS_DIM * 4 + RS_WAVE * 4 + 2 * RS_WAVE) % 16 == 0, "exchange arrays: 16-byte aligned");
+
 // Diagnostic build only (-DRS_K6_STAMPS, scripts/k6_stamps.py): s_memtime stamps at the phase boundaries of wave 0's lock-step,
 // summed per wave in scalar registers and added (lane 0, plain vector atomics) to a table no other code reads.  Slot 14 holds the
 // launch's 100 MHz ticks, slot 15 the lock-steps counted.  Slots 8..12 look into the draws: 8 the cycles of the measurement draw inside
 // "env step", 9 the trips rs_poisson's serial loop needs per lock-step (the candidates of the wave's slowest env), summed, 10 the same
 // beyond three (the serial trips the grouped sampler has left), 11 the cycles spent counting them (inside "env step": the script takes
 // them out), 12 the cycles of the Philox call of the action draw (group_draw: of the lock-step's one call).  The product build
-// contains none of it.  Slot 13 is a phase of its own: that one call ("draw blocks"), kept out of "hidden layers".
+// contains none of it.  Slot 13 is a phase of its own: that one call ("draw blocks"), kept out of "hidden layers".  Slots 16 and 17
+// belong to "hidden layers" with tile waves: wave 0's cycles from its H1 (H2) tile store to the last tile of the exchange read back,
+// i.e. the workgroup barrier, the wait for the slowest tile wave, and the 16-byte loads.
 #ifdef RS_K6_STAMPS
-#define RS_K6_NPH 16
+#define RS_K6_NPH 20
 __device__ unsigned long long rs_k6_stamp_table[2][RS_K6_NPH];
 __device__ __forceinline__ unsigned long long rs_k6_now() {
     unsigned long long t;
@@ -260,8 +355,8 @@ __device__ __forceinline__ unsigned long long rs_k6_now() {
 #define RS_K6STAMP_EXIT(tmpl, steps) do {} while (0)
 #endif
 
-template <bool HAS_OBS>
-__global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpParams pa, RsMlpParams pc, rs_rollout_args R) {
+template <bool HAS_OBS, int TW>
+__device__ __forceinline__ void rs_rollout16_body(const RsParams& P, const RsMlpParams& pa, const RsMlpParams& pc, const rs_rollout_args& R) {
     extern __shared__ __align__(16) unsigned char smem[];
     float* wts = reinterpret_cast<float*>(smem);
     unsigned char* p = smem + sizeof(float) * (size_t)(rs_mlp16_lds_floats(8) + rs_mlp16_lds_floats(1));
@@ -274,6 +369,8 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
     uint8_t* lds_done = reinterpret_cast<uint8_t*>(lds_rew + RS_WAVE);
     uint8_t* lds_oob = lds_done + RS_WAVE;
     float* mbox = reinterpret_cast<float*>(lds_oob + RS_WAVE);          // [2 slots][pre 16 x 12 | post 16 x 12 | flags 16]
+    f32x4* xch1 = reinterpret_cast<f32x4*>(mbox + 2 * RS_MB_SLOT);      // tile waves: [4 tiles][64 lanes] accumulators of layer 1
+    f32x4* xch2 = xch1 + 4 * RS_WAVE;                                   // ... and of layer 2
 
     RsMlp16<8> ACT; RsMlp16<1> CRT;
     ACT.carve(wts);
@@ -295,12 +392,46 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
     }
     __syncthreads();
 
-    if (wave == 1) {
-        // ---- the critic's wave: message t (t = -1: the epoch's first observation) is written by wave 0 before barrier t
+    using Cfg = RsK6Cfg<HAS_OBS, TW>;
+    // tile waves: the wave's first output tile of the actor's hidden layers, and whether it has any
+    constexpr int NT = Cfg::tiles_per_wave;
+    const int it0 = Cfg::tile_waves == 4 ? (wave == 0 ? 0 : wave == 1 ? 3 : wave - 1) : (wave == 3 ? 2 : 0);
+    const bool tiler = Cfg::tile_waves == 4 || (Cfg::tile_waves == 2 && wave >= 2);
+    typename RsMlp16<8>::template TileRegs<NT> TR;
+    if constexpr (Cfg::tile_waves != 0) {
+        if (tiler) ACT.template load_tiles<NT>(TR, it0);
+    }
+
+    if (wave != 0) {
+        // ---- the critic's wave (1): message t (t = -1: the epoch's first observation) is written by wave 0 before barrier t.
+        // Tile waves (1..3): from message t they first compute their tiles of lock-step t + 1's hidden layers, see "Tile waves"
         for (int t = -1; t < T; ++t) {
             __syncthreads();
             const float* M = mbox + (t & 1) * RS_MB_SLOT;
-            if constexpr (RsK6Cfg<HAS_OBS>::obs_by_wave1) {
+            if constexpr (Cfg::tile_waves != 0) {
+                if (t + 1 < T) {                                  // lock-step t + 1 exists: its two exchange barriers
+                    f32x4 H1[4], Ht[NT];
+                    if (tiler) {
+                        // the observation wave 0 goes on with: the post-reset row where the env was cut, as in the row writer below
+                        const float* x = M + ((reinterpret_cast<const int*>(M + RS_MB_FLAGS)[j] & 1) ? RS_MB_POST : RS_MB_PRE) + j * RS_IN_PAD + cj;
+                        const float b[3] = {x[0], x[4], x[8]};
+                        ACT.template tile_layer1<NT>(b, TR, Ht);
+#pragma unroll
+                        for (int i = 0; i < NT; ++i) xch1[(it0 + i) * RS_WAVE + lane] = Ht[i];
+                    }
+                    __syncthreads();
+                    if (tiler) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) H1[i] = xch1[i * RS_WAVE + lane];
+                        ACT.template tile_layer2<NT>(H1, TR, Ht);
+#pragma unroll
+                        for (int i = 0; i < NT; ++i) xch2[(it0 + i) * RS_WAVE + lane] = Ht[i];
+                    }
+                    __syncthreads();
+                }
+                if (wave != 1) continue;
+            }
+            if constexpr (Cfg::obs_by_wave1) {
                 if (t + 1 < T) {                                  // the 16 rows of lock-step t + 1, 704 contiguous bytes
                     float* dst = R.obs + ((size_t)(t + 1) * N + (size_t)blockIdx.x * 16) * RS_OBS_DIM;
                     const int* F = reinterpret_cast<const int*>(M + RS_MB_FLAGS);
@@ -348,13 +479,16 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
     // env arrays are written before a reset, which works on them, re-read after it, and written at the end of the launch.
     // Without Cfg::reg_state the step goes through the arrays (rs_env_step_lane) and E only mirrors what the sampler's Philox
     // counter and the source target need.
-    using Cfg = RsK6Cfg<HAS_OBS>;
     RsEnvRegs E;
     RsAgentRegs S;
     E.load(P, n);
     S.load(P, (size_t)n);                                         // single agent: row 0
     RsMlp16<8>::Regs AR;
-    if constexpr (Cfg::reg_weights) ACT.load(AR);
+    if constexpr (Cfg::tile_waves != 0 && Cfg::reg_weights) {     // of the full set, the output layer's operands only
+        ACT.load_w3(AR.w3);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) AR.w3[i >> 4][i & 15] = RsMlp16<8>::park(AR.w3[i >> 4][i & 15]);
+    } else if constexpr (Cfg::reg_weights) ACT.load(AR);
 
     float xo[RS_IN_PAD], xs[RS_IN_PAD];
 #pragma unroll
@@ -396,8 +530,37 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
         }
         {
             f32x4 H2[4];
-            ACT.template hidden<Cfg::reg_weights>(xs, H2, AR);
-            RS_K6STAMP(0);                                       // hidden layers
+            if constexpr (Cfg::tile_waves != 0) {
+                if constexpr (Cfg::tile_waves == 4) {
+                    f32x4 Ht[NT];
+                    const float b[3] = {(cj == 0) ? xs[0] : (cj == 1) ? xs[1] : (cj == 2) ? xs[2] : xs[3],
+                                        (cj == 0) ? xs[4] : (cj == 1) ? xs[5] : (cj == 2) ? xs[6] : xs[7],
+                                        (cj == 0) ? xs[8] : (cj == 1) ? xs[9] : (cj == 2) ? xs[10] : xs[11]};
+                    ACT.template tile_layer1<NT>(b, TR, Ht);
+                    xch1[it0 * RS_WAVE + lane] = Ht[0];
+                    RS_K6STAMP(0);
+                    __syncthreads();
+                    f32x4 H1[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) H1[i] = xch1[i * RS_WAVE + lane];
+                    RS_K6STAMP(16);                              // (inside hidden layers: the H1 exchange)
+                    ACT.template tile_layer2<NT>(H1, TR, Ht);
+                    xch2[it0 * RS_WAVE + lane] = Ht[0];
+                    RS_K6STAMP(0);
+                    __syncthreads();
+                } else {                                         // waves 2 and 3 compute; the two exchange barriers of the lock-step
+                    RS_K6STAMP(0);
+                    __syncthreads();
+                    RS_K6STAMP(16);
+                    __syncthreads();
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) H2[i] = xch2[i * RS_WAVE + lane];
+                RS_K6STAMP(17);                                  // (inside hidden layers: the H2 exchange)
+            } else {
+                ACT.template hidden<Cfg::reg_weights>(xs, H2, AR);
+                RS_K6STAMP(0);                                   // hidden layers
+            }
             if constexpr (!Cfg::mfma_out) ACT.output(H2, lg);
             else if constexpr (Cfg::reg_weights) ACT.output_mfma(H2, lg, AR.w3);
             else { float w3[2][16]; ACT.load_w3(w3); ACT.output_mfma(H2, lg, w3); }
@@ -547,4 +710,14 @@ __global__ void __launch_bounds__(128) rs_rollout16_kernel(RsParams P, RsMlpPara
         R.ep_ret_sum[n] = ep_ret_sum; R.ep_len_sum[n] = ep_len_sum;
         R.ep_ret_sq_sum[n] = ep_ret_sq; R.ep_ret_max[n] = ep_ret_max; R.ep_ret_min[n] = ep_ret_min;
     }
+}
+
+template <bool HAS_OBS>
+__global__ void __launch_bounds__(RsK6Cfg<HAS_OBS>::waves * RS_WAVE) rs_rollout16_kernel(RsParams P, RsMlpParams pa, RsMlpParams pc, rs_rollout_args R) {
+    rs_rollout16_body<HAS_OBS, RsK6Cfg<HAS_OBS>::tile_waves>(P, pa, pc, R);
+}
+// Without obstacles and with more workgroups than CUs (more than 4096 envs on 256 CUs): the two-wave workgroup, of which a CU holds two
+// at once.  Four-wave workgroups have a CU each and would run in twice as many rounds, which costs more than the tile waves save.
+__global__ void __launch_bounds__(2 * RS_WAVE) rs_rollout16_wide_kernel(RsParams P, RsMlpParams pa, RsMlpParams pc, rs_rollout_args R) {
+    rs_rollout16_body<false, 0>(P, pa, pc, R);
 }

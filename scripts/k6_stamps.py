@@ -4,11 +4,14 @@ stamps at the phase boundaries of wave 0's loop:
     python -c "from radiation_ppo_amd.build import build; build(defines=['RS_K6_STAMPS'], suffix='_k6stamps')"
     python -c "from radiation_ppo_amd.build import build; build(defines=['RS_K6_STAMPS', 'RS_K6_PARENT_CHAIN'], suffix='_k6stamps_parent')"
     python -c "from radiation_ppo_amd.build import build; build(defines=['RS_K6_STAMPS', 'RS_K6_SERIAL_DRAW'], suffix='_k6stamps_serial')"
+    python -c "from radiation_ppo_amd.build import build; build(defines=['RS_K6_STAMPS', 'RS_K6_TILE_WAVES=2'], suffix='_k6stamps_tw2')"
+    python -c "from radiation_ppo_amd.build import build; build(defines=['RS_K6_STAMPS', 'RS_K6_TILE_WAVES=0'], suffix='_k6stamps_tw0')"
     python scripts/k6_stamps.py [N] [obstruction_count]            # RS_STAMPS_LIB selects the library (default: lib/librs_hip_k6stamps.so)
 
 RS_K6_PARENT_CHAIN compiles the chain as it was before the weights, the output layer and the env state left it: the 'before' column.
 RS_K6_SERIAL_DRAW compiles the serial measurement draw (rs_poisson) and the action draw's own Philox call inside the softmax: the
-'before' column of the grouped draw.  Below the phase table: the measurement draw's cycles inside "env step", the trips of the
+'before' column of the grouped draw.  RS_K6_TILE_WAVES=2 / =0 compile the actor's hidden layers on two tile waves / in wave 0 alone
+(the 'before' column of the tile waves); with tile waves "hidden layers" includes wave 0's waits at the two exchanges, shown below it.  Below the phase table: the measurement draw's cycles inside "env step", the trips of the
 serial loop per lock-step (the candidates the wave's slowest env needs) and the cycles of the action draw's Philox call.
 Read the SHARES, not the run time: every stamp waits for the wave's outstanding LDS and scalar-memory operations, which forbids
 overlaps the product kernel has."""
@@ -38,7 +41,8 @@ lib = _lib.load()
 lib.rs_debug_k6_stamps.restype = C.c_int
 lib.rs_debug_k6_stamps.argtypes = [C.c_void_p, C.c_int]
 col.collect()
-buf = (C.c_ulonglong * 32)()
+NPH = 20                                    # RS_K6_NPH
+buf = (C.c_ulonglong * (2 * NPH))()
 lib.rs_debug_k6_stamps(buf, 1)
 R = 3
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -48,8 +52,10 @@ for _ in range(R):
 e1.record()
 torch.cuda.synchronize()
 lib.rs_debug_k6_stamps(buf, 0)
-row = 16 * (1 if OBST != 0 else 0)
+row = NPH * (1 if OBST != 0 else 0)
 cyc = [buf[row + q] for q in range(8)]
+xch = [buf[row + 16], buf[row + 17]]       # tile waves: from wave 0's tile store to the exchanged tiles read back (barrier included)
+cyc[0] += sum(xch)
 cyc[4] -= buf[row + 11]                     # counting the candidates is the diagnostic's own work inside "env step"
 if buf[row + 13]:
     PH.append("draw blocks (one Philox call)")
@@ -61,6 +67,8 @@ print(f"stamped build: {e0.elapsed_time(e1) / R:.3f} ms per collect() (slower th
 print(f"in-kernel clock {tot / max(ticks, 1) * 100:.0f} MHz; {tot / max(steps, 1):.0f} wave-cycles per lock-step (mean over {N // 16} waves)")
 for q, c in enumerate(cyc):
     print(f"   {PH[q]:28s} {c / max(steps, 1):8.0f} cyc  {100.0 * c / max(tot, 1):5.1f} %")
+if sum(xch):
+    print(f"   inside hidden layers: H1 exchange {xch[0] / max(steps, 1):.0f} cyc, H2 exchange {xch[1] / max(steps, 1):.0f} cyc (barrier, wait for the slowest tile wave, loads)")
 poi, trips, left, phx = (buf[row + q] / max(steps, 1) for q in (8, 9, 10, 12))
 print(f"   inside env step: measurement draw {poi:.0f} cyc ({100.0 * poi * steps / max(tot, 1):.1f} %); a serial loop needs {trips:.3f} trips per lock-step, "
       f"{left:.3f} of them beyond candidate 3; Philox call of the action draw {phx:.0f} cyc")

@@ -600,7 +600,32 @@ int rs_cnn_trunk_infer(const float* maps, const int64_t* cells, const int64_t* p
  * Backward: da2 [S][16*P*P]; slab [slab_rows][rs_cnn_sized_slab_row(Cin)] with slab_rows >= rs_cnn_sized_slab_rows(S, M, Cin) receives
  * per-workgroup partial sums {dW1 8*Cin*9 | db1 8 | dW2 1152 | db2 16}; the caller sums the first rs_cnn_sized_slab_rows rows.  No
  * atomics: the result is bit-identical from one call to the next.
- * A side outside [8, 256] returns RS_ERR_UNSUPPORTED (the slab functions return 0). */
+ * A side outside [8, 256] returns RS_ERR_UNSUPPORTED (the slab functions return 0).
+ *
+ * The occupancy-aware training passes (walls-off maps are mostly empty).  A unit is (image, tile of 16 x 16 pooled cells); its forward
+ * window is the pixels [2 ty0 - 3, 2 ty0 + 35) x [2 tx0 - 3, 2 tx0 + 35) of the four planes, clipped to the map.  A unit is EMPTY when
+ * every element of that window compares equal to 0.0f (a NaN does not, -0.0f does) and, for an actor, neither the owner's cell nor its
+ * prediction cell (-1: none) lies in the window.
+ *   rs_cnn_sized_tiles: units per image, 0 for a side outside [8, 256].
+ *   rs_cnn_sized_occupancy: flags [S][tiles], bit 0 = the window holds an element != 0.0f.  One read of the maps; the stored maps of an
+ *   update do not change, so once per update.  The owner's cells are not in the flag: they differ per agent, the trunk passes test them.
+ *   rs_cnn_sized_forward_occ: the training forward (p1, amax, relu_mask required) with flags (NULL: RS_ERR_INVALID_ARG).  Every output of
+ *   every unit is written and is bit-identical to rs_cnn_sized_forward's; an empty unit neither reads its window nor evaluates conv1
+ *   (p1 = max(0 + b1, 0), amax = 0) and takes its conv2 outputs from one evaluation per place in the map (first / inner / last row x column).
+ *   rs_cnn_sized_backward_occ: rs_cnn_sized_backward with flags; p1 must be the forward's.  The same slab layout and rows, no atomics (two
+ *   calls write identical slabs).  An empty unit reads only its da2 / relu_mask halo: with dZ2 the gated da2 and c1 = max(0 + b1, 0),
+ *   db2 += sum dZ2, dW2[co][ci][ky][kx] += c1[ci] S[co][ky][kx] (S: dZ2 summed over the tile's pixels whose tap neighbour is in the map),
+ *   db1[ci] += [c1[ci] > 0] sum w2[co][ci][ky][kx] R[co][ky][kx] (R: the tile's dZ2 sums shifted by the tap), dW1 += 0.  The sums are
+ *   reassociated: equal to rs_cnn_sized_backward to float32 summation order, not bit for bit. */
+int32_t rs_cnn_sized_tiles(int32_t map_side);
+int rs_cnn_sized_occupancy(const float* maps, int64_t num_samples, int32_t map_side, uint8_t* flags, rs_stream_t stream);
+int rs_cnn_sized_forward_occ(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,
+                             int64_t num_samples, int32_t map_side, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* a2, float* p1, uint8_t* amax, uint16_t* relu_mask, const uint8_t* flags, rs_stream_t stream);
+int rs_cnn_sized_backward_occ(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,
+                              int64_t num_samples, int32_t map_side, const float* w2, const float* da2, const uint16_t* relu_mask,
+                              const float* p1, const uint8_t* amax, float* slab, int32_t slab_rows, const uint8_t* flags,
+                              rs_stream_t stream);
 int32_t rs_cnn_sized_slab_row(int32_t in_channels);
 int32_t rs_cnn_sized_slab_rows(int64_t num_samples, int32_t map_side, int32_t in_channels);
 int rs_cnn_sized_forward(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,

@@ -189,6 +189,12 @@ SYMBOLS = [
     ("rs_cnn_sized_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6),
     ("rs_cnn_sized_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6
      + [C.c_int32, C.c_void_p]),
+    # the occupancy-aware training passes: flags [S][tiles] once per update, then the forward / backward with the flags in front of the stream
+    ("rs_cnn_sized_tiles", C.c_int32, [C.c_int32]),
+    ("rs_cnn_sized_occupancy", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("rs_cnn_sized_forward_occ", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 10),
+    ("rs_cnn_sized_backward_occ", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6
+     + [C.c_int32, C.c_void_p, C.c_void_p]),
     ("rs_cnn_head", C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                               C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     ("rs_store_rows", C.c_int, [C.c_void_p] * 17 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

@@ -18,7 +18,10 @@
 //     plane pair, tile row).  Accumulators stay in registers across all tiles of a workgroup, which writes one slab row at the end
 //     (fixed-order reduction, no atomics: bit-identical from one run to the next);
 //   * the Monte-Carlo evaluation's team forward (rs_sized_team_fwd, rs_cnn_sized_team_infer): every agent's actor trunk in one launch
-//     over (image, tile, agent) units, the same unit function, conv1 skipped over empty input windows (bit for bit: fwd_unit).
+//     over (image, tile, agent) units, the same unit function, conv1 skipped over empty input windows (bit for bit: fwd_unit);
+//   * the occupancy-aware training passes (rs_sized_occupancy once per update, rs_sized_trunk_fwd_occ, rs_sized_trunk_bwd_occ): walls-off
+//     maps are mostly empty and do not change over an update's iterations, so the units whose window is all zero are flagged once; the
+//     forward then writes such a unit's constants and the backward reduces it to a few sums of dZ2 (see the kernels).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -83,6 +86,19 @@ __device__ __forceinline__ void owner_cells(const SzIn& in, long long s, int& lo
     }
 }
 
+// The occupancy-aware training passes: a unit is empty when its forward window (38 x 38 pixels of the four planes, clipped to the map)
+// holds nothing but zeros -- bit 0 of its flag, written once per update by rs_sized_occupancy -- and neither of the owner's cells.  The
+// rule of fwd_unit's SKIP branch; the backward's 34 x 34 window and the 18 x 18 P1 halo lie inside that window, so one flag serves both.
+// The flag is tested first and alone: an occupied window then never waits for the owner's cells, which the dense unit needs late.
+__device__ __forceinline__ bool unit_is_empty(const SzIn& in, uint8_t flag, int ty0, int tx0, int loc, int pc) {
+    if (flag & 1) return false;
+    auto inside = [&](int at) {
+        const int r = at / in.M - (2 * ty0 - 3), c = at % in.M - (2 * tx0 - 3);
+        return at >= 0 && r >= 0 && r < FWS && c >= 0 && c < FWS;
+    };
+    return !inside(loc) && !inside(pc);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Forward: maps -> a2 [S][16 P P] (torch Flatten order c P P + y P + x); TRAIN also writes p1 [S][P P][8], amax [S][P P][8] (0..3,
 // row-major, first maximum) and relu_mask [S][P P] (bit c = a2 channel c > 0), the schema of K9 with P P in place of 169.
@@ -106,7 +122,9 @@ __device__ __forceinline__ void fwd_stamps(const float* __restrict__ w1, float* 
 // SKIP (the evaluation's team kernel): a unit whose staged window holds nothing but zeros and neither cell does not evaluate conv1.
 // There every conv1 accumulator is +0 (they start at +0 and fmaf(w, +-0, +0) = +0), so every pooled cell inside the map is
 // max(0 + b1, 0), the maximum of four equal values: the same bits.  One block-wide OR decides, uniform over the workgroup.
-template <int CIN, bool TRAIN, bool SKIP>
+// CALLER: a second kernel that calls the same instantiation changes hipcc's inlining order and with it the first kernel's schedule;
+// rs_sized_trunk_fwd_occ therefore takes an instantiation of its own (1) and leaves rs_sized_trunk_fwd's code as it was.
+template <int CIN, bool TRAIN, bool SKIP, int CALLER = 0>
 __device__ __forceinline__ void fwd_unit(const SzIn& in, long long s, int tile, int loc, int pc, const float* __restrict__ w1,
                                          const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
                                          float* __restrict__ a2, float* __restrict__ p1g, uint8_t* __restrict__ amax,
@@ -329,170 +347,118 @@ template <int CIN>
 __global__ void __launch_bounds__(NT, 2) rs_sized_trunk_bwd(SzIn in, const float* __restrict__ w2, const float* __restrict__ da2,
                                                            const uint16_t* __restrict__ relu_mask, const float* __restrict__ p1g,
                                                            const uint8_t* __restrict__ amax, float* __restrict__ slab) {
-    __shared__ __align__(16) float smem[DP * BWS * BWS + C1 * HC + C2 * HC + C1 * NT + 2 * NT];
-    float* xs = smem;                         // input window [plane][34][34]
-    float* ps = xs + DP * BWS * BWS;          // P1 with halo [ci][18][18]
-    float* dz = ps + C1 * HC;                 // dZ2 = ReLU-gated da2 with halo [co][18][18]
-    float* gb = dz + C2 * HC;                 // dL/d(P1) gated by P1 > 0, the tile's cells [ci][256]
-    uint8_t* am = reinterpret_cast<uint8_t*>(gb + C1 * NT);     // arg-max codes of the tile's cells [256][8]
-    constexpr int K1 = CIN * 9, CH0 = (CIN == 6) ? 2 : 0;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = in.P, PP = P * P;
-    const int ly = tid / TS, lx = tid - ly * TS;
-    // dW2 / db2: thread = (output channel co2, input channel ci2, half of the tile's rows) -> 9 taps + db2;
-    // dW1 / db1: thread = (output channel co1, plane pair, tile row ly) -> 2 x 9 taps + db1
-    const int co2 = tid & 15, ci2 = (tid >> 4) & 7, half2 = tid >> 7;
-    const int co1 = tid & 7, half = (tid >> 3) & 1;
-    float aw2[10], aw1[19], gst = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) aw2[k] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 19; ++k) aw1[k] = 0.0f;
+    constexpr bool OCC = false;
+    const uint8_t* flags = nullptr;
+#include "rs_cnn_sized_bwd.inc"
+}
+
+// The occupancy-aware backward.  An empty unit's inputs are zero and its P1 is the per-channel constant c1 = max(0 + b1, 0) inside the
+// map, so with dZ2 = da2 gated by relu_mask (zero outside the map) its contributions are
+//   db2[co]             += sum of dZ2[co] over the tile's pixels                                  (= S[co][1][1])
+//   dW2[co][ci][ky][kx] += c1[ci] S[co][ky][kx],   S = sum of dZ2[co][y][x] over the pixels whose neighbour (y + ky - 1, x + kx - 1) is in the map
+//   db1[ci]             += [c1[ci] > 0] sum_{co,ky,kx} w2[co][ci][ky][kx] R[co][ky][kx],   R = sum over own cells of dZ2[co][cy - ky + 1][cx - kx + 1]
+//   dW1                 += 0 (the one-hot gathers too: neither owner cell is in the window)
+// S and R are summed in registers over a workgroup's empty units, c1 and w2 folded in once in front of the slab row.  The slab's layout
+// and rows are the dense kernel's; the sums are reassociated, not bit-identical to it, and bit-identical from one call to the next.
+template <int CIN>
+__global__ void __launch_bounds__(NT, 2) rs_sized_trunk_bwd_occ(SzIn in, const float* __restrict__ w2, const float* __restrict__ da2,
+                                                               const uint16_t* __restrict__ relu_mask, const float* __restrict__ p1g,
+                                                               const uint8_t* __restrict__ amax, const uint8_t* __restrict__ flags,
+                                                               float* __restrict__ slab) {
+    constexpr bool OCC = true;
+#include "rs_cnn_sized_bwd.inc"
+}
+
+// The occupancy-aware training forward: fwd_unit for the occupied units; an empty unit neither stages its window nor evaluates conv1
+// (p1 = c1, amax = 0, the first of four equal values), and its conv2 outputs are one of 9 x 16 values: a pixel's 3 x 3 P1 neighbourhood is
+// c1 where it lies inside the map and conv2's zero padding outside, so only the pixel's place (first / inner / last row x column of the
+// map) matters.  Thread (pattern, co) evaluates dense conv2's fmaf chain -- b2, then (ci, ky, kx) in order -- once per launch and keeps
+// the result in a register; an empty unit broadcasts the table through ps.  Bit-identical to rs_sized_trunk_fwd<CIN, true>.
+template <int CIN>
+__global__ void __launch_bounds__(NT, 3) rs_sized_trunk_fwd_occ(SzIn in, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                               const float* __restrict__ w2, const float* __restrict__ b2,
+                                                               float* __restrict__ a2, float* __restrict__ p1g, uint8_t* __restrict__ amax,
+                                                               uint16_t* __restrict__ relu_mask, const uint8_t* __restrict__ flags) {
+    __shared__ FwdLds lds;
+    if (CIN == 6) fwd_stamps(w1, lds.stl);
+    const int tid = threadIdx.x, P = in.P, PP = P * P;
+    float ev = 0.0f;
+    if (tid < 9 * C2) {
+        const int pat = tid / C2, co = tid - pat * C2, py = pat / 3, px = pat - py * 3;      // 0: first row / column, 1: inner, 2: last
+        float acc = b2[co];
+        for (int ci = 0; ci < C1; ++ci) {
+            const float c = fmaxf(0.0f + b1[ci], 0.0f);
+            for (int ky = 0; ky < 3; ++ky)
+                for (int kx = 0; kx < 3; ++kx) {
+                    const bool in_map = !(py == 0 && ky == 0) && !(py == 2 && ky == 2) && !(px == 0 && kx == 0) && !(px == 2 && kx == 2);
+                    acc = __builtin_fmaf(w2[co * 72 + ci * 9 + ky * 3 + kx], in_map ? c : 0.0f, acc);
+                }
+        }
+        ev = fmaxf(acc, 0.0f);
+    }
+    bool table = false;                        // ps holds the table (the last unit was empty too)
     const int nt2 = in.ntile * in.ntile;
     const long long units = in.S * nt2;
+    uint8_t ahead = blockIdx.x < units ? flags[blockIdx.x] : 1;      // a unit's flag is read one unit ahead: no unit starts with a wait for it
     for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const uint8_t flag = ahead;
+        if (u + gridDim.x < units) ahead = flags[u + gridDim.x];
         const long long s = u / nt2;
         const int tile = (int)(u - s * nt2), ty0 = (tile / in.ntile) * TS, tx0 = (tile % in.ntile) * TS;
         int loc, pc;
         owner_cells(in, s, loc, pc);
-        cmem_t w2c = as_cmem(w2);                 // per iteration, as in the forward kernel
-        asm volatile("" : "+s"(w2c));
-        stage_window<BWS>(in, s, 2 * ty0 - 1, 2 * tx0 - 1, xs);
-#pragma unroll 1
-        for (int h = tid; h < HC; h += NT) {
-            const int hy = h / HS, hx = h - hy * HS, gy = ty0 - 1 + hy, gx = tx0 - 1 + hx;
-            const bool in_map = gy >= 0 && gy < P && gx >= 0 && gx < P;
-            const size_t cell = (size_t)s * PP + (in_map ? gy * P + gx : 0);
-            float4 pa = make_float4(0.f, 0.f, 0.f, 0.f), pb = pa;
+        if (!unit_is_empty(in, flag, ty0, tx0, loc, pc)) {
+            fwd_unit<CIN, true, false, 1>(in, s, tile, loc, pc, w1, b1, w2, b2, a2, p1g, amax, relu_mask, lds);
+            table = false;
+            continue;
+        }
+        if (!table) {
+            __syncthreads();                   // the last unit's conv2 has read ps
+            if (tid < 9 * C2) lds.ps[tid] = ev;
+            __syncthreads();
+            table = true;
+        }
+        const int ly = tid / TS, lx = tid - ly * TS, oy = ty0 + ly, ox = tx0 + lx;
+        if (oy < P && ox < P) {
+            cmem_t b1c = as_cmem(b1);
+            const size_t cell = (size_t)s * PP + oy * P + ox;
+            float c[C1];
+#pragma unroll
+            for (int co = 0; co < C1; ++co) c[co] = fmaxf(0.0f + b1c[co], 0.0f);
+            float4* dst1 = reinterpret_cast<float4*>(p1g + cell * C1);
+            dst1[0] = make_float4(c[0], c[1], c[2], c[3]);
+            dst1[1] = make_float4(c[4], c[5], c[6], c[7]);
+            *reinterpret_cast<uint2*>(amax + cell * C1) = make_uint2(0u, 0u);
+            const int pat = ((oy == 0 ? 0 : oy == P - 1 ? 2 : 1) * 3 + (ox == 0 ? 0 : ox == P - 1 ? 2 : 1)) * C2;
             uint32_t live = 0u;
-            if (in_map) {
-                pa = reinterpret_cast<const float4*>(p1g + cell * C1)[0];
-                pb = reinterpret_cast<const float4*>(p1g + cell * C1)[1];
-                live = relu_mask[cell];
+            float* dst = a2 + (size_t)s * C2 * PP + oy * P + ox;
+#pragma unroll
+            for (int co = 0; co < C2; ++co) {
+                const float o = lds.ps[pat + co];
+                dst[(size_t)co * PP] = o;
+                live |= (o > 0.0f ? 1u : 0u) << co;
             }
-            ps[0 * HC + h] = pa.x; ps[1 * HC + h] = pa.y; ps[2 * HC + h] = pa.z; ps[3 * HC + h] = pa.w;
-            ps[4 * HC + h] = pb.x; ps[5 * HC + h] = pb.y; ps[6 * HC + h] = pb.z; ps[7 * HC + h] = pb.w;
-            const float* g = da2 + (size_t)s * C2 * PP + (in_map ? gy * P + gx : 0);
-#pragma unroll
-            for (int co = 0; co < C2; ++co) dz[co * HC + h] = ((live >> co) & 1u) ? g[(size_t)co * PP] : 0.0f;
+            relu_mask[cell] = (uint16_t)live;
         }
-        {
-            const int gy = ty0 + ly, gx = tx0 + lx;
-            uint2 code = make_uint2(0u, 0u);
-            if (gy < P && gx < P) code = *reinterpret_cast<const uint2*>(amax + ((size_t)s * PP + gy * P + gx) * C1);
-            *reinterpret_cast<uint2*>(am + tid * C1) = code;
-        }
-        __syncthreads();
-        // ---- dW2[co][ci][ky][kx] += sum_px dZ2[co][px] P1[ci][px + (ky - 1, kx - 1)], db2[co] += sum_px dZ2[co][px]: eight rows of 16
-        // pixels; a P1 row of 18 values serves the three kx taps of all 16 pixels of a row
-#pragma unroll 1
-        for (int yy = 0; yy < TS / 2; ++yy) {
-            const int y = half2 * (TS / 2) + yy;
-            float dzr[TS];
-#pragma unroll
-            for (int x = 0; x < TS; ++x) { dzr[x] = dz[co2 * HC + (y + 1) * HS + x + 1]; aw2[9] += dzr[x]; }
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                float r[HS];
-#pragma unroll
-                for (int x = 0; x < HS; ++x) r[x] = ps[ci2 * HC + (y + ky) * HS + x];
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-                    for (int x = 0; x < TS; ++x) aw2[ky * 3 + kx] = __builtin_fmaf(dzr[x], r[x + kx], aw2[ky * 3 + kx]);
-            }
-        }
-        // ---- dP1[ci][cell] = sum_{co,ky,kx} w2[co][ci][ky][kx] dZ2[co][cell - (ky - 1, kx - 1)], gated by P1 > 0 (cells outside the map have
-        // P1 = 0 in ps: no gradient)
-        {
-            float g[C1];
-#pragma unroll
-            for (int ci = 0; ci < C1; ++ci) g[ci] = 0.0f;
-            const float* dq = dz + (ly + 2) * HS + lx + 2;
-#pragma unroll 1
-            for (int q = 0; q < C2 * 3; ++q) {               // rolled over (co, ky): 24 weights per trip
-                const int co = q / 3, ky = q - co * 3;
-                const cmem_t wq = w2c + co * 72 + ky * 3;
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const float v = dq[co * HC - ky * HS - kx];
-#pragma unroll
-                    for (int ci = 0; ci < C1; ++ci) g[ci] = __builtin_fmaf(wq[ci * 9 + kx], v, g[ci]);
-                }
-            }
-#pragma unroll
-            for (int ci = 0; ci < C1; ++ci) gb[ci * NT + tid] = ps[ci * HC + (ly + 1) * HS + lx + 1] > 0.0f ? g[ci] : 0.0f;
-        }
-        __syncthreads();
-        // ---- dW1[co1][plane][ky][kx] += g[co1][cell] x[plane] at the cell's arg-max pixel + (ky - 1, kx - 1); db1[co1] += g
-        {
-#pragma unroll 1
-            for (int x = 0; x < TS; ++x) {
-                const int cell = ly * TS + x;
-                const float gv = gb[co1 * NT + cell];
-                const int code = am[cell * C1 + co1];
-                const float* base = xs + (2 * half) * BWS * BWS + (2 * ly + (code >> 1)) * BWS + 2 * x + (code & 1);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int kk = 0; kk < 9; ++kk) aw1[j * 9 + kk] = __builtin_fmaf(gv, base[j * BWS * BWS + (kk / 3) * BWS + kk % 3], aw1[j * 9 + kk]);
-                aw1[18] += gv;
-            }
-        }
-        if (CIN == 6 && tid < 2 * C1 * 9) {
-            // the one-hot channels: input (r, c) meets tap (ky, kx) at conv pixel (r - ky + 1, c - kx + 1), which carries gradient iff it
-            // is its pool window's arg-max for channel co; the tile that owns the pooled cell adds it
-            const int which = tid / (C1 * 9), co = (tid % (C1 * 9)) / 9, kk = tid % 9;
-            const int at = which ? loc : pc;
-            if (at >= 0) {
-                const int r = at / in.M, c = at - r * in.M;
-                const int y = r - kk / 3 + 1, x = c - kk % 3 + 1;
-                if (y >= 0 && y < 2 * P && x >= 0 && x < 2 * P) {
-                    const int cy = (y >> 1) - ty0, cx = (x >> 1) - tx0;
-                    if (cy >= 0 && cy < TS && cx >= 0 && cx < TS && am[(cy * TS + cx) * C1 + co] == (uint8_t)((y & 1) * 2 + (x & 1)))
-                        gst += gb[co * NT + cy * TS + cx];
-                }
-            }
-        }
-        __syncthreads();
     }
-    // ---- workgroup reduction in a fixed order.  dW1: the four tile rows of a wave by lane swaps (lanes l, l ^ 16, l ^ 32), then the
-    // four waves; dW2: the two row halves
-#pragma unroll
-    for (int k = 0; k < 19; ++k) { aw1[k] += __shfl_xor(aw1[k], 16); aw1[k] += __shfl_xor(aw1[k], 32); }
-    float* red2 = smem;                        // [2 halves][8 ci][16 co][10]
-    float* red1 = red2 + NT * 10;              // [4 waves][16 (co1, half)][19]
-    float* gred = red1 + 4 * 16 * 19;          // [2][8][9]
-#pragma unroll
-    for (int k = 0; k < 10; ++k) red2[tid * 10 + k] = aw2[k];
-    if (lane < 16) {
-#pragma unroll
-        for (int k = 0; k < 19; ++k) red1[(wave * 16 + lane) * 19 + k] = aw1[k];
-    }
-    if (tid < 2 * C1 * 9) gred[tid] = gst;
-    __syncthreads();
-    constexpr int ROW = C1 * K1 + C1 + C2 * 72 + C2;
-    float* out = slab + (size_t)blockIdx.x * ROW;
-    for (int e = tid; e < ROW; e += NT) {
-        float sum = 0.0f;
-        if (e < C1 * K1) {
-            const int o1 = e / K1, k = e - o1 * K1, i0 = k / 9, kk = k - i0 * 9;     // i0: the logical input channel
-            if (i0 < CH0) { out[e] = gred[(i0 * C1 + o1) * 9 + kk]; continue; }   // prediction (0) / location (1): the stamp gathers
-            const int d = i0 - CH0, combo = o1 + 8 * (d >> 1), slot = (d & 1) * 9 + kk;
-            if (CIN == 6 && d == 0) sum = -gred[(C1 + o1) * 9 + kk];                 // others = combined - location
-#pragma unroll
-            for (int w = 0; w < 4; ++w) sum += red1[(w * 16 + combo) * 19 + slot];
-        } else if (e < C1 * K1 + C1) {
-            const int o1 = e - C1 * K1;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) sum += red1[(w * 16 + o1) * 19 + 18];
-        } else if (e < C1 * K1 + C1 + C2 * 72) {
-            const int q = e - (C1 * K1 + C1), co = q / 72, k = q - co * 72, ci = k / 9, kk = k - ci * 9;
-            sum = red2[(ci * 16 + co) * 10 + kk] + red2[(NT / 2 + ci * 16 + co) * 10 + kk];
-        } else {
-            const int co = e - (C1 * K1 + C1 + C2 * 72);
-            sum = red2[co * 10 + 9] + red2[(NT / 2 + co) * 10 + 9];
+}
+
+// flags [S][tiles]: bit 0 = the unit's forward window, clipped to the map, holds an element != 0.0f (a NaN does, -0.0f does not).  One
+// read of the maps (the windows overlap by 6 of 38 pixels a side; the second read of an overlap comes from the cache).
+__global__ void __launch_bounds__(NT) rs_sized_occupancy(SzIn in, uint8_t* __restrict__ flags) {
+    const int nt2 = in.ntile * in.ntile, M = in.M;
+    const long long units = in.S * nt2;
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const long long s = u / nt2;
+        const int tile = (int)(u - s * nt2), r0 = 2 * (tile / in.ntile) * TS - 3, c0 = 2 * (tile % in.ntile) * TS - 3;
+        const float* src = in.maps + (size_t)s * DP * M * M;
+        bool nz = false;
+        for (int e = threadIdx.x; e < DP * FWS * FWS; e += NT) {
+            const int d = e / (FWS * FWS), rem = e - d * (FWS * FWS), wr = rem / FWS, r = r0 + wr, c = c0 + rem - wr * FWS;
+            if (r >= 0 && r < M && c >= 0 && c < M) nz |= src[((size_t)d * M + r) * M + c] != 0.0f;
         }
-        out[e] = sum;
+        const int any = __syncthreads_or(nz);
+        if (threadIdx.x == 0) flags[u] = any ? 1 : 0;
     }
 }
 
@@ -602,6 +568,54 @@ int rs_cnn_sized_backward(const float* maps, const int64_t* cells, const int64_t
     hipStream_t s = (hipStream_t)stream;
     if (agent >= 0) hipLaunchKernelGGL(rs_sized_trunk_bwd<6>, dim3(grid), dim3(NT), 0, s, in, w2, da2, relu_mask, p1, amax, slab);
     else hipLaunchKernelGGL(rs_sized_trunk_bwd<4>, dim3(grid), dim3(NT), 0, s, in, w2, da2, relu_mask, p1, amax, slab);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int32_t rs_cnn_sized_tiles(int32_t map_side) { return side_ok(map_side) ? tiles(map_side) * tiles(map_side) : 0; }
+
+int rs_cnn_sized_occupancy(const float* maps, int64_t num_samples, int32_t map_side, uint8_t* flags, rs_stream_t stream) {
+    if (!maps || !flags || num_samples < 0) return RS_ERR_INVALID_ARG;
+    if (!side_ok(map_side)) return RS_ERR_UNSUPPORTED;
+    if (num_samples == 0) return RS_OK;
+    SzIn in{maps, nullptr, nullptr, 0, -1, map_side, map_side / 2, tiles(map_side), (long long)num_samples};
+    const long long units = (long long)num_samples * in.ntile * in.ntile, cap = 1 << 20;
+    hipLaunchKernelGGL(rs_sized_occupancy, dim3((unsigned)(units < cap ? units : cap)), dim3(NT), 0, (hipStream_t)stream, in, flags);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_cnn_sized_forward_occ(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,
+                             int64_t num_samples, int32_t map_side, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* a2, float* p1, uint8_t* amax, uint16_t* relu_mask, const uint8_t* flags, rs_stream_t stream) {
+    if (!maps || !w1 || !b1 || !w2 || !b2 || !a2 || !p1 || !amax || !relu_mask || !flags || num_samples < 0) return RS_ERR_INVALID_ARG;
+    if (agent >= 0 && (!cells || !pcells || agent >= num_agents)) return RS_ERR_INVALID_ARG;
+    if (!side_ok(map_side)) return RS_ERR_UNSUPPORTED;
+    if (num_samples == 0) return RS_OK;
+    SzIn in{maps, cells, pcells, num_agents, agent, map_side, map_side / 2, tiles(map_side), (long long)num_samples};
+    const long long units = (long long)num_samples * in.ntile * in.ntile;
+    hipStream_t s = (hipStream_t)stream;
+    if (agent >= 0)
+        hipLaunchKernelGGL(rs_sized_trunk_fwd_occ<6>, dim3(sized_grid(rs_sized_trunk_fwd_occ<6>, units)), dim3(NT), 0, s, in, w1, b1, w2, b2, a2,
+                           p1, amax, relu_mask, flags);
+    else
+        hipLaunchKernelGGL(rs_sized_trunk_fwd_occ<4>, dim3(sized_grid(rs_sized_trunk_fwd_occ<4>, units)), dim3(NT), 0, s, in, w1, b1, w2, b2, a2,
+                           p1, amax, relu_mask, flags);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_cnn_sized_backward_occ(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,
+                              int64_t num_samples, int32_t map_side, const float* w2, const float* da2, const uint16_t* relu_mask,
+                              const float* p1, const uint8_t* amax, float* slab, int32_t slab_rows, const uint8_t* flags,
+                              rs_stream_t stream) {
+    if (!maps || !w2 || !da2 || !relu_mask || !p1 || !amax || !slab || !flags || num_samples <= 0) return RS_ERR_INVALID_ARG;
+    if (agent >= 0 && (!cells || !pcells || agent >= num_agents)) return RS_ERR_INVALID_ARG;
+    if (!side_ok(map_side)) return RS_ERR_UNSUPPORTED;
+    // the dense entry's rows (the caller sizes one slab for either pass); the kernel's own residency is no smaller than the dense one's
+    const int grid = rs_cnn_sized_slab_rows(num_samples, map_side, agent >= 0 ? 6 : 4);
+    if (slab_rows < grid) return RS_ERR_INVALID_ARG;
+    SzIn in{maps, cells, pcells, num_agents, agent, map_side, map_side / 2, tiles(map_side), (long long)num_samples};
+    hipStream_t s = (hipStream_t)stream;
+    if (agent >= 0) hipLaunchKernelGGL(rs_sized_trunk_bwd_occ<6>, dim3(grid), dim3(NT), 0, s, in, w2, da2, relu_mask, p1, amax, flags, slab);
+    else hipLaunchKernelGGL(rs_sized_trunk_bwd_occ<4>, dim3(grid), dim3(NT), 0, s, in, w2, da2, relu_mask, p1, amax, flags, slab);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

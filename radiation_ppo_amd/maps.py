@@ -204,10 +204,12 @@ class ConvTrunk(torch.autograd.Function):
 
 class SizedConvTrunk(torch.autograd.Function):
     """ConvTrunk for square maps of any side 8 <= M <= 256 (rs_cnn_sized_forward / _backward: tiled, so that the 147 x 147 maps of
-    walls-off runs stay on HIP kernels).  a2 [S, 16 P P] with P = M // 2; same arguments and agent convention as ConvTrunk."""
+    walls-off runs stay on HIP kernels).  a2 [S, 16 P P] with P = M // 2; same arguments and agent convention as ConvTrunk.
+    occ: sized_occupancy(maps) -- the training passes then take rs_cnn_sized_forward_occ / _backward_occ, which skip the work of empty
+    units (the same a2 bit for bit, the gradients to float32 summation order); an inference forward ignores it."""
 
     @staticmethod
-    def forward(ctx, maps, cells, pcells, agent, w1, b1, w2, b2, grad_mode=True):
+    def forward(ctx, maps, cells, pcells, agent, w1, b1, w2, b2, grad_mode=True, occ=None):
         lib = _lib.load()
         S, M = maps.shape[0], maps.shape[-1]
         assert maps.dtype == torch.float32 and maps.is_contiguous() and maps.shape[1:] == (4, M, M)
@@ -226,13 +228,22 @@ class SizedConvTrunk(torch.autograd.Function):
         mask = torch.empty(S, P * P, dtype=torch.int16, device=maps.device) if train else None
         stream = torch.cuda.current_stream(maps.device).cuda_stream
         ptr = lambda t: None if t is None else t.data_ptr()
-        with _lib.timed("rs_cnn_sized_forward_train" if train else "rs_cnn_sized_forward"):
-            _lib.check(lib.rs_cnn_sized_forward(maps.data_ptr(), ptr(cells) if agent >= 0 else None, ptr(pcells) if agent >= 0 else None, A,
-                                                agent, S, M, w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), a2.data_ptr(),
-                                                ptr(p1), ptr(amax), ptr(mask), stream), "rs_cnn_sized_forward")
+        if occ is not None:
+            assert occ.dtype == torch.uint8 and occ.is_contiguous() and occ.shape == (S, lib.rs_cnn_sized_tiles(M)), (occ.dtype, occ.shape)
+        if occ is not None and train:
+            with _lib.timed("rs_cnn_sized_forward_occ"):
+                _lib.check(lib.rs_cnn_sized_forward_occ(maps.data_ptr(), ptr(cells) if agent >= 0 else None,
+                                                        ptr(pcells) if agent >= 0 else None, A, agent, S, M, w1c.data_ptr(), b1c.data_ptr(),
+                                                        w2c.data_ptr(), b2c.data_ptr(), a2.data_ptr(), ptr(p1), ptr(amax), ptr(mask),
+                                                        occ.data_ptr(), stream), "rs_cnn_sized_forward_occ")
+        else:
+            with _lib.timed("rs_cnn_sized_forward_train" if train else "rs_cnn_sized_forward"):
+                _lib.check(lib.rs_cnn_sized_forward(maps.data_ptr(), ptr(cells) if agent >= 0 else None, ptr(pcells) if agent >= 0 else None,
+                                                    A, agent, S, M, w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(),
+                                                    a2.data_ptr(), ptr(p1), ptr(amax), ptr(mask), stream), "rs_cnn_sized_forward")
         if train:
             ctx.save_for_backward(maps, cells if agent >= 0 else maps, pcells if agent >= 0 else maps, w2c, mask, p1, amax)
-            ctx.agent, ctx.A, ctx.cin = agent, A, (6 if agent >= 0 else 4)
+            ctx.agent, ctx.A, ctx.cin, ctx.occ = agent, A, (6 if agent >= 0 else 4), occ
         return a2
 
     @staticmethod
@@ -244,15 +255,38 @@ class SizedConvTrunk(torch.autograd.Function):
         rows, row = lib.rs_cnn_sized_slab_rows(S, M, cin), lib.rs_cnn_sized_slab_row(cin)
         slab = torch.empty(rows, row, dtype=torch.float32, device=maps.device)
         stream = torch.cuda.current_stream(maps.device).cuda_stream
-        with _lib.timed("rs_cnn_sized_backward"):
-            _lib.check(lib.rs_cnn_sized_backward(maps.data_ptr(), cells.data_ptr() if agent >= 0 else None,
-                                                 pcells.data_ptr() if agent >= 0 else None, ctx.A, agent, S, M, w2c.data_ptr(),
-                                                 da2.data_ptr(), mask.data_ptr(), p1.data_ptr(), amax.data_ptr(), slab.data_ptr(), rows,
-                                                 stream), "rs_cnn_sized_backward")
+        if ctx.occ is not None:
+            with _lib.timed("rs_cnn_sized_backward_occ"):
+                _lib.check(lib.rs_cnn_sized_backward_occ(maps.data_ptr(), cells.data_ptr() if agent >= 0 else None,
+                                                         pcells.data_ptr() if agent >= 0 else None, ctx.A, agent, S, M, w2c.data_ptr(),
+                                                         da2.data_ptr(), mask.data_ptr(), p1.data_ptr(), amax.data_ptr(), slab.data_ptr(), rows,
+                                                         ctx.occ.data_ptr(), stream), "rs_cnn_sized_backward_occ")
+        else:
+            with _lib.timed("rs_cnn_sized_backward"):
+                _lib.check(lib.rs_cnn_sized_backward(maps.data_ptr(), cells.data_ptr() if agent >= 0 else None,
+                                                     pcells.data_ptr() if agent >= 0 else None, ctx.A, agent, S, M, w2c.data_ptr(),
+                                                     da2.data_ptr(), mask.data_ptr(), p1.data_ptr(), amax.data_ptr(), slab.data_ptr(), rows,
+                                                     stream), "rs_cnn_sized_backward")
         g = slab.sum(dim=0)
         n1 = 8 * cin * 9
         return (None, None, None, None, g[:n1].view(8, cin, 3, 3), g[n1:n1 + 8], g[n1 + 8:n1 + 8 + 1152].view(16, 8, 3, 3),
-                g[n1 + 8 + 1152:], None)
+                g[n1 + 8 + 1152:], None, None)
+
+
+def sized_occupancy(maps: torch.Tensor) -> torch.Tensor:
+    """uint8 [S, tiles] for square maps [S, 4, M, M]: bit 0 = the unit's forward window holds an element != 0 (rs_cnn_sized_occupancy).
+    The maps an update reads do not change over its iterations: once per update, then a slice per chunk (SizedConvTrunk's occ)."""
+    lib = _lib.load()
+    S, M = maps.shape[0], maps.shape[-1]
+    assert maps.dtype == torch.float32 and maps.is_contiguous() and maps.shape[1:] == (4, M, M)
+    tiles = lib.rs_cnn_sized_tiles(M)
+    if tiles == 0:
+        raise ValueError(f"the tiled CNN trunk takes map sides 8..256, got {M}")
+    flags = torch.empty(S, tiles, dtype=torch.uint8, device=maps.device)
+    with _lib.timed("rs_cnn_sized_occupancy"):
+        _lib.check(lib.rs_cnn_sized_occupancy(maps.data_ptr(), S, M, flags.data_ptr(), torch.cuda.current_stream(maps.device).cuda_stream),
+                   "rs_cnn_sized_occupancy")
+    return flags
 
 
 def sized_trunk_sample_bytes(side: int) -> int:
@@ -262,14 +296,15 @@ def sized_trunk_sample_bytes(side: int) -> int:
     return 2 * 4 * 16 * P * P + (32 + 8 + 2) * P * P + 4 * 4 * 32
 
 
-def _trunk(maps, cells, pcells, agent, conv1, conv2):
-    """The conv trunk on the resident maps: K9 / K10 at 27 x 27, the tiled kernels at any other square side."""
+def _trunk(maps, cells, pcells, agent, conv1, conv2, occ=None):
+    """The conv trunk on the resident maps: K9 / K10 at 27 x 27 (occ is ignored there), the tiled kernels at any other square side
+    (occ: sized_occupancy of these maps, or None for the dense passes)."""
     X, Y = maps.shape[-2:]
     if (X, Y) == (27, 27):
         return ConvTrunk.apply(maps, cells, pcells, agent, conv1.weight, conv1.bias, conv2.weight, conv2.bias, torch.is_grad_enabled())
     if X != Y:
         raise ValueError(f"the HIP CNN trunk takes square heat maps, got {X} x {Y}")
-    return SizedConvTrunk.apply(maps, cells, pcells, agent, conv1.weight, conv1.bias, conv2.weight, conv2.bias, torch.is_grad_enabled())
+    return SizedConvTrunk.apply(maps, cells, pcells, agent, conv1.weight, conv1.bias, conv2.weight, conv2.bias, torch.is_grad_enabled(), occ)
 
 
 class _LinearTall(torch.autograd.Function):
@@ -330,13 +365,14 @@ class CNNActor(nn.Module):
             x = layer(x)
         return x
 
-    def logits_from_maps(self, maps, cells, pcells, agent: int):
+    def logits_from_maps(self, maps, cells, pcells, agent: int, occ=None):
         """Owner `agent`'s logits for samples described by the resident shared maps [S,4,X,Y] + cell indices [S,A]:
         HIP trunk + the three Linear layers.  The trunk kernels K9 / K10 (ConvTrunk) hold one 27 x 27 image in LDS (the walls-enforced
         size every CLI of the reference trains with, main.py:311-316); any other square size -- 147 x 147 without enforced walls,
-        RADTEAM_core.py:1727-1738 -- takes the tiled kernels (SizedConvTrunk)."""
+        RADTEAM_core.py:1727-1738 -- takes the tiled kernels (SizedConvTrunk), with occ = sized_occupancy(maps) their occupancy-aware
+        training passes."""
         a = self.actor
-        x = _trunk(maps, cells, pcells, agent, a[0], a[3])
+        x = _trunk(maps, cells, pcells, agent, a[0], a[3], occ)
         for layer in list(a)[6:-1]:
             x = _head(layer, x)
         return x
@@ -360,10 +396,10 @@ class CNNCritic(nn.Module):
         """Dense [B,4,X,Y] input through the nn.Sequential (library convolutions): the plain-PyTorch reference."""
         return self.critic(x).squeeze(-1)
 
-    def value_from_maps(self, maps):
+    def value_from_maps(self, maps, occ=None):
         """V for samples given as resident shared maps [S,4,X,Y]: HIP trunk + the Linear layers (see CNNActor.logits_from_maps)."""
         c = self.critic
-        x = _trunk(maps, None, None, -1, c[0], c[3])
+        x = _trunk(maps, None, None, -1, c[0], c[3], occ)
         for layer in list(c)[6:]:
             x = _head(layer, x)
         return x.squeeze(-1)

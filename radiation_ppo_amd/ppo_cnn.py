@@ -21,7 +21,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .envs import RadSearchVec
-from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from, cnn_conv_params, cnn_head_params, cnn_trunk_prepare, sized_trunk_sample_bytes
+from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from, cnn_conv_params, cnn_head_params, cnn_trunk_prepare, sized_occupancy, sized_trunk_sample_bytes
 from .pfgru import PredictorBank, hash_bits, hash_uniform
 from .ppo import (EpochStats, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
                   reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
@@ -267,6 +267,9 @@ class CNNCollector:
         self._act8 = torch.empty(self.N, self.A, dtype=torch.int8, device=dev)
         self.complete_len = torch.zeros(self.N, dtype=torch.int64, device=dev)
         self.epoch = 0                                  # updates done: keys the minibatch draws (and travels with resume.pt)
+        # update(): the tiled trunk's occupancy-aware training passes (square maps of a side other than 27, on the GPU); False selects the
+        # dense passes, for A/B runs
+        self.use_occupancy = True
         # one lock-step of the loop is ~60 small launches (maps, 5 trunk + head evaluations, sampling, env step, bootstrap
         # round, resets): launch bound.  The step is therefore captured ONCE into a HIP graph and replayed T - 1 times per
         # epoch (the epoch's last step, which raises epoch_end, runs eagerly).  Everything a step reads or writes lives at a
@@ -721,11 +724,20 @@ class CNNCollector:
         cells = self.cells.view(T * N, self.A)
         pcells = self.pcells.view(T * N, self.A)
         out = {}
+        # the tiled trunk's unit flags (maps.sized_occupancy): the stored maps stay as they are over every iteration of every agent, so
+        # one pass over them serves the whole update; the trunk's training passes then skip the work of the empty units
+        occ = None
+        if self.use_occupancy and X == Y and X != 27 and shared.is_cuda:
+            occ = sized_occupancy(shared)
         env_ids = int(self.env.cfg.env_id_base) + torch.arange(N, device=buf.rew.device, dtype=torch.int64)
         for a, ag in self.agents.items():
             adv = normalize_advantages(buf.adv[:, :, a]).reshape(-1)
-            actor_in = lambda lo, hi, a=a: (shared[lo:hi], cells[lo:hi], pcells[lo:hi], a)
-            critic_in = lambda lo, hi: (shared[lo:hi],)
+            if occ is None:
+                actor_in = lambda lo, hi, a=a: (shared[lo:hi], cells[lo:hi], pcells[lo:hi], a)
+                critic_in = lambda lo, hi: (shared[lo:hi],)
+            else:
+                actor_in = lambda lo, hi, a=a: (shared[lo:hi], cells[lo:hi], pcells[lo:hi], a, occ[lo:hi])
+                critic_in = lambda lo, hi: (shared[lo:hi], occ[lo:hi])
             upd_c = (not ag.global_critic) or a == 0
             w_for = None
             if ag.minibatch > 1:                                        # sample() (ppo.py:754-766): a fresh draw per actor iteration

@@ -352,9 +352,12 @@ int rs_maps_field(rs_maps* m, const char* name, void** dev_ptr, int32_t* elem_by
  *   pixel (0..3, row-major, first maximum) of each 2x2 pool window, relu_mask [S][169] uint16 bit c = (a2 channel c > 0).
  * Backward: da2 [S][2704] = dL/d(a2); slab [rs_cnn_trunk_slab_rows(S, Cin)][rs_cnn_trunk_slab_row(Cin)] receives
  * per-workgroup partial sums laid out {dW1 8*Cin*9 | db1 8 | dW2 1152 | db2 16}; the caller sums the rows.
- * wscratch: device scratch of rs_cnn_trunk_scratch_floats(Cin) floats (the weights re-laid-out for scalar loads). */
+ * wscratch: device scratch of rs_cnn_trunk_scratch_floats(Cin) floats (the weights re-laid-out for scalar loads).
+ * rs_cnn_trunk_forward_grid (host only, for tests): the workgroup count rs_cnn_trunk_forward launches for num_samples images, three
+ * images per workgroup round. */
 int32_t rs_cnn_trunk_slab_row(int32_t in_channels);
 int32_t rs_cnn_trunk_slab_rows(int64_t num_samples, int32_t in_channels);
+int32_t rs_cnn_trunk_forward_grid(int64_t num_samples, int32_t in_channels);
 int32_t rs_cnn_trunk_scratch_floats(int32_t in_channels);
 int rs_cnn_trunk_forward(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,
                          int64_t num_samples, const float* w1, const float* b1, const float* w2, const float* b2, float* a2,

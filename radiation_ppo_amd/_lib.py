@@ -139,6 +139,7 @@ SYMBOLS = [
                                 C.POINTER(C.c_int32)]),
     ("rs_cnn_trunk_slab_row", C.c_int32, [C.c_int32]),
     ("rs_cnn_trunk_slab_rows", C.c_int32, [C.c_int64, C.c_int32]),
+    ("rs_cnn_trunk_forward_grid", C.c_int32, [C.c_int64, C.c_int32]),
     ("rs_cnn_trunk_scratch_floats", C.c_int32, [C.c_int32]),
     ("rs_cnn_trunk_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -848,6 +848,11 @@ int32_t rs_cnn_trunk_slab_rows(int64_t num_samples, int32_t in_channels) {
     return in_channels == 6 ? cnn_grid(rs_cnn_bwd_kernel<6>, CNN_NT_BWD, bwd_lds(6), num_samples) : cnn_grid(rs_cnn_bwd_kernel<4>, CNN_NT_BWD, bwd_lds(4), num_samples);
 }
 int32_t rs_cnn_trunk_scratch_floats(int32_t in_channels) { return WT_TOTAL(in_channels); }
+// host only: the workgroup count rs_cnn_trunk_forward passes to the launch (cnn_grid of the round count)
+int32_t rs_cnn_trunk_forward_grid(int64_t num_samples, int32_t in_channels) {
+    const long long rounds = (num_samples + FW_IMG - 1) / FW_IMG;
+    return in_channels == 6 ? cnn_grid(rs_cnn_fwd_kernel<6>, FW_NT, fwd_lds(6), rounds) : cnn_grid(rs_cnn_fwd_kernel<4>, FW_NT, fwd_lds(4), rounds);
+}
 
 int rs_cnn_trunk_forward(const float* maps, const int64_t* cells, const int64_t* pcells, int32_t num_agents, int32_t agent,
                          int64_t num_samples, const float* w1, const float* b1, const float* w2, const float* b2, float* a2,

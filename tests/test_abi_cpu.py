@@ -26,6 +26,7 @@ def _declared_symbols():
 def test_header_symbols_exported(lib):
     names = _declared_symbols()
     assert "rs_step" in names and "rs_reset" in names and "rs_gae" in names and "rs_create" in names
+    assert "rs_cnn_trunk_forward_grid" in names and "rs_cnn_trunk_slab_rows" in names        # the host-only grid queries of the CNN trunk
     for n in names:
         assert hasattr(lib, n), f"librs_hip.so does not export {n}"
 

@@ -305,6 +305,21 @@ class RolloutBuffer:
         self.adv = torch.zeros(T, N, A, **f)
         self.ret = torch.zeros(T, N, A, **f)
 
+    def row_args(self, t, k_act, k_f, x, src_x, src_y, rew, cut, boot) -> tuple:
+        """rs_store_rows' arguments before the stream; a caller whose rows keep their addresses computes them once."""
+        p = lambda v: v.data_ptr()
+        return (p(t), p(k_act), p(k_f), p(x), p(src_x), p(src_y), p(rew), p(cut), p(boot), p(self.act), p(self.logp), p(self.val),
+                p(self.last_val), p(self.obs), p(self.source_tar), p(self.rew), p(self.cut), self.N, self.A, self.T)
+
+    def store_rows(self, t, k_act, k_f, x, src_x, src_y, rew, cut, boot, stream) -> None:
+        """PPOBuffer.store for one lock-step in one launch (rs_store_rows): row t[0] <- the actions k_act [A, N], logp / value /
+        bootstrap value k_f [A, 3, N], the policy input x [N, A, 11], the source position src_x / src_y [N] int32, the reward rew [N, A]
+        and the flags cut / boot [N] u8 (last_val is the bootstrap value where boot, else 0)."""
+        self.store_row_args(self.row_args(t, k_act, k_f, x, src_x, src_y, rew, cut, boot), stream)
+
+    def store_row_args(self, args: tuple, stream) -> None:
+        _lib.check(_lib.load().rs_store_rows(*args, stream), "rs_store_rows")
+
     def finish(self, gamma: float, lam: float) -> None:
         """GAE_advantage_and_rewardsToGO for every trajectory slice of the buffer in one kernel (rs_gae)."""
         rs_gae_call(self.rew, self.val, self.cut, self.last_val, gamma, lam, adv=self.adv, ret=self.ret)
@@ -655,6 +670,117 @@ def _welford_load(w: "DeviceWelford", st) -> None:
     w.count.copy_(st["count"]); w.mean.copy_(st["mean"]); w.sq.copy_(st["sq"]); w.std.copy_(st["std"])
 
 
+class CollectGlue:
+    """The lock-step glue between the policy launches of TeamCollector, RNNCollector and CNNCollector (rs_collect_* over one
+    rs_collect_state, rs_store_rows, rs_epoch_stats, the env's reset beside the bootstrap round) and, at fixed addresses, what only it
+    touches: the flags, the reward in use, the copies of the env's rows, the policy round's k_act [A, N] and k_f [A, 3, N] (logp, value,
+    bootstrap value), the EpochStats, the step counter t (the collector's own where it has one) and, with policy_input, the policy
+    inputs x / xb [N, A, 11].  stat, bank, episodes_begun, complete_len: the optional fields of rs_collect_state (include/radsearch.h).
+    Building it loads no library and touches no stream: the first launch does."""
+
+    def __init__(self, env, buf: "RolloutBuffer", obs: torch.Tensor, ep_ret: torch.Tensor, steps_in_ep: torch.Tensor, L: int, *,
+                 team_reward: bool = False, stat: Optional["DeviceWelford"] = None, policy_input: bool = True, bank=None,
+                 episodes_begun: Optional[torch.Tensor] = None, complete_len: Optional[torch.Tensor] = None,
+                 t: Optional[torch.Tensor] = None):
+        N, A = ep_ret.shape
+        dev = obs.device
+        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
+        self.env, self.buf, self.ep_ret, self.steps_in_ep, self.device = env, buf, ep_ret, steps_in_ep, dev
+        self.flags = z(3, N, dtype=torch.uint8)
+        self.over, self.cut, self.boot = self.flags[0], self.flags[1], self.flags[2]
+        self.rew_used = z(N, A, dtype=torch.float32)
+        self.done_oob = z(2, N, A, dtype=torch.uint8)
+        self.done, self.oob = self.done_oob[0], self.done_oob[1]
+        self.src_copy = z(2, N, dtype=torch.int32)
+        self.k_act = z(A, N, dtype=torch.int64)
+        self.k_f = z(A, 3, N, dtype=torch.float32)
+        self.t = z(1, dtype=torch.int64) if t is None else t
+        self.acc = EpochStats(A, dev)
+        self.x, self.xb = (z(N, A, _lib.RS_OBS_DIM, dtype=torch.float32) for _ in range(2)) if policy_input else (None, None)
+        p = lambda v: None if v is None else v.data_ptr()                   # an unnamed or None field is NULL
+        of = lambda o, name: None if o is None else getattr(o, name).data_ptr()
+        self.cs = _lib.RsCollectState(
+            num_envs=N, num_agents=A, steps_per_episode=L, team_reward=1 if team_reward else 0,
+            env_obs=p(env.obs), env_reward=p(env.reward), env_team=p(env.team), env_done=p(env.done),
+            obs=p(obs), ep_ret=p(ep_ret), steps_in_ep=p(steps_in_ep),
+            w_count=of(stat, "count"), w_mean=of(stat, "mean"), w_sq=of(stat, "sq"), w_std=of(stat, "std"), x=p(self.x), xb=p(self.xb),
+            reward_used=p(self.rew_used), over=p(self.over), cut=p(self.cut), boot=p(self.boot),
+            pf_episode=of(bank, "episode"), pf_calls=of(bank, "calls"), episodes_begun=p(episodes_begun), t=p(self.t),
+            env_oob=p(env.oob), env_src_x=p(env.state("src_x")), env_src_y=p(env.state("src_y")),
+            done_copy=p(self.done), oob_copy=p(self.oob), src_copy=p(self.src_copy), complete_len=p(complete_len))
+        # what every launch passes, computed once: TeamCollector's eager loop is bound by host issue
+        self._cs = C.byref(self.cs)
+        self._over = self.over.view(torch.bool)
+        self._own_rows = None if self.x is None else self._rows(self.x)
+
+    def _rows(self, x: torch.Tensor) -> tuple:
+        return self.buf.row_args(self.t, self.k_act, self.k_f, x, self.src_copy[0], self.src_copy[1], self.rew_used, self.cut, self.boot)
+
+    def stream(self) -> "C.c_void_p":
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    # the launches take the stream to launch on (stream(); TeamCollector reads it once per epoch)
+    def pre(self, st) -> None:
+        """x <- obs, the reading standardised (train.py:334-341)."""
+        _lib.check(_lib.load().rs_collect_pre(self._cs, st), "rs_collect_pre")
+
+    def post_step(self, epoch_ended: bool, st) -> None:
+        """After the env's step: returns, counters, flags, Welford update, obs / xb and the copies of the env's rows (train.py:366-487)."""
+        _lib.check(_lib.load().rs_collect_post_step(self._cs, 1 if epoch_ended else 0, st), "rs_collect_post_step")
+
+    def post_reset(self, reset_hidden: bool, st) -> None:
+        """After the env's reset: the cut envs start over, with reset_hidden their draw counters advance; t += 1 (train.py:504-548)."""
+        _lib.check(_lib.load().rs_collect_post_reset(self._cs, 1 if reset_hidden else 0, st), "rs_collect_post_reset")
+
+    def store_rows(self, st, x: Optional[torch.Tensor] = None) -> None:
+        """RolloutBuffer.store_rows of post_step's copies and k_act / k_f; x: the step's policy input where it is not the glue's own."""
+        self.buf.store_row_args(self._own_rows if x is None else self._rows(x), st)
+
+    def stats(self) -> None:
+        """EpochStats.step_and_episodes of the lock-step, on post_step's copies."""
+        self.acc.step_and_episodes(self.oob, self.done, self.ep_ret, self.steps_in_ep, self._over)
+
+    # The env's reset is latency bound (one env's spawn is a 15 k-instruction chain on four lanes; ~50-110 us) and rewrites the env's
+    # reward / done / out-of-bounds rows and the sources of the cut envs.  Between reset_on_side() and join_reset() it runs on the side
+    # stream beside the bootstrap round, the buffer rows and the statistics, and what is launched between the two reads post_step's
+    # COPIES (rew_used, done, oob, src_copy, obs / xb), never the env's own rows.
+    def reset_on_side(self, epoch_ended: bool) -> None:
+        side = side_stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            if epoch_ended:
+                self.env.set_epoch_end()                                     # train.py:482-484
+            self.env.reset(self.cut)                                         # train.py:530
+
+    def join_reset(self) -> None:
+        """Before post_reset, which reads the reset's observation rows."""
+        torch.cuda.current_stream(self.device).wait_stream(side_stream(self.device))
+
+
+def collect_epoch(col, warm_up) -> None:
+    """The T lock-steps of an epoch for a collector whose _step keeps all state in place (RNNCollector, CNNCollector): _step(False),
+    dozens of small launches, is captured ONCE into a HIP graph (col._graph) and replayed T - 1 times; the last step, which raises
+    epoch_end, runs eagerly, as every step does without col.use_graph.  warm_up() runs on the side stream before the capture: what a
+    library initialises lazily (GEMM handles, workspaces) must not fall into it."""
+    dev, T = col.env.device, col.T
+    if col.use_graph and col._graph is None and T > 1:
+        side = side_stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            warm_up()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        col._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(col._graph):
+            col._step(False)
+    for _ in range(T - 1):
+        if col._graph is not None:
+            col._graph.replay()
+        else:
+            col._step(False)
+    col._step(True)
+
+
 class Collector:
     """The epoch loop body of train_PPO.train (train.py:332-548) for N envs at once: policy forward,
     Philox inverse-CDF sampling, env lock-step, buffer write, episode/epoch cut logic, bootstrap values,
@@ -846,8 +972,8 @@ class FusedCollector:
 
 class TeamCollector:
     """Same contract as Collector for a feed-forward team on the GPU, the lock-step in HIP: ONE policy launch for all agents
-    (rs_ff_team_step: every agent's own actor and critic on its own rows, the draw, rs_step's action rows) between the glue launches
-    RNNCollector._step_glued uses (rs_collect_pre / _post_step / _post_reset, rs_store_rows, rs_epoch_stats).  Ten launches per
+    (rs_ff_team_step: every agent's own actor and critic on its own rows, the draw, rs_step's action rows) between CollectGlue's
+    launches (rs_collect_pre / _post_step / _post_reset, rs_store_rows, rs_epoch_stats), as in RNNCollector._step_glued.  Ten launches per
     lock-step, eleven at the epoch's last, on one stream, where Collector composes several dozen library ops per agent:
     pre, uniforms, policy (step round), env step, post_step, policy (bootstrap round on the envs that need a value), store_rows,
     epoch_stats, (epoch end) env reset, post_reset.  Every tensor keeps its address: the glue's argument block holds them."""
@@ -869,29 +995,10 @@ class TeamCollector:
         self.obs = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)
         self._u = torch.empty(N, A, dtype=torch.float32, device=dev)
         self._act8 = torch.zeros(N, A, dtype=torch.int8, device=dev)
-        self._x = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)
-        self._xb = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)
-        self._flags = torch.zeros(3, N, dtype=torch.uint8, device=dev)                      # over, cut, boot
-        self._rew_used = torch.zeros(N, A, dtype=torch.float32, device=dev)
-        self._done_oob = torch.zeros(2, N, A, dtype=torch.uint8, device=dev)                # copies of the env's done / out_of_bounds rows
-        self._src_copy = torch.zeros(2, N, dtype=torch.int32, device=dev)
-        self._t = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._acc = EpochStats(A, dev)
-        self._k_act = torch.zeros(A, N, dtype=torch.int64, device=dev)
-        self._k_f = torch.zeros(A, 3, N, dtype=torch.float32, device=dev)                   # logp, value, bootstrap value
-        p = lambda t: t.data_ptr()
-        st = self.stat
-        w = [p(st.count), p(st.mean), p(st.sq), p(st.std)] if standardize else [None] * 4
-        # no PFGRU, no GRU: pf_episode / pf_calls / episodes_begun stay NULL
-        self._cs = _lib.RsCollectState(N, A, self.L, 1 if self.team_reward else 0, p(env.obs), p(env.reward), p(env.team), p(env.done), p(self.obs),
-                                       p(self.ep_ret), p(self.steps_in_ep), *w, p(self._x), p(self._xb), p(self._rew_used), p(self._flags[0]),
-                                       p(self._flags[1]), p(self._flags[2]), None, None, None, p(self._t), p(env.oob), p(env.state("src_x")),
-                                       p(env.state("src_y")), p(self._done_oob[0]), p(self._done_oob[1]), p(self._src_copy), None)
-        b = self.buf
-        self._store_args = (p(self._t), p(self._k_act), p(self._k_f), p(self._x), p(self._src_copy[0]), p(self._src_copy[1]), p(self._rew_used),
-                            p(self._flags[1]), p(self._flags[2]), p(b.act), p(b.logp), p(b.val), p(b.last_val), p(b.obs), p(b.source_tar),
-                            p(b.rew), p(b.cut), N, A, self.T)
-        self._over = self._flags[0].view(torch.bool)
+        # no PFGRU, no GRU: the glue's pf_episode / pf_calls / episodes_begun stay NULL
+        self._cg = CollectGlue(env, self.buf, self.obs, self.ep_ret, self.steps_in_ep, self.L, team_reward=self.team_reward,
+                               stat=self.stat if standardize else None)
+        self._t = self._cg.t
         self.started = False
 
     def start(self) -> None:
@@ -908,36 +1015,35 @@ class TeamCollector:
                 arr(*[mlp_params(self.agents[a].agent.critic) for a in range(self.A)]))
 
     def _step(self, nets, epoch_ended: bool, st) -> None:
-        lib, env, cs, N, A = self.lib, self.env, C.byref(self._cs), self.N, self.A
+        lib, env, g, N, A = self.lib, self.env, self._cg, self.N, self.A
         pa, pc = nets
-        cut, boot = self._flags[1], self._flags[2]
-        _lib.check(lib.rs_collect_pre(cs, st), "rs_collect_pre")                                # train.py:334-341
+        g.pre(st)                                                                               # train.py:334-341
         env.action_uniforms(self._u)
-        _lib.check(lib.rs_ff_team_step(pa, pc, A, self._x.data_ptr(), self._u.data_ptr(), self._k_act.data_ptr(), self._k_f.data_ptr(),
+        _lib.check(lib.rs_ff_team_step(pa, pc, A, g.x.data_ptr(), self._u.data_ptr(), g.k_act.data_ptr(), g.k_f.data_ptr(),
                                        self._act8.data_ptr(), None, N, st), "rs_ff_team_step")  # train.py:345-357
         env.step(self._act8)
-        _lib.check(lib.rs_collect_post_step(cs, 1 if epoch_ended else 0, st), "rs_collect_post_step")
-        _lib.check(lib.rs_ff_team_step(pa, pc, A, self._xb.data_ptr(), None, None, self._k_f.data_ptr(), None, boot.data_ptr(), N, st),
+        g.post_step(epoch_ended, st)
+        _lib.check(lib.rs_ff_team_step(pa, pc, A, g.xb.data_ptr(), None, None, g.k_f.data_ptr(), None, g.boot.data_ptr(), N, st),
                    "rs_ff_team_step")                                                           # train.py:462-487: the bootstrap value
-        _lib.check(lib.rs_store_rows(*self._store_args, st), "rs_store_rows")
-        self._acc.step_and_episodes(self._done_oob[1], self._done_oob[0], self.ep_ret, self.steps_in_ep, self._over)
-        if epoch_ended:
+        g.store_rows(st)
+        g.stats()
+        if epoch_ended:                                                                         # the reset: on the main stream here
             env.set_epoch_end()                                                                 # train.py:482-484
-        env.reset(cut)                                                                          # train.py:530
-        _lib.check(lib.rs_collect_post_reset(cs, 0, st), "rs_collect_post_reset")
+        env.reset(g.cut)                                                                        # train.py:530
+        g.post_reset(False, st)
 
     @torch.no_grad()
     def collect(self) -> Dict[str, torch.Tensor]:
         if not self.started:
             self.start()
-        self._acc.zero_()
+        self._cg.acc.zero_()
         self._t.zero_()
         nets = self._nets()
-        st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        st = self._cg.stream()
         for t in range(self.T):
             self._step(nets, t == self.T - 1, st)
         self.buf.finish(self.agents[0].gamma, self.agents[0].lam)
-        return self._acc.result()
+        return self._cg.acc.result()
 
     def update(self) -> Dict[int, UpdateResult]:
         return ppo_update_from_buffer(self)

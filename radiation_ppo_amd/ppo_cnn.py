@@ -23,8 +23,8 @@ from . import _lib
 from .envs import RadSearchVec
 from .maps import CNNActor, CNNCritic, HeatMaps, actor_stack_from, cnn_conv_params, cnn_head_params, cnn_trunk_prepare, sized_occupancy, sized_trunk_sample_bytes
 from .pfgru import PredictorBank, hash_bits, hash_uniform
-from .ppo import (EpochStats, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
-                  reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
+from .ppo import (CollectGlue, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
+                  collect_epoch, reduce_grads_and_stats, reject_unknown_kwargs)
 
 
 def minibatch_weights(complete_len: torch.Tensor, T: int, minibatch: int, key: torch.Tensor, n_total: int) -> torch.Tensor:
@@ -276,12 +276,18 @@ class CNNCollector:
         # fixed address: state is updated in place, the buffer row is addressed by a device-side step counter.
         self.use_graph = use_graph
         self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self._t = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._acc = EpochStats(self.A, dev)
+        self._t = torch.zeros(1, dtype=torch.int64, device=dev)                            # the buffer row a lock-step writes
         self._row_act = torch.zeros(self.N, self.A, dtype=torch.int64, device=dev)
         self._row_f = torch.zeros(3, self.N, self.A, dtype=torch.float32, device=dev)      # logp, val, last_val of the step
         self.obs = None
-        self._cs = None                                 # rs_collect_state: the lock-step's bookkeeping kernels (see _glue_state)
+        self._cg: Optional[CollectGlue] = None          # built by start(), over the first observation
+        # A/B switches, settable before the first collect(); False selects the form the bit-identity tests compare against.  glue:
+        # _step_glued in place of _step's torch composition; heads (with glue): use_heads; team_round / sized_team_round (with heads):
+        # use_team_round / use_sized_team_round in place of the per-agent round
+        self.glue = True
+        self.heads = True
+        self.team_round = True
+        self.sized_team_round = True
         # CNNBase.model (RADTEAM_core.py:1790-1795): one PFGRU cell per owner, all envs at once
         self.predictor: Optional[PredictorBank] = None
         if use_predictor:
@@ -293,6 +299,10 @@ class CNNCollector:
     def start(self) -> None:
         obs, *_ = self.env.reset()
         self.obs = obs.clone()                                      # from here on updated in place (fixed address)
+        # the lock-step glue (returns, counters, cut flags, observation copies and draw counters in two launches instead of ~27); no
+        # statistics, no policy input: the networks read heat maps.  The torch composition uses its statistics too
+        self._cg = CollectGlue(self.env, self.buf, self.obs, self.ep_ret, self.steps_in_ep, self.L, team_reward=self.team_reward,
+                               policy_input=False, bank=self.predictor, complete_len=self.complete_len, t=self._t)
         if self.predictor is not None:
             self.predictor.reset()                                  # ac.reset_hidden() (test_cnn/train.py:686)
 
@@ -302,24 +312,6 @@ class CNNCollector:
     @property
     def use_glue(self) -> bool:
         return self.env.device.type == "cuda" and (self.predictor is None or self.predictor.impl == "hip")
-
-    def _glue_state(self) -> "_lib.RsCollectState":
-        """rs_collect_state over the collector's buffers (rs_collect_post_step / _post_reset: the lock-step's returns, counters, cut
-        flags, observation copies and draw counters in two launches instead of ~27 element-wise ones)."""
-        if self._cs is None:
-            env, dev, N, A = self.env, self.env.device, self.N, self.A
-            self._flags = torch.zeros(3, N, dtype=torch.uint8, device=dev)                  # over, cut, boot
-            self._rew_used = torch.zeros(N, A, dtype=torch.float32, device=dev)
-            self._done_oob = torch.zeros(2, N, A, dtype=torch.uint8, device=dev)            # copies of the env's done / out_of_bounds rows
-            self._src_copy = torch.zeros(2, N, dtype=torch.int32, device=dev)
-            p = lambda t: None if t is None else t.data_ptr()
-            pf = self.predictor
-            self._cs = _lib.RsCollectState(N, A, self.L, 1 if self.team_reward else 0, p(env.obs), p(env.reward), p(env.team), p(env.done),
-                                           p(self.obs), p(self.ep_ret), p(self.steps_in_ep), None, None, None, None, None, None, p(self._rew_used),
-                                           p(self._flags[0]), p(self._flags[1]), p(self._flags[2]), p(pf.episode if pf else None),
-                                           p(pf.calls if pf else None), None, p(self._t), p(env.oob), p(env.state("src_x")), p(env.state("src_y")),
-                                           p(self._done_oob[0]), p(self._done_oob[1]), p(self._src_copy), p(self.complete_len))
-        return self._cs
 
     @torch.no_grad()
     def _round_glued(self, mask8: Optional[torch.Tensor] = None, cells: bool = True):
@@ -336,7 +328,7 @@ class CNNCollector:
     def use_heads(self) -> bool:
         """The select_action round of every agent as trunk (one launch) + BLAS Linear(16 P P, 32) + rs_cnn_head, buffer rows by
         rs_store_rows; any map size (K9 at 27 x 27, the tiled trunk elsewhere)."""
-        return self.use_glue and getattr(self, "heads", True)
+        return self.use_glue and self.heads
 
     @property
     def use_team_round(self) -> bool:
@@ -344,7 +336,7 @@ class CNNCollector:
         agent): rs_cnn_team_trunk_infer, the critic trunk(s), rs_cnn_team_step_head; the bootstrap round in two.  `team_round = False`
         selects the per-agent round (the A/B form); on by default for every team size, one agent included: it measured faster
         for 1, 2, 4 and 8 agents in both critic modes (profiles/cnn_team_collect_timing.txt)."""
-        if not (self.use_heads and getattr(self, "team_round", True)):
+        if not (self.use_heads and self.team_round):
             return False
         if tuple(self.maps.map_dimensions) != (27, 27) or sorted(self.agents) != list(range(self.A)):
             return False
@@ -362,7 +354,7 @@ class CNNCollector:
         k across workgroups; the bootstrap round is the critic trunk(s) and the head.  `sized_team_round = False` selects the per-agent
         round (the A/B form).  The a2 rows [A + C][N][16 P P] and the head's scratch must fit SIZED_TEAM_BYTES; the measured epochs are
         in profiles/cnn_sized_team_collect_timing.txt."""
-        if not (self.use_heads and getattr(self, "sized_team_round", True)):
+        if not (self.use_heads and self.sized_team_round):
             return False
         X, Y = self.maps.map_dimensions
         if X != Y or (X, Y) == (27, 27) or not 8 <= X <= 256 or sorted(self.agents) != list(range(self.A)):
@@ -389,8 +381,6 @@ class CNNCollector:
             self._wt_c = {a: self._wt_c_all[i] for i, a in enumerate(sorted(self.agents))}
             P = self.maps.map_dimensions[0] // 2
             self._a2 = torch.empty(N, 16 * P * P, dtype=torch.float32, device=dev)
-            self._k_act = torch.zeros(A, N, dtype=torch.int64, device=dev)
-            self._k_f = torch.zeros(A, 3, N, dtype=torch.float32, device=dev)                   # logp, value, bootstrap value
             self._x_buf = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)   # the step's observation (buffer row)
         if tuple(self.maps.map_dimensions) != (27, 27):
             if self.use_sized_team_round:
@@ -424,10 +414,10 @@ class CNNCollector:
             self._hp_cri = (_lib.RsCnnHeadParams * nc)(*[cnn_head_params(ag.critic.critic) for ag in ags[:nc]])
 
     def _team_round(self, maps, mask8=None) -> None:
-        """The step round (mask8 None: every agent's action, log-probability and value into self._k_act / _k_f[:, 0] / _k_f[:, 1] /
-        self._act8) or the bootstrap round (the values of the envs in mask8 into self._k_f[:, 2]) in three / two launches."""
-        lib, N, A = _lib.load(), self.N, self.A
-        st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        """The step round (mask8 None: every agent's action, log-probability and value into the glue's k_act / k_f[:, 0] / k_f[:, 1] /
+        self._act8) or the bootstrap round (the values of the envs in mask8 into k_f[:, 2]) in three / two launches."""
+        lib, g, N, A = _lib.load(), self._cg, self.N, self.A
+        st = g.stream()
         p = lambda t: t.data_ptr()
         step = mask8 is None
         nc = self._a2_cri.shape[0]
@@ -439,15 +429,15 @@ class CNNCollector:
         else:
             _lib.check(lib.rs_cnn_team_critic_trunk_infer(p(maps), nc, N, p(self._wt_c_all), p(self._a2_cri), st),
                        "rs_cnn_team_critic_trunk_infer")
-        o = (p(self._u), p(self._k_act), p(self._k_f), p(self._act8), None) if step else (None, None, p(self._k_f), None, p(mask8))
+        o = (p(self._u), p(g.k_act), p(g.k_f), p(self._act8), None) if step else (None, None, p(g.k_f), None, p(mask8))
         _lib.check(lib.rs_cnn_team_step_head(self._hp_act, A, self._hp_cri, nc, p(self._a2_act), p(self._a2_cri), *o, None, N, st),
                    "rs_cnn_team_step_head")
 
     def _sized_team_round(self, maps, mask8=None) -> None:
         """_team_round on maps of any side (use_sized_team_round): the actors' tiled trunks in one launch, the critic trunk(s) in one,
         the k-split first layer and the heads in two; the bootstrap round without the first of them."""
-        lib, N, A = _lib.load(), self.N, self.A
-        st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        lib, g, N, A = _lib.load(), self._cg, self.N, self.A
+        st = g.stream()
         p = lambda t: t.data_ptr()
         step = mask8 is None
         nc, flat, M = self._sz_a2_cri.shape[0], self._sz_a2_cri.shape[2], self.maps.map_dimensions[0]
@@ -461,12 +451,12 @@ class CNNCollector:
         else:
             _lib.check(lib.rs_cnn_sized_team_critic_infer(p(maps), nc, N, M, self._cv_cri, p(self._sz_a2_cri), st),
                        "rs_cnn_sized_team_critic_infer")
-        o = (p(self._u), p(self._k_act), p(self._k_f), p(self._act8), None) if step else (None, None, p(self._k_f), None, p(mask8))
+        o = (p(self._u), p(g.k_act), p(g.k_f), p(self._act8), None) if step else (None, None, p(g.k_f), None, p(mask8))
         _lib.check(lib.rs_cnn_sized_team_step_head(self._hp_act, A, self._hp_cri, nc, flat, p(self._sz_a2_act), p(self._sz_a2_cri), *o, None,
                                                    p(self._sz_scratch), self._sz_scratch.numel(), N, st), "rs_cnn_sized_team_step_head")
 
     def _values_fused(self, critic_maps, slot: int, mask8=None) -> None:
-        """V(s) of every env into self._k_f[:, slot] (slot 1: the step's value, 2: the bootstrap value): one evaluation serves every
+        """V(s) of every env into the glue's k_f[:, slot] (slot 1: the step's value, 2: the bootstrap value): one evaluation serves every
         owner of a global critic (train.py:191-206)."""
         lib, N, A = _lib.load(), self.N, self.A
         st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
@@ -479,7 +469,7 @@ class CNNCollector:
             y1 = torch.nn.functional.linear(self._a2, c[6].weight, c[6].bias)
             copies = A if ag.global_critic else 1
             _lib.check(lib.rs_cnn_head(y1.data_ptr(), c[8].weight.data_ptr(), c[8].bias.data_ptr(), c[10].weight.data_ptr(), c[10].bias.data_ptr(), 1,
-                                       None, 1, None, None, None, 1, self._k_f[0 if ag.global_critic else a, slot].data_ptr(), copies, 3 * N,
+                                       None, 1, None, None, None, 1, self._cg.k_f[0 if ag.global_critic else a, slot].data_ptr(), copies, 3 * N,
                                        None if mask8 is None else mask8.data_ptr(), N, st), "rs_cnn_head")
 
     def _trunk_infer(self, maps, cells, pcells, agent: int, seq, wt, st) -> None:
@@ -504,10 +494,9 @@ class CNNCollector:
         torch composition took ~110; with use_team_round the policy round is three launches and the bootstrap round two (_team_round), with
         use_sized_team_round (any other map side) four and three (_sized_team_round)."""
         env, buf, N, A = self.env, self.buf, self.N, self.A
-        acc, ti = self._acc, self._t
-        lib, cs = _lib.load(), self._glue_state()
-        st = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
-        over, cut, boot = self._flags[0], self._flags[1], self._flags[2]
+        lib, g = _lib.load(), self._cg
+        st = g.stream()
+        ti, cut, boot = g.t, g.cut, g.boot
         put = lambda dst, row: dst.index_copy_(0, ti, row.unsqueeze(0))
         heads, sized = self.use_heads, self.use_sized_team_round
         team = self.use_team_round or sized
@@ -525,7 +514,7 @@ class CNNCollector:
                 self._trunk_infer(critic, cells, pcells, a, m, self._wt[a], st)
                 y1 = torch.nn.functional.linear(self._a2, m[6].weight, m[6].bias)
                 _lib.check(lib.rs_cnn_head(y1.data_ptr(), m[8].weight.data_ptr(), m[8].bias.data_ptr(), m[10].weight.data_ptr(), m[10].bias.data_ptr(), 8,
-                                           self._u.data_ptr() + 4 * a, A, self._k_act[a].data_ptr(), self._k_f[a, 0].data_ptr(),
+                                           self._u.data_ptr() + 4 * a, A, g.k_act[a].data_ptr(), g.k_f[a, 0].data_ptr(),
                                            self._act8.data_ptr() + a, A, None, 1, 0, None, N, st), "rs_cnn_head")
             self._values_fused(critic, 1)
         else:
@@ -541,31 +530,20 @@ class CNNCollector:
             put(buf.act, self._row_act); put(buf.logp, self._row_f[0]); put(buf.val, self._row_f[1])
             put(buf.obs, self.obs)
         env.step(self._act8)
-        _lib.check(lib.rs_collect_post_step(C.byref(cs), 1 if epoch_ended else 0, st), "rs_collect_post_step")
-        done, oob_now = self._done_oob[0], self._done_oob[1]           # post_step's copies: the env's own rows are rewritten by the reset
+        g.post_step(epoch_ended, st)
         # bootstrap: ac.step(observations) once more for the envs that time out / are cut (train.py:462-480)
         critic_b, _, _ = self._round_glued(mask8=boot, cells=not team)
-        # the heat maps have seen the agents' last positions: from here the env's reset (latency bound, ~110 us) runs on the side stream
-        # beside the critic's bootstrap evaluation, the buffer rows and the statistics (which read post_step's copies)
-        main = torch.cuda.current_stream(env.device)
-        side = side_stream(env.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            if epoch_ended:
-                env.set_epoch_end()
-            env.reset(cut)
+        # the heat maps have seen the agents' last positions: from here the env's reset runs beside the critic's bootstrap evaluation,
+        # the buffer rows and the statistics, up to join_reset()
+        g.reset_on_side(epoch_ended)
         if heads:
             if team:
                 team_round(critic_b, mask8=boot)
             else:
                 self._values_fused(critic_b, 2, mask8=boot)
-            _lib.check(lib.rs_store_rows(ti.data_ptr(), self._k_act.data_ptr(), self._k_f.data_ptr(), self._x_buf.data_ptr(),
-                                         self._src_copy[0].data_ptr(), self._src_copy[1].data_ptr(), self._rew_used.data_ptr(), cut.data_ptr(),
-                                         boot.data_ptr(), buf.act.data_ptr(), buf.logp.data_ptr(), buf.val.data_ptr(), buf.last_val.data_ptr(),
-                                         buf.obs.data_ptr(), buf.source_tar.data_ptr(), buf.rew.data_ptr(), buf.cut.data_ptr(), N, A, self.T, st),
-                       "rs_store_rows")
+            g.store_rows(st, self._x_buf)
         else:
-            put(buf.rew, self._rew_used)
+            put(buf.rew, g.rew_used)
             put(buf.cut, cut.unsqueeze(1).expand(N, A).contiguous())
             bc = boot.view(torch.bool)
             vb = None
@@ -574,10 +552,10 @@ class CNNCollector:
                     vb = ag._values((critic_b,))
                 self._row_f[2, :, a] = torch.where(bc, vb, torch.zeros_like(vb))
             put(buf.last_val, self._row_f[2])
-        acc.step_and_episodes(oob_now, done, self.ep_ret, self.steps_in_ep, over.view(torch.bool))
+        g.stats()
         self.maps.reset(cut)                                             # ac.reset_agent() (train.py:537-540)
-        main.wait_stream(side)
-        _lib.check(lib.rs_collect_post_reset(C.byref(cs), 1, st), "rs_collect_post_reset")
+        g.join_reset()
+        g.post_reset(True, st)
         if self.predictor is not None:
             self.predictor.reset_kernel(cut)                            # hidden = ac.reset_hidden() (test_cnn/train.py:770)
 
@@ -594,10 +572,11 @@ class CNNCollector:
     @torch.no_grad()
     def _step(self, epoch_ended: bool) -> None:
         """One lock-step of train.py:332-548 for all envs; row self._t of the buffers is written, then self._t advances."""
-        if self.use_glue and getattr(self, "glue", True):
+        if self.use_glue and self.glue:
             return self._step_glued(epoch_ended)
         env, buf, L, N, A = self.env, self.buf, self.L, self.N, self.A
-        acc, ti = self._acc, self._t
+        g = self._cg
+        acc, ti = g.acc, g.t
         put = lambda dst, row: dst.index_copy_(0, ti, row.unsqueeze(0))
         critic, cells, pcells = self._round()
         put(self.shared, critic); put(self.cells, cells); put(self.pcells, pcells)
@@ -653,40 +632,26 @@ class CNNCollector:
     def collect(self) -> Dict[str, torch.Tensor]:
         if self.obs is None:
             self.start()
-        T = self.T
-        self._acc.zero_()
+        g = self._cg
+        g.acc.zero_()
+        g.t.zero_()
         self.complete_len.zero_()
-        self._t.zero_()
-        if self.use_glue and getattr(self, "glue", True):
-            self._glue_state()
-            if self.use_heads:
-                self._prepare_heads()
-        if self.use_graph and self._graph is None and T > 1:
-            # lazy library initialisation (rocBLAS handles / workspaces) must not fall into the capture: evaluate the
-            # networks once on the current maps (pure functions, no collector state changes), then record the step
-            side = side_stream(self.env.device)                               # library warm-up (GEMM handles) outside the capture
-            side.wait_stream(torch.cuda.current_stream(self.env.device))
-            with torch.cuda.stream(side):
-                critic = self.maps.shared_maps()
-                cells, pcells = self.maps.field("cell").long(), self.maps.field("pred_cell").long()
-                if not (self.use_glue and getattr(self, "glue", True) and (self.use_team_round or self.use_sized_team_round)):     # the team rounds call no library GEMM
-                    for a, ag in self.agents.items():
-                        ag.act((critic, cells, pcells, a), self._u[:, a]); ag._values((critic,))
-                if self.predictor is not None:
-                    self.predictor._packed()
-            torch.cuda.current_stream(self.env.device).wait_stream(side)
-            torch.cuda.synchronize(self.env.device)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._step(False)
-        for t in range(T - 1):
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self._step(False)
-        self._step(True)
+        if self.use_glue and self.glue and self.use_heads:
+            self._prepare_heads()
+        collect_epoch(self, self._warm_up)
         self.buf.finish(self.agents[0].gamma, self.agents[0].lam)
-        return self._acc.result()
+        return g.acc.result()
+
+    def _warm_up(self) -> None:
+        """Lazy library initialisation (rocBLAS handles / workspaces) must not fall into the capture: evaluate the networks once on
+        the current maps (pure functions, no collector state changes)."""
+        critic = self.maps.shared_maps()
+        cells, pcells = self.maps.field("cell").long(), self.maps.field("pred_cell").long()
+        if not (self.use_glue and self.glue and (self.use_team_round or self.use_sized_team_round)):     # the team rounds call no library GEMM
+            for a, ag in self.agents.items():
+                ag.act((critic, cells, pcells, a), self._u[:, a]); ag._values((critic,))
+        if self.predictor is not None:
+            self.predictor._packed()
 
     def resume_state(self) -> Dict[str, Any]:
         if self.obs is None:

@@ -43,8 +43,8 @@ import torch.nn.functional as F
 from . import _lib
 from .envs import RadSearchVec
 from .pfgru import SIZED_WIDTHS, PFGRUCell, PredictorBank, _s64, draw_key, hash_normal, hash_uniform, lane_offsets
-from .ppo import (DeviceWelford, EpochStats, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
-                  reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
+from .ppo import (CollectGlue, DeviceWelford, RolloutBuffer, UpdateResult, _world, check_minibatch, host_read, normalize_advantages,
+                  collect_epoch, reduce_grads_and_stats, reject_unknown_kwargs, side_stream)
 
 
 def _mlp_tanh(sizes) -> nn.Sequential:
@@ -1282,8 +1282,7 @@ class RNNCollector:
         # one lock-step is ~45 small launches: captured once as a HIP graph and replayed (see CNNCollector); all state in place
         self.use_graph = use_graph
         self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self._t = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._acc = EpochStats(self.A, dev)
+        self._t = torch.zeros(1, dtype=torch.int64, device=dev)                                   # the buffer row a lock-step writes
         self._row_act = torch.zeros(self.N, self.A, dtype=torch.int64, device=dev)
         self._row_f = torch.zeros(3, self.N, self.A, dtype=torch.float32, device=dev)
         self._src = torch.zeros(self.N, 2, dtype=torch.float32, device=dev)
@@ -1291,14 +1290,12 @@ class RNNCollector:
         self.use_k14 = torch.device(dev).type == "cuda" and all(ag.agent.fused_policy for ag in agents.values())
         # the sized step (rs_rnn_sized_step) in K14's place for the other widths it serves (RNNModelActorCritic.sized_policy)
         self.use_sized = torch.device(dev).type == "cuda" and not self.use_k14 and all(ag.agent.sized_policy for ag in agents.values())
-        self._k_act = torch.zeros(self.A, self.N, dtype=torch.int64, device=dev)
-        self._k_f = torch.zeros(self.A, 3, self.N, dtype=torch.float32, device=dev)          # logp, value, bootstrap value
         self.obs = None
         self.started = False
         self.epoch = 0
         # the lock-step's element-wise bookkeeping as three launches (rs_collect_*; ~30 torch launches before): needs K14 and the fused bank
         self.use_glue = (self.use_k14 or self.use_sized) and fused_pf
-        self._cs = None
+        self._cg: Optional[CollectGlue] = None          # built by start(), over the first observation
         # teams: each policy round of the glued lock-step as one launch for all agents (rs_rnn_team_step / rs_rnn_sized_team_step) in
         # place of one K14 / sized-step launch per agent; one agent keeps its launch.  Like use_glue, settable before the first collect()
         self.use_team_step = bool(self.A >= 2 and self.use_glue
@@ -1309,26 +1306,6 @@ class RNNCollector:
         """The policy step runs as one launch (K14 or the sized step) and the buffer rows are written by rs_store_rows."""
         return self.use_k14 or self.use_sized
 
-    def _glue_state(self) -> "_lib.RsCollectState":
-        """rs_collect_state over the collector's (fixed-address) buffers, built once the first observation exists."""
-        if self._cs is None:
-            env, dev, N, A = self.env, self.env.device, self.N, self.A
-            self._x_buf = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)
-            self._xb_buf = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)
-            self._flags = torch.zeros(3, N, dtype=torch.uint8, device=dev)                  # over, cut, boot
-            self._rew_used = torch.zeros(N, A, dtype=torch.float32, device=dev)
-            self._done_oob = torch.zeros(2, N, A, dtype=torch.uint8, device=dev)            # copies of the env's done / out_of_bounds rows
-            self._src_copy = torch.zeros(2, N, dtype=torch.int32, device=dev)
-            self._side = side_stream(dev)
-            p = lambda t: t.data_ptr()
-            st = self.stat
-            self._cs = _lib.RsCollectState(N, A, self.L, 0, p(env.obs), p(env.reward), p(env.team), p(env.done), p(self.obs), p(self.ep_ret),
-                                           p(self.steps_in_ep), p(st.count), p(st.mean), p(st.sq), p(st.std), p(self._x_buf), p(self._xb_buf),
-                                           p(self._rew_used), p(self._flags[0]), p(self._flags[1]), p(self._flags[2]), p(self.bank.episode),
-                                           p(self.bank.calls), p(self.episodes_begun), p(self._t), p(env.oob), p(env.state("src_x")),
-                                           p(env.state("src_y")), p(self._done_oob[0]), p(self._done_oob[1]), p(self._src_copy), None)
-        return self._cs
-
     def _team_round(self, x, loc, u, act, act8, mask8) -> None:
         """One policy round of every agent in one launch (rs_rnn_team_step, or rs_rnn_sized_team_step at the other widths) on the
         collector's [N, A, .] rows: u given = the step round (h in place, act / act8, logp and value into _k_f slots 0 and 1), u None =
@@ -1337,7 +1314,7 @@ class RNNCollector:
         ptr = lambda t: None if t is None else t.data_ptr()
         wp = (C.c_void_p * self.A)(*[self.agents[a].policy_weights().data_ptr() for a in range(self.A)])
         st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
-        tail = (ptr(x), ptr(loc), ptr(self.h), ptr(u), ptr(act), ptr(self._k_f), ptr(act8), ptr(mask8), self.N, st)
+        tail = (ptr(x), ptr(loc), ptr(self.h), ptr(u), ptr(act), ptr(self._cg.k_f), ptr(act8), ptr(mask8), self.N, st)
         if self.use_k14:
             _lib.check(_lib.load().rs_rnn_team_step(wp, self.A, *tail), "rs_rnn_team_step")
         else:
@@ -1350,44 +1327,31 @@ class RNNCollector:
         (pre, uniforms, K11, K14, env step, post_step, K11 + K14 of the bootstrap round, store_rows, epoch_stats, env reset, post_reset,
         particle-set and GRU-state resets) where the torch composition took ~45.  Same arithmetic, operation by operation.  A team's
         two K14 rounds are one launch each for all agents (use_team_step; one K14 launch per agent and round without it)."""
-        env, buf, N, A = self.env, self.buf, self.N, self.A
-        lib, cs = _lib.load(), self._glue_state()
-        st = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
-        over, cut, boot = self._flags[0], self._flags[1], self._flags[2]
-        _lib.check(lib.rs_collect_pre(C.byref(cs), st), "rs_collect_pre")                       # train.py:334-341
-        x = self._x_buf
+        env, N, A = self.env, self.N, self.A
+        lib, g = _lib.load(), self._cg
+        st = g.stream()
+        x, xb, cut, boot = g.x, g.xb, g.cut, g.boot
+        g.pre(st)                                                                              # train.py:334-341
         env.action_uniforms(self._u)
         loc = self.bank.predict_kernel(x)                                                      # PFGRU (K11), carried particle sets
         if self.use_team_step:
-            self._team_round(x, loc, self._u, self._k_act, self._act8, None)
+            self._team_round(x, loc, self._u, g.k_act, self._act8, None)
         else:
             for a, ag in self.agents.items():
-                ag.policy_step_rows(x, loc, self.h[a], self._u, a, value=self._k_f[a, 1], act=self._k_act[a], logp=self._k_f[a, 0], act8=self._act8)
+                ag.policy_step_rows(x, loc, self.h[a], self._u, a, value=g.k_f[a, 1], act=g.k_act[a], logp=g.k_f[a, 0], act8=self._act8)
         env.step(self._act8)
-        _lib.check(lib.rs_collect_post_step(C.byref(cs), 1 if epoch_ended else 0, st), "rs_collect_post_step")
-        # the env's reset (a latency-bound ~50 us: one env's spawn is a 15 k-instruction chain on four lanes) runs on a side stream
-        # beside the bootstrap round, the buffer rows and the statistics: those read post_step's COPIES of the reward / done / out-of-
-        # bounds rows and of the source positions, which the reset rewrites
-        main = torch.cuda.current_stream(env.device)
-        self._side.wait_stream(main)
-        with torch.cuda.stream(self._side):
-            if epoch_ended:
-                env.set_epoch_end()
-            env.reset(cut)
-        locb = self.bank.predict_kernel(self._xb_buf, mask8=boot)                              # train.py:462-487: one more ac.step for the value
+        g.post_step(epoch_ended, st)
+        g.reset_on_side(epoch_ended)                                                           # beside everything up to join_reset()
+        locb = self.bank.predict_kernel(xb, mask8=boot)                                        # train.py:462-487: one more ac.step for the value
         if self.use_team_step:
-            self._team_round(self._xb_buf, locb, None, None, None, boot)
+            self._team_round(xb, locb, None, None, None, boot)
         else:
             for a, ag in self.agents.items():
-                ag.policy_step_rows(self._xb_buf, locb, self.h[a], None, a, value=self._k_f[a, 2], mask8=boot)
-        _lib.check(lib.rs_store_rows(self._t.data_ptr(), self._k_act.data_ptr(), self._k_f.data_ptr(), x.data_ptr(),
-                                     self._src_copy[0].data_ptr(), self._src_copy[1].data_ptr(), self._rew_used.data_ptr(), cut.data_ptr(),
-                                     boot.data_ptr(), buf.act.data_ptr(), buf.logp.data_ptr(), buf.val.data_ptr(), buf.last_val.data_ptr(),
-                                     buf.obs.data_ptr(), buf.source_tar.data_ptr(), buf.rew.data_ptr(), buf.cut.data_ptr(), N, A, self.T, st),
-                   "rs_store_rows")
-        self._acc.step_and_episodes(self._done_oob[1], self._done_oob[0], self.ep_ret, self.steps_in_ep, over.view(torch.bool))
-        main.wait_stream(self._side)
-        _lib.check(lib.rs_collect_post_reset(C.byref(cs), 0 if epoch_ended else 1, st), "rs_collect_post_reset")
+                ag.policy_step_rows(xb, locb, self.h[a], None, a, value=g.k_f[a, 2], mask8=boot)
+        g.store_rows(st)
+        g.stats()
+        g.join_reset()
+        g.post_reset(not epoch_ended, st)
         if not epoch_ended:                                                                    # train.py:505-518 (reset_hidden)
             self.bank.reset_kernel(cut)
             hid = self.agents[0].agent.hid
@@ -1430,6 +1394,9 @@ class RNNCollector:
         obs, *_ = self.env.reset()
         self.obs = obs.clone()                                    # from here on updated in place (fixed address)
         self.stat.update(self.obs[..., 0])
+        # the lock-step glue over the fixed-address buffers; the torch composition uses its t, acc and k_act / k_f rows too
+        self._cg = CollectGlue(self.env, self.buf, self.obs, self.ep_ret, self.steps_in_ep, self.L, stat=self.stat, bank=self.bank,
+                               episodes_begun=self.episodes_begun, t=self._t)
         self.started = True
 
     @torch.no_grad()
@@ -1438,16 +1405,17 @@ class RNNCollector:
         if self.use_glue:
             return self._step_glued(epoch_ended)
         env, buf, L, N, A = self.env, self.buf, self.L, self.N, self.A
-        acc, ti = self._acc, self._t
+        g = self._cg
+        acc, ti = g.acc, g.t
         put = lambda dst, row: dst.index_copy_(0, ti, row.unsqueeze(0))
         x = self._x(self.obs)                                                 # train.py:334-341
         env.action_uniforms(self._u)
         loc = self.bank.predict(x)                                            # PFGRU (K11), carried particle sets
         for a, ag in self.agents.items():
             if self._kstep:
-                act = self._k_act[a]
+                act = g.k_act[a]
                 ag.policy_step_hip(x[:, a].contiguous(), loc[:, a].contiguous(), self.h[a], u=self._u[:, a].contiguous(), h_out=self.h[a],
-                                   value=self._k_f[a, 1], act=act, logp=self._k_f[a, 0])
+                                   value=g.k_f[a, 1], act=act, logp=g.k_f[a, 0])
                 self._act8[:, a] = act.to(torch.int8)                         # the buffer rows are written by rs_store_rows below
                 continue
             logits, v, h1 = ag.agent.policy_step(x[:, a], loc[:, a], self.h[a])
@@ -1485,18 +1453,15 @@ class RNNCollector:
         locb = self.bank.predict(xb, mask=boot)
         for a, ag in self.agents.items():
             if self._kstep:
-                ag.policy_step_hip(xb[:, a].contiguous(), locb[:, a].contiguous(), self.h[a], value=self._k_f[a, 2])
+                ag.policy_step_hip(xb[:, a].contiguous(), locb[:, a].contiguous(), self.h[a], value=g.k_f[a, 2])
                 continue
             _, vb, _ = ag.agent.policy_step(xb[:, a], locb[:, a], self.h[a])
             self._row_f[2, :, a] = torch.where(boot, vb, torch.zeros_like(vb))
         if fast:
             # PPOBuffer.store for the whole lock-step; before the reset moves the sources of the envs that start a new episode
-            _lib.check(_lib.load().rs_store_rows(ti.data_ptr(), self._k_act.data_ptr(), self._k_f.data_ptr(), x.data_ptr(),
-                                                 env.state("src_x").data_ptr(), env.state("src_y").data_ptr(), rew.data_ptr(),
-                                                 cut.view(torch.uint8).data_ptr(), boot.view(torch.uint8).data_ptr(), buf.act.data_ptr(),
-                                                 buf.logp.data_ptr(), buf.val.data_ptr(), buf.last_val.data_ptr(), buf.obs.data_ptr(),
-                                                 buf.source_tar.data_ptr(), buf.rew.data_ptr(), buf.cut.data_ptr(), N, A, self.T,
-                                                 C.c_void_p(torch.cuda.current_stream(self.h.device).cuda_stream)), "rs_store_rows")
+            # (the env's live rows, not the glue's copies: nothing has reset them yet)
+            buf.store_rows(ti, g.k_act, g.k_f, x, env.state("src_x"), env.state("src_y"), rew, cut.view(torch.uint8), boot.view(torch.uint8),
+                           g.stream())
         else:
             put(buf.last_val, self._row_f[2])
         acc.step_and_episodes(oob_now, done, self.ep_ret, self.steps_in_ep, episode_over)     # before the reset rewrites the env's rows
@@ -1517,39 +1482,26 @@ class RNNCollector:
         """T - 1 replays of one captured lock-step (HIP graph, as in CNNCollector) + the epoch's last step run eagerly."""
         if not self.started:
             self.start()
-        T = self.T
-        self._acc.zero_()
-        self._t.zero_()
+        g = self._cg
+        g.acc.zero_()
+        g.t.zero_()
         self._reset_hidden(None)                                              # train.py:322-329: every epoch starts fresh
         if self._kstep:
             for ag in self.agents.values():
                 ag.policy_weights()                                           # re-packed in place after an update
         if self.bank.impl == "hip":
             self.bank._packed()                # the captured K11 launch reads this buffer: update_model changed the PFGRU since
-        if self.use_glue:
-            self._glue_state()                 # its buffers exist before the lock-step is captured
-        if self.use_graph and self._graph is None and T > 1:
-            side = side_stream(self.env.device)                               # library warm-up (GEMM handles) outside the capture
-            side.wait_stream(torch.cuda.current_stream(self.env.device))
-            with torch.cuda.stream(side):
-                x = self._x(self.obs)
-                for a, ag in self.agents.items():
-                    ag.agent.policy_step(x[:, a], torch.zeros(self.N, 2, device=x.device), self.h[a])
-                if self.bank.impl == "hip":                                   # (the library-op bank has no packed weights)
-                    self.bank._packed()
-            torch.cuda.current_stream(self.env.device).wait_stream(side)
-            torch.cuda.synchronize(self.env.device)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._step(False)
-        for _ in range(T - 1):
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self._step(False)
-        self._step(True)
+        collect_epoch(self, self._warm_up)
         self.buf.finish(self.agents[0].gamma, self.agents[0].lam)
-        return self._acc.result()
+        return g.acc.result()
+
+    def _warm_up(self) -> None:
+        """Library warm-up (GEMM handles) outside the capture."""
+        x = self._x(self.obs)
+        for a, ag in self.agents.items():
+            ag.agent.policy_step(x[:, a], torch.zeros(self.N, 2, device=x.device), self.h[a])
+        if self.bank.impl == "hip":                                           # (the library-op bank has no packed weights)
+            self.bank._packed()
 
     def resume_state(self) -> Dict[str, Any]:
         from .ppo import _welford_state

@@ -29,10 +29,11 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_cnn_head.hpp"
 
 namespace {
 
-constexpr int FLAT = 2704, H1 = 32, H2 = 16, NACT = 8;
+constexpr int FLAT = 2704, H1 = RS_HEAD_H1, H2 = RS_HEAD_H2, NACT = RS_HEAD_NA;      // (csrc/rs_cnn_head.hpp)
 constexpr int EH_WAVES = 4, EH_NT = 64 * EH_WAVES;
 constexpr int EH_TILE = 64;                         // images per workgroup: two MFMA column tiles
 constexpr int EH_KW = FLAT / EH_WAVES;              // 676 k per wave
@@ -61,6 +62,12 @@ __device__ __forceinline__ void eh_step(v16f& acc0, v16f& acc1, const float4& w,
     acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, b.w, acc1, 0, 0, 0);
 }
 
+// eh_finish, and ts_hidden / ts_draw further down, write out the arithmetic of csrc/rs_cnn_head.hpp, which rs_cnn_head_kernel and
+// sk_heads_kernel run; keep them in step by hand.  Rebuilt from the shared pieces (with the evaluation kernel calling ts_k2704) the
+// evaluation heads kept their 164 / 196 registers and their bits, but the fused evaluation at 1000 lanes timed 0.1277 ms against
+// 0.1275 ms + 0.0001 ms of spread with one agent and 0.3134 ms against 0.3125 ms + 0.0008 ms with four (three alternated rounds), and
+// rs_cnn_team_step_head_kernel's bootstrap round with eight critics 0.0824 ms against 0.0810 ms + 0.0009 ms (five rounds): outside the
+// rule (profiles/policy_pieces_timing.txt).
 // Behind the k loop, the same for every depth: the waves' partial sums meet in LDS; wave 0 adds them in wave order, then the bias, and
 // runs rs_cnn_head_kernel<8>'s arithmetic, the draw and the idle rule, one image per lane.
 __device__ __forceinline__ void eh_finish(float (*part)[EH_TILE][EH_ROW], const v16f& acc0, const v16f& acc1, const rs_cnn_head_params& P,
@@ -606,37 +613,27 @@ __global__ void __launch_bounds__(EH_NT) sk_heads_kernel(TsNets nets, int A, int
     }
     __syncthreads();
     if (wave != 0) return;
-    // ---- ts_hidden behind y1: ReLU -> Linear(32, 16) -> ReLU
-    const eh_cmem_t w2 = eh_cmem(P.w2), b2 = eh_cmem(P.b2);
+    // ---- behind y1: ReLU, then csrc/rs_cnn_head.hpp's layers
     float h1[H1], h2[H2];
 #pragma unroll
     for (int k = 0; k < H1; k += 4) {
         const float4 s = *reinterpret_cast<const float4*>(&y1s[lane][k]);
         h1[k] = fmaxf(s.x, 0.0f); h1[k + 1] = fmaxf(s.y, 0.0f); h1[k + 2] = fmaxf(s.z, 0.0f); h1[k + 3] = fmaxf(s.w, 0.0f);
     }
-#pragma unroll
-    for (int o = 0; o < H2; ++o) {
-        float s = b2[o];
-#pragma unroll
-        for (int k = 0; k < H1; ++k) s = __builtin_fmaf(w2[o * H1 + k], h1[k], s);
-        h2[o] = fmaxf(s, 0.0f);
-    }
+    rs_cnn_head_layer2(P.w2, P.b2, h1, h2);
     const int nc = n < N ? n : N - 1;
     if (y < A) {
         int a;
         float lp_sel;
-        ts_draw(P, h2, u[(size_t)nc * A + y], a, lp_sel);
+        rs_cnn_head_draw(P.w3, P.b3, h2, u[(size_t)nc * A + y], a, lp_sel);
         if (on) {
             act[(size_t)y * N + n] = a;
             f[(size_t)y * 3 * N + n] = lp_sel;
             act8[(size_t)n * A + y] = (int8_t)a;
         }
     } else {
-        // rs_cnn_head_kernel<1>: the state value, to its owner's row or (global critic) to every agent's
-        const eh_cmem_t w3 = eh_cmem(P.w3), b3 = eh_cmem(P.b3);
-        float v = b3[0];
-#pragma unroll
-        for (int k = 0; k < H2; ++k) v = __builtin_fmaf(w3[k], h2[k], v);
+        // the state value, to its owner's row or (global critic) to every agent's
+        const float v = rs_cnn_head_value(P.w3, P.b3, h2);
         if (on) {
             if (C == 1) for (int a = 0; a < A; ++a) f[((size_t)a * 3 + slot) * N + n] = v;
             else f[((size_t)(y - A) * 3 + slot) * N + n] = v;

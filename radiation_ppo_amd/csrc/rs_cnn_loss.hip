@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/radsearch.h"
+#include "rs_cnn_head.hpp"
 
 namespace {
 
@@ -74,10 +75,7 @@ __global__ void __launch_bounds__(256) rs_actor_loss_kernel(const float* __restr
 //   OUT = 8: log-softmax, the inverse-CDF draw on the env's uniform (Categorical.sample as CNNAgentPPO.act composes it: a = #{j < 7 :
 //            cdf_j <= u}), log-probability of the drawn action -- the collector did this with ~14 element-wise launches per agent;
 //   OUT = 1: the state value, written `copies` times at a stride (one row per agent that shares a global critic).
-// One env per lane; the 16 x 32 and OUT x 16 weights are wave uniform (scalar loads).
-typedef const float __attribute__((address_space(4))) * hd_cmem_t;
-__device__ __forceinline__ hd_cmem_t hd_cmem(const float* p) { return (hd_cmem_t)(uintptr_t)p; }
-
+// One env per lane; the layers behind h1 = ReLU(y1) and the draw are csrc/rs_cnn_head.hpp's, shared with the team heads (rs_cnn_eval.hip).
 template <int OUT>
 __global__ void __launch_bounds__(64) rs_cnn_head_kernel(const float* __restrict__ y1, const float* w2_, const float* b2_, const float* w3_,
                                                          const float* b3_, const float* __restrict__ u, int us, int64_t* __restrict__ act,
@@ -88,52 +86,23 @@ __global__ void __launch_bounds__(64) rs_cnn_head_kernel(const float* __restrict
     const bool live = e < N && (mask == nullptr || mask[e] != 0);
     if (!__any(live)) return;
     const int ec = e < N ? e : N - 1;
-    const hd_cmem_t w2 = hd_cmem(w2_), b2 = hd_cmem(b2_), w3 = hd_cmem(w3_), b3 = hd_cmem(b3_);
-    float h1[32];
+    float h1[RS_HEAD_H1];
 #pragma unroll
-    for (int k = 0; k < 32; k += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(y1 + (size_t)ec * 32 + k);
+    for (int k = 0; k < RS_HEAD_H1; k += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(y1 + (size_t)ec * RS_HEAD_H1 + k);
         h1[k] = fmaxf(v.x, 0.0f); h1[k + 1] = fmaxf(v.y, 0.0f); h1[k + 2] = fmaxf(v.z, 0.0f); h1[k + 3] = fmaxf(v.w, 0.0f);
     }
-    float h2[16];
-#pragma unroll
-    for (int o = 0; o < 16; ++o) {
-        float s = b2[o];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) s = __builtin_fmaf(w2[o * 32 + k], h1[k], s);
-        h2[o] = fmaxf(s, 0.0f);
-    }
-    float lg[OUT];
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) {
-        float s = b3[o];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s = __builtin_fmaf(w3[o * 16 + k], h2[k], s);
-        lg[o] = s;
-    }
+    float h2[RS_HEAD_H2];
+    rs_cnn_head_layer2(w2_, b2_, h1, h2);
     if (OUT == 1) {
+        const float v = rs_cnn_head_value(w3_, b3_, h2);
         if (live)
-            for (int c = 0; c < copies; ++c) value[(size_t)c * vstride + e] = lg[0];
+            for (int c = 0; c < copies; ++c) value[(size_t)c * vstride + e] = v;
         return;
     }
-    float mx = lg[0];
-#pragma unroll
-    for (int o = 1; o < OUT; ++o) mx = fmaxf(mx, lg[o]);
-    float se = 0.0f;
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) se += expf(lg[o] - mx);
-    const float lse = logf(se);
-    const float uu = u[(size_t)ec * us];
-    float cdf = 0.0f, lp_sel = (lg[0] - mx) - lse;
-    int a = 0;
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) {
-        const float lp = (lg[o] - mx) - lse;
-        cdf += expf(lp);
-        if (o < OUT - 1 && cdf <= uu) a = o + 1;
-    }
-#pragma unroll
-    for (int o = 1; o < OUT; ++o) if (a == o) lp_sel = (lg[o] - mx) - lse;
+    int a;
+    float lp_sel;
+    rs_cnn_head_draw(w3_, b3_, h2, u[(size_t)ec * us], a, lp_sel);
     if (live) {
         if (act) act[e] = a;
         if (logp) logp[e] = lp_sel;

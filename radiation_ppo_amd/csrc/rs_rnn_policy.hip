@@ -148,6 +148,13 @@ __global__ void __launch_bounds__(64) rs_rnn_policy_kernel(PolArgs a_) {
     }
 }
 
+// The three kernels of this file carry the same GRU cell, heads and draw (the draw: csrc/rs_action.hpp's text), kept in step by hand.
+// Shared as small inline pieces (cell, value head, policy head, draw) the arithmetic and the bits were the same, but two of the three
+// fell outside the timing rule against their own copies (profiles/policy_pieces_timing.txt): K14 went from 195 to 197 VGPRs and eight
+// launches at 1000 lanes timed 0.1578 ms against 0.1573 ms + 0.0004 ms of spread (five alternated rounds), rs_rnn_team_collect_kernel's
+// bootstrap round at 4096 envs 0.0136 ms against 0.0135 ms + 0.0000 ms (three rounds).  rs_rnn_team_step_kernel stayed inside its
+// spread, and has no partner left to share with.
+//
 // The policy round of a whole team in one launch: grid = (64-lane groups, agent), blockIdx.y's agent works on its rows of
 // x [N][A][11], loc [N][A][2], u [N][A] and act8 [N][A] with its own weights and its own slab of h [A][N][24], updated in place (a
 // lane has its row in registers before it stores).  K14's arithmetic, operation by operation and in K14's order, for the outputs an

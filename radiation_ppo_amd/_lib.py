@@ -5,242 +5,131 @@ our library makes the dynamic loader resolve our DT_NEEDED entry to the SAME run
 device pointers and streams created by torch are valid in our launches."""
 import ctypes as C
 import os
+import re
 
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RS_LIB_PATH") or os.path.join(_PKG, "lib", "librs_hip.so")   # override: A/B builds
 
-RS_OBS_DIM = 11
-RS_MAX_AGENTS = 8
-RS_MAX_OBS = 7
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "radsearch.h")
 
-ENVERR_ZERO_DIST = 1
-ENVERR_IDLE_STALL = 2
-ENVERR_CORRECT_CAP = 4
-ENVERR_BAD_ACTION = 8
-ENVERR_NO_PATH = 16
-
-MAPERR_RING_FULL = 1
-MAPERR_VISIT_OVERFLOW = 2
-MAPERR_OFF_MAP = 4
+# The one mapping from the header's C types to ctypes.  A scalar argument, return value or field is one of _SCALARS; the _POINTEES stand
+# behind a pointer only.  Pointers: `const char*` is c_char_p, a pointer to a struct the header defines POINTER(its class), a pointer to
+# a pointer POINTER(c_void_p), every other pointer c_void_p (callers pass tensor.data_ptr(), or byref() of an out-parameter).
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "size_t": C.c_size_t,
+            "float": C.c_float, "double": C.c_double, "rs_stream_t": C.c_void_p}
+_POINTEES = ("void", "char", "int8_t", "uint8_t", "uint16_t")
+# ... but rs_update_state lives in device memory (FusedPPOGrad.state is a tensor): a pointer to it is an address like any tensor's, c_void_p
+_DEVICE_STRUCTS = ("rs_update_state",)
 
 
-class RsConfig(C.Structure):
-    _fields_ = [
-        ("num_envs", C.c_int32), ("num_agents", C.c_int32), ("obstruction_count", C.c_int32),
-        ("enforce_grid_boundaries", C.c_int32), ("bbox", C.c_int32 * 4), ("observation_area", C.c_int32 * 2),
-        ("falloff", C.c_int32), ("geom_group_size", C.c_int32), ("seed", C.c_uint32), ("env_id_base", C.c_uint32),
-        ("coord_noise", C.c_int32), ("debug_spawn", C.c_int32),
-    ]
+def _ctype(t, classes):
+    """'int32_t', 'const float*', 'const rs_config*', 'void**' -> the ctypes type; classes {struct name: its Structure, None if opaque}"""
+    name, stars = t.rstrip("*").replace("const ", ""), t.count("*")
+    if stars == 0:
+        if name not in _SCALARS:
+            raise ValueError(f"radsearch.h: {t!r} is passed by value, and the binding has no ctypes type for it")
+        return _SCALARS[name]
+    if stars > 1:
+        return C.POINTER(C.c_void_p)
+    if t == "const char*":
+        return C.c_char_p
+    return C.POINTER(classes[name]) if classes.get(name) and name not in _DEVICE_STRUCTS else C.c_void_p
 
 
-class RsCollectState(C.Structure):
-    """rs_collect_state (include/radsearch.h)."""
-    _fields_ = [("num_envs", C.c_int32), ("num_agents", C.c_int32), ("steps_per_episode", C.c_int32), ("team_reward", C.c_int32)] + [
-        (n, C.c_void_p) for n in ("env_obs", "env_reward", "env_team", "env_done", "obs", "ep_ret", "steps_in_ep", "w_count", "w_mean", "w_sq",
-                                  "w_std", "x", "xb", "reward_used", "over", "cut", "boot", "pf_episode", "pf_calls", "episodes_begun", "t",
-                                  "env_oob", "env_src_x", "env_src_y", "done_copy", "oob_copy", "src_copy", "complete_len")]
+_STARS = r"((?:\*\s*(?:const\b\s*)?)*)"
+_FIRST = re.compile(r"(const\s+)?(\w+)\s*" + _STARS + r"(\w+)\s*(?:\[(\d+)\])?")
+_NEXT = re.compile(_STARS + r"(\w+)\s*(?:\[(\d+)\])?")
 
 
-class RsEvalState(C.Structure):
-    """rs_eval_state (include/radsearch.h)."""
-    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("use_team_reward", C.c_int32)] + [
-        (n, C.c_void_p) for n in ("env_obs", "env_reward", "env_team", "env_done", "cur_obs", "w_count", "w_mean", "w_sq", "w_std", "alive",
-                                  "success", "ep_len", "ep_ret", "finished")]
+def parse_header(text):
+    """The C ABI out of the header's text: (functions, structs, enums, defines).
+    functions {name: (return type, [(type, argument name), ...])}; structs {name: [(type, field name, array length or None), ...]}, or
+    None for an opaque `typedef struct X X;`; enums and defines {NAME: int}.  A type is spelt 'int32_t', 'const float*', 'void**'.
+    Whatever is not one of the forms include/radsearch.h uses raises ValueError with the offending text; nothing is skipped."""
+    functions, structs, enums, defines = {}, {}, {}, {}
+
+    def integer(term, where):
+        try:
+            return defines[term] if term in defines else int(term, 0)
+        except ValueError:
+            raise ValueError(f"radsearch.h: {term!r} is no integer in {where!r}") from None
+
+    def declarators(decl):
+        """'const float *w1, *b1' -> [('const float*', 'w1', None), ('const float*', 'b1', None)]; 'int32_t bbox[4]' -> [('int32_t', 'bbox', 4)]"""
+        first, *rest = [p.strip() for p in decl.split(",")]
+        m = _FIRST.fullmatch(first)
+        more = [_NEXT.fullmatch(p) for p in rest]
+        if not m or not all(more):
+            raise ValueError(f"radsearch.h: cannot split the declaration {decl!r}")
+        if m.group(2) not in _SCALARS and m.group(2) not in _POINTEES and m.group(2) not in structs:
+            raise ValueError(f"radsearch.h: unknown type {m.group(2)!r} in {decl!r}")
+        base = ("const " if m.group(1) else "") + m.group(2)
+        return [(base + "*" * stars.count("*"), name, n and int(n)) for stars, name, n in [m.groups()[2:]] + [x.groups() for x in more]]
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    for line in re.findall(r"^[ \t]*#.*$", text, re.M):               # #define NAME int | #define NAME (int + NAME); the guards
+        line = " ".join(line.split())
+        if re.fullmatch(r"#(include <\w+\.h>|ifn?def \w+|endif|define \w+)", line):
+            continue
+        m = re.fullmatch(r"#define (\w+) \(?([^()]+)\)?", line)
+        if not m:
+            raise ValueError(f"radsearch.h: not an integer #define: {line!r}")
+        defines[m.group(1)] = sum(integer(t.strip(), line) for t in m.group(2).split("+"))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    if m := re.search(r'extern\s*"C"\s*\{', text):                    # ... and its closing brace, the last one of the file
+        text = text[:m.start()] + text[m.end():text.rindex("}")] + text[text.rindex("}") + 1:]
+    stmt, depth = "", 0
+    for ch in text:
+        depth += (ch == "{") - (ch == "}")
+        if ch != ";" or depth:
+            stmt += ch
+            continue
+        s, stmt = " ".join(stmt.split()), ""
+        if m := re.fullmatch(r"typedef struct (\w+) (\w+)", s):
+            structs[m.group(2)] = None
+        elif m := re.fullmatch(r"typedef struct (?:\w+ )?\{(.*)\} (\w+)", s):
+            structs[m.group(2)] = [f for decl in m.group(1).split(";") if decl.strip() for f in declarators(decl.strip())]
+        elif m := re.fullmatch(r"enum \{(.*)\}", s):
+            for member in m.group(1).split(","):
+                if not (e := re.fullmatch(r"(\w+) = (-?\w+)", member.strip())):
+                    raise ValueError(f"radsearch.h: not an enum member NAME = int: {member.strip()!r}")
+                enums[e.group(1)] = integer(e.group(2), member.strip())
+        elif m := re.fullmatch(r"typedef void ?\* ?(\w+)", s):
+            if _SCALARS.get(m.group(1)) is not C.c_void_p:
+                raise ValueError(f"radsearch.h: unknown type {m.group(1)!r} in {s!r}")
+        elif m := re.fullmatch(r"([^()]+?) ?\((.*)\)", s):            # `return type name` splits as a declarator does
+            (ret, name, _), = declarators(m.group(1))
+            functions[name] = (ret, [] if m.group(2).strip() == "void" else [declarators(a)[0][:2] for a in m.group(2).split(",")])
+        else:
+            raise ValueError(f"radsearch.h: not a declaration this reader knows: {s!r}")
+    if stmt.strip():
+        raise ValueError(f"radsearch.h: unterminated declaration: {' '.join(stmt.split())!r}")
+    return functions, structs, enums, defines
 
 
-class RsRnnEvalState(C.Structure):
-    """rs_rnn_eval_state (include/radsearch.h)."""
-    _fields_ = [("N", C.c_int32), ("runs_per_lane", C.c_int32), ("steps_per_episode", C.c_int32)] + [
-        (n, C.c_void_p) for n in ("env_obs", "env_reward", "env_done", "cur_obs", "x", "w_count", "w_mean", "w_sq", "w_std", "active", "again",
-                                  "run", "steps", "ret", "rec_len", "rec_ret", "rec_suc", "pf_calls", "idle_act8", "finished")]
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes binding of librs_hip.so is read from the C header at import, "
+                       "so the package needs the source tree's include/ directory next to it.")
+_functions, _structs, _enums, _defines = parse_header(open(HEADER_PATH).read())
 
+# the header's structs by their C names; each also under its class name, rs_collect_state -> RsCollectState
+STRUCTS = {}
+for _name, _fields in _structs.items():
+    if _fields:                                                       # an opaque one stays a pointee
+        STRUCTS[_name] = type("".join(w.capitalize() for w in _name.split("_")), (C.Structure,), {
+            "__doc__": f"{_name} (include/radsearch.h)",
+            "_fields_": [(f, _ctype(t, STRUCTS) * n if n else _ctype(t, STRUCTS)) for t, f, n in _fields]})
+globals().update({c.__name__: c for c in STRUCTS.values()})
 
-class RsRnnTeamEvalState(C.Structure):
-    """rs_rnn_team_eval_state (include/radsearch.h)."""
-    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("runs_per_lane", C.c_int32), ("steps_per_episode", C.c_int32)] + [
-        (n, C.c_void_p) for n in ("env_obs", "env_reward", "env_done", "cur_obs", "x", "w_count", "w_mean", "w_sq", "w_std", "active", "again",
-                                  "run", "steps", "ret", "rec_len", "rec_ret", "rec_suc", "pf_calls", "idle_act8", "finished")]
+# the header's enum members and integer #defines under their own names: RS_ABI_VERSION, RS_ERR_INVALID_ARG, RS_ENVERR_NO_PATH, ...
+CONSTANTS = {**_enums, **_defines}
+globals().update(CONSTANTS)
 
-
-class RsMlpParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
-
-
-class RsCnnHeadParams(C.Structure):
-    """rs_cnn_head_params (include/radsearch.h): a CNN actor's three Linear layers in torch's layouts."""
-    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
-
-
-class RsCnnConvParams(C.Structure):
-    """rs_cnn_conv_params (include/radsearch.h): a CNN actor's two convolutions in torch's layouts."""
-    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2")]
-
-
-class RsRolloutArgs(C.Structure):
-    _fields_ = [("steps_per_epoch", C.c_int32), ("steps_per_episode", C.c_int32)] + [
-        (n, C.c_void_p) for n in ("obs", "act", "logp", "val", "rew", "last_val", "cut", "source_tar", "cur_obs", "w_count",
-                                  "w_mean", "w_sq", "w_std", "steps_in_ep", "ep_ret", "done_count", "oob_count",
-                                  "ep_ret_sum", "ep_len_sum", "ep_count", "ep_ret_sq_sum", "ep_ret_max", "ep_ret_min")]
-
-
-class RsPpoBatch(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("act", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p), ("logp_old", C.c_void_p),
-                ("w", C.c_void_p), ("M", C.c_int32), ("clip_ratio", C.c_float), ("alpha", C.c_float), ("vf_coef", C.c_float)]
-
-
-class RsInfo(C.Structure):
-    _fields_ = [("out_of_bounds", C.c_void_p), ("out_of_bounds_count", C.c_void_p), ("blocked", C.c_void_p),
-                ("collision", C.c_void_p)]
-
-
-# every symbol include/radsearch.h declares: (name, restype, argtypes)
-SYMBOLS = [
-    ("rs_strerror", C.c_char_p, [C.c_int]),
-    ("rs_abi_version", C.c_int, []),
-    ("rs_state_bytes", C.c_size_t, [C.POINTER(RsConfig)]),
-    ("rs_create", C.c_int, [C.POINTER(RsConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
-    ("rs_destroy", None, [C.c_void_p]),
-    ("rs_state_field", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
-                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    ("rs_set_epoch_end", C.c_int, [C.c_void_p, C.c_void_p]),
-    ("rs_reset", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                           C.POINTER(RsInfo), C.c_void_p]),
-    ("rs_refresh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RsInfo), C.c_void_p]),
-    ("rs_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                          C.POINTER(RsInfo), C.c_void_p]),
-    ("rs_action_uniforms", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_poisson_probe", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_error_flags", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
-    ("rs_policy_forward", C.c_int, [C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.c_void_p, C.c_int32, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]),
-    ("rs_ff_team_step", C.c_int, [C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
-    ("rs_rollout", C.c_int, [C.c_void_p, C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.POINTER(RsRolloutArgs), C.c_void_p]),
-    ("rs_rollout_lds_bytes", C.c_size_t, [C.c_int]),
-    ("rs_ppo_grad_workspace_bytes", C.c_size_t, []),
-    ("rs_ppo_grad", C.c_int, [C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.POINTER(RsPpoBatch), C.c_void_p, C.c_void_p,
-                              C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_adam_step", C.c_int, [C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
-    ("rs_ppo_update_step", C.c_int, [C.POINTER(RsMlpParams), C.POINTER(RsMlpParams), C.POINTER(RsPpoBatch), C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
-    ("rs_maps_state_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    ("rs_maps_create", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
-                                 C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
-    ("rs_maps_destroy", None, [C.c_void_p]),
-    ("rs_maps_reset", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_maps_update", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_maps_stack", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_maps_field", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                C.POINTER(C.c_int32)]),
-    ("rs_cnn_trunk_slab_row", C.c_int32, [C.c_int32]),
-    ("rs_cnn_trunk_slab_rows", C.c_int32, [C.c_int64, C.c_int32]),
-    ("rs_cnn_trunk_forward_grid", C.c_int32, [C.c_int64, C.c_int32]),
-    ("rs_cnn_trunk_scratch_floats", C.c_int32, [C.c_int32]),
-    ("rs_cnn_trunk_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_cnn_trunk_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_gae", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                         C.c_int32, C.c_double, C.c_double, C.c_void_p]),
-    ("rs_ppo_prepare_workspace_bytes", C.c_size_t, [C.c_int32]),
-    ("rs_ppo_prepare", C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_pfgru_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_pfgru_step_recorded", C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_pfgru_pass", C.c_int, [C.c_void_p] * 7 + [C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_pfgru_reset", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                 C.c_void_p]),
-    ("rs_pfgru_sized_weight_floats", C.c_int32, [C.c_int32]),
-    ("rs_pfgru_sized_step", C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_pfgru_sized_pass", C.c_int, [C.c_void_p] * 7 + [C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_pfgru_sized_step_recorded", C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                                                    C.c_void_p]),
-    ("rs_pfgru_sized_reset", C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_pfgru_draws", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_pfgru_train", C.c_int, [C.c_void_p] * 15 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
-    ("rs_pfgru_train_keyed", C.c_int, [C.c_void_p] * 14 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
-    ("rs_pfgru_sized_train_weight_floats", C.c_int32, [C.c_int32]),
-    ("rs_pfgru_sized_train_grad_floats", C.c_int32, [C.c_int32]),
-    ("rs_pfgru_sized_draws", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_pfgru_sized_train", C.c_int, [C.c_void_p] * 15 + [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
-                                       C.c_void_p]),
-    ("rs_rnn_policy_step", C.c_int, [C.c_void_p] * 10 + [C.c_int32, C.c_void_p]),
-    ("rs_rnn_policy_step_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    ("rs_collect_pre", C.c_int, [C.POINTER(RsCollectState), C.c_void_p]),
-    ("rs_collect_post_step", C.c_int, [C.POINTER(RsCollectState), C.c_int32, C.c_void_p]),
-    ("rs_collect_post_reset", C.c_int, [C.POINTER(RsCollectState), C.c_int32, C.c_void_p]),
-    ("rs_welford_update", C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_welford_reset", C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_welford_standardize", C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
-    ("rs_gru_h0_reset", C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_epoch_stats", C.c_int, [C.c_void_p] * 13 + [C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_a2c_heads_loss", C.c_int, [C.c_void_p] * 11 + [C.c_int64, C.c_double, C.c_double, C.c_void_p]),
-    ("rs_actor_loss", C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_double, C.c_void_p]),
-    ("rs_cnn_trunk_prepare", C.c_int, [C.c_int32] + [C.c_void_p] * 6),
-    ("rs_cnn_trunk_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_cnn_sized_slab_row", C.c_int32, [C.c_int32]),
-    ("rs_cnn_sized_slab_rows", C.c_int32, [C.c_int64, C.c_int32, C.c_int32]),
-    ("rs_cnn_sized_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 9),
-    ("rs_cnn_sized_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6),
-    ("rs_cnn_sized_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6
-     + [C.c_int32, C.c_void_p]),
-    # the occupancy-aware training passes: flags [S][tiles] once per update, then the forward / backward with the flags in front of the stream
-    ("rs_cnn_sized_tiles", C.c_int32, [C.c_int32]),
-    ("rs_cnn_sized_occupancy", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    ("rs_cnn_sized_forward_occ", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 10),
-    ("rs_cnn_sized_backward_occ", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 6
-     + [C.c_int32, C.c_void_p, C.c_void_p]),
-    ("rs_cnn_head", C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                              C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
-    ("rs_store_rows", C.c_int, [C.c_void_p] * 17 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_gru_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_gru_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                  C.c_int32, C.c_void_p]),
-    ("rs_rnn_sized_weight_floats", C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
-    ("rs_gru_sized_weight_floats", C.c_int32, [C.c_int32]),
-    ("rs_gru_sized_gate_floats", C.c_int32, [C.c_int32]),
-    ("rs_rnn_sized_step", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                    C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    ("rs_gru_sized_forward", C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_gru_sized_backward", C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    ("rs_a2c_sized_heads_loss", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10
-     + [C.c_int64, C.c_double, C.c_double, C.c_void_p]),
-    ("rs_gru_h0_reset_sized", C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    # a recurrent team's policy round in one launch (the collectors' step and bootstrap rounds, the evaluation at sized widths)
-    ("rs_rnn_team_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_void_p]),
-    ("rs_rnn_sized_team_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8
-     + [C.c_int32, C.c_void_p]),
-    ("rs_ff_eval_step", C.c_int, [C.POINTER(RsMlpParams), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
-    ("rs_eval_post_step", C.c_int, [C.POINTER(RsEvalState), C.c_void_p]),
-    ("rs_rnn_eval_post_step", C.c_int, [C.POINTER(RsRnnEvalState), C.c_void_p]),
-    ("rs_rnn_eval_post_refresh", C.c_int, [C.POINTER(RsRnnEvalState), C.c_void_p]),
-    # the RAD-TEAM (CNN) evaluation's two entries (the header lists them last; this list's order binds nothing)
-    ("rs_cnn_team_trunk_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_cnn_team_eval_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]),
-    # ... and their forms for maps of any side (walls off)
-    ("rs_cnn_sized_team_infer", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.POINTER(RsCnnConvParams),
-                                          C.c_void_p, C.c_void_p]),
-    ("rs_cnn_sized_team_eval_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]),
-    # the RAD-TEAM (CNN) training round: every critic's trunk, every actor's and critic's head
-    ("rs_cnn_team_critic_trunk_infer", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("rs_cnn_team_step_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32, C.POINTER(RsCnnHeadParams), C.c_int32] + [C.c_void_p] * 8
-     + [C.c_int32, C.c_void_p]),
-    # the same round on maps of any side: every critic's tiled trunk, the k-split first layer and the heads behind it
-    ("rs_cnn_sized_team_head_slice_floats", C.c_int32, []),
-    ("rs_cnn_sized_team_head_scratch_floats", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
-    ("rs_cnn_sized_team_critic_infer", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.POINTER(RsCnnConvParams), C.c_void_p, C.c_void_p]),
-    ("rs_cnn_sized_team_step_head", C.c_int, [C.POINTER(RsCnnHeadParams), C.c_int32, C.POINTER(RsCnnHeadParams), C.c_int32, C.c_int32]
-     + [C.c_void_p] * 9 + [C.c_int64, C.c_int32, C.c_void_p]),
-    ("rs_rnn_team_eval_step", C.c_int, [C.POINTER(C.c_void_p), C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
-    ("rs_rnn_team_eval_post_step", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),
-    ("rs_rnn_team_eval_post_refresh", C.c_int, [C.POINTER(RsRnnTeamEvalState), C.c_void_p]),
-]
+# every function the header declares, in its order: (name, restype, argtypes)
+SYMBOLS = [(_name, None if _ret == "void" else _ctype(_ret, STRUCTS), [_ctype(t, STRUCTS) for t, _ in _args])
+           for _name, (_ret, _args) in _functions.items()]
 
 _lib = None
 
@@ -282,7 +171,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.rs_abi_version() != 4:
+    if lib.rs_abi_version() != RS_ABI_VERSION:
         raise RuntimeError("librs_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -298,13 +298,13 @@ class RadSearch:
         done_c = done[0].cpu().numpy()
         oob, oobc, blk = (info[k][0].cpu().numpy() for k in ("out_of_bounds", "out_of_bounds_count", "blocked"))
         flags = self._vec.error_flags()
-        if flags & _lib.ENVERR_BAD_ACTION:
+        if flags & _lib.RS_ENVERR_BAD_ACTION:
             raise AssertionError("action out of range")
-        if flags & _lib.ENVERR_IDLE_STALL:
+        if flags & _lib.RS_ENVERR_IDLE_STALL:
             raise ValueError("Agent should not return false if the tentative step is an idle step")
-        if flags & _lib.ENVERR_ZERO_DIST:
+        if flags & _lib.RS_ENVERR_ZERO_DIST:
             raise ValueError("lam value too large")     # numpy's poisson(inf) error in the reference
-        if flags & _lib.ENVERR_NO_PATH:
+        if flags & _lib.RS_ENVERR_NO_PATH:
             raise RuntimeError("no obstacle-free path from the detector to the source")
         observation = {i: obs_c[i] for i in range(A)}
         reward = {"team_reward": float(np.float32(team[0].item())),

@@ -398,7 +398,7 @@ def run_test_environments_rnn_team(agents: Dict[int, Any], env_sets: Dict[str, t
             it += 1
     # lanes whose runs are over idle on purpose; stacked agents may "stall".  One agent's idle step is a move by (0, 0): it never stalls
     return _close(vec, keys, saved, R, rec_len.reshape(-1), rec_ret.reshape(-1), rec_suc.reshape(-1).bool(),
-                  log=log[:it] if return_actions else None, ignore_flags=_lib.ENVERR_IDLE_STALL if A > 1 else 0)
+                  log=log[:it] if return_actions else None, ignore_flags=_lib.RS_ENVERR_IDLE_STALL if A > 1 else 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -450,7 +450,7 @@ def run_test_environments_cnn(agents: Dict[int, Any], env_sets: Dict[str, tuple]
             break
     # finished episodes idle on purpose; stacked agents may "stall"
     return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=torch.stack(log) if return_actions else None,
-                  ignore_flags=_lib.ENVERR_IDLE_STALL)
+                  ignore_flags=_lib.RS_ENVERR_IDLE_STALL)
 
 
 @torch.no_grad()
@@ -516,7 +516,7 @@ def _run_lane_per_run_team(rounds, agents, env_sets, montecarlo_runs, steps_per_
         it += 1
     # finished episodes idle on purpose; stacked agents may "stall"
     return _close(vec, keys, saved, R, ep_len, ep_ret, success, log=log[:it] if return_actions else None,
-                  ignore_flags=_lib.ENVERR_IDLE_STALL)
+                  ignore_flags=_lib.RS_ENVERR_IDLE_STALL)
 
 
 def _ff_rounds(run, fused, agents):

@@ -88,6 +88,7 @@ def lane_offsets(P: int, H: int, device) -> torch.Tensor:
 _PF_K = 27                      # the two [k][48] blocks are padded to 28 k rows (row 27 = 0)
 _PF_ZR, _PF_ZRB, _PF_N, _PF_NB, _PF_O, _PF_OB, _PF_H0, _PF_H0B, _PF_H2, _PF_H2B, PF_WEIGHT_FLOATS = (
     0, 1344, 1392, 2736, 2784, 2811, 2816, 3392, 3416, 3464, 3472)
+assert PF_WEIGHT_FLOATS == _lib.RS_PFGRU_WEIGHT_FLOATS
 
 
 def pack_weights(cells) -> torch.Tensor:

@@ -532,7 +532,7 @@ def pack_episodes(obs, act, adv, ret, logp, src, cut, n_total: int, env_id_base:
 
 
 # ------------------------------------------------------------------------------------------------ K13 plumbing
-PF_TRAIN_WEIGHT_FLOATS, PF_TRAIN_GRAD_FLOATS = 3680, 3376            # include/radsearch.h
+PF_TRAIN_WEIGHT_FLOATS, PF_TRAIN_GRAD_FLOATS = _lib.RS_PFGRU_TRAIN_WEIGHT_FLOATS, _lib.RS_PFGRU_TRAIN_GRAD_FLOATS
 
 
 def pack_train_weights(cell) -> torch.Tensor:
@@ -604,7 +604,7 @@ def unpack_sized_train_grads(cell, g: torch.Tensor) -> Dict[str, torch.Tensor]:
     return out
 
 
-PF_POLICY_WEIGHT_FLOATS = 5296                                       # include/radsearch.h: RS_RNN_POLICY_WEIGHT_FLOATS
+PF_POLICY_WEIGHT_FLOATS = _lib.RS_RNN_POLICY_WEIGHT_FLOATS
 
 
 def pack_policy_weights(ac: "RNNModelActorCritic") -> torch.Tensor:

@@ -46,7 +46,7 @@ import _f64_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SENTINEL = -12345.678
-RS_ERR_INVALID_ARG = 1               # include/radsearch.h
+from radiation_ppo_amd._lib import RS_ERR_INVALID_ARG  # noqa: E402
 TRUNK_SIZES = (1, 2, 3, 4, 64, 65, 193)            # three images make one workgroup round
 
 

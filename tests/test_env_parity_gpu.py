@@ -126,7 +126,7 @@ def test_debug_spawn(A, obst):
     intensity 1e6, background 0 -- bit-exact like every other env output.  With rectangles the fixed source may lie inside one (the
     reference resamples nothing under DEBUG; visilibity is then undefined): kernel and oracle raise the same RS_ENVERR_NO_PATH bit."""
     from radiation_ppo_amd import _lib
-    refs = _run(N=64, A=A, obst=obst, enforce=True, steps=40, seed=5, allow_err=_lib.ENVERR_NO_PATH if obst else 0, DEBUG=True)
+    refs = _run(N=64, A=A, obst=obst, enforce=True, steps=40, seed=5, allow_err=_lib.RS_ENVERR_NO_PATH if obst else 0, DEBUG=True)
     assert all(e.src == (500, 500) and e.intensity == 1000000 and e.bkg_intensity == 0 for e in refs)
 
 

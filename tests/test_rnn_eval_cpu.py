@@ -1,11 +1,12 @@
-"""rs_rnn_eval_post_step and rs_rnn_eval_post_refresh at the C boundary, without a GPU: the built library exports both under ABI
-version 4 (append-only), and every invalid argument is refused with RS_ERR_INVALID_ARG.  This machine has no device, so a refusal
-here proves that the validation runs before any HIP call: a launch would have come back as RS_ERR_HIP."""
+"""rs_rnn_eval_post_step and rs_rnn_eval_post_refresh at the C boundary, without a GPU: every invalid argument is refused with
+RS_ERR_INVALID_ARG.  This machine has no device, so a refusal here proves that the validation runs before any HIP call: a launch would
+have come back as RS_ERR_HIP.  (Their signatures, rs_rnn_eval_state's layout and their export: tests/test_abi_cpu.py.)"""
 import ctypes as C
 
 import pytest
 
-RS_ERR_INVALID_ARG = 1
+from radiation_ppo_amd._lib import RS_ERR_INVALID_ARG
+
 ENTRIES = ("rs_rnn_eval_post_step", "rs_rnn_eval_post_refresh")
 
 
@@ -15,23 +16,6 @@ def lib():
     build.build(verbose=False)
     from radiation_ppo_amd import _lib
     return _lib.load()
-
-
-def test_symbols_are_exported_and_the_abi_version_stays_4(lib):
-    from radiation_ppo_amd import _lib
-    names = {s[0] for s in _lib.SYMBOLS}
-    for sym in ENTRIES:
-        assert hasattr(lib, sym) and sym in names
-        assert getattr(lib, sym).argtypes is not None                # bound by _lib.load()
-    assert lib.rs_abi_version() == 4
-
-
-def test_the_ctypes_mirror_has_the_header_s_fields_in_order():
-    from radiation_ppo_amd import _lib
-    assert [f[0] for f in _lib.RsRnnEvalState._fields_] == [
-        "N", "runs_per_lane", "steps_per_episode", "env_obs", "env_reward", "env_done", "cur_obs", "x", "w_count", "w_mean", "w_sq", "w_std",
-        "active", "again", "run", "steps", "ret", "rec_len", "rec_ret", "rec_suc", "pf_calls", "idle_act8", "finished"]
-    assert C.sizeof(_lib.RsRnnEvalState) == 16 + 20 * 8             # three int32 padded to the pointers' alignment, twenty pointers
 
 
 # a valid state over fake (never dereferenced) addresses, then one field spoilt per case

@@ -328,22 +328,17 @@ class PredictorBank:
         m1 = torch.ones(self.N, dtype=torch.bool, device=self.dev) if mask is None else mask.bool()
         self.episode.add_(m1.long())                      # counters change in place: a captured collector step refers to them
         self.calls.masked_fill_(m1, 0)
-        if self.impl == "hip":
-            self.reset_kernel(None if mask is None else m1.to(torch.uint8))
-            return
-        k = self._key(0)
-        u = hash_uniform(k.view(self.A, self.N, 1, 1) * 1048583 + self._pu.view(1, 1, self.P, self.H)).float()
-        m = m1.view(1, self.N, 1, 1)
-        self.h = torch.where(m, u, self.h)
-        self.p = torch.where(m.view(1, self.N, 1), torch.full_like(self.p, math.log(1.0 / self.P)), self.p)
+        self.restart(None if mask is None else m1.to(torch.uint8))
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
 
-    # the two kernels alone, for the collectors whose bookkeeping kernels (rs_collect_post_step / _post_reset) keep the draw counters:
-    # `episode` / `calls` are NOT touched here, `mask8` is a uint8 tensor or None, the prediction comes back as the bank's own buffer
-    def predict_kernel(self, obs: torch.Tensor, mask8: Optional[torch.Tensor] = None) -> torch.Tensor:
-        assert self.impl == "hip" and obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape == (self.N, self.A, _lib.RS_OBS_DIM)
+    # the step and the reset alone, in either impl, for the collectors whose glue (ppo.CollectGlue) keeps the draw counters: `episode` /
+    # `calls` are read, NOT advanced; `mask8` is a uint8 (or bool) tensor or None; impl "hip" returns the bank's own prediction buffer
+    def step(self, obs: torch.Tensor, mask8: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.impl != "hip":
+            return self._step_torch(obs, mask8)
+        assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape == (self.N, self.A, _lib.RS_OBS_DIM)
         args = (self._packed().data_ptr(), obs.data_ptr(), self._hq.data_ptr(), self.p.data_ptr(), self._base.data_ptr(),
                 self.episode.data_ptr(), self.calls.data_ptr(), None if mask8 is None else mask8.data_ptr(), 1 if self.carry_hidden else 0,
                 float(self.cells[0].resamp_alpha), self._pred.data_ptr(), self.N, self.A)
@@ -355,8 +350,15 @@ class PredictorBank:
                 _lib.check(self._lib.rs_pfgru_step(*args, self._stream()), "rs_pfgru_step")
         return self._pred
 
-    def reset_kernel(self, mask8: Optional[torch.Tensor] = None) -> None:
-        assert self.impl == "hip"
+    def restart(self, mask8: Optional[torch.Tensor] = None) -> None:
+        if self.impl != "hip":
+            m1 = torch.ones(self.N, dtype=torch.bool, device=self.dev) if mask8 is None else mask8.bool()
+            k = self._key(0)
+            u = hash_uniform(k.view(self.A, self.N, 1, 1) * 1048583 + self._pu.view(1, 1, self.P, self.H)).float()
+            m = m1.view(1, self.N, 1, 1)
+            self.h = torch.where(m, u, self.h)
+            self.p = torch.where(m.view(1, self.N, 1), torch.full_like(self.p, math.log(1.0 / self.P)), self.p)
+            return
         args = (self._hq.data_ptr(), self.p.data_ptr(), self._base.data_ptr(), self.episode.data_ptr(), self.calls.data_ptr(),
                 None if mask8 is None else mask8.data_ptr(), self.N, self.A)
         if self.sized:
@@ -365,6 +367,8 @@ class PredictorBank:
         else:
             with _lib.timed("rs_pfgru_reset"):
                 _lib.check(self._lib.rs_pfgru_reset(*args, self._stream()), "rs_pfgru_reset")
+
+    predict_kernel, reset_kernel = step, restart          # the names they had while only impl "hip" had them
 
     def _packed(self) -> torch.Tensor:
         ver = tuple(p._version for c in self.cells for p in c.parameters())
@@ -397,14 +401,15 @@ class PredictorBank:
     @torch.no_grad()
     def predict(self, obs: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """select_action's `self.model(obs_tensor, hidden)` (:1872-1879) for every owner and env: obs [N, A, 11] -> pred [N, A, 2]
-        (scaled coordinates).  `mask`: the envs this round counts for (bootstrap rounds); the others' rows are to be discarded.
-        All owners go through the same batched matrix products (PFGRUCell.forward's arithmetic, owner axis first)."""
+        (scaled coordinates).  `mask`: the envs this round counts for (bootstrap rounds); the others' rows are to be discarded."""
+        pred = self.step(obs, None if mask is None else mask.to(torch.uint8))
+        self.calls.add_(1 if mask is None else mask.long())
+        return pred.clone() if self.impl == "hip" else pred
+
+    @torch.no_grad()
+    def _step_torch(self, obs: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
+        """All owners go through the same batched matrix products (PFGRUCell.forward's arithmetic, owner axis first)."""
         A, N, P, H = self.A, self.N, self.P, self.H
-        if self.impl == "hip":
-            assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape == (N, A, _lib.RS_OBS_DIM)
-            self.predict_kernel(obs, None if mask is None else mask.to(torch.uint8))
-            self.calls.add_(1 if mask is None else mask.long())
-            return self._pred.clone()
         W = self._stacked()
         k_eps, k_res = self._key(1), self._key(2)                                                           # [A, N]
         eps = hash_normal(k_eps.view(A, N, 1, 1) * 1048583 + self._pu.view(1, 1, P, H))                     # [A, N, P, H]
@@ -440,7 +445,6 @@ class PredictorBank:
                 m = mask.bool()
                 self.h = torch.where(m.view(1, N, 1, 1), h1, self.h)
                 self.p = torch.where(m.view(1, N, 1), p1, self.p)
-        self.calls.add_(1 if mask is None else mask.long())
         return loc.permute(1, 0, 2).contiguous()
 
     def resume_state(self):

@@ -676,16 +676,24 @@ class CollectGlue:
     touches: the flags, the reward in use, the copies of the env's rows, the policy round's k_act [A, N] and k_f [A, 3, N] (logp, value,
     bootstrap value), the EpochStats, the step counter t (the collector's own where it has one) and, with policy_input, the policy
     inputs x / xb [N, A, 11].  stat, bank, episodes_begun, complete_len: the optional fields of rs_collect_state (include/radsearch.h).
-    Building it loads no library and touches no stream: the first launch does."""
+    Building it loads no library and touches no stream: the first launch does.
+
+    impl, as DeviceWelford's: "hip" (default on a cuda device) = one launch per call; "torch" = each kernel of csrc/rs_welford.hip
+    transcribed on whole tensors, what the launches are tested against, what CPU tensors use and the product path where a kernel family
+    does not serve the configuration.  Both forms write the same tensors in place: a captured step refers to them by address."""
 
     def __init__(self, env, buf: "RolloutBuffer", obs: torch.Tensor, ep_ret: torch.Tensor, steps_in_ep: torch.Tensor, L: int, *,
                  team_reward: bool = False, stat: Optional["DeviceWelford"] = None, policy_input: bool = True, bank=None,
                  episodes_begun: Optional[torch.Tensor] = None, complete_len: Optional[torch.Tensor] = None,
-                 t: Optional[torch.Tensor] = None):
+                 t: Optional[torch.Tensor] = None, impl: Optional[str] = None):
         N, A = ep_ret.shape
         dev = obs.device
+        self.impl = impl or ("hip" if dev.type == "cuda" else "torch")
+        assert self.impl in ("hip", "torch") and (self.impl == "torch" or dev.type == "cuda")
         z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
         self.env, self.buf, self.ep_ret, self.steps_in_ep, self.device = env, buf, ep_ret, steps_in_ep, dev
+        self.obs, self.L, self.team_reward, self.stat, self.bank = obs, L, team_reward, stat, bank
+        self.episodes_begun, self.complete_len = episodes_begun, complete_len
         self.flags = z(3, N, dtype=torch.uint8)
         self.over, self.cut, self.boot = self.flags[0], self.flags[1], self.flags[2]
         self.rew_used = z(N, A, dtype=torch.float32)
@@ -710,31 +718,93 @@ class CollectGlue:
             done_copy=p(self.done), oob_copy=p(self.oob), src_copy=p(self.src_copy), complete_len=p(complete_len))
         # what every launch passes, computed once: TeamCollector's eager loop is bound by host issue
         self._cs = C.byref(self.cs)
-        self._over = self.over.view(torch.bool)
+        self._over, self._cut, self._boot = (f.view(torch.bool) for f in (self.over, self.cut, self.boot))
+        self._env_src = (env.state("src_x").view(-1), env.state("src_y").view(-1))
         self._own_rows = None if self.x is None else self._rows(self.x)
 
     def _rows(self, x: torch.Tensor) -> tuple:
         return self.buf.row_args(self.t, self.k_act, self.k_f, x, self.src_copy[0], self.src_copy[1], self.rew_used, self.cut, self.boot)
 
-    def stream(self) -> "C.c_void_p":
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def stream(self) -> Optional["C.c_void_p"]:
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else None
 
-    # the launches take the stream to launch on (stream(); TeamCollector reads it once per epoch)
+    def _standardized(self, src: torch.Tensor, dst: torch.Tensor) -> None:
+        dst.copy_(src)
+        if self.stat is not None:
+            self.stat.standardize(src[..., 0], out=dst[..., 0])
+
+    # the launches take the stream to launch on (stream(); TeamCollector reads it once per epoch); the torch bodies run on the current one
     def pre(self, st) -> None:
         """x <- obs, the reading standardised (train.py:334-341)."""
-        _lib.check(_lib.load().rs_collect_pre(self._cs, st), "rs_collect_pre")
+        if self.impl == "hip":
+            _lib.check(_lib.load().rs_collect_pre(self._cs, st), "rs_collect_pre")
+            return
+        self._standardized(self.obs, self.x)
 
     def post_step(self, epoch_ended: bool, st) -> None:
         """After the env's step: returns, counters, flags, Welford update, obs / xb and the copies of the env's rows (train.py:366-487)."""
-        _lib.check(_lib.load().rs_collect_post_step(self._cs, 1 if epoch_ended else 0, st), "rs_collect_post_step")
+        if self.impl == "hip":
+            _lib.check(_lib.load().rs_collect_post_step(self._cs, 1 if epoch_ended else 0, st), "rs_collect_post_step")
+            return
+        env, (N, A) = self.env, self.ep_ret.shape
+        self.rew_used.copy_(env.team.unsqueeze(1).expand(N, A) if self.team_reward else env.reward)
+        self.ep_ret += self.rew_used
+        self.done.copy_(env.done); self.oob.copy_(env.oob)                   # the copies: the reset rewrites the env's rows
+        self.src_copy[0].copy_(self._env_src[0]); self.src_copy[1].copy_(self._env_src[1])
+        self.steps_in_ep += 1
+        terminal = env.done.bool().any(dim=1)                                # train.py:387-391
+        timeout = self.steps_in_ep == self.L                                 # train.py:394-405
+        self._over.copy_(terminal | timeout)
+        if epoch_ended:
+            self._cut.fill_(True)
+        else:
+            self._cut.copy_(self._over)
+        self._boot.copy_(self._cut if epoch_ended else timeout)              # train.py:462-487: a value on timeout / epoch cut, 0 on a pure terminal
+        if self.complete_len is not None:
+            self.complete_len.copy_(torch.where(self._over, (self.t + 1).expand(N), self.complete_len))
+        if self.stat is not None:
+            self.stat.update(env.obs[..., 0])                                # train.py:432-436
+        self.obs.copy_(env.obs)
+        if self.xb is not None:
+            self._standardized(env.obs, self.xb)
+        if self.bank is not None:
+            self.bank.calls.add_(1)                                          # the step round's prediction
 
     def post_reset(self, reset_hidden: bool, st) -> None:
         """After the env's reset: the cut envs start over, with reset_hidden their draw counters advance; t += 1 (train.py:504-548)."""
-        _lib.check(_lib.load().rs_collect_post_reset(self._cs, 1 if reset_hidden else 0, st), "rs_collect_post_reset")
+        if self.impl == "hip":
+            _lib.check(_lib.load().rs_collect_post_reset(self._cs, 1 if reset_hidden else 0, st), "rs_collect_post_reset")
+            return
+        cut = self._cut
+        if self.bank is not None:
+            self.bank.calls.add_(self._boot.long())                          # the bootstrap round's prediction (masked to these envs)
+        self.obs.copy_(torch.where(cut.view(-1, 1, 1), self.env.obs, self.obs))          # train.py:530
+        self.ep_ret.masked_fill_(cut.unsqueeze(1), 0.0)
+        self.steps_in_ep.masked_fill_(cut, 0)
+        if self.stat is not None:
+            self.stat.reset(cut)                                             # train.py:504-509
+            self.stat.update(self.obs[..., 0], mask=cut)                     # train.py:542-548
+        if reset_hidden:                                                     # train.py:505-518: new draw counters
+            if self.bank is not None:
+                self.bank.episode.add_(cut.long())
+                self.bank.calls.masked_fill_(cut, 0)
+            if self.episodes_begun is not None:
+                self.episodes_begun.add_(cut.long())
+        self.t.add_(1)
 
     def store_rows(self, st, x: Optional[torch.Tensor] = None) -> None:
         """RolloutBuffer.store_rows of post_step's copies and k_act / k_f; x: the step's policy input where it is not the glue's own."""
-        self.buf.store_row_args(self._own_rows if x is None else self._rows(x), st)
+        if self.impl == "hip":
+            self.buf.store_row_args(self._own_rows if x is None else self._rows(x), st)
+            return
+        buf, f, (N, A) = self.buf, self.k_f, self.ep_ret.shape
+        put = lambda dst, row: dst.index_copy_(0, self.t, row.unsqueeze(0))
+        put(buf.act, self.k_act.t()); put(buf.logp, f[:, 0].t()); put(buf.val, f[:, 1].t())
+        put(buf.last_val, torch.where(self._boot.unsqueeze(1), f[:, 2].t(), 0.0))
+        put(buf.obs, self.x if x is None else x)
+        put(buf.source_tar, self.src_copy.t().float())
+        put(buf.rew, self.rew_used)
+        put(buf.cut, self.cut.unsqueeze(1).expand(N, A))
 
     def stats(self) -> None:
         """EpochStats.step_and_episodes of the lock-step, on post_step's copies."""
@@ -743,18 +813,21 @@ class CollectGlue:
     # The env's reset is latency bound (one env's spawn is a 15 k-instruction chain on four lanes; ~50-110 us) and rewrites the env's
     # reward / done / out-of-bounds rows and the sources of the cut envs.  Between reset_on_side() and join_reset() it runs on the side
     # stream beside the bootstrap round, the buffer rows and the statistics, and what is launched between the two reads post_step's
-    # COPIES (rew_used, done, oob, src_copy, obs / xb), never the env's own rows.
+    # COPIES (rew_used, done, oob, src_copy, obs / xb), never the env's own rows.  Both forms; without a cuda device the reset runs inline.
     def reset_on_side(self, epoch_ended: bool) -> None:
-        side = side_stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
+        cuda = self.device.type == "cuda"
+        if cuda:
+            side = side_stream(self.device)
+            side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side if cuda else None):
             if epoch_ended:
                 self.env.set_epoch_end()                                     # train.py:482-484
             self.env.reset(self.cut)                                         # train.py:530
 
     def join_reset(self) -> None:
         """Before post_reset, which reads the reset's observation rows."""
-        torch.cuda.current_stream(self.device).wait_stream(side_stream(self.device))
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).wait_stream(side_stream(self.device))
 
 
 def collect_epoch(col, warm_up) -> None:
@@ -973,7 +1046,7 @@ class FusedCollector:
 class TeamCollector:
     """Same contract as Collector for a feed-forward team on the GPU, the lock-step in HIP: ONE policy launch for all agents
     (rs_ff_team_step: every agent's own actor and critic on its own rows, the draw, rs_step's action rows) between CollectGlue's
-    launches (rs_collect_pre / _post_step / _post_reset, rs_store_rows, rs_epoch_stats), as in RNNCollector._step_glued.  Ten launches per
+    launches (rs_collect_pre / _post_step / _post_reset, rs_store_rows, rs_epoch_stats), as in RNNCollector._step.  Ten launches per
     lock-step, eleven at the epoch's last, on one stream, where Collector composes several dozen library ops per agent:
     pre, uniforms, policy (step round), env step, post_step, policy (bootstrap round on the envs that need a value), store_rows,
     epoch_stats, (epoch end) env reset, post_reset.  Every tensor keeps its address: the glue's argument block holds them."""

@@ -277,13 +277,12 @@ class CNNCollector:
         self.use_graph = use_graph
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._t = torch.zeros(1, dtype=torch.int64, device=dev)                            # the buffer row a lock-step writes
-        self._row_act = torch.zeros(self.N, self.A, dtype=torch.int64, device=dev)
-        self._row_f = torch.zeros(3, self.N, self.A, dtype=torch.float32, device=dev)      # logp, val, last_val of the step
+        self._x_buf = torch.zeros(self.N, self.A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)   # the step's observation (buffer row)
         self.obs = None
         self._cg: Optional[CollectGlue] = None          # built by start(), over the first observation
         # A/B switches, settable before the first collect(); False selects the form the bit-identity tests compare against.  glue:
-        # _step_glued in place of _step's torch composition; heads (with glue): use_heads; team_round / sized_team_round (with heads):
-        # use_team_round / use_sized_team_round in place of the per-agent round
+        # the HIP form of the lock-step glue in place of its torch form; heads (with glue): use_heads; team_round / sized_team_round
+        # (with heads): use_team_round / use_sized_team_round in place of the per-agent round
         self.glue = True
         self.heads = True
         self.team_round = True
@@ -299,10 +298,11 @@ class CNNCollector:
     def start(self) -> None:
         obs, *_ = self.env.reset()
         self.obs = obs.clone()                                      # from here on updated in place (fixed address)
-        # the lock-step glue (returns, counters, cut flags, observation copies and draw counters in two launches instead of ~27); no
-        # statistics, no policy input: the networks read heat maps.  The torch composition uses its statistics too
+        # the lock-step glue (returns, counters, cut flags, observation copies and draw counters; in its HIP form two launches instead of
+        # ~27); no statistics, no policy input: the networks read heat maps
         self._cg = CollectGlue(self.env, self.buf, self.obs, self.ep_ret, self.steps_in_ep, self.L, team_reward=self.team_reward,
-                               policy_input=False, bank=self.predictor, complete_len=self.complete_len, t=self._t)
+                               policy_input=False, bank=self.predictor, complete_len=self.complete_len, t=self._t,
+                               impl="hip" if self.use_glue and self.glue else "torch")
         if self.predictor is not None:
             self.predictor.reset()                                  # ac.reset_hidden() (test_cnn/train.py:686)
 
@@ -314,11 +314,13 @@ class CNNCollector:
         return self.env.device.type == "cuda" and (self.predictor is None or self.predictor.impl == "hip")
 
     @torch.no_grad()
-    def _round_glued(self, mask8: Optional[torch.Tensor] = None, cells: bool = True):
-        """cells=False: without the int64 copies of the owners' cells (the team round reads the heat maps' own int32 fields)."""
+    def _round(self, mask8: Optional[torch.Tensor] = None, cells: bool = True):
+        """One select_action round of every owner's MapsBuffer (maps updated once, shared by all owners; mask8: the envs of a bootstrap
+        round): returns the resident shared maps [N,4,X,Y] and the owners' location / prediction cells [N,A].  cells=False: without the
+        int64 copies of the owners' cells (the team round reads the heat maps' own int32 fields)."""
         pred = None
-        if self.predictor is not None:
-            pred = self.predictor.predict_kernel(self.obs, mask8=mask8)
+        if self.predictor is not None:                              # select_action: location_prediction, _ = self.model(obs, hidden)
+            pred = self.predictor.step(self.obs, mask8=mask8)       # the glue keeps the draw counters
         self.maps.update(self.obs, pred=pred, mask=mask8)
         if not cells:
             return self.maps.shared_maps(), None, None
@@ -326,9 +328,9 @@ class CNNCollector:
 
     @property
     def use_heads(self) -> bool:
-        """The select_action round of every agent as trunk (one launch) + BLAS Linear(16 P P, 32) + rs_cnn_head, buffer rows by
-        rs_store_rows; any map size (K9 at 27 x 27, the tiled trunk elsewhere)."""
-        return self.use_glue and self.heads
+        """The select_action round of every agent as trunk (one launch) + BLAS Linear(16 P P, 32) + rs_cnn_head; any map size (K9 at
+        27 x 27, the tiled trunk elsewhere).  With the HIP glue only."""
+        return self.use_glue and self.glue and self.heads
 
     @property
     def use_team_round(self) -> bool:
@@ -381,7 +383,6 @@ class CNNCollector:
             self._wt_c = {a: self._wt_c_all[i] for i, a in enumerate(sorted(self.agents))}
             P = self.maps.map_dimensions[0] // 2
             self._a2 = torch.empty(N, 16 * P * P, dtype=torch.float32, device=dev)
-            self._x_buf = torch.zeros(N, A, _lib.RS_OBS_DIM, dtype=torch.float32, device=dev)   # the step's observation (buffer row)
         if tuple(self.maps.map_dimensions) != (27, 27):
             if self.use_sized_team_round:
                 ags = [self.agents[a] for a in range(A)]
@@ -488,27 +489,28 @@ class CNNCollector:
                                               st), "rs_cnn_sized_infer")
 
     @torch.no_grad()
-    def _step_glued(self, epoch_ended: bool) -> None:
-        """_step with the element-wise bookkeeping between the library calls in rs_collect_post_step / _post_reset and (27 x 27 maps) every
-        agent's select_action as trunk + Linear + rs_cnn_head, the buffer rows by rs_store_rows: ~40 launches per lock-step where the
-        torch composition took ~110; with use_team_round the policy round is three launches and the bootstrap round two (_team_round), with
+    def _step(self, epoch_ended: bool) -> None:
+        """One lock-step of train.py:332-548 for all envs; row self._t of the buffers is written, then self._t advances.  The element-wise
+        bookkeeping between the library calls is the glue's (post_step / post_reset / store_rows), in either form.  With the HIP glue and
+        use_heads every agent's select_action is trunk + Linear + rs_cnn_head: ~40 launches per lock-step where the torch glue with the
+        module path takes ~110; with use_team_round the policy round is three launches and the bootstrap round two (_team_round), with
         use_sized_team_round (any other map side) four and three (_sized_team_round)."""
-        env, buf, N, A = self.env, self.buf, self.N, self.A
-        lib, g = _lib.load(), self._cg
+        env, N, A = self.env, self.N, self.A
+        g = self._cg
         st = g.stream()
         ti, cut, boot = g.t, g.cut, g.boot
         put = lambda dst, row: dst.index_copy_(0, ti, row.unsqueeze(0))
         heads, sized = self.use_heads, self.use_sized_team_round
         team = self.use_team_round or sized
         team_round = self._sized_team_round if sized else self._team_round
-        critic, cells, pcells = self._round_glued()
+        critic, cells, pcells = self._round()
         put(self.shared, critic); put(self.cells, cells); put(self.pcells, pcells)
         env.action_uniforms(self._u)
+        self._x_buf.copy_(self.obs)
         if team:
-            self._x_buf.copy_(self.obs)
             team_round(critic)
         elif heads:
-            self._x_buf.copy_(self.obs)
+            lib = _lib.load()
             for a, ag in self.agents.items():
                 m = ag.pi.actor
                 self._trunk_infer(critic, cells, pcells, a, m, self._wt[a], st)
@@ -523,110 +525,35 @@ class CNNCollector:
                 act, logp = ag.act((critic, cells, pcells, a), self._u[:, a])
                 if not ag.global_critic or v_shared is None:          # one evaluation serves every owner of a global critic
                     v_shared = ag._values((critic,))
-                self._row_act[:, a] = act
-                self._row_f[0, :, a] = logp
-                self._row_f[1, :, a] = v_shared
+                g.k_act[a] = act
+                g.k_f[a, 0] = logp
+                g.k_f[a, 1] = v_shared
                 self._act8[:, a] = act.to(torch.int8)
-            put(buf.act, self._row_act); put(buf.logp, self._row_f[0]); put(buf.val, self._row_f[1])
-            put(buf.obs, self.obs)
         env.step(self._act8)
         g.post_step(epoch_ended, st)
-        # bootstrap: ac.step(observations) once more for the envs that time out / are cut (train.py:462-480)
-        critic_b, _, _ = self._round_glued(mask8=boot, cells=not team)
+        # bootstrap: ac.step(observations) once more for the envs that time out / are cut (train.py:462-480);
+        # the maps of those envs see the final observation a second time, exactly as in the reference
+        critic_b, _, _ = self._round(mask8=boot, cells=not team)
         # the heat maps have seen the agents' last positions: from here the env's reset runs beside the critic's bootstrap evaluation,
         # the buffer rows and the statistics, up to join_reset()
         g.reset_on_side(epoch_ended)
-        if heads:
-            if team:
-                team_round(critic_b, mask8=boot)
-            else:
-                self._values_fused(critic_b, 2, mask8=boot)
-            g.store_rows(st, self._x_buf)
+        if team:
+            team_round(critic_b, mask8=boot)
+        elif heads:
+            self._values_fused(critic_b, 2, mask8=boot)
         else:
-            put(buf.rew, g.rew_used)
-            put(buf.cut, cut.unsqueeze(1).expand(N, A).contiguous())
-            bc = boot.view(torch.bool)
             vb = None
             for a, ag in self.agents.items():
                 if not ag.global_critic or vb is None:
                     vb = ag._values((critic_b,))
-                self._row_f[2, :, a] = torch.where(bc, vb, torch.zeros_like(vb))
-            put(buf.last_val, self._row_f[2])
+                g.k_f[a, 2] = vb                                         # store_rows keeps it where boot
+        g.store_rows(st, self._x_buf)
         g.stats()
         self.maps.reset(cut)                                             # ac.reset_agent() (train.py:537-540)
         g.join_reset()
         g.post_reset(True, st)
         if self.predictor is not None:
-            self.predictor.reset_kernel(cut)                            # hidden = ac.reset_hidden() (test_cnn/train.py:770)
-
-    @torch.no_grad()
-    def _round(self, mask: Optional[torch.Tensor] = None):
-        """One select_action round of every owner's MapsBuffer (maps updated once, shared by all owners): returns
-        the resident shared maps [N,4,X,Y] and the owners' location / prediction cells [N,A]."""
-        pred = None
-        if self.predictor is not None:                              # select_action: location_prediction, _ = self.model(obs, hidden)
-            pred = self.predictor.predict(self.obs, mask=mask)
-        self.maps.update(self.obs, pred=pred, mask=mask)
-        return self.maps.shared_maps(), self.maps.field("cell").long(), self.maps.field("pred_cell").long()
-
-    @torch.no_grad()
-    def _step(self, epoch_ended: bool) -> None:
-        """One lock-step of train.py:332-548 for all envs; row self._t of the buffers is written, then self._t advances."""
-        if self.use_glue and self.glue:
-            return self._step_glued(epoch_ended)
-        env, buf, L, N, A = self.env, self.buf, self.L, self.N, self.A
-        g = self._cg
-        acc, ti = g.acc, g.t
-        put = lambda dst, row: dst.index_copy_(0, ti, row.unsqueeze(0))
-        critic, cells, pcells = self._round()
-        put(self.shared, critic); put(self.cells, cells); put(self.pcells, pcells)
-        env.action_uniforms(self._u)
-        v_shared = None
-        for a, ag in self.agents.items():
-            act, logp = ag.act((critic, cells, pcells, a), self._u[:, a])
-            if not ag.global_critic or v_shared is None:          # one evaluation serves every owner of a global critic
-                v_shared = ag._values((critic,))
-            self._row_act[:, a] = act
-            self._row_f[0, :, a] = logp
-            self._row_f[1, :, a] = v_shared
-            self._act8[:, a] = act.to(torch.int8)
-        put(buf.act, self._row_act); put(buf.logp, self._row_f[0]); put(buf.val, self._row_f[1])
-        put(buf.obs, self.obs)
-        next_obs, rew, team, done, info = env.step(self._act8)
-        r_used = team.unsqueeze(1).expand(N, A) if self.team_reward else rew
-        put(buf.rew, r_used.contiguous())
-        self.ep_ret += r_used
-        self.steps_in_ep += 1
-        terminal = done.bool().any(dim=1)
-        oob_now = info["out_of_bounds"]
-        timeout = self.steps_in_ep == L
-        episode_over = terminal | timeout
-        cut = torch.ones_like(episode_over) if epoch_ended else episode_over
-        boot = cut if epoch_ended else timeout
-        put(buf.cut, cut.unsqueeze(1).to(torch.uint8).expand(N, A).contiguous())
-        self.obs.copy_(next_obs)
-        # bootstrap: ac.step(observations) once more for the envs that time out / are cut (train.py:462-480);
-        # the maps of those envs see the final observation a second time, exactly as in the reference
-        bc = boot & cut
-        critic_b, _, _ = self._round(mask=bc)
-        vb = None
-        for a, ag in self.agents.items():
-            if not ag.global_critic or vb is None:
-                vb = ag._values((critic_b,))
-            self._row_f[2, :, a] = torch.where(bc, vb, torch.zeros_like(vb))
-        put(buf.last_val, self._row_f[2])
-        acc.step_and_episodes(oob_now, done, self.ep_ret, self.steps_in_ep, episode_over)   # one launch (rs_epoch_stats); before the reset
-        self.complete_len.copy_(torch.where(episode_over, (ti + 1).expand(N), self.complete_len))
-        if epoch_ended:
-            env.set_epoch_end()
-        self.maps.reset(cut)                                             # ac.reset_agent() (train.py:537-540)
-        obs_r, *_ = env.reset(cut)
-        self.obs.copy_(obs_r)
-        if self.predictor is not None:
-            self.predictor.reset(mask=cut)                              # hidden = ac.reset_hidden() (test_cnn/train.py:770)
-        self.ep_ret.masked_fill_(cut.unsqueeze(1), 0.0)
-        self.steps_in_ep.masked_fill_(cut, 0)
-        ti.add_(1)
+            self.predictor.restart(cut)                                  # hidden = ac.reset_hidden() (test_cnn/train.py:770)
 
     @torch.no_grad()
     def collect(self) -> Dict[str, torch.Tensor]:
@@ -636,7 +563,7 @@ class CNNCollector:
         g.acc.zero_()
         g.t.zero_()
         self.complete_len.zero_()
-        if self.use_glue and self.glue and self.use_heads:
+        if self.use_heads:
             self._prepare_heads()
         collect_epoch(self, self._warm_up)
         self.buf.finish(self.agents[0].gamma, self.agents[0].lam)
@@ -647,7 +574,7 @@ class CNNCollector:
         the current maps (pure functions, no collector state changes)."""
         critic = self.maps.shared_maps()
         cells, pcells = self.maps.field("cell").long(), self.maps.field("pred_cell").long()
-        if not (self.use_glue and self.glue and (self.use_team_round or self.use_sized_team_round)):     # the team rounds call no library GEMM
+        if not (self.use_team_round or self.use_sized_team_round):      # the team rounds call no library GEMM
             for a, ag in self.agents.items():
                 ag.act((critic, cells, pcells, a), self._u[:, a]); ag._values((critic,))
         if self.predictor is not None:

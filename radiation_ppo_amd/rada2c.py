@@ -1283,9 +1283,6 @@ class RNNCollector:
         self.use_graph = use_graph
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._t = torch.zeros(1, dtype=torch.int64, device=dev)                                   # the buffer row a lock-step writes
-        self._row_act = torch.zeros(self.N, self.A, dtype=torch.int64, device=dev)
-        self._row_f = torch.zeros(3, self.N, self.A, dtype=torch.float32, device=dev)
-        self._src = torch.zeros(self.N, 2, dtype=torch.float32, device=dev)
         # K14 (rs_rnn_policy_step): GRU cell + heads + draw in one launch instead of ~35 library kernels per call
         self.use_k14 = torch.device(dev).type == "cuda" and all(ag.agent.fused_policy for ag in agents.values())
         # the sized step (rs_rnn_sized_step) in K14's place for the other widths it serves (RNNModelActorCritic.sized_policy)
@@ -1293,10 +1290,11 @@ class RNNCollector:
         self.obs = None
         self.started = False
         self.epoch = 0
-        # the lock-step's element-wise bookkeeping as three launches (rs_collect_*; ~30 torch launches before): needs K14 and the fused bank
+        # the lock-step's element-wise bookkeeping as three launches (the HIP form of the glue: rs_collect_*; ~30 launches in its torch
+        # form, which False selects): needs K14 or the sized step and the fused bank
         self.use_glue = (self.use_k14 or self.use_sized) and fused_pf
         self._cg: Optional[CollectGlue] = None          # built by start(), over the first observation
-        # teams: each policy round of the glued lock-step as one launch for all agents (rs_rnn_team_step / rs_rnn_sized_team_step) in
+        # teams: each policy round of the lock-step on the HIP glue as one launch for all agents (rs_rnn_team_step / rs_rnn_sized_team_step) in
         # place of one K14 / sized-step launch per agent; one agent keeps its launch.  Like use_glue, settable before the first collect()
         self.use_team_step = bool(self.A >= 2 and self.use_glue
                                   and len({(ag.agent.hid, tuple(ag.agent.pol), tuple(ag.agent.val)) for ag in agents.values()}) == 1)
@@ -1306,176 +1304,105 @@ class RNNCollector:
         """The policy step runs as one launch (K14 or the sized step) and the buffer rows are written by rs_store_rows."""
         return self.use_k14 or self.use_sized
 
-    def _team_round(self, x, loc, u, act, act8, mask8) -> None:
-        """One policy round of every agent in one launch (rs_rnn_team_step, or rs_rnn_sized_team_step at the other widths) on the
-        collector's [N, A, .] rows: u given = the step round (h in place, act / act8, logp and value into _k_f slots 0 and 1), u None =
-        the bootstrap round (the value into slot 2 on the envs of mask8).  The pointer array is rebuilt from policy_weights() on every
-        call, as the per-agent calls do: the buffers are re-packed in place, so a captured launch keeps reading the right addresses."""
-        ptr = lambda t: None if t is None else t.data_ptr()
-        wp = (C.c_void_p * self.A)(*[self.agents[a].policy_weights().data_ptr() for a in range(self.A)])
-        st = C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
-        tail = (ptr(x), ptr(loc), ptr(self.h), ptr(u), ptr(act), ptr(self._cg.k_f), ptr(act8), ptr(mask8), self.N, st)
-        if self.use_k14:
-            _lib.check(_lib.load().rs_rnn_team_step(wp, self.A, *tail), "rs_rnn_team_step")
-        else:
-            ac = self.agents[0].agent
-            _lib.check(_lib.load().rs_rnn_sized_team_step(wp, self.A, ac.hid, ac.pol[0], ac.val[0], *tail), "rs_rnn_sized_team_step")
-
-    @torch.no_grad()
-    def _step_glued(self, epoch_ended: bool) -> None:
-        """_step with the bookkeeping between the library calls in rs_collect_pre / _post_step / _post_reset: 15 launches per lock-step
-        (pre, uniforms, K11, K14, env step, post_step, K11 + K14 of the bootstrap round, store_rows, epoch_stats, env reset, post_reset,
-        particle-set and GRU-state resets) where the torch composition took ~45.  Same arithmetic, operation by operation.  A team's
-        two K14 rounds are one launch each for all agents (use_team_step; one K14 launch per agent and round without it)."""
-        env, N, A = self.env, self.N, self.A
-        lib, g = _lib.load(), self._cg
-        st = g.stream()
-        x, xb, cut, boot = g.x, g.xb, g.cut, g.boot
-        g.pre(st)                                                                              # train.py:334-341
-        env.action_uniforms(self._u)
-        loc = self.bank.predict_kernel(x)                                                      # PFGRU (K11), carried particle sets
-        if self.use_team_step:
-            self._team_round(x, loc, self._u, g.k_act, self._act8, None)
-        else:
-            for a, ag in self.agents.items():
-                ag.policy_step_rows(x, loc, self.h[a], self._u, a, value=g.k_f[a, 1], act=g.k_act[a], logp=g.k_f[a, 0], act8=self._act8)
-        env.step(self._act8)
-        g.post_step(epoch_ended, st)
-        g.reset_on_side(epoch_ended)                                                           # beside everything up to join_reset()
-        locb = self.bank.predict_kernel(xb, mask8=boot)                                        # train.py:462-487: one more ac.step for the value
-        if self.use_team_step:
-            self._team_round(xb, locb, None, None, None, boot)
-        else:
-            for a, ag in self.agents.items():
-                ag.policy_step_rows(xb, locb, self.h[a], None, a, value=g.k_f[a, 2], mask8=boot)
-        g.store_rows(st)
-        g.stats()
-        g.join_reset()
-        g.post_reset(not epoch_ended, st)
-        if not epoch_ended:                                                                    # train.py:505-518 (reset_hidden)
-            self.bank.reset_kernel(cut)
-            hid = self.agents[0].agent.hid
+    def _policy_round(self, x, loc, u, mask8) -> None:
+        """One policy round of every agent on the collector's [N, A, .] rows: u given = the step round (h in place, the action into the
+        glue's k_act and _act8, logp and value into k_f slots 0 and 1), u None = the bootstrap round (the value into slot 2, by the kernels
+        only on the envs of mask8; store_rows keeps it where boot).  With the HIP glue a team's round is one launch for all agents
+        (use_team_step: rs_rnn_team_step, or rs_rnn_sized_team_step at the other widths); else one K14 / sized-step launch per agent
+        (_kstep), or the torch modules."""
+        g, step = self._cg, u is not None
+        if self.use_team_step and g.impl == "hip":
+            # the pointer array is rebuilt from policy_weights() on every call, as the per-agent calls do: the buffers are re-packed in
+            # place, so a captured launch keeps reading the right addresses
+            ptr = lambda t: None if t is None else t.data_ptr()
+            wp = (C.c_void_p * self.A)(*[self.agents[a].policy_weights().data_ptr() for a in range(self.A)])
+            tail = (ptr(x), ptr(loc), ptr(self.h), ptr(u), ptr(g.k_act) if step else None, ptr(g.k_f), ptr(self._act8) if step else None,
+                    ptr(mask8), self.N, g.stream())
             if self.use_k14:
-                _lib.check(lib.rs_gru_h0_reset(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(), cut.data_ptr(),
-                                               1.0 / math.sqrt(hid), N, A, st), "rs_gru_h0_reset")
+                _lib.check(_lib.load().rs_rnn_team_step(wp, self.A, *tail), "rs_rnn_team_step")
             else:
-                _lib.check(lib.rs_gru_h0_reset_sized(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(), cut.data_ptr(),
-                                                     1.0 / math.sqrt(hid), hid, N, A, st), "rs_gru_h0_reset_sized")
-
-    def _x(self, obs: torch.Tensor) -> torch.Tensor:
-        x = obs.clone()
-        self.stat.standardize(obs[..., 0], out=x[..., 0])
-        return x
+                ac = self.agents[0].agent
+                _lib.check(_lib.load().rs_rnn_sized_team_step(wp, self.A, ac.hid, ac.pol[0], ac.val[0], *tail), "rs_rnn_sized_team_step")
+            return
+        for a, ag in self.agents.items():
+            if self._kstep and step:
+                ag.policy_step_rows(x, loc, self.h[a], u, a, value=g.k_f[a, 1], act=g.k_act[a], logp=g.k_f[a, 0], act8=self._act8)
+            elif self._kstep:
+                ag.policy_step_rows(x, loc, self.h[a], None, a, value=g.k_f[a, 2], mask8=mask8)
+            else:
+                logits, v, h1 = ag.agent.policy_step(x[:, a], loc[:, a], self.h[a])
+                if not step:
+                    g.k_f[a, 2] = v
+                    continue
+                self.h[a] = h1
+                logp_all = torch.log_softmax(logits, dim=-1)
+                cdf = torch.cumsum(logp_all.exp(), dim=-1)
+                act = (cdf[:, :-1] <= u[:, a].unsqueeze(-1)).sum(dim=-1)          # inverse CDF on the env's Philox uniform (FF_core.py:101-104)
+                g.k_act[a] = act
+                g.k_f[a, 0] = logp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1)
+                g.k_f[a, 1] = v
+                self._act8[:, a] = act.to(torch.int8)
 
     def _reset_hidden(self, mask: Optional[torch.Tensor]) -> None:
-        """reset_hidden (:583-586) for the masked envs: fresh particle sets (K11's reset kernel) and GRU h0 ~ U(-1/sqrt(hid), .)."""
+        """reset_hidden (:583-586) for the masked envs, the draw counters included (the epoch's start; inside the lock-step the glue's
+        post_reset advances them): fresh particle sets (K11's reset kernel) and GRU h0 ~ U(-1/sqrt(hid), .)."""
         self.bank.reset(mask)
         m = torch.ones(self.N, dtype=torch.bool, device=self.h.device) if mask is None else mask.bool()
         self.episodes_begun.add_(m.long())
-        if self.use_k14:                                                       # the same hash in one launch (rs_gru_h0_reset)
-            m8 = m.view(torch.uint8)
-            _lib.check(_lib.load().rs_gru_h0_reset(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(), m8.data_ptr(),
-                                                   1.0 / math.sqrt(self.agents[0].agent.hid), self.N, self.A,
+        self._h0_reset(m.view(torch.uint8))
+
+    def _h0_reset(self, mask8: torch.Tensor) -> None:
+        """GRU h0 of the envs in mask8 [N] uint8 from the hash of (env, agent, episodes_begun)."""
+        hid = self.agents[0].agent.hid
+        if self.use_k14:                                                       # the hash in one launch (rs_gru_h0_reset)
+            _lib.check(_lib.load().rs_gru_h0_reset(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(), mask8.data_ptr(),
+                                                   1.0 / math.sqrt(hid), self.N, self.A,
                                                    C.c_void_p(torch.cuda.current_stream(self.h.device).cuda_stream)), "rs_gru_h0_reset")
             return
         if self.use_sized:                                                     # the same at the agent's GRU width
-            m8 = m.view(torch.uint8)
-            hid = self.agents[0].agent.hid
             _lib.check(_lib.load().rs_gru_h0_reset_sized(self.h.data_ptr(), self.bank._base.data_ptr(), self.episodes_begun.data_ptr(),
-                                                         m8.data_ptr(), 1.0 / math.sqrt(hid), hid, self.N, self.A,
+                                                         mask8.data_ptr(), 1.0 / math.sqrt(hid), hid, self.N, self.A,
                                                          C.c_void_p(torch.cuda.current_stream(self.h.device).cuda_stream)), "rs_gru_h0_reset_sized")
             return
         key = draw_key(self.bank._base, self.episodes_begun.view(1, -1) * 8 + 5)                                        # [A, N]
         u = hash_uniform(key.unsqueeze(-1) * 1048583 + self._gidx.view(1, 1, -1))
         h0 = self.agents[0].agent.gru_h0(u)
-        self.h.copy_(torch.where(m.view(1, -1, 1), h0, self.h))
+        self.h.copy_(torch.where(mask8.view(torch.bool).view(1, -1, 1), h0, self.h))
 
     def start(self) -> None:
         obs, *_ = self.env.reset()
         self.obs = obs.clone()                                    # from here on updated in place (fixed address)
         self.stat.update(self.obs[..., 0])
-        # the lock-step glue over the fixed-address buffers; the torch composition uses its t, acc and k_act / k_f rows too
+        # the lock-step glue over the fixed-address buffers, in its HIP form with use_glue
         self._cg = CollectGlue(self.env, self.buf, self.obs, self.ep_ret, self.steps_in_ep, self.L, stat=self.stat, bank=self.bank,
-                               episodes_begun=self.episodes_begun, t=self._t)
+                               episodes_begun=self.episodes_begun, t=self._t, impl="hip" if self.use_glue else "torch")
         self.started = True
 
     @torch.no_grad()
     def _step(self, epoch_ended: bool) -> None:
-        """One lock-step of train.py:332-548 ('rnn' branches) for all envs; row self._t of the buffers is written."""
-        if self.use_glue:
-            return self._step_glued(epoch_ended)
-        env, buf, L, N, A = self.env, self.buf, self.L, self.N, self.A
-        g = self._cg
-        acc, ti = g.acc, g.t
-        put = lambda dst, row: dst.index_copy_(0, ti, row.unsqueeze(0))
-        x = self._x(self.obs)                                                 # train.py:334-341
+        """One lock-step of train.py:332-548 ('rnn' branches) for all envs; row self._t of the buffers is written.  The bookkeeping between
+        the library calls is the glue's, in either form.  With the HIP glue 15 launches (pre, uniforms, K11, K14, env step, post_step, K11 +
+        K14 of the bootstrap round, store_rows, epoch_stats, env reset, post_reset, particle-set and GRU-state resets) where the torch form
+        takes ~45, same arithmetic, operation by operation; a team's two K14 rounds are one launch each for all agents (_policy_round)."""
+        env, g = self.env, self._cg
+        st = g.stream()
+        x, xb, cut, boot = g.x, g.xb, g.cut, g.boot
+        g.pre(st)                                                                              # train.py:334-341
         env.action_uniforms(self._u)
-        loc = self.bank.predict(x)                                            # PFGRU (K11), carried particle sets
-        for a, ag in self.agents.items():
-            if self._kstep:
-                act = g.k_act[a]
-                ag.policy_step_hip(x[:, a].contiguous(), loc[:, a].contiguous(), self.h[a], u=self._u[:, a].contiguous(), h_out=self.h[a],
-                                   value=g.k_f[a, 1], act=act, logp=g.k_f[a, 0])
-                self._act8[:, a] = act.to(torch.int8)                         # the buffer rows are written by rs_store_rows below
-                continue
-            logits, v, h1 = ag.agent.policy_step(x[:, a], loc[:, a], self.h[a])
-            self.h[a] = h1
-            logp_all = torch.log_softmax(logits, dim=-1)
-            cdf = torch.cumsum(logp_all.exp(), dim=-1)
-            act = (cdf[:, :-1] <= self._u[:, a].unsqueeze(-1)).sum(dim=-1)    # inverse CDF on the env's Philox uniform (FF_core.py:101-104)
-            self._row_act[:, a] = act
-            self._row_f[0, :, a] = logp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1)
-            self._row_f[1, :, a] = v
-            self._act8[:, a] = act.to(torch.int8)
-        fast = self._kstep                                                    # one store kernel per lock-step instead of ~19 launches
-        if not fast:
-            put(buf.act, self._row_act); put(buf.logp, self._row_f[0]); put(buf.val, self._row_f[1])
-            put(buf.obs, x)
-            self._src[:, 0] = env.state("src_x")[0].float()
-            self._src[:, 1] = env.state("src_y")[0].float()
-            put(buf.source_tar, self._src)
-        next_obs, rew, team, done, info = env.step(self._act8)
-        if not fast:
-            put(buf.rew, rew)
-        self.ep_ret += rew
-        self.steps_in_ep += 1
-        terminal = done.bool().any(dim=1)
-        oob_now = info["out_of_bounds"]
-        timeout = self.steps_in_ep == L
-        episode_over = terminal | timeout
-        cut = torch.ones_like(episode_over) if epoch_ended else episode_over
-        if not fast:
-            put(buf.cut, cut.unsqueeze(1).to(torch.uint8).expand(N, A).contiguous())
-        self.stat.update(next_obs[..., 0])
-        self.obs.copy_(next_obs)
-        boot = cut if epoch_ended else timeout                                # train.py:462-487: one more ac.step for the value
-        xb = self._x(self.obs)
-        locb = self.bank.predict(xb, mask=boot)
-        for a, ag in self.agents.items():
-            if self._kstep:
-                ag.policy_step_hip(xb[:, a].contiguous(), locb[:, a].contiguous(), self.h[a], value=g.k_f[a, 2])
-                continue
-            _, vb, _ = ag.agent.policy_step(xb[:, a], locb[:, a], self.h[a])
-            self._row_f[2, :, a] = torch.where(boot, vb, torch.zeros_like(vb))
-        if fast:
-            # PPOBuffer.store for the whole lock-step; before the reset moves the sources of the envs that start a new episode
-            # (the env's live rows, not the glue's copies: nothing has reset them yet)
-            buf.store_rows(ti, g.k_act, g.k_f, x, env.state("src_x"), env.state("src_y"), rew, cut.view(torch.uint8), boot.view(torch.uint8),
-                           g.stream())
-        else:
-            put(buf.last_val, self._row_f[2])
-        acc.step_and_episodes(oob_now, done, self.ep_ret, self.steps_in_ep, episode_over)     # before the reset rewrites the env's rows
-        if epoch_ended:
-            env.set_epoch_end()
-        self.stat.reset(cut)
-        obs_r, *_ = env.reset(cut)
-        self.obs.copy_(obs_r)
-        self.ep_ret.masked_fill_(cut.unsqueeze(1), 0.0)
-        self.steps_in_ep.masked_fill_(cut, 0)
-        self.stat.update(self.obs[..., 0], mask=cut)
-        if not epoch_ended:
-            self._reset_hidden(cut)                                           # train.py:505-518
-        ti.add_(1)
+        loc = self.bank.step(x)                                                                # PFGRU (K11), carried particle sets
+        self._policy_round(x, loc, self._u, None)
+        env.step(self._act8)
+        g.post_step(epoch_ended, st)
+        g.reset_on_side(epoch_ended)                                                           # beside everything up to join_reset()
+        locb = self.bank.step(xb, mask8=boot)                                                  # train.py:462-487: one more ac.step for the value
+        self._policy_round(xb, locb, None, boot)
+        g.store_rows(st)
+        g.stats()
+        g.join_reset()
+        g.post_reset(not epoch_ended, st)
+        if not epoch_ended:                                                                    # train.py:505-518 (reset_hidden)
+            self.bank.restart(cut)
+            self._h0_reset(cut)
 
     @torch.no_grad()
     def collect(self) -> Dict[str, torch.Tensor]:
@@ -1497,9 +1424,8 @@ class RNNCollector:
 
     def _warm_up(self) -> None:
         """Library warm-up (GEMM handles) outside the capture."""
-        x = self._x(self.obs)
         for a, ag in self.agents.items():
-            ag.agent.policy_step(x[:, a], torch.zeros(self.N, 2, device=x.device), self.h[a])
+            ag.agent.policy_step(self.obs[:, a], torch.zeros(self.N, 2, device=self.obs.device), self.h[a])
         if self.bank.impl == "hip":                                           # (the library-op bank has no packed weights)
             self.bank._packed()
 

@@ -1017,6 +1017,45 @@ int rs_cnn_sized_team_step_head(const rs_cnn_head_params* actors, int32_t num_ag
                                 int64_t* act, float* logp_val_boot, int8_t* act8, const uint8_t* mask, float* y1_out,
                                 float* scratch, int64_t scratch_floats, int32_t num_envs, rs_stream_t stream);
 
+/* ---- The env's look-ahead and the gradient-search baseline on top of it (radiation_ppo_amd/evaluate.py:
+ * run_test_environments_gradient_search; csrc/rs_lookahead.hpp, csrc/rs_lookahead.hip).
+ *
+ * rs_peek: RadSearch.FIM_step (rad_search_env.py:1768-1799) for every agent of every env and all eight moves in one launch, one lane
+ * per (env, agent, move), with the measurement a step to the candidate position would take.  For move k of agent a of env n:
+ *   start = from_xy[n][a] where given, else the agent's position; tent = start + get_step(k) (:205-224); blocked = tent outside the bbox
+ *   by take_action's own test under enforced boundaries (:917-925) or in_obstruction(tent) (:935-937); no collision rule -- FIM_step
+ *   passes proposed_coordinates = [] (:1789), the rule of rs_step's single-int form 16 + a; xy = blocked ? start : tent, moved = !blocked.
+ *   lam is the rate at xy computed fresh as agent_step computes it for an agent that has moved (:486-512): shortest path, Euclidean
+ *   distance r, is_intersect; bkg if intersected, else I / r + bkg (I / r^2 + bkg under falloff 1); r == 0 is taken as 1 and no error
+ *   bit is set.  meas = Poisson(lam) from the env's serial sampler: key (seed, global env id), counter (candidate index, step index of
+ *   the NEXT rs_step, episode, 128 + 8 a + k) -- streams 128..191, the step and episode words rs_action_uniforms uses.  lam and meas
+ *   are computed for an unmoved candidate too (at its start); the gradient search ignores them.
+ * NOTHING in the env changes: positions, out-of-bounds counts, flags, distances, error bits, step and episode counters and the output
+ * rows are as before, and an rs_step after a peek returns the same bits as one without it.  (The reference's take_action bumps
+ * out_of_bounds_count and sets the blocking flag even in a look-ahead.)
+ *   from_xy [N][A][2] or NULL; xy [N][A][8][2]; moved [N][A][8]; lam [N][A][8] or NULL; meas [N][A][8] or NULL
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL handle, xy or moved. */
+int rs_peek(rs_handle* h, const int32_t* from_xy, int32_t* xy, uint8_t* moved, double* lam, int64_t* meas, rs_stream_t stream);
+
+/* rs_gs_eval_step: the policy round of the gradient-search controller (GradSearch.step, algos/test_environment/eval/core.py:636-653;
+ * 'gs' in eval/test_policy.py:73-108) for every agent of every lane in one launch: rs_peek's look-ahead, bit for bit (both kernels run
+ * one lane function), then on a lane whose episode runs
+ *   g_k = moved_k ? (float)(((double)meas_k - (double)obs[n][a][0]) * 0.01 * q_rec) : 0.0f      (core.py:641-644; q_rec = 1 / q, :624)
+ * -- float64 arithmetic rounded once, what assigning a Python float into the reference's float32 `grad` tensor does -- and the action
+ * Categorical(softmax(g)).sample() (:649-653) as the inverse-CDF draw of the policy kernels (rs_action.hpp) from u[n][a].  A finished
+ * lane (alive[n] == 0) looks nowhere and gets act8 = 8 (idle) and a gradient row of zeros.
+ * One difference from the reference: it decides "the move did not take place" by comparing observation coordinates (:641); this uses
+ * `moved`.  The two agree except under coord_noise, where the reference compares noisy coordinates and the test means nothing.
+ * One evaluation lock-step is rs_action_uniforms, rs_gs_eval_step, rs_step, rs_eval_post_step (its four Welford pointers NULL) on one
+ * stream.
+ *   obs [N][A][11]        the current observation (element 0: the reading at the agent's position)
+ *   u [N][A], alive [N]   the uniforms of rs_action_uniforms; alive[n] != 0 while lane n's episode runs
+ *   act8 [N][A]           rs_step's action rows
+ *   grad_out [N][A][8]    or NULL: the gradients (for tests)
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL handle, obs, u, alive or act8. */
+int rs_gs_eval_step(rs_handle* h, const float* obs, double q_rec, const float* u, const uint8_t* alive, int8_t* act8, float* grad_out,
+                    rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,28 @@ class RadSearchVec:
         _lib.check(self.lib.rs_action_uniforms(self._h, out.data_ptr(), self._stream()), "rs_action_uniforms")
         return out
 
+    def peek(self, from_xy: Optional[torch.Tensor] = None, lam: bool = True, meas: bool = True):
+        """The look-ahead of every agent over all eight moves (rs_peek; RadSearch.FIM_step, rad_search_env.py:1768-1799, batched):
+        returns (xy int32 [N,A,8,2], moved uint8 [N,A,8], lam float64 [N,A,8] or None, meas int64 [N,A,8] or None) -- the candidate
+        position of move k (the start where the move is blocked by an enforced wall or an obstruction; no collision rule), whether it
+        moved, the Poisson rate there and a measurement drawn from streams 128 + 8 a + k at the next step's counter.  from_xy
+        [N,A,2] int32: start from these coordinates instead of the agents' positions.  Nothing in the env changes.  The tensors are
+        buffers of this object, allocated once and overwritten by the next call."""
+        N, A = self.num_envs, self.number_agents
+        if from_xy is not None:
+            assert from_xy.dtype == torch.int32 and tuple(from_xy.shape) == (N, A, 2) and from_xy.is_contiguous() and from_xy.device == self.device
+            self._peek_keepalive = from_xy
+        if not hasattr(self, "_peek"):
+            with torch.cuda.device(self.device):
+                self._peek = (torch.zeros(N, A, 8, 2, dtype=torch.int32, device=self.device),
+                              torch.zeros(N, A, 8, dtype=torch.uint8, device=self.device),
+                              torch.zeros(N, A, 8, dtype=torch.float64, device=self.device),
+                              torch.zeros(N, A, 8, dtype=torch.int64, device=self.device))
+        xy, moved, lam_t, meas_t = self._peek
+        _lib.check(self.lib.rs_peek(self._h, _ptr(from_xy), xy.data_ptr(), moved.data_ptr(), lam_t.data_ptr() if lam else None,
+                                    meas_t.data_ptr() if meas else None, self._stream()), "rs_peek")
+        return xy, moved, (lam_t if lam else None), (meas_t if meas else None)
+
     def error_flags(self) -> int:
         f = C.c_uint32(0)
         _lib.check(self.lib.rs_error_flags(self._h, self._stream(), C.byref(f)), "rs_error_flags")
@@ -218,7 +240,8 @@ class RadSearch:
 
     Differences (documented in DESIGN.md): randomness comes from the library's Philox stream keyed by
     `seed` (an int, or derived from np_random) instead of the numpy Generator's own sequence;
-    render()/FIM_step are not part of the hot path and raise NotImplementedError."""
+    render() is not part of the hot path and raises NotImplementedError; FIM_step, the look-ahead, changes nothing in the
+    environment, where the reference's bumps the out-of-bounds count and the blocking flag."""
 
     metadata = {"render.modes": ["human"], "video.frames_per_second": 5}
     step_size = DET_STEP
@@ -289,6 +312,39 @@ class RadSearch:
 
     def get_agent_outOfBounds_count(self, id: int) -> int:
         return int(self._vec.state("oob_count")[id, 0].item())
+
+    @property
+    def agents(self) -> Dict[int, SimpleNamespace]:
+        """{id: agent} with the fields a look-ahead reads, `id` and `det_coords` (a tuple of floats, as src_coords): a snapshot of
+        the device state, not a handle on it."""
+        x, y = self._vec.state("x")[:, 0].tolist(), self._vec.state("y")[:, 0].tolist()
+        return {i: SimpleNamespace(id=i, det_coords=(float(x[i]), float(y[i]))) for i in range(self.number_agents)}
+
+    def FIM_step(self, agent, action: int, coords=None) -> Tuple[float, float]:
+        """rad_search_env.py:1768-1799: where `action` (0..7; 8 = idle) would put the detector of `agent` -- an id, or an entry of
+        `agents` -- from its position, or from `coords` (on the 1 cm lattice) where given, without moving it: take_action with no
+        proposed coordinates, so no collision rule; a move into an enforced wall or an obstruction returns the start.  Returns the
+        coordinates in det_coords' type.
+        One deliberate difference: the reference's take_action bumps out_of_bounds_count and sets the blocking flag even in a
+        look-ahead; here a look-ahead changes nothing in the environment (rs_peek)."""
+        i = int(getattr(agent, "id", agent))
+        if not 0 <= i < self.number_agents:
+            raise ValueError(f"no agent {i}")
+        assert type(action) == int and 0 <= action <= 8, "Action not an integer in 0..8."
+        start = None
+        if coords is not None:
+            if float(coords[0]) != int(coords[0]) or float(coords[1]) != int(coords[1]):
+                raise ValueError("coords must lie on the 1 cm lattice the environment samples from")
+            start = self._vec.state("x").new_zeros(1, self.number_agents, 2)
+            start[0, :, 0] = self._vec.state("x")[:, 0]
+            start[0, :, 1] = self._vec.state("y")[:, 0]
+            start[0, i, 0], start[0, i, 1] = int(coords[0]), int(coords[1])
+        if action == 8:                                                   # get_step(8) = (0, 0): taken or rolled back, the result is the start
+            x, y = (start[0, i] if start is not None else torch.stack([self._vec.state("x")[i, 0], self._vec.state("y")[i, 0]])).tolist()
+            return (float(x), float(y))
+        xy = self._vec.peek(start, lam=False, meas=False)[0]
+        x, y = xy[0, i, action].tolist()
+        return (float(x), float(y))
 
     def _tuple(self, outs):
         obs, rew, team, done, info = outs

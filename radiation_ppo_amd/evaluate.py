@@ -15,7 +15,9 @@ of up to 8 on 27 x 27 maps (csrc/rs_cnn.hip, csrc/rs_cnn_eval.hip), `run_test_en
 any side 8..256 (walls off: 147 x 147; csrc/rs_cnn_sized.hip, csrc/rs_cnn_eval.hip), `run_test_environments_team` for feed-forward agents and
 teams of up to 8 -- these three are fronts to one lock-step loop, `_run_lane_per_run_team` --, `run_test_environments_rnn_team` for recurrent (RAD-A2C) teams of 1 to 8 -- it holds the recurrent lock-step, fused in
 HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip) and composed; `run_test_environments_rnn` is its front for one agent, and
-`run_test_environments` sends a recurrent agent there --, `summarize` the result statistics
+`run_test_environments` sends a recurrent agent there --, `run_test_environments_gradient_search` the reference's non-learned
+gradient-search controller over the env's look-ahead (csrc/rs_lookahead.hip), a fourth front to `_run_lane_per_run_team` --,
+`summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
 """
 import ctypes as C
@@ -457,7 +459,8 @@ def run_test_environments_cnn(agents: Dict[int, Any], env_sets: Dict[str, tuple]
 def _run_lane_per_run_team(rounds, agents, env_sets, montecarlo_runs, steps_per_episode, team_mode, obstruction_count,
                            enforce_grid_boundaries, seed, device, return_actions, fused, welford, id_hint="", cuda_front="", setup=None,
                            **vec_kwargs):
-    """The loop under run_test_environments_team, run_test_environments_cnn_team and run_test_environments_cnn_team_sized: E * R lanes
+    """The loop under run_test_environments_team, run_test_environments_cnn_team, run_test_environments_cnn_team_sized and
+    run_test_environments_gradient_search (whose `agents` are placeholders: it has no networks): E * R lanes
     of one episode each; a lane ends when any agent's terminal flag rises or at steps_per_episode and then idles (rows of 8), its
     records frozen.  Ids other than 0..A-1 (id_hint ends that message) and, for the front named in cuda_front, a device that is not
     cuda are refused before the library is loaded or an environment is built.  setup(run), where given, runs right after the opening
@@ -741,6 +744,58 @@ def run_test_environments_team(agents: Dict[int, VecAgentPPO], env_sets: Dict[st
                                   falloff=falloff)
 
 
+def _gs_rounds(run, fused, q):
+    """The gradient-search policy round (GradSearch.step, algos/test_environment/eval/core.py:636-653).  fused: rs_gs_eval_step (the
+    look-ahead over 8 moves, the gradient, the draw, idle rows).  composed: rs_peek, then in torch the gradient in float64 rounded
+    once to float32, log-softmax, cumsum, compare and the idle rule."""
+    lib, vec, obs, N, u, alive, alive8, st = run.lib, run.vec, run.obs, run.N, run.u, run.alive, run.alive8, run.st
+    p = lambda t: t.data_ptr()
+    q_rec = 1 / q                                                 # core.py:624
+    if fused:
+        step, fixed = lib.rs_gs_eval_step, (vec._h, p(obs), q_rec, p(u), p(alive8))
+
+        def policy_round(a8):
+            _lib.check(step(*fixed, p(a8), None, st), "rs_gs_eval_step")
+    else:
+        def policy_round(a8):
+            _, moved, _, meas = vec.peek(lam=False)
+            g = ((meas.double() - obs[..., 0:1].double()) * 0.01 * q_rec).float()
+            g = torch.where(moved.bool(), g, torch.zeros_like(g))
+            cdf = torch.cumsum(torch.exp(torch.log_softmax(g, dim=-1)), dim=-1)
+            act = (cdf[..., :-1] <= u.unsqueeze(-1)).sum(dim=-1)
+            a8.copy_(torch.where(alive.view(N, 1), act, torch.full_like(act, 8)).to(torch.int8))      # finished episodes idle
+    return None, policy_round
+
+
+def run_test_environments_gradient_search(env_sets: Dict[str, tuple], number_of_agents: int = 1, q: float = 1.0, montecarlo_runs: int = 100,
+                                          steps_per_episode: int = 120, team_mode: str = "individual", obstruction_count: int = 0,
+                                          enforce_grid_boundaries: bool = True, seed: int = 0, device: str = "cuda:0",
+                                          return_actions: bool = False, falloff: str = "reference", fused: bool = True):
+    """The reference's gradient-search controller ('gs' in algos/test_environment/eval/test_policy.py:73-108; GradSearch,
+    eval/core.py:622-653) on saved test environments: the non-learned baseline the learned policies' success rates are reported
+    against.  At every step every agent looks ahead over the 8 moves, takes a measurement at each candidate position,
+    grad[k] = (meas_k - meas_now) * 0.01 / q (0 where the move is blocked by a wall or an obstruction) and samples its action from
+    softmax(grad).  q = 1e30 makes every gradient vanish (below 1e-24, so softmax(grad) is 1/8 eight times in float32) -- a uniform
+    random walk over the 8 moves, the second baseline this runner gives.
+    Teams of 1..8: every agent searches on its own (nothing is shared) and rs_step applies the real collision rule; an episode ends
+    when any agent's terminal flag rises or at steps_per_episode.  One lane per (saved environment, Monte-Carlo run); no statistics
+    buffer -- the controller reads raw counts.  team_mode "individual": agent 0's own reward is accumulated, otherwise the team reward.
+
+    fused=True: a lock-step is rs_action_uniforms, rs_gs_eval_step (look-ahead, gradient, draw, idle rows: one launch for every agent
+    of every lane), rs_step, rs_eval_post_step on one stream; the host reads the finished-lane count once every 16 lock-steps.
+    fused=False: the same lock-step composed from rs_peek and torch (gradient, log-softmax, cumsum, compare, idle rule) with the torch
+    bookkeeping: the A/B baseline.
+
+    "Blocked" is the look-ahead's own `moved` flag where the reference compares observation coordinates (core.py:641); the two agree
+    except under coord_noise.  Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps run, N, A] int8 log
+    of rs_step's action rows (8 where a lane had finished)."""
+    if not q > 0:
+        raise ValueError("q must be positive")
+    return _run_lane_per_run_team(lambda run, f: _gs_rounds(run, f, float(q)), {i: None for i in range(int(number_of_agents))}, env_sets,
+                                  montecarlo_runs, steps_per_episode, team_mode, obstruction_count, enforce_grid_boundaries, seed, device,
+                                  return_actions, fused, welford=False, falloff=falloff)
+
+
 def _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg) -> List[MonteCarloResults]:
     ep_len_c, ep_ret_c, suc = ep_len.cpu().numpy(), ep_ret.cpu().numpy(), success.cpu().numpy()
     i_c, b_c = inten.cpu().numpy(), bkg.cpu().numpy()
@@ -816,7 +871,8 @@ class evaluate_PPO:
     """evaluate_PPO (evaluate.py:581-643): `eval_kwargs` as the reference builds them in main.py -- test_env_path (directory of the
     saved sets), obstruction_count (0..7, not -1), snr ('none' | 'low' | 'med' | 'high'), episodes, montecarlo_runs, model_path
     (directory holding `<id>_agent*/actor.pt, critic.pt[, predictor.pt]` or `<id>_agent*/pyt_save/model.pt`),
-    actor_critic_architecture ('cnn' | 'rnn' | 'ff' / 'mlp'), number_of_agents, steps_per_episode, enforce_boundaries, team_mode, seed.
+    actor_critic_architecture ('cnn' | 'rnn' | 'ff' / 'mlp' | 'gs', the gradient-search baseline, which reads no model_path and takes
+    `q`, default 1.0), number_of_agents, steps_per_episode, enforce_boundaries, team_mode, seed.
     The set is read with the safe reader (radiation_ppo_amd.testsets); all episodes x runs advance in lock-step on the device."""
     eval_kwargs: Dict[str, Any]
 
@@ -894,6 +950,10 @@ class evaluate_PPO:
                                                                             carry_hidden_across_runs=carry, **common)
             else:
                 self.results, self.summary = run_test_environments_rnn(rnn_agent(0), sets, fused=None, carry_hidden_across_runs=carry, **common)
+        elif arch == "gs":
+            # the gradient-search baseline (eval/test_policy.py:73-108): no network, so no model_path is read
+            self.results, self.summary = run_test_environments_gradient_search(sets, number_of_agents=A, q=float(kw.get("q", 1.0)),
+                                                                               team_mode=kw.get("team_mode", "individual"), **common)
         elif A >= 2:
             # a feed-forward team: every agent's own network on its own rows (evaluate.py:305-331)
             team_mode = kw.get("team_mode", "individual")

@@ -1017,6 +1017,94 @@ int rs_cnn_sized_team_step_head(const rs_cnn_head_params* actors, int32_t num_ag
                                 int64_t* act, float* logp_val_boot, int8_t* act8, const uint8_t* mask, float* y1_out,
                                 float* scratch, int64_t scratch_floats, int32_t num_envs, rs_stream_t stream);
 
+/* ---- The bootstrap particle filter and the RID-FIM controller on top of it ('rid-fim' in algos/test_environment/eval/test_policy.py:
+ * 184-231, 573-574; ParticleFilter, FIC and ssp in eval/core.py:528-620, 655-764, 767-799; radiation_ppo_amd/bpf.py,
+ * radiation_ppo_amd/evaluate.py: run_test_environments_rid_fim; csrc/rs_bpf.hpp, csrc/rs_bpf.hip).  Declared ahead of the look-ahead
+ * entries, which stay the header's last two.  Everything is float64.
+ *
+ * Every (env, agent) pair = n * A + a runs a filter of its own over (intensity, x, y); nothing is shared between agents.  The state is
+ * the caller's, in device memory (handed over with rs_bpf_state_create):
+ *   xp [pairs][3][NP]     particles: intensity in the filter's units (x 1e4 in the measurement model), then x and y in cm
+ *   w, logw [pairs][NP]   normalised weights and their logarithms (-inf where w is 0, as np.log gives)
+ *   est [pairs][3]        xpHatMean (core.py:613-615); neff [pairs] the effective particle count of the last track
+ *   rdiv [pairs]          the controller's latch RDIV_FLAG (core.py:674, 758-759); rs_bpf_track with first != 0 sets it to 1
+ *   flags [pairs]         RS_BPF_RESAMPLED: the last track resampled; RS_BPF_ERR_SSP (sticky): the resampler's child counts did not
+ *                         add up to NP -- ssp's ValueError (core.py:796-798) --, the particles were left ungathered
+ *   scratch               rs_bpf_scratch_bytes(pairs, NP) bytes: a second particle buffer for the gather (the controller keeps each
+ *                         move's rates there) and the resampler's child counts.  The resampler's xi are computed where they are read. */
+#define RS_BPF_RESAMPLED 1
+#define RS_BPF_ERR_SSP 2
+#define RS_BPF_MAX_WINDOW 1024     /* interval[0] + interval[1] at most */
+
+/* Both objects are opaque host objects the library makes from the caller's values and pointers (the binding's record of the header's
+ * structs with fields is closed); the device memory behind a state stays the caller's.
+ * rs_bpf_params_create: the filter's and the controller's settings, in this order:
+ *   num_particles           NP >= 2, any (not only multiples of 64)
+ *   sigma_xy, sigma_I       proSigma = [noise_params[1], noise_params[0], noise_params[0]] (core.py:540): sigma_I = noise_params[1]
+ *   thresh                  resample where neff < thresh * NP (core.py:544, 573)
+ *   intensity[2], coord[2]  the uniform prior's box (core.py:556-557); host arrays, copied
+ *   alpha, fim_thresh       the Renyi order (not 1) and the latch's threshold (core.py:673-675)
+ *   interval[2]             candidate readings z = clip(x0 - interval[0], 1, inf) .. x0 + interval[1] - 1 (core.py:708); host array, copied
+ * RS_ERR_INVALID_ARG: a NULL pointer, NP < 2, a negative sigma or thresh, a prior box with hi < lo, alpha == 1 or nan, interval entries
+ * below 0 or their sum above RS_BPF_MAX_WINDOW.
+ * rs_bpf_state_create: num_pairs (N * A of the handle the calls are made with) and the device pointers listed above.
+ * RS_ERR_INVALID_ARG: a NULL pointer, num_pairs < 1. */
+typedef struct rs_bpf_params rs_bpf_params;
+typedef struct rs_bpf_state rs_bpf_state;
+int rs_bpf_params_create(int32_t num_particles, double sigma_xy, double sigma_I, double thresh, const double* intensity, const double* coord,
+                         double alpha, double fim_thresh, const int32_t* interval, rs_bpf_params** out);
+void rs_bpf_params_destroy(rs_bpf_params* p);
+int rs_bpf_state_create(int32_t num_pairs, double* xp, double* w, double* logw, double* est, double* neff, uint8_t* rdiv, uint32_t* flags,
+                        void* scratch, size_t scratch_bytes, rs_bpf_state** out);
+void rs_bpf_state_destroy(rs_bpf_state* s);
+
+/* bytes of a state's scratch for num_pairs filters of num_particles; 0 for num_pairs < 1 or num_particles < 2 */
+size_t rs_bpf_scratch_bytes(int32_t num_pairs, int32_t num_particles);
+
+/* rs_bpf_track: ParticleFilter.track (core.py:554-591) for every pair of a lane with alive[n] != 0; the state of the others is not touched.
+ *   first != 0: the uniform prior xp = lo + (hi - lo) u over intensity x coord x coord, w = 1 / NP, logw = log(1 / NP) (:556-561), rdiv = 1
+ *   else the process model (:598-601): x, y += sigma_xy z, intensity = max(intensity + sigma_I z, 0)
+ *   then the Poisson log-likelihood (:594-596, 603-607) of the reading k = obs[n][a][0] at the agent's position d (the handle's):
+ *     R = square(sqrt(|xp_xy - d|^2)), lam = rint(I 1e4 / R) + bkg (the env's own background rate), logw += xlogy(k, lam) - lgamma(k + 1) - lam
+ *   w = exp(logw - max), w /= sum, neff = rint(1 / sum w^2) (:569-571); where neff < thresh NP the reference's SSP resampler (ssp,
+ *   :767-799) operation for operation on NP - 1 uniforms, one lane per pair walking the chain, the gather, logw = 0 and the
+ *   likelihood and normalisation again (:573-579); then est = sum w xp (:615) and logw = log(w) (:588).
+ * Draws: Philox, key (seed, global env id), counter (slot, step index of the NEXT rs_step, episode, 192 + a).  Slot 2 p and 2 p + 1 are
+ * particle p's: the prior's three uniforms (words 0-1, 2-3 of the first block, 0-1 of the second), or the process model's three normals
+ * by Box-Muller in float64 (intensity and x from the first block's pair, y the cosine branch of the second's); slot 2 NP + k is the
+ * resampler's uniform k.  Sums are taken lane by lane, wave by wave in a fixed order, not in numpy's pairwise order.
+ *   obs [N][A][11], alive [N]
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL handle, params, state, obs or alive, num_pairs not the handle's N * A,
+ * scratch_bytes below rs_bpf_scratch_bytes(num_pairs, NP). */
+int rs_bpf_track(rs_handle* h, const rs_bpf_params* p, const rs_bpf_state* s, const float* obs, const uint8_t* alive, int32_t first,
+                 rs_stream_t stream);
+
+/* rs_ridfim_eval_step: FIC.optim_action with L = 1 (core.py:703-764) for every pair of a lane with alive[n] != 0, one launch.  For each
+ * of the eight moves the candidate position c is rs_peek's (the same lane function; a blocked move: the current position) and
+ *   J_fish = sum_p w_p (g0^2 s 1e10 + g1^2 s + g2^2 s),  I4 = I_p 1e4, d = c - xp_xy, den = |d|^2, g0 = 1 / den, g_xy = 2 d I4 / den^2,
+ *            s = 1 / (I4 / den + bkg)            -- trace(particle_FIM) with scale = diag(1e10, 1, 1) (:686-694; no rint there)
+ *   while rdiv[pair] == 1:  J = renyi_div (:696-701) over the candidate readings z above, x0 = obs[n][a][0], with the filter's rounded
+ *            rate lam_p at c:  p_z = sum_p w_p pmf(z; lam_p), p_za = sum_p w_p pmf(z; lam_p)^alpha,
+ *            J = 1 / (alpha - 1) sum_z p_z (log p_za - alpha log p_z);   with rdiv[pair] == 0:  J = J_fish.
+ * The action is the first index of the largest J (np.argmax); rdiv == 1 and max J > fim_thresh clears the latch (:758-759).
+ * A nan J (a particle exactly at a candidate position: lam = inf) is treated as np.argmax and np.max treat it: the first nan index
+ * is the action and the latch stays as it is.
+ * Two rules the reference leaves to IEEE accidents: a z whose p_z is 0 contributes 0 (the reference computes 0 * (-inf + inf) = nan
+ * there); and two moves with the same candidate position give bit-equal J (one code path, one reduction order for every move), so
+ * ties from blocked moves go to the lowest index, as the reference's do.
+ * pmf is evaluated as exp(xlogy(z, lam) - lgamma(z + 1) - lam) at every 16th reading and carried by pmf(z + 1) = pmf(z) lam / (z + 1),
+ * pmf(z + 1)^alpha = pmf(z)^alpha lam^alpha (z + 1)^-alpha in between.  A finished lane gets act8 = 8 and nothing else of it is written.
+ *   act8 [N][A]; J, J_fish [N][A][8] or NULL
+ * RS_ERR_INVALID_ARG, before anything is launched: what rs_bpf_track refuses, a NULL act8. */
+int rs_ridfim_eval_step(rs_handle* h, const rs_bpf_params* p, const rs_bpf_state* s, const float* obs, const uint8_t* alive, int8_t* act8,
+                        double* J, double* J_fish, rs_stream_t stream);
+
+/* rs_bpf_draws (for tests and the composed runner): the draws rs_bpf_track would consume at the env's present step, through the same
+ * device functions, for every pair:  prior_u [N][A][3][NP] uniforms in [0, 1), normals [N][A][3][NP] standard normals (intensity, x, y),
+ * resample_u [N][A][NP - 1]; any of the three may be NULL.
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL handle, num_particles < 2. */
+int rs_bpf_draws(rs_handle* h, int32_t num_particles, double* prior_u, double* normals, double* resample_u, rs_stream_t stream);
+
 /* ---- The env's look-ahead and the gradient-search baseline on top of it (radiation_ppo_amd/evaluate.py:
  * run_test_environments_gradient_search; csrc/rs_lookahead.hpp, csrc/rs_lookahead.hip).
  *

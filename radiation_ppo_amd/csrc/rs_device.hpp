@@ -40,6 +40,7 @@
 #define RS_STREAM_GEOM 64u
 #define RS_STREAM_NOISE 96u    // + agent id: the coordinate noise of the observation
 #define RS_STREAM_PEEK 128u    // + 8 * agent id + move: the look-ahead's measurement draws (rs_lookahead.hpp), 128..191
+#define RS_STREAM_BPF 192u     // + agent id: the particle filter's draws (rs_bpf.hpp); counter word 0 carries the particle / slot index
 
 // ---------------------------------------------------------------------------------------------
 // Kernel parameter block (passed by value as kernarg).  All arrays are SoA, env index fastest, so a

@@ -51,18 +51,26 @@ __device__ __forceinline__ void rs_peek_load_geo(const RsParams& P, int n, bool 
     g.r = lds_geo; g.stride = RS_PEEK_PAIRS; g.off = slot; g.n = no;
 }
 
-// The look-ahead of env n, agent a, move k (0..7) from (x, y).  Reads the env's state, writes nothing.
+// The candidate position of move k (0..7) from (x, y) alone -- what the RID-FIM controller needs of the look-ahead (rs_bpf.hip) --:
+// true where the move takes place.
 template <bool HAS_OBS>
-__device__ __forceinline__ RsPeek rs_lookahead_lane(const RsParams& P, const RsGeo& g, int n, int a, int k, int x, int y) {
-    const int sx = P.src_x[n], sy = P.src_y[n], intensity = P.intensity[n], bkg = P.bkg[n];
-    const uint32_t episode = P.episode[n] - 1u, t = P.tstep[n];
+__device__ __forceinline__ bool rs_lookahead_xy(const RsParams& P, const RsGeo& g, int k, int x, int y, int& cx, int& cy) {
     int dx, dy; rs_action_step(k, dx, dy);
     const int tx = x + dx, ty = y + dy;
     bool blocked = false;
     if (P.enforce) blocked = (tx < P.bx0 || ty < P.by0) || (P.bx1 <= tx || P.by1 <= ty);
     if (HAS_OBS && g.n > 0 && rs_in_obstruction(g, tx, ty)) blocked = true;
+    cx = blocked ? x : tx; cy = blocked ? y : ty;
+    return !blocked;
+}
+
+// The look-ahead of env n, agent a, move k (0..7) from (x, y).  Reads the env's state, writes nothing.
+template <bool HAS_OBS>
+__device__ __forceinline__ RsPeek rs_lookahead_lane(const RsParams& P, const RsGeo& g, int n, int a, int k, int x, int y) {
+    const int sx = P.src_x[n], sy = P.src_y[n], intensity = P.intensity[n], bkg = P.bkg[n];
+    const uint32_t episode = P.episode[n] - 1u, t = P.tstep[n];
     RsPeek r;
-    r.x = blocked ? x : tx; r.y = blocked ? y : ty; r.moved = !blocked;
+    r.moved = rs_lookahead_xy<HAS_OBS>(P, g, k, x, y, r.x, r.y);
     const double euc = rs_dist_i(r.x, r.y, sx, sy);
     const double sp = (HAS_OBS && g.n > 0) ? rs_shortest_path<1>(g, P.dsrc, P.N, n, sx, sy, r.x, r.y, 0) : euc;
     const bool inter = (HAS_OBS && g.n > 0) ? rs_is_intersect<1>(g, r.x, r.y, sx, sy, euc, sp, 0) : false;

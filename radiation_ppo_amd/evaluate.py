@@ -17,6 +17,8 @@ teams of up to 8 -- these three are fronts to one lock-step loop, `_run_lane_per
 HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip) and composed; `run_test_environments_rnn` is its front for one agent, and
 `run_test_environments` sends a recurrent agent there --, `run_test_environments_gradient_search` the reference's non-learned
 gradient-search controller over the env's look-ahead (csrc/rs_lookahead.hip), a fourth front to `_run_lane_per_run_team` --,
+`run_test_environments_rid_fim` the reference's bootstrap particle filter with the RID-FIM controller (csrc/rs_bpf.hip,
+radiation_ppo_amd/bpf.py), a fifth --,
 `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
 """
@@ -796,6 +798,109 @@ def run_test_environments_gradient_search(env_sets: Dict[str, tuple], number_of_
                                   return_actions, fused, welford=False, falloff=falloff)
 
 
+def _rid_fim_rounds(run, fused, bpf_kwargs, loc_err):
+    """The RID-FIM lock-step's two rounds over one BootstrapParticleFilter per (lane, agent) (radiation_ppo_amd/bpf.py).  before():
+    ParticleFilter.track on the current reading -- the first call of a run draws the prior and sets the latch --, then, where loc_err
+    (a dict) is given, the squared distance of agent 0's estimate from the source is added to the lane's sum.  policy_round:
+    FIC.optim_action.  fused: rs_bpf_track and rs_ridfim_eval_step; composed: rs_bpf_draws, rs_peek and float64 torch ops."""
+    from .bpf import BootstrapParticleFilter
+    bpf = BootstrapParticleFilter(run.vec, **bpf_kwargs)
+    obs, alive, alive8 = run.obs, run.alive, run.alive8
+    track, act = (bpf.track, bpf.act) if fused else (bpf.track_composed, bpf.act_composed)
+    calls = [0]
+    if loc_err is not None:
+        src = torch.stack([run.vec.state("src_x").view(-1), run.vec.state("src_y").view(-1)], dim=-1).double()
+        loc_err.update(sq=torch.zeros(run.N, dtype=torch.float64, device=run.dev), n=torch.zeros(run.N, dtype=torch.float64, device=run.dev),
+                       last=torch.zeros(run.N, dtype=torch.float64, device=run.dev))
+
+    def before():
+        track(obs, alive8, calls[0] == 0)
+        calls[0] += 1
+        if loc_err is not None:
+            d2 = ((bpf.estimate[:, 0, 1:] - src) ** 2).sum(dim=-1)
+            loc_err["sq"] += torch.where(alive, d2, torch.zeros_like(d2))
+            loc_err["n"] += alive.double()
+            loc_err["last"].copy_(torch.where(alive, d2.sqrt(), loc_err["last"]))
+
+    def policy_round(a8):
+        act(obs, alive8, a8)
+    run.bpf = bpf
+    return before, policy_round
+
+
+def run_test_environments_rid_fim(env_sets: Dict[str, tuple], number_of_agents: int = 1, montecarlo_runs: int = 100, steps_per_episode: int = 120,
+                                  team_mode: str = "individual", obstruction_count: int = 0, enforce_grid_boundaries: bool = True,
+                                  seed: int = 0, device: str = "cuda:0", return_actions: bool = False, falloff: str = "reference",
+                                  fused: bool = True, lanes_per_pass: int = None, return_estimates: bool = False, **bpf_kwargs):
+    """The reference's information-driven baseline ('rid-fim' in algos/test_environment/eval/test_policy.py:184-231; FIC and
+    ParticleFilter, eval/core.py:528-620, 655-764) on saved test environments: every agent runs a bootstrap particle filter over
+    (intensity, x, y) on its own readings and moves where the Renyi divergence of the predicted readings -- after the latch has
+    fallen, the trace of the particles' Fisher information -- is largest.  A lock-step is rs_action_uniforms (unused: the controller
+    draws no action), the filter's track on the current reading, the controller round, rs_step and the bookkeeping, on
+    _run_lane_per_run_team like the gradient search: one lane per (saved environment, Monte-Carlo run), teams of 1..8 with nothing
+    shared between agents, no statistics buffer.  bpf_kwargs go to BootstrapParticleFilter (nParticles, noise_params, thresh, intensity,
+    coord, alpha, fim_thresh, interval; the reference's values by default).
+
+    fused=True: rs_bpf_track and rs_ridfim_eval_step, one launch each for every agent of every lane.  fused=False: the same lock-step
+    composed from rs_bpf_draws, rs_peek and float64 torch ops with the torch bookkeeping: the A/B baseline (its resampler walks the
+    chain one batched torch step per particle).
+
+    The filter's measurement model is the inverse-square law I 1e4 / R^2 + bkg (core.py:594-596), while the env's reference falloff is
+    I / r (rad_search_env.py:501): under falloff="reference" -- the default, as for every runner -- the filter is mis-specified, as it is
+    in the reference, and does not localise; falloff="inverse_square" is the env the filter models.
+
+    One difference from the reference, on purpose: it rebuilds only the filter between runs (test_policy.py:230-231, 493) and lets the
+    controller's latch RDIV_FLAG leak from one run into the next; here every run starts with a fresh filter AND the latch set.
+
+    At 6000 particles a pair's state takes about 0.4 MB, so the saved environments are run in passes of at most lanes_per_pass lanes
+    (whole environments, so a given lanes_per_pass below montecarlo_runs is refused; default: what a third of the free device memory holds, one environment at least) and the results are concatenated; every lane keeps
+    the Philox key of its place in the whole set, so the split does not change a result.
+
+    Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps, N, A] int8 action log (rows of 8 where a lane
+    had finished; passes that stopped early are padded with 8); with return_estimates also a dict of per-lane float64 arrays:
+    "rmse", the root of the mean squared distance of agent 0's estimates from the source over the lane's steps (the reference's
+    LocEstErr, test_policy.py:444, without its initial prior-mean entry), and "final", the distance of the last estimate."""
+    A, R = int(number_of_agents), int(montecarlo_runs)
+    if not 1 <= A <= _lib.RS_MAX_AGENTS:
+        raise ValueError(f"number_of_agents must be in 1..{_lib.RS_MAX_AGENTS}")
+    if torch.device(device).type != "cuda":
+        raise ValueError("run_test_environments_rid_fim needs a cuda device")
+    NP = int(bpf_kwargs.get("nParticles", 6000))
+    if NP < 2:
+        raise ValueError("nParticles must be at least 2")
+    if lanes_per_pass is not None and lanes_per_pass < R:
+        raise ValueError("lanes_per_pass must hold one environment's runs at least (montecarlo_runs lanes): a pass runs whole environments")
+    from .bpf import BootstrapParticleFilter
+    if lanes_per_pass is None:
+        free = torch.cuda.mem_get_info(torch.device(device))[0]
+        lanes_per_pass = max(1, int(free // 3 // (BootstrapParticleFilter.bytes_per_pair(NP) * A)))
+    keys = sorted(env_sets, key=lambda k: int(k.split("_")[1]))
+    per = max(1, int(lanes_per_pass) // R)                        # the free-memory default may be below R: one environment is the minimum
+    results, logs, est = [], [], {"rmse": [], "final": []}
+    for e0 in range(0, len(keys), per):
+        part = {f"env_{i}": env_sets[k] for i, k in enumerate(keys[e0:e0 + per])}
+        loc = {} if return_estimates else None
+        out = _run_lane_per_run_team(lambda run, f: _rid_fim_rounds(run, f, bpf_kwargs, loc), {i: None for i in range(A)}, part, R,
+                                     steps_per_episode, team_mode, obstruction_count, enforce_grid_boundaries, seed, device, return_actions,
+                                     fused, welford=False, falloff=falloff, env_id_base=e0 * R)
+        for res, k in zip(out[0], keys[e0:e0 + per]):
+            res.id = int(k.split("_")[1])
+        results += out[0]
+        if return_actions:
+            logs.append(out[2])
+        if return_estimates:
+            est["rmse"].append((loc["sq"] / loc["n"].clamp(min=1.0)).sqrt().cpu().numpy())
+            est["final"].append(loc["last"].cpu().numpy())
+    ret = [results, summarize(results)]
+    if return_actions:
+        L = max(l.shape[0] for l in logs)
+        logs = [np.concatenate([l, np.full((L - l.shape[0],) + l.shape[1:], 8, dtype=np.int8)]) for l in logs]
+        ret.append(np.concatenate(logs, axis=1))
+    if return_estimates:
+        ret.append({k: np.concatenate(v) for k, v in est.items()})
+    return tuple(ret)
+
+
 def _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg) -> List[MonteCarloResults]:
     ep_len_c, ep_ret_c, suc = ep_len.cpu().numpy(), ep_ret.cpu().numpy(), success.cpu().numpy()
     i_c, b_c = inten.cpu().numpy(), bkg.cpu().numpy()
@@ -872,7 +977,8 @@ class evaluate_PPO:
     saved sets), obstruction_count (0..7, not -1), snr ('none' | 'low' | 'med' | 'high'), episodes, montecarlo_runs, model_path
     (directory holding `<id>_agent*/actor.pt, critic.pt[, predictor.pt]` or `<id>_agent*/pyt_save/model.pt`),
     actor_critic_architecture ('cnn' | 'rnn' | 'ff' / 'mlp' | 'gs', the gradient-search baseline, which reads no model_path and takes
-    `q`, default 1.0), number_of_agents, steps_per_episode, enforce_boundaries, team_mode, seed.
+    `q`, default 1.0 | 'rid-fim', the particle-filter baseline, which reads no model_path either and takes BootstrapParticleFilter's
+    parameters), number_of_agents, steps_per_episode, enforce_boundaries, team_mode, seed.
     The set is read with the safe reader (radiation_ppo_amd.testsets); all episodes x runs advance in lock-step on the device."""
     eval_kwargs: Dict[str, Any]
 
@@ -954,6 +1060,11 @@ class evaluate_PPO:
             # the gradient-search baseline (eval/test_policy.py:73-108): no network, so no model_path is read
             self.results, self.summary = run_test_environments_gradient_search(sets, number_of_agents=A, q=float(kw.get("q", 1.0)),
                                                                                team_mode=kw.get("team_mode", "individual"), **common)
+        elif arch == "rid-fim":
+            # the information-driven baseline (eval/test_policy.py:184-231): no network, so no model_path is read
+            bpf = {k: kw[k] for k in ("nParticles", "noise_params", "thresh", "intensity", "coord", "alpha", "fim_thresh", "interval") if k in kw}
+            self.results, self.summary = run_test_environments_rid_fim(sets, number_of_agents=A, team_mode=kw.get("team_mode", "individual"),
+                                                                       falloff=kw.get("falloff", "reference"), **common, **bpf)
         elif A >= 2:
             # a feed-forward team: every agent's own network on its own rows (evaluate.py:305-331)
             team_mode = kw.get("team_mode", "individual")

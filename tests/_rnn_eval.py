@@ -1,10 +1,8 @@
 """What the two GPU suites of the RAD-A2C evaluation share (tests/test_rnn_eval_gpu.py: one agent, through the rs_rnn_eval_* entries
-and run_test_environments_rnn; tests/test_rnn_team_eval_gpu.py: teams): the seeded agents, the state of the two bookkeeping kernels
-with their torch composition, and the comparisons of records and of a carried-hidden log against the oracle.  One agent is the team
-of one throughout: [N][1] rows.  torch and the package are imported inside the functions that run on the device."""
+and run_test_environments_rnn; tests/test_rnn_team_eval_gpu.py: teams): the seeded agents and the state of the two bookkeeping kernels
+with their torch composition.  (The comparisons of records and of a carried-hidden log against the oracle: tests/_eval_runs.py.)  One
+agent is the team of one throughout: [N][1] rows.  torch and the package are imported inside the functions that run on the device."""
 import ctypes as C
-
-import numpy as np
 
 DEV = "cuda:0"
 
@@ -130,49 +128,3 @@ def same(k, t, what=""):
     import torch
     for (name, a), b in zip(k.arrays().items(), t.arrays().values()):
         assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), (what, name, (a != b).nonzero()[:6].tolist())
-
-
-def same_records(res_a, res_b, runs):
-    assert len(res_a) == len(res_b)
-    for a, b in zip(res_a, res_b):
-        assert a.id == b.id and a.completed_runs == b.completed_runs == runs and a.success_counter == b.success_counter
-        assert a.total_episode_length == b.total_episode_length
-        for x, y in ((a.successful, b.successful), (a.unsuccessful, b.unsuccessful)):
-            assert x.episode_length == y.episode_length and x.episode_return == y.episode_return
-            assert x.intensity == y.intensity and x.background_intensity == y.background_intensity
-
-
-def replays_through_the_oracle(sets, results, actions, seed, obst, R, L):
-    """A carried-hidden run's log, actions [lock-steps, E, A], replayed lane by lane through the oracle -- refresh_environment, every
-    agent's logged action, refresh again ... -- a run ending when any agent's flag rises or at L, returns from individual_reward[0]:
-    the same lengths and success flags in run order, returns within 1e-4 (tests/test_evaluate_gpu.py's tolerance).  An idle row (8)
-    ends a lane's replay: the policy draws 0..7."""
-    from oracle.radsearch_oracle import PhiloxDraws, RadSearchOracle
-    A = actions.shape[2]
-    for e, res in enumerate(results):
-        s = sets[f"env_{e}"]
-        rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]]
-        ref = RadSearchOracle(PhiloxDraws(seed, e), number_agents=A, obstruction_count=obst, enforce_grid_boundaries=True)
-        ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-        lens, rets, sucs = [], [], []
-        ret, steps = np.float32(0.0), 0
-        t_end = actions.shape[0]
-        for t in range(actions.shape[0]):
-            if actions[t, e, 0] == 8:
-                t_end = t
-                break
-            o, rew, done, _ = ref.step({a: int(actions[t, e, a]) for a in range(A)})
-            ret = np.float32(ret + np.float32(rew["individual_reward"][0]))
-            steps += 1
-            found = any(done[a] for a in range(A))
-            if found or steps == L:
-                lens.append(steps); rets.append(float(ret)); sucs.append(bool(found))
-                ret, steps = np.float32(0.0), 0
-                ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-        assert (actions[t_end:, e] == 8).all(), e                   # a lane with every run behind it idles to the end
-        assert len(lens) == R and res.total_episode_length == lens, (e, lens, res.total_episode_length)
-        assert res.success_counter == sum(sucs)
-        assert res.successful.episode_length == [l for l, k in zip(lens, sucs) if k]
-        assert res.unsuccessful.episode_length == [l for l, k in zip(lens, sucs) if not k]
-        assert np.allclose(res.successful.episode_return, [r for r, k in zip(rets, sucs) if k], atol=1e-4)
-        assert np.allclose(res.unsuccessful.episode_return, [r for r, k in zip(rets, sucs) if not k], atol=1e-4)

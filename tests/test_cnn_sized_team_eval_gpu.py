@@ -26,6 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
 import _cnn_sized_team_ref as S  # noqa: E402
+import _eval_runs as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SENTINEL = -12345.678
@@ -369,36 +370,13 @@ def _sets(E, obst, seed, near=(0,)):
 
 
 def _replay(sets, results, actions, A, R, seed, obst, team_mode, near=(0,)):
-    """every lane through the oracle, walls off, with the logged joint actions: the same last step, success flag and return; finished
-    lanes log 8.  The runs of the `near` environments end (at the first lock-step in which an agent moves), no other run ends."""
-    from oracle.radsearch_oracle import PhiloxDraws, RadSearchOracle
-    for e, res in enumerate(results):
-        s = sets[f"env_{e}"]
-        rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]] if obst else None
-        for r in range(R):
-            n = e * R + r
-            ref = RadSearchOracle(PhiloxDraws(seed, n), number_agents=A, obstruction_count=obst, enforce_grid_boundaries=False)
-            ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-            ret, steps, found = np.float32(0.0), 0, False
-            for t in range(actions.shape[0]):
-                o, rew, done, _ = ref.step({i: int(actions[t, n, i]) for i in range(A)})
-                rr = rew["individual_reward"][0] if team_mode == "individual" else rew["team_reward"]
-                ret = np.float32(ret + np.float32(rr))
-                steps += 1
-                if any(done.values()):
-                    found = True
-                    break
-            assert found == (e in near) and (found or steps == L_RUN), (e, r, steps, found)
-            assert res.total_episode_length[r] == steps, (e, r)
-            bucket = res.successful if found else res.unsuccessful
-            assert steps in bucket.episode_length, (e, r)
-            assert any(abs(v - float(ret)) < 1e-4 for v in bucket.episode_return), (e, r, float(ret), bucket.episode_return)
-            assert (actions[:steps, n] < 8).all() and (actions[steps:, n] == 8).all(), (e, r)      # a finished lane idles
-    assert sum(r.success_counter for r in results) == len(near) * R
-
-
-def _records(results):
-    return [(r.id, r.success_counter, r.total_episode_length, r.successful.episode_return, r.unsuccessful.episode_return) for r in results]
+    """every lane through the oracle, walls off, with the logged joint actions: the same last step, success flag and return in run
+    order; finished lanes log 8 (tests/_eval_runs.py).  The runs of the `near` environments end (at the first lock-step in which an
+    agent moves), no other run ends."""
+    runs = V.replay_lane_per_run(sets, actions, A, R, L_RUN, seed, obst, team_mode=team_mode, enforce_grid_boundaries=False)
+    for n, (steps, found, _) in enumerate(runs):
+        assert found == (n // R in near) and (found or steps == L_RUN), (n, steps, found)
+    assert V.check_records(results, runs, R) == len(near) * R
 
 
 @pytest.mark.parametrize("A,team_mode", [(2, "individual"), (2, "team"), (4, "individual"), (4, "team")])
@@ -418,7 +396,8 @@ def test_fused_run_replays_through_the_oracle_and_equals_the_composed_run(A, tea
     _replay(sets, results, actions, A, R, RUN_SEEDS["run"], obst, team_mode)
     res_c, sum_c, act_c = run_test_environments_cnn_team_sized(agents, sets, fused=False, **kw)
     assert act_c.shape == actions.shape and np.array_equal(act_c, actions)
-    assert _records(res_c) == _records(results) and sum_c["success_rate"] == summary["success_rate"]
+    V.same_records(res_c, results, R)
+    assert sum_c["success_rate"] == summary["success_rate"]
 
 
 def test_the_scratch_bound_does_not_change_the_records():
@@ -434,7 +413,8 @@ def test_the_scratch_bound_does_not_change_the_records():
     assert actions.shape == (L_RUN, 132, A) and (actions[0] < 8).all() and (actions[-1, :R] == 8).all() and (actions[:, R:] < 8).all()
     for fused in (True, False):
         res_s, _, act_s = run_test_environments_cnn_team_sized(agents, sets, a2_bytes=1, fused=fused, **kw)
-        assert np.array_equal(act_s, actions) and _records(res_s) == _records(results), fused
+        assert np.array_equal(act_s, actions), fused
+        V.same_records(res_s, results, R)
 
 
 def test_the_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
@@ -442,16 +422,9 @@ def test_the_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
     16 lock-steps: 16 rows, rows 1..15 idle, in both forms (steps_per_episode = 20: 47 x 47 maps)."""
     from radiation_ppo_amd.evaluate import run_test_environments_cnn_team_sized
     E, R = 3, 4
-    sets = {f"env_{i}": (np.array([1350.0, 1350.0]), np.array([1353.0, 1354.0]), 2_000_000 + 1000 * i, 20 + i) for i in range(E)}
     agents = _agents(1, 11, side=47)
-    for fused in (True, False):
-        results, summary, actions = run_test_environments_cnn_team_sized(agents, sets, montecarlo_runs=R, steps_per_episode=20, seed=5,
-                                                                         enforce_grid_boundaries=False, return_actions=True, fused=fused)
-        assert actions.shape == (16, E * R, 1), (fused, actions.shape)
-        assert (actions[0] < 8).all() and (actions[1:] == 8).all()
-        assert summary["completed_runs"] == E * R and summary["success_rate"] == 1.0
-        for res in results:
-            assert res.success_counter == R and res.total_episode_length == [1] * R and res.unsuccessful.episode_length == []
+    V.check_stops_at_the_sixteenth(lambda sets, fused: run_test_environments_cnn_team_sized(
+        agents, sets, montecarlo_runs=R, steps_per_episode=20, seed=5, enforce_grid_boundaries=False, return_actions=True, fused=fused), E, R, 1)
 
 
 def test_the_runner_without_predictor_and_its_refusals():
@@ -464,8 +437,9 @@ def test_the_runner_without_predictor_and_its_refusals():
         results, summary, actions = run_test_environments_cnn_team_sized(agents, sets, use_predictor=False, return_actions=True, fused=fused,
                                                                          **kw)
         assert summary["completed_runs"] == 4 and actions.shape == (L_RUN, 4, 2)
-        out[fused] = (actions, _records(results))
-    assert np.array_equal(out[True][0], out[False][0]) and out[True][1] == out[False][1]
+        out[fused] = (actions, results)
+    assert np.array_equal(out[True][0], out[False][0])
+    V.same_records(out[True][1], out[False][1], 2)
     results, summary = run_test_environments_cnn_team_sized(agents, sets, **kw)                  # no log: one fixed action buffer
     assert summary["completed_runs"] == 4
     with pytest.raises(ValueError, match="run_test_environments_cnn"):

@@ -21,6 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
 import _cnn_team_ref as T  # noqa: E402
+import _eval_runs as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SENTINEL = -12345.678
@@ -232,45 +233,12 @@ def _agents(A, seed, scale=1.0):
     return agents
 
 
-def _replay(sets, results, actions, A, R, seed, obst, team_mode):
-    """every lane through the oracle with the logged joint actions: the same last step, success flag and return; finished lanes log 8"""
-    from oracle.radsearch_oracle import PhiloxDraws, RadSearchOracle
-    n_success = 0
-    for e, res in enumerate(results):
-        s = sets[f"env_{e}"]
-        rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]] if obst else None
-        for r in range(R):
-            n = e * R + r
-            ref = RadSearchOracle(PhiloxDraws(seed, n), number_agents=A, obstruction_count=obst, enforce_grid_boundaries=True)
-            ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-            ret, steps, found = np.float32(0.0), 0, False
-            for t in range(actions.shape[0]):
-                o, rew, done, _ = ref.step({i: int(actions[t, n, i]) for i in range(A)})
-                rr = rew["individual_reward"][0] if team_mode == "individual" else rew["team_reward"]
-                ret = np.float32(ret + np.float32(rr))
-                steps += 1
-                if any(done.values()):
-                    found = True
-                    break
-            assert res.total_episode_length[r] == steps, (e, r)
-            n_success += int(found)
-            bucket = res.successful if found else res.unsuccessful
-            assert steps in bucket.episode_length, (e, r)
-            assert any(abs(v - float(ret)) < 1e-4 for v in bucket.episode_return), (e, r, float(ret), bucket.episode_return)
-            assert (actions[:steps, n] < 8).all() and (actions[steps:, n] == 8).all(), (e, r)      # a finished lane idles
-    assert sum(r.success_counter for r in results) == n_success
-    return n_success
-
-
-def _records(results):
-    return [(r.id, r.success_counter, r.total_episode_length, r.successful.episode_return, r.unsuccessful.episode_return) for r in results]
-
-
 @pytest.mark.parametrize("team_mode", ["individual", "team"])
 def test_fused_run_replays_through_the_oracle_and_equals_the_composed_run(team_mode):
-    """2 agents, E = 4, R = 3, L = 30, 2 obstructions.  (a) every lane of the fused run replays through the oracle, both outcomes are
-    among the lanes; (b) the composed form gives the same action log and the same records.  The BLAS first layer rounds differently
-    from the MFMA one, so a seed could in principle put a uniform between the two paths' CDF steps; these seeds do not."""
+    """2 agents, E = 4, R = 3, L = 30, 2 obstructions.  (a) every lane of the fused run replays through the oracle (the same last step,
+    success flag and return in run order, finished lanes log 8: tests/_eval_runs.py), both outcomes are among the lanes; (b) the
+    composed form gives the same action log and the same records.  The BLAS first layer rounds differently from the MFMA one, so a
+    seed could in principle put a uniform between the two paths' CDF steps; these seeds do not."""
     from radiation_ppo_amd.evaluate import run_test_environments_cnn_team, sample_test_environments
     E, R, L, A, obst = 4, 3, 30, 2, 2
     sets = sample_test_environments(E, obstruction_count=obst, seed=RUN_SEEDS["sets"])
@@ -278,11 +246,12 @@ def test_fused_run_replays_through_the_oracle_and_equals_the_composed_run(team_m
     kw = dict(montecarlo_runs=R, steps_per_episode=L, team_mode=team_mode, obstruction_count=obst, seed=RUN_SEEDS["run"], return_actions=True)
     results, summary, actions = run_test_environments_cnn_team(agents, sets, fused=True, **kw)
     assert len(results) == E and summary["completed_runs"] == E * R and actions.shape[1:] == (E * R, A) and actions.dtype == np.int8
-    n_success = _replay(sets, results, actions, A, R, RUN_SEEDS["run"], obst, team_mode)
+    n_success = V.check_records(results, V.replay_lane_per_run(sets, actions, A, R, L, RUN_SEEDS["run"], obst, team_mode=team_mode), R)
     assert 0 < n_success < E * R, n_success
     res_c, sum_c, act_c = run_test_environments_cnn_team(agents, sets, fused=False, **kw)
     assert act_c.shape == actions.shape and np.array_equal(act_c, actions)
-    assert _records(res_c) == _records(results) and sum_c["success_rate"] == summary["success_rate"]
+    V.same_records(res_c, results, R)
+    assert sum_c["success_rate"] == summary["success_rate"]
 
 
 def test_fused_run_of_four_agents_replays_and_equals_the_composed_run():
@@ -292,10 +261,11 @@ def test_fused_run_of_four_agents_replays_and_equals_the_composed_run():
     agents = _agents(A, RUN_SEEDS["torch"], RUN_SCALE)
     kw = dict(montecarlo_runs=R, steps_per_episode=L, obstruction_count=obst, seed=RUN_SEEDS["run"], return_actions=True)
     results, summary, actions = run_test_environments_cnn_team(agents, sets, fused=True, **kw)
-    n_success = _replay(sets, results, actions, A, R, RUN_SEEDS["run"], obst, "individual")
+    n_success = V.check_records(results, V.replay_lane_per_run(sets, actions, A, R, L, RUN_SEEDS["run"], obst), R)
     assert 0 < n_success < E * R, n_success
     res_c, _, act_c = run_test_environments_cnn_team(agents, sets, fused=False, **kw)
-    assert np.array_equal(act_c, actions) and _records(res_c) == _records(results)
+    assert np.array_equal(act_c, actions)
+    V.same_records(res_c, results, R)
 
 
 def test_the_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
@@ -304,16 +274,9 @@ def test_the_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
     reads the finished-lane count every 16 lock-steps: 16 rows, rows 1..15 idle, in both forms."""
     from radiation_ppo_amd.evaluate import run_test_environments_cnn_team
     E, R = 3, 4
-    sets = {f"env_{i}": (np.array([1350.0, 1350.0]), np.array([1353.0, 1354.0]), 2_000_000 + 1000 * i, 20 + i) for i in range(E)}
     agents = _agents(1, 11)
-    for fused in (True, False):
-        results, summary, actions = run_test_environments_cnn_team(agents, sets, montecarlo_runs=R, steps_per_episode=40, seed=5,
-                                                                   return_actions=True, fused=fused)
-        assert actions.shape == (16, E * R, 1), (fused, actions.shape)
-        assert (actions[0] < 8).all() and (actions[1:] == 8).all()
-        assert summary["completed_runs"] == E * R and summary["success_rate"] == 1.0
-        for res in results:
-            assert res.success_counter == R and res.total_episode_length == [1] * R and res.unsuccessful.episode_length == []
+    V.check_stops_at_the_sixteenth(lambda sets, fused: run_test_environments_cnn_team(
+        agents, sets, montecarlo_runs=R, steps_per_episode=40, seed=5, return_actions=True, fused=fused), E, R, 1)
 
 
 def test_the_runner_without_predictor_and_its_refusals():
@@ -326,8 +289,9 @@ def test_the_runner_without_predictor_and_its_refusals():
     for fused in (True, False):
         results, summary, actions = run_test_environments_cnn_team(agents, sets, use_predictor=False, return_actions=True, fused=fused, **kw)
         assert summary["completed_runs"] == 4 and actions.shape == (6, 4, 2)
-        out[fused] = (actions, _records(results))
-    assert np.array_equal(out[True][0], out[False][0]) and out[True][1] == out[False][1]
+        out[fused] = (actions, results)
+    assert np.array_equal(out[True][0], out[False][0])
+    V.same_records(out[True][1], out[False][1], 2)
     results, summary = run_test_environments_cnn_team(agents, sets, **kw)                       # no log: one fixed action buffer
     assert summary["completed_runs"] == 4
     with pytest.raises(ValueError, match="run_test_environments_cnn"):

@@ -2,12 +2,13 @@
 every (saved environment, Monte-Carlo run) episode is replayed through the oracle -- refresh_environment, then the logged
 actions -- and must end at the same step with the same success flag and return; the per-environment records add up."""
 import os
+import sys
 
-import numpy as np
 import pytest
 import torch
 
-from oracle.radsearch_oracle import PhiloxDraws, RadSearchOracle
+sys.path.insert(0, os.path.dirname(__file__))
+import _eval_runs as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -28,33 +29,8 @@ def test_monte_carlo_evaluation_matches_oracle_replay(obst, arch):
     results, summary, actions = run_test_environments(agent, sets, montecarlo_runs=R, steps_per_episode=L, obstruction_count=obst,
                                                       seed=seed, return_actions=True)
     assert len(results) == E and summary["completed_runs"] == E * R
-    n_success = 0
-    for e, res in enumerate(results):
-        assert res.id == e and res.completed_runs == R and len(res.total_episode_length) == R
-        assert len(res.successful.episode_length) == res.success_counter
-        assert len(res.successful.episode_length) + len(res.unsuccessful.episode_length) == R
-        s = sets[f"env_{e}"]
-        rects = None
-        if obst:
-            rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]]
-        for r in range(R):
-            n = e * R + r
-            ref = RadSearchOracle(PhiloxDraws(seed, n), number_agents=1, obstruction_count=obst, enforce_grid_boundaries=True)
-            ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-            ret, steps, found = np.float32(0.0), 0, False
-            for t in range(actions.shape[0]):
-                o, rew, done, _ = ref.step({0: int(actions[t, n])})
-                ret = np.float32(ret + np.float32(rew["individual_reward"][0]))
-                steps += 1
-                if done[0]:
-                    found = True
-                    break
-            assert res.total_episode_length[r] == steps, (e, r)
-            bucket = res.successful if found else res.unsuccessful
-            n_success += int(found)
-            assert steps in bucket.episode_length
-            assert any(abs(v - float(ret)) < 1e-4 for v in bucket.episode_return), (e, r, float(ret), bucket.episode_return)
-    assert sum(r.success_counter for r in results) == n_success
+    # the feed-forward log is int64 and keeps the unused draws of finished lanes: no idle rule
+    n_success = V.check_records(results, V.replay_lane_per_run(sets, actions, 1, R, L, seed, obst, idle_rule=False), R)
     assert abs(summary["success_rate"] - n_success / (E * R)) < 1e-9
 
 
@@ -72,25 +48,7 @@ def test_cnn_monte_carlo_evaluation_matches_oracle_replay(team_mode):
     results, summary, actions = run_test_environments_cnn(agents, sets, montecarlo_runs=R, steps_per_episode=L, team_mode=team_mode,
                                                           obstruction_count=obst, seed=seed, return_actions=True)
     assert len(results) == E and summary["completed_runs"] == E * R and len(summary["scenarios"]) == E
-    for e, res in enumerate(results):
-        s = sets[f"env_{e}"]
-        rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]]
-        for r in range(R):
-            n = e * R + r
-            ref = RadSearchOracle(PhiloxDraws(seed, n), number_agents=A, obstruction_count=obst, enforce_grid_boundaries=True)
-            ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-            ret, steps, found = np.float32(0.0), 0, False
-            for t in range(actions.shape[0]):
-                o, rew, done, _ = ref.step({i: int(actions[t, n, i]) for i in range(A)})
-                rr = rew["individual_reward"][0] if team_mode == "individual" else rew["team_reward"]
-                ret = np.float32(ret + np.float32(rr))
-                steps += 1
-                if any(done.values()):
-                    found = True
-                    break
-            assert res.total_episode_length[r] == steps, (e, r)
-            bucket = res.successful if found else res.unsuccessful
-            assert any(abs(v - float(ret)) < 1e-4 for v in bucket.episode_return), (e, r, float(ret), bucket.episode_return)
+    V.check_records(results, V.replay_lane_per_run(sets, actions, A, R, L, seed, obst, team_mode=team_mode), R)
     again = summarize(results)
     assert again["success_rate"] == summary["success_rate"]
     q = summary["success_count_weighted_quantiles"]
@@ -174,25 +132,4 @@ def test_sequential_runs_carry_the_hidden_state_like_the_reference(monkeypatch):
                                                          carry_hidden_across_runs=True, return_actions=True)
     assert calls["h0"] == 1 and calls["bank_reset"] == 1 and calls["stat_reset"] == actions.shape[0]
     assert summary["completed_runs"] == E * R
-    for e, res in enumerate(results):
-        s = sets[f"env_{e}"]
-        rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]]
-        ref = RadSearchOracle(PhiloxDraws(seed, e), number_agents=1, obstruction_count=obst, enforce_grid_boundaries=True)
-        ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-        lens, rets, sucs = [], [], []
-        ret, steps = np.float32(0.0), 0
-        for t in range(actions.shape[0]):
-            if actions[t, e] == 8:                              # idle: the lane has no run going
-                break
-            o, rew, done, _ = ref.step({0: int(actions[t, e])})
-            ret = np.float32(ret + np.float32(rew["individual_reward"][0]))
-            steps += 1
-            if done[0] or steps == L:
-                lens.append(steps); rets.append(float(ret)); sucs.append(bool(done[0]))
-                ret, steps = np.float32(0.0), 0
-                ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-        assert len(lens) == R and res.total_episode_length == lens, (e, lens, res.total_episode_length)
-        assert res.success_counter == sum(sucs)
-        assert res.successful.episode_length == [l for l, k in zip(lens, sucs) if k]
-        assert np.allclose(res.successful.episode_return, [r for r, k in zip(rets, sucs) if k], atol=1e-4)
-        assert np.allclose(res.unsuccessful.episode_return, [r for r, k in zip(rets, sucs) if not k], atol=1e-4)
+    V.check_records(results, V.replay_carried(sets, actions[:, :, None], seed, obst, R, L), R)

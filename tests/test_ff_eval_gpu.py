@@ -4,12 +4,14 @@ both bit for bit; the fused run against the composed one; every lane of a team's
 the device-side finished-lane count; and the evaluate_PPO driver, which loads every agent of a feed-forward team."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from oracle.radsearch_oracle import PhiloxDraws, RadSearchOracle
+sys.path.insert(0, os.path.dirname(__file__))
+import _eval_runs as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -163,12 +165,7 @@ def test_fused_run_equals_the_composed_run(A, obst):
     assert act_f.dtype == np.int8 and act_f.shape[1:] == (E * R, A) and 1 <= act_f.shape[0] <= 40
     assert np.array_equal(act_f, act_c)
     assert len(res_f) == len(res_c) == E and sum_f["completed_runs"] == E * R
-    for a, b in zip(res_f, res_c):
-        assert a.id == b.id and a.completed_runs == b.completed_runs == R and a.success_counter == b.success_counter
-        assert a.total_episode_length == b.total_episode_length
-        for x, y in ((a.successful, b.successful), (a.unsuccessful, b.unsuccessful)):
-            assert x.episode_length == y.episode_length and x.episode_return == y.episode_return
-            assert x.intensity == y.intensity and x.background_intensity == y.background_intensity
+    V.same_records(res_f, res_c, R)
     assert sum_f["success_rate"] == sum_c["success_rate"]
 
 
@@ -179,37 +176,14 @@ REPLAY = [(2, 77, 7), (3, 11, 321)]
 @pytest.mark.parametrize("A,set_seed,seed", REPLAY, ids=[f"A{c[0]}" for c in REPLAY])
 def test_team_monte_carlo_evaluation_matches_oracle_replay(A, set_seed, seed):
     """Every (environment, run) lane replayed through the oracle -- refresh_environment, then the logged joint actions -- ends at the
-    same step with the same success flag and agent 0's accumulated float32 return within 1e-4 (the tolerance and the form of
-    test_cnn_monte_carlo_evaluation_matches_oracle_replay)."""
+    same step with the same success flag and agent 0's accumulated float32 return within 1e-4, in run order; a finished lane idles
+    (tests/_eval_runs.py)."""
     from radiation_ppo_amd.evaluate import sample_test_environments
     E, R, L, obst = 6, 5, 40, 2
     sets = sample_test_environments(E, obstruction_count=obst, seed=set_seed)
     results, summary, actions = _run(_team(A), sets, obst, seed, True)
     assert len(results) == E and summary["completed_runs"] == E * R
-    n_success = 0
-    for e, res in enumerate(results):
-        s = sets[f"env_{e}"]
-        rects = [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]]
-        assert len(res.successful.episode_length) == res.success_counter
-        for r in range(R):
-            n = e * R + r
-            ref = RadSearchOracle(PhiloxDraws(seed, n), number_agents=A, obstruction_count=obst, enforce_grid_boundaries=True)
-            ref.refresh_environment(s[0], s[1], s[2], s[3], rects)
-            ret, steps, found = np.float32(0.0), 0, False
-            for t in range(min(actions.shape[0], L)):
-                o, rew, done, _ = ref.step({i: int(actions[t, n, i]) for i in range(A)})
-                ret = np.float32(ret + np.float32(rew["individual_reward"][0]))
-                steps += 1
-                if any(done.values()):
-                    found = True
-                    break
-            assert res.total_episode_length[r] == steps, (e, r)
-            n_success += int(found)
-            bucket = res.successful if found else res.unsuccessful
-            assert steps in bucket.episode_length, (e, r)
-            assert any(abs(v - float(ret)) < 1e-4 for v in bucket.episode_return), (e, r, float(ret), bucket.episode_return)
-            assert (actions[steps:, n] == 8).all(), (e, r)         # a finished lane idles
-    assert sum(r.success_counter for r in results) == n_success
+    n_success = V.check_records(results, V.replay_lane_per_run(sets, actions, A, R, L, seed, obst), R)
     assert 0 < n_success < E * R, n_success
 
 
@@ -218,15 +192,7 @@ def test_the_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
     lock-step 1 whatever is drawn.  (One agent: two agents that start on one spot and draw the same direction collide, neither moves,
     and a terminal flag is only raised by a move.)  The host reads the finished-lane count every 16 lock-steps: 16 rows, rows 1..15 idle."""
     E, R, A = 3, 4, 1
-    sets = {f"env_{i}": (np.array([1350.0, 1350.0]), np.array([1353.0, 1354.0]), 2_000_000 + 1000 * i, 20 + i) for i in range(E)}
-    for fused in (True, False):
-        results, summary, actions = _run(_team(A), sets, 0, 5, fused, R=R)
-        assert actions.shape == (16, E * R, A), (fused, actions.shape)
-        assert (actions[0] < 8).all() and (actions[1:] == 8).all()
-        assert summary["completed_runs"] == E * R and summary["success_rate"] == 1.0
-        for res in results:
-            assert res.success_counter == R and res.total_episode_length == [1] * R and res.successful.episode_length == [1] * R
-            assert res.unsuccessful.episode_length == []
+    V.check_stops_at_the_sixteenth(lambda sets, fused: _run(_team(A), sets, 0, 5, fused, R=R), E, R, A)
 
 
 def test_the_runner_refuses_agent_ids_that_are_not_0_to_a_minus_1():

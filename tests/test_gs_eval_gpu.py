@@ -13,6 +13,7 @@ import torch
 from oracle.radsearch_oracle import PhiloxDraws, RadSearchOracle
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _eval_runs as V  # noqa: E402
 import _lookahead_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -75,40 +76,25 @@ def test_gs_eval_step_matches_the_reference_controller(N, A):
     assert np.array_equal(g[live].view(np.uint32), rgrad[:N][live].view(np.uint32))
 
 
-def _rects(s):
-    return [(int(o[0][:, 0].min()), int(o[0][:, 1].min()), int(o[0][:, 0].max()), int(o[0][:, 1].max())) for o in s[4]]
-
-
 _REPLAYS = {}
 
 
 def _replay(sets, actions, A, obst, seed, q, R_, L):
-    """Every lane's logged actions followed in the oracle.  Returns per lane (steps, found, return) and the counts (draws, draws where
-    the reference controller chose another action, of those the ones not near a CDF edge); the same log is replayed once."""
+    """Every lane's logged actions followed in the oracle (tests/_eval_runs.py).  Returns per lane (steps, found, return) and the
+    counts [draws, draws where the reference controller chose another action, of those the ones not near a CDF edge]; the same log is
+    replayed once."""
     key = (A, obst, seed, q, actions.tobytes())
     if key in _REPLAYS:
         return _REPLAYS[key]
-    lanes, draws, differ, unexplained = [], 0, 0, 0
-    for e in range(len(sets)):
-        s = sets[f"env_{e}"]
-        for r in range(R_):
-            n = e * R_ + r
-            ref = RadSearchOracle(PhiloxDraws(seed, n), number_agents=A, obstruction_count=obst, enforce_grid_boundaries=True)
-            o = ref.refresh_environment(s[0], s[1], s[2], s[3], _rects(s) if obst else None)
-            ret, steps, found = np.float32(0.0), 0, False
-            for t in range(actions.shape[0]):
-                if found:
-                    assert (actions[t, n] == 8).all(), (n, t)
-                    continue
-                want, edge, _ = R.controller_action(ref, [float(np.float32(o[a][0])) for a in range(A)], R.action_uniforms(ref), q)
-                other = actions[t, n] != want
-                draws, differ, unexplained = draws + A, differ + int(other.sum()), unexplained + int((other & ~edge).sum())
-                o, rew, done, _ = ref.step({a: int(actions[t, n, a]) for a in range(A)})
-                ret = np.float32(ret + np.float32(rew["individual_reward"][0]))
-                steps += 1
-                found = any(done.values())
-            lanes.append((steps, found, float(ret)))
-    _REPLAYS[key] = (lanes, draws, differ, unexplained)
+    counts = np.zeros(3, dtype=np.int64)
+
+    def on_step(ref, o, t, n):
+        want, edge, _ = R.controller_action(ref, [float(np.float32(o[a][0])) for a in range(A)], R.action_uniforms(ref), q)
+        other = actions[t, n] != want
+        counts[:] += (A, int(other.sum()), int((other & ~edge).sum()))
+
+    lanes = V.replay_lane_per_run(sets, actions, A, R_, L, seed, obst, on_step=on_step)
+    _REPLAYS[key] = (lanes, *counts.tolist())
     return _REPLAYS[key]
 
 
@@ -125,16 +111,7 @@ def test_whole_runs_replay_through_the_oracle(obst, A, fused):
     lanes, draws, differ, unexplained = _replay(sets, actions, A, obst, seed, q, R_, L)
     print(f"obst={obst} A={A} fused={fused}: {differ} of {draws} logged actions differ from the float64 draw, {unexplained} away from a CDF edge")
     assert unexplained == 0 and differ <= CAP * draws
-    for e, res in enumerate(results):
-        assert res.id == e and res.completed_runs == R_
-        for r in range(R_):
-            steps, found, ret = lanes[e * R_ + r]
-            steps = min(steps, L)
-            assert res.total_episode_length[r] == steps, (e, r)
-            bucket = res.successful if found else res.unsuccessful
-            assert steps in bucket.episode_length
-            assert any(abs(v - ret) < 1e-4 for v in bucket.episode_return), (e, r, ret, bucket.episode_return)
-    assert sum(r.success_counter for r in results) == sum(f for _, f, _ in lanes)
+    V.check_records(results, lanes, R_)
 
 
 def test_the_controller_searches():

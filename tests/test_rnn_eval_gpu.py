@@ -3,7 +3,7 @@ evaluate.run_test_environments_rnn, a front to run_test_environments_rnn_team): 
 the entries that widen rs_rnn_eval_state to a team of one -- against the torch composition, bit for bit; the fused run against the
 composed one with carried and with fresh hidden states, at the default and at sized widths; the fused sequential run replayed through
 the oracle; the early stop on the device-side finished-lane count; the guard and the evaluate_PPO driver.  The shared pieces are in
-tests/_rnn_eval.py."""
+tests/_rnn_eval.py and tests/_eval_runs.py."""
 import ctypes as C
 import os
 import sys
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _eval_runs as V  # noqa: E402
 import _rnn_eval as H  # noqa: E402
 from _rnn_eval import DEV, WIDTHS, _args  # noqa: E402
 
@@ -127,7 +128,7 @@ def test_fused_run_equals_the_composed_run(widths, carry, obst):
     assert (act_f[common:] == 8).all() and (act_c[common:] == 8).all()
     assert int(act_f.min()) >= 0 and (act_f < 8).any()
     assert len(res_f) == len(res_c) == E and sum_f["completed_runs"] == sum_c["completed_runs"] == E * R
-    H.same_records(res_f, res_c, R)
+    V.same_records(res_f, res_c, R)
     assert sum_f["success_rate"] == sum_c["success_rate"]
     n_success = sum(r.success_counter for r in res_f)
     timed_out = sum(l == L for r in res_f for l in r.unsuccessful.episode_length)
@@ -151,15 +152,16 @@ def test_fused_sequential_run_replays_through_the_oracle(monkeypatch):
     results, summary, actions = _run(agent, sets, obst, seed, True, True)
     assert calls == {"h0": 1, "bank_reset": 1}
     assert summary["completed_runs"] == E * R and actions.shape[1] == E and 0 < sum(r.success_counter for r in results) < E * R
-    H.replays_through_the_oracle(sets, results, actions[:, :, None], seed, obst, R, L)
+    V.check_records(results, V.replay_carried(sets, actions[:, :, None], seed, obst, R, L), R)
 
 
 def test_the_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
     """The detector starts 5 cm from the source; a step moves at most 100 cm and the terminal radius is 110 cm, so every run ends at its
     first step whatever is drawn.  Carried hidden states: a lane's 4 runs take lock-steps 0..3; a lane per run: lock-step 0.  The host
-    reads the finished-lane count every 16 lock-steps: 16 rows, idle (8) from there on."""
+    reads the finished-lane count every 16 lock-steps: 16 rows, idle (8) from there on.  (The fused form alone, carried runs, a
+    [lock-steps, lanes] log: not the assertions of _eval_runs.check_stops_at_the_sixteenth.)"""
     Es, Rs = 3, 4
-    sets = {f"env_{i}": (np.array([1350.0, 1350.0]), np.array([1353.0, 1354.0]), 2_000_000 + 1000 * i, 20 + i) for i in range(Es)}
+    sets = V.near_sets(Es)
     agent = H.agent()
     for carry, busy in ((True, Rs), (False, 1)):
         results, summary, actions = _run(agent, sets, 0, 5, True, carry, runs=Rs, steps=40)

@@ -4,7 +4,7 @@ one K14 launch per agent, bit for bit; the two bookkeeping kernels against the t
 the composed one at the default and a sized width with both hidden-state lifetimes; one agent through the team runner against the
 records of the commit that still had a one-agent lock-step (tests/golden/rnn_eval_parent.npz); a carried-hidden fused run of two
 agents replayed through the oracle; the early stop on the device-side count; the refusals and the evaluate_PPO driver.  The shared
-pieces are in tests/_rnn_eval.py."""
+pieces are in tests/_rnn_eval.py and tests/_eval_runs.py."""
 import ctypes as C
 import os
 import sys
@@ -14,6 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _eval_runs as V  # noqa: E402
 import _k7_bits as K  # noqa: E402
 import _rnn_eval as H  # noqa: E402
 from _rnn_eval import DEV, WIDTHS, _args  # noqa: E402
@@ -174,7 +175,7 @@ def test_fused_run_equals_the_composed_run(A, widths, carry, obst):
     assert int(act_f.min()) >= 0 and (act_f < 8).any()
     assert ((act_f == 8).all(axis=2) | (act_f < 8).all(axis=2)).all()                     # a lane's agents idle together
     assert sum_f["completed_runs"] == sum_c["completed_runs"] == E * R and len(res_f) == E
-    H.same_records(res_f, res_c, R)
+    V.same_records(res_f, res_c, R)
     assert sum_f["success_rate"] == sum_c["success_rate"]
     n_success = sum(r.success_counter for r in res_f)
     timed_out = sum(l == L for r in res_f for l in r.unsuccessful.episode_length)
@@ -231,7 +232,7 @@ def test_fused_sequential_team_run_replays_through_the_oracle(monkeypatch):
     results, summary, actions = _run(team, sets, obst, seed, True, True)
     assert calls == {"h0": A, "bank_reset": 1}
     assert summary["completed_runs"] == E * R and actions.shape[1:] == (E, A) and 0 < sum(r.success_counter for r in results) < E * R
-    H.replays_through_the_oracle(sets, results, actions, seed, obst, R, L)
+    V.check_records(results, V.replay_carried(sets, actions, seed, obst, R, L), R)
 
 
 def test_the_team_run_stops_on_the_device_side_count_at_the_next_sixteenth_step():
@@ -239,9 +240,10 @@ def test_the_team_run_stops_on_the_device_side_count_at_the_next_sixteenth_step(
     first step in which an agent moves or idles unhindered -- its first step, unless the two stacked agents draw the same move: then
     both are refused and the env makes no terminal test (a second step is needed).  Every run is therefore a success after a step or
     two and a lane's at most 4 runs are over well inside 16 lock-steps.  A lane's rows hold actions for exactly as many lock-steps as
-    its runs took, then 8; the host reads the finished-lane count every 16 lock-steps: 16 rows."""
+    its runs took, then 8; the host reads the finished-lane count every 16 lock-steps: 16 rows.  (The fused form alone, two agents,
+    carried runs: not the assertions of _eval_runs.check_stops_at_the_sixteenth.)"""
     Es, Rs, A = 3, 4, 2
-    sets = {f"env_{i}": (np.array([1350.0, 1350.0]), np.array([1353.0, 1354.0]), 2_000_000 + 1000 * i, 20 + i) for i in range(Es)}
+    sets = V.near_sets(Es)
     team = H.team(A)
     for carry in (True, False):
         results, summary, actions = _run(team, sets, 0, 5, True, carry, runs=Rs, steps=40)

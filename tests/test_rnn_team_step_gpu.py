@@ -13,6 +13,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _eval_runs as V  # noqa: E402
 import _rnn_eval as H  # noqa: E402
 from _rnn_eval import DEV, WIDTHS, _args  # noqa: E402
 from test_ppo_gpu import SEED  # noqa: E402
@@ -248,7 +249,7 @@ def test_fused_sized_team_run_equals_the_composed_run_at_another_tier():
     assert (act_f[common:] == 8).all() and (act_c[common:] == 8).all()
     assert int(act_f.min()) >= 0 and (act_f < 8).any()
     assert sum_f["completed_runs"] == sum_c["completed_runs"] == E * R and len(res_f) == E
-    H.same_records(res_f, res_c, R)
+    V.same_records(res_f, res_c, R)
     assert sum_f["success_rate"] == sum_c["success_rate"]
     n_success = sum(r.success_counter for r in res_f)
     timed_out = sum(l == L for r in res_f for l in r.unsuccessful.episode_length)

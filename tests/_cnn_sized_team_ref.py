@@ -1,14 +1,14 @@
-"""The cases, the float64 reference and the host-side model of rs_cnn_sized_team_infer / rs_cnn_sized_team_eval_head
-(tests/test_cnn_sized_team_eval_gpu.py) and their CPU self-check (tests/test_cnn_sized_team_eval_cpu.py).
+"""The cases, the teams and the host-side model of the any-side RAD-TEAM (CNN) team kernels (tests/test_cnn_sized_team_eval_gpu.py,
+tests/test_cnn_sized_team_step_gpu.py, through tests/_cnn_team_drive.py) and their CPU self-check (tests/test_cnn_sized_team_eval_cpu.py).
 
-The rule is tests/_cnn_team_ref.py's (its docstring; ratios / passes / torch32 are reused from there) with the first layer's term taken
-at the case's depth: a dot product of depth flat = 16 P P behind the bias, K1 = 2 (sqrt(flat + 1) + 1).  At these depths the rule is
-loose -- the float32 torch composition sits at 0.07 of the y1 allowance at depth 256 and at 0.0003 at depth 85 264, a dropped tail of 4
-terms would pass --, which is why the GPU test also has an exact one-hot check of the first layer (onehot_ks)."""
+The rule is tests/_cnn_team_ref.py's, in its one copy there (its docstring; reference / value_ratios / ratios / passes / torch32), with
+the first layer's term taken at the case's depth: a dot product of depth flat = 16 P P behind the bias, K1 = k1(flat) =
+2 (sqrt(flat + 1) + 1).  At these depths the rule is loose -- the float32 torch composition sits at 0.07 of the y1 allowance at depth 256
+and at 0.0003 at depth 85 264, a dropped tail of 4 terms would pass --, which is why the GPU tests also have an exact one-hot check of the
+first layer, at the k listed here: onehot_ks (the evaluation head's wave quarters) and onehot_ks_sliced (the k-split step head's)."""
 import torch
 
 import _cnn_team_ref as T
-import _f64_ref as R
 
 DRAW_CAP = T.DRAW_CAP
 SCALE = T.SCALE
@@ -116,22 +116,7 @@ def trunk_cpu(t):
 
 def reference(seq, a2, u):
     """_cnn_team_ref.reference with K1 at a2's depth: the float64 policy round of one agent on a float32 a2 [N, flat] and u [N]."""
-    s64 = R.f64(seq)
-    K1 = k1(a2.shape[1])
-    r = T.Ref()
-    with torch.no_grad():
-        x = a2.detach().double().cpu()
-        W1, b1, W2, W3 = s64[6].weight, s64[6].bias, s64[8].weight, s64[10].weight
-        r.y1 = x @ W1.t() + b1
-        mag1 = x.abs() @ W1.abs().t() + b1.abs()
-        r.y1_allow = R.FF_RTOL * r.y1.abs() + K1 * R.U * mag1 + R.FF_TINY
-        r.lg, mag3, carried = R.cnn_head_f64(s64, r.y1)
-        through = (mag1 @ W2.abs().t()) @ W3.abs().t()
-        e_lg = R.FF_RTOL * r.lg.abs() + R.U * (K1 * through + R.HEAD_K2 * carried + R.HEAD_K3 * mag3) + R.FF_TINY
-        spread = r.lg.amax(dim=1) - r.lg.amin(dim=1)
-        r.act, r.lp, r.cdf = R.draw_f64(r.lg, u.cpu())
-        r.lp_allow = 2 * e_lg.amax(dim=1) + 2 * R.U * (9.8 + spread)
-    return r
+    return T.reference(seq, a2, u, k1(a2.shape[1]))
 
 
 ratios, passes, torch32, distinct_actions, alive_for, clone_seq = T.ratios, T.passes, T.torch32, T.distinct_actions, T.alive_for, T.clone_seq
@@ -151,4 +136,25 @@ def onehot_ks(P):
         if tail == 16:
             rel |= {32 * np_ + 7, 32 * np_ + 8}
         ks |= {w * kw + k for k in rel}
+    return sorted(ks)
+
+
+def onehot_ks_sliced(flat, sl):
+    """The k of the exact check of the k-split step head, from its slice length: in the first, a middle and the last slice, per wave
+    quarter (a quarter of the slice length, cut at the slice's end) its first and last float, 15 / 16, 31 / 32, the last float of its
+    whole pieces, the first and last float of a tail and 7 / 8 inside it; and both sides of every slice boundary."""
+    n_sl, q = -(-flat // sl), sl // 4
+    ks = set()
+    for s in sorted({0, n_sl // 2, n_sl - 1}):
+        L = min(sl, flat - s * sl)
+        for w in range(4):
+            lw = max(0, min(q, L - w * q))
+            np_, tail = lw // 32, lw % 32
+            rel = {0, lw - 1, 15, 16, 31, 32, 32 * np_ - 1}
+            if tail:
+                rel |= {32 * np_, 32 * np_ + 7, 32 * np_ + 8, 32 * np_ + tail - 1}
+            ks |= {s * sl + w * q + k for k in rel if 0 <= k < lw}
+    for s in range(1, n_sl):
+        ks |= {s * sl - 1, s * sl}
+    assert all(0 <= k < flat for k in ks) and {0, flat - 1} <= ks
     return sorted(ks)

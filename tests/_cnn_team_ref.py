@@ -1,6 +1,9 @@
-"""The float64 reference, the cases and the tolerance rule of rs_cnn_team_eval_head (tests/test_cnn_team_eval_gpu.py) and their CPU
-self-check (tests/test_cnn_team_eval_cpu.py).  The head behind the first layer and its rule are tests/_f64_ref.py's (cnn_head_f64,
-HEAD_K2, HEAD_K3, draw_f64); this module puts a float64 first layer in front of them.
+"""The float64 reference, the cases and the tolerance rule of the RAD-TEAM (CNN) team heads, in its one copy: reference() for the actor
+rows of rs_cnn_team_eval_head / rs_cnn_team_step_head and, with k1 at the case's depth (tests/_cnn_sized_team_ref.py: k1()), of their
+any-side twins; value_ratios() for the step heads' critic rows; both on first_layer().  The GPU suites reach the kernels through
+tests/_cnn_team_drive.py; the CPU self-checks are tests/test_cnn_team_eval_cpu.py and tests/test_cnn_team_drive_cpu.py.  The head behind
+the first layer and its rule are tests/_f64_ref.py's (cnn_head_f64, HEAD_K2, HEAD_K3, draw_f64); this module puts a float64 first layer
+in front of them.
 
 The rule.  a2 is the trunk's float32 output (an input here: exact, non-negative, sparse), U = 2^-24:
   y1        Linear(2704, 32): a dot product of depth 2704 behind the bias, whatever the order (one fmaf chain, four chains of 676 and
@@ -24,6 +27,7 @@ import torch
 
 import _f64_ref as R
 
+FLAT = 2704                                      # 16 x 13 x 13: the trunk's output on a 27 x 27 map
 K1 = 2.0 * (2705 ** 0.5 + 1)
 DRAW_CAP = 2
 SIZES = (1, 31, 32, 33, 63, 64, 65, 130)         # a 32-image MFMA tile, the 64-image workgroup and ragged tiles
@@ -67,7 +71,7 @@ def team(A):
         return _TEAMS[A]
     from radiation_ppo_amd.maps import CNNActor
     t = Team()
-    t.A = A
+    t.A, t.M, t.flat, t.N = A, 27, FLAT, MASTER
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(7100 + A)
         t.actors = [CNNActor() for _ in range(A)]
@@ -106,24 +110,52 @@ class Ref:
     pass
 
 
-def reference(seq, a2, u):
-    """The float64 policy round of one agent on a float32 a2 [N, 2704] (widened) and its uniforms u [N]: y1, logits, the draw, and
-    the allowances of the module docstring."""
+def first_layer(s64, a2, k1):
+    """The float64 first layer of the module s64 on a float32 a2 [N, flat] (widened), and what its error may be and become:
+    (y1, mag1, y1_allow, through), through = |W3| |W2| mag1, the factor of k1 U in the allowance of an output of the last layer."""
+    x = a2.detach().double().cpu()
+    W1, b1, W2, W3 = s64[6].weight, s64[6].bias, s64[8].weight, s64[10].weight
+    y1 = x @ W1.t() + b1
+    mag1 = x.abs() @ W1.abs().t() + b1.abs()
+    y1_allow = R.FF_RTOL * y1.abs() + k1 * R.U * mag1 + R.FF_TINY
+    return y1, mag1, y1_allow, (mag1 @ W2.abs().t()) @ W3.abs().t()
+
+
+def output_allow(out, through, carried, mag3, k1):
+    """the allowance of the last layer's outputs (logits, or a critic's value): the module docstring's E_lg"""
+    return R.FF_RTOL * out.abs() + R.U * (k1 * through + R.HEAD_K2 * carried + R.HEAD_K3 * mag3) + R.FF_TINY
+
+
+def reference(seq, a2, u, k1=K1):
+    """The float64 policy round of one agent on a float32 a2 [N, flat] (widened) and its uniforms u [N]: y1, logits, the draw, and
+    the allowances of the module docstring, the first layer's constant k1 that of a2's depth (K1: 2704)."""
     s64 = R.f64(seq)
     r = Ref()
     with torch.no_grad():
-        x = a2.detach().double().cpu()
-        W1, b1, W2, W3 = s64[6].weight, s64[6].bias, s64[8].weight, s64[10].weight
-        r.y1 = x @ W1.t() + b1
-        mag1 = x.abs() @ W1.abs().t() + b1.abs()
-        r.y1_allow = R.FF_RTOL * r.y1.abs() + K1 * R.U * mag1 + R.FF_TINY
+        r.y1, _, r.y1_allow, through = first_layer(s64, a2, k1)
         r.lg, mag3, carried = R.cnn_head_f64(s64, r.y1)
-        through = (mag1 @ W2.abs().t()) @ W3.abs().t()
-        e_lg = R.FF_RTOL * r.lg.abs() + R.U * (K1 * through + R.HEAD_K2 * carried + R.HEAD_K3 * mag3) + R.FF_TINY
+        e_lg = output_allow(r.lg, through, carried, mag3, k1)
         spread = r.lg.amax(dim=1) - r.lg.amin(dim=1)
         r.act, r.lp, r.cdf = R.draw_f64(r.lg, u.cpu())
         r.lp_allow = 2 * e_lg.amax(dim=1) + 2 * R.U * (9.8 + spread)         # + FF_RTOL |lp| where it is applied
     return r
+
+
+def value_ratios(seq_cpu, a2, got_v, got_y1, k1):
+    """A critic row of the step heads under the same lines: (worst |y1 - ref| / allowance, worst |value - ref| / allowance), the one
+    output held to the allowance reference() gives a logit."""
+    s64 = R.f64(seq_cpu)
+    with torch.no_grad():
+        y1, _, y1_allow, through = first_layer(s64, a2, k1)
+        val, mag3, carried = R.cnn_head_f64(s64, y1)
+        allow = output_allow(val, through, carried, mag3, k1)
+        gv, gy = got_v.detach().double().cpu().reshape(val.shape), got_y1.detach().double().cpu()
+        assert bool(torch.isfinite(gv).all()) and bool(torch.isfinite(gy).all())
+        return float(((gy - y1).abs() / y1_allow).max()), float(((gv - val).abs() / allow).max())
+
+
+def value_passes(q_y1, q_value):
+    return q_y1 <= 1.0 and q_value <= 1.0
 
 
 def ratios(r, u, alive, act, logp, act8, y1=None):

@@ -137,17 +137,17 @@ def _sized_actors(P, A, M):
 def cnn_team_inputs(P, A, C_):
     """actors' and critics' Sequentials on the CPU and a2 rows [A][N][flat], [C][N][flat]"""
     torch = _torch()
+    import _cnn_team_drive as D
     if P is None:
         import _cnn_team_ref as T
-        import test_cnn_team_step_gpu as G
         flat = 2704
         actors = [ac.actor for ac in T.team(A).actors]
-        critics = [m.critic for m in G._critics(C_, 7300 + A)]
+        critics = [m.critic for m in D.critics(C_, 7300 + A)]
     else:
         import test_cnn_sized_team_step_gpu as G
         flat, M = 16 * P * P, G._side(P)
         actors = [ac.actor for ac in _sized_actors(P, A, M)]
-        critics = [m.critic for m in G._critics(C_, 7400 + P, M)]
+        critics = [m.critic for m in D.critics(C_, 7400 + P, M)]
     g = torch.Generator().manual_seed(3000 + flat + 10 * A + C_)
     sparse = lambda rows: (torch.rand(rows, N, flat, generator=g) * A2_SCALE * (torch.rand(rows, N, flat, generator=g) < A2_DENSITY)).contiguous()
     return dict(actors=actors, critics=critics, a2a=sparse(A), a2c=sparse(C_), u=uniforms(A, g), flat=flat)
@@ -345,13 +345,13 @@ def _run_cnn_head(case, form, c):
 def _run_cnn_team(case, form, c):
     torch = _torch()
     from radiation_ppo_amd import _lib
-    import test_cnn_team_step_gpu as G
+    import _cnn_team_drive as D
     lib = _lib.load()
     P, A, nc = c["P"], c["A"], c["C"]
     i = cnn_team_inputs(P, A, nc)
     flat = i["flat"]
     actors, critics = [copy.deepcopy(s).cuda() for s in i["actors"]], [copy.deepcopy(s).cuda() for s in i["critics"]]   # shared teams stay on the CPU
-    pa, pc = G._params(actors), G._params(critics)
+    pa, pc = D.head_params(actors), D.head_params(critics)
     a2a, a2c, u = i["a2a"].cuda(), i["a2c"].cuda(), i["u"].cuda()
     mask = mask_cpu().cuda() if form == "mask" else None
     off = (mask == 0).nonzero().flatten() if form == "mask" else None

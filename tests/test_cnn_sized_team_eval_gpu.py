@@ -10,13 +10,15 @@ cell; the host-side model (_cnn_sized_team_ref.shortcut_units) says which units 
 
 rs_cnn_sized_team_eval_head at P = 4, 5, 14, 15, 16, 73 (wave quarters of 2 and 3 pieces, tails of 0, 16 and 4 floats, the walls-off
 depth 85 264): (1) one-hot rows of a2 must give y1 == float32(W1[j][k] + b1[j]) bit for bit at every edge k of the quarters, pieces,
-lane halves and tails; (2) the float64 rule of tests/_cnn_sized_team_ref.py on a2 from the trunk kernel, for the kernel and for the
-existing path (rs_cnn_sized_infer + BLAS linear + rs_cnn_head) on the same a2 bits.  Every worst ratio is printed;
+lane halves and tails; (2) the float64 rule of tests/_cnn_team_ref.py with K1 at the case's depth on a2 from the trunk kernel, for the
+kernel and for the existing path (rs_cnn_sized_infer + BLAS linear + rs_cnn_head) on the same a2 bits.  Every worst ratio is printed;
 profiles/cnn_sized_team_head_float64_ratios.txt keeps a copy.
+
+The trunk check, the guarded head call and the body of (2) are tests/_cnn_team_drive.py's, run here with SIZED; the 27 x 27 twin is
+tests/test_cnn_team_eval_gpu.py.  The lanes of the shortcut, the 147-side and resident-grid cases and (1) are this family's own.
 
 Whole runs, walls off, steps_per_episode = 8 (35 x 35 maps): every lane of a fused run replayed through the oracle, fused against
 composed, the scratch bound, the early stop, the arguments, the driver."""
-import ctypes as C
 import os
 import sys
 
@@ -26,48 +28,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
 import _cnn_sized_team_ref as S  # noqa: E402
+import _cnn_team_drive as D  # noqa: E402
 import _eval_runs as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -12345.678
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32).cpu()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _conv_params(seqs):
-    from radiation_ppo_amd import _lib
-    p = lambda t: t.data_ptr()
-    return (_lib.RsCnnConvParams * len(seqs))(*[_lib.RsCnnConvParams(p(s[0].weight), p(s[0].bias), p(s[3].weight), p(s[3].bias)) for s in seqs])
-
-
-def _head_params(seqs):
-    from radiation_ppo_amd import _lib
-    p = lambda t: t.data_ptr()
-    return (_lib.RsCnnHeadParams * len(seqs))(*[_lib.RsCnnHeadParams(p(s[6].weight), p(s[6].bias), p(s[8].weight), p(s[8].bias), p(s[10].weight),
-                                                                      p(s[10].bias)) for s in seqs])
-
-
-def _team_trunk(lib, maps, cells32, pcells32, seqs, out):
-    from radiation_ppo_amd import _lib
-    N, _, M, _ = maps.shape
-    _lib.check(lib.rs_cnn_sized_team_infer(maps.data_ptr(), cells32.data_ptr(), pcells32.data_ptr(), len(seqs), N, M, _conv_params(seqs),
-                                           out.data_ptr(), _stream()), "rs_cnn_sized_team_infer")
-    torch.cuda.synchronize()
-
-
-def _one_trunk(lib, maps, cells64, pcells64, A, a, seq, out):
-    from radiation_ppo_amd import _lib
-    N, _, M, _ = maps.shape
-    _lib.check(lib.rs_cnn_sized_infer(maps.data_ptr(), cells64.data_ptr(), pcells64.data_ptr(), A, a, N, M, seq[0].weight.data_ptr(),
-                                      seq[0].bias.data_ptr(), seq[3].weight.data_ptr(), seq[3].bias.data_ptr(), out.data_ptr(), _stream()),
-               "rs_cnn_sized_infer")
-    torch.cuda.synchronize()
 
 
 # ------------------------------------------------------------------------------------------------ the team trunk
@@ -114,39 +78,8 @@ def _lanes(M, A, N, seed):
     return maps[:N].contiguous(), cells[:N].contiguous(), pcells[:N].contiguous(), tags[:N]
 
 
-def _actors(A, M, seed):
-    from radiation_ppo_amd.maps import CNNActor
-    torch.manual_seed(seed)
-    seqs = [CNNActor(map_dim=(M, M)).cuda().actor for _ in range(A)]
-    with torch.no_grad():                                  # make biases matter (the shortcut's max(0 + b1, 0), pool ties, ReLU gates)
-        for s in seqs:
-            s[0].bias.uniform_(-0.05, 0.15)
-            s[3].bias.uniform_(-0.1, 0.1)
-    return seqs
-
-
 def _check_team_trunk(M, N, A, maps, cells, pcells):
-    from radiation_ppo_amd import _lib
-    lib = _lib.load()
-    seqs = _actors(A, M, 100 * N + A + M)
-    flat = 16 * (M // 2) ** 2
-    maps, cells, pcells = maps.cuda(), cells.cuda(), pcells.cuda()
-    G = 2 * flat                                           # guard rows on both sides of [A][N][flat]
-    buf = torch.full((G + A * N * flat + G,), SENTINEL, device="cuda")
-    _team_trunk(lib, maps, cells.int().contiguous(), pcells.int().contiguous(), seqs, buf[G:])
-    got = buf[G:G + A * N * flat].view(A, N, flat)
-    sent = _bits(torch.full((G,), SENTINEL, device="cuda"))
-    assert torch.equal(_bits(buf[:G]), sent) and torch.equal(_bits(buf[G + A * N * flat:]), sent), (M, N, A)
-    assert not bool((got == SENTINEL).any()), (M, N, A)    # every element written
-    for a in range(A):
-        want = torch.full((N, flat), SENTINEL, device="cuda")
-        _one_trunk(lib, maps, cells, pcells, A, a, seqs[a], want)
-        assert float(want.abs().max()) > 0 and bool(torch.isfinite(want).all())
-        bad = (_bits(got[a]) != _bits(want)).nonzero()
-        assert bad.numel() == 0, (M, N, A, a, bad[:4].tolist())
-    if A > 1:
-        assert not torch.equal(got[0], got[A - 1])         # the agents are told apart: their own weights and cell columns
-    return got
+    D.check_team_trunk(D.SIZED, "actor", D.actors(A, M, 100 * N + A + M), maps, cells, pcells)
 
 
 TRUNK_CASES = [(M, N, A) for M in (8, 31, 33, 35) for N in (1, 2, 5) for A in (1, 3, 8)]
@@ -207,132 +140,23 @@ def test_sized_team_trunk_with_more_units_than_the_resident_grid():
 
 
 # ------------------------------------------------------------------------------------------------ the head
-_MASTER = {}
-
-
-def _head(lib, seqs, flat, a2, u, alive, A, N, outputs=True):
-    """rs_cnn_sized_team_eval_head into sentinel-guarded buffers: dict(act8 [N, A], act [A, N], logp [A, N], y1 [A, N, 32]);
-    outputs=False: the three optional outputs NULL."""
-    from radiation_ppo_amd import _lib
-    act8 = torch.full((N + 2, A), -1, dtype=torch.int8, device="cuda")
-    act = torch.full((A * N + 2,), -1, dtype=torch.int64, device="cuda")
-    logp = torch.full((A * N + 2,), SENTINEL, device="cuda")
-    y1 = torch.full((A * N + 2, 32), SENTINEL, device="cuda")
-    o = (act[1:].data_ptr(), logp[1:].data_ptr(), y1[1:].data_ptr()) if outputs else (None, None, None)
-    _lib.check(lib.rs_cnn_sized_team_eval_head(_head_params(seqs), A, flat, a2.data_ptr(), u.data_ptr(), alive.data_ptr(), act8[1:].data_ptr(),
-                                               *o, N, _stream()), "rs_cnn_sized_team_eval_head")
-    torch.cuda.synchronize()
-    assert bool((act8[0] == -1).all()) and bool((act8[N + 1] == -1).all())          # the guards on both sides
-    assert int(act[0]) == -1 and int(act[-1]) == -1
-    for t in (logp[0], logp[-1], y1[0], y1[-1]):
-        assert torch.equal(_bits(t), _bits(torch.full_like(t, SENTINEL)))
-    if not outputs:
-        assert bool((act == -1).all()) and torch.equal(_bits(logp), _bits(torch.full_like(logp, SENTINEL)))
-    return dict(act8=act8[1:N + 1], act=act[1:A * N + 1].view(A, N), logp=logp[1:A * N + 1].view(A, N), y1=y1[1:A * N + 1].view(A, N, 32))
-
-
-def _master(P, A):
-    """Once per (depth, team size): the actors on the GPU, a2 [A, master lanes, flat] from the team trunk on the master maps, the
-    float64 references and the head's outputs on all master lanes (what a case's lanes must equal bit for bit)."""
-    if (P, A) in _MASTER:
-        return _MASTER[P, A]
-    from radiation_ppo_amd import _lib
-    lib = _lib.load()
-    t = S.team(P, A)
-    seqs = [S.clone_seq(ac.actor, "cuda") for ac in t.actors]
-    a2 = torch.empty(A, t.N, t.flat, device="cuda")
-    _team_trunk(lib, t.maps.cuda(), t.cells.int().cuda(), t.pcells.int().cuda(), seqs, a2)
-    assert float(a2.min()) >= 0.0 and float((a2 == 0).float().mean()) > 0.2        # non-negative and sparse, as in a run
-    m = dict(t=t, seqs=seqs, a2=a2)
-    m["refs"] = [S.reference(t.actors[a].actor, a2[a], t.u[:, a]) for a in range(A)]
-    m["out"] = _head(lib, seqs, t.flat, a2, t.u.cuda(), S.alive_for(t, t.N).cuda(), A, t.N)
-    _MASTER[P, A] = m
-    return m
-
-
-def _existing_path(lib, m, a, N, u, alive):
-    """The composed runner's path for agent a on the case's lanes: rs_cnn_sized_infer + BLAS linear + rs_cnn_head + the idle rule."""
-    from radiation_ppo_amd import _lib
-    t, s = m["t"], m["seqs"][a]
-    a2 = torch.empty(N, t.flat, device="cuda")
-    _one_trunk(lib, t.maps[:N].cuda().contiguous(), t.cells[:N].cuda().contiguous(), t.pcells[:N].cuda().contiguous(), t.A, a, s, a2)
-    with torch.no_grad():
-        y1 = torch.nn.functional.linear(a2, s[6].weight, s[6].bias)
-    act = torch.empty(N, dtype=torch.int64, device="cuda")
-    logp = torch.empty(N, device="cuda")
-    _lib.check(lib.rs_cnn_head(y1.data_ptr(), s[8].weight.data_ptr(), s[8].bias.data_ptr(), s[10].weight.data_ptr(), s[10].bias.data_ptr(), 8,
-                               u.data_ptr() + 4 * a, t.A, act.data_ptr(), logp.data_ptr(), None, 1, None, 1, 0, None, N, _stream()), "rs_cnn_head")
-    torch.cuda.synchronize()
-    return a2, y1, act, logp, torch.where(alive != 0, act, torch.full_like(act, 8)).to(torch.int8)
-
-
 @pytest.mark.parametrize("P", sorted(S.SIDE))
 def test_sized_team_head_first_layer_is_exact_on_one_hot_rows(P):
     """a2 rows that are 1.0 at one k and 0 elsewhere: y1[j] = a single term plus exact zeros, then the bias = float32(W1[j][k] + b1[j]),
     bit for bit, at the first and last float of every wave's quarter and of its tail, at the piece boundaries 31 / 32 and the lane
     halves' 15 / 16.  A dropped or doubled float at any of these edges fails here; the float64 rule below would let it pass."""
-    from radiation_ppo_amd import _lib
-    lib = _lib.load()
     A, flat = 2, S.flat_of(P)
-    seqs = _actors(A, S.SIDE[P], 40 + P)
+    seqs = D.actors(A, S.SIDE[P], 40 + P)
     ks = S.onehot_ks(P)
-    N = len(ks)
-    a2 = torch.zeros(A, N, flat, device="cuda")
-    a2[:, torch.arange(N), torch.tensor(ks)] = 1.0
-    u = torch.rand(N, A, device="cuda")
-    got = _head(lib, seqs, flat, a2, u, torch.ones(N, dtype=torch.uint8, device="cuda"), A, N)
-    for a, s in enumerate(seqs):
-        with torch.no_grad():
-            want = s[6].weight[:, ks].t().contiguous() + s[6].bias                    # [N, 32], one float32 add each
-        bad = (_bits(got["y1"][a]) != _bits(want)).nonzero()
-        assert bad.numel() == 0, (P, a, [(ks[n], j) for n, j in bad[:6].tolist()])
-        assert float(want.abs().min()) > 0
+    a2, u = D.onehot_rows(A, flat, ks)
+    got = D.eval_head(D.SIZED, seqs, flat, a2, u, torch.ones(len(ks), dtype=torch.uint8, device="cuda"), len(ks))
+    D.check_onehot_y1(got["y1"], seqs, ks, P)
 
 
 @pytest.mark.parametrize("P,N,A", S.HEAD_CASES, ids=[f"P{p}-N{n}-A{a}" for p, n, a in S.HEAD_CASES])
 def test_sized_team_head_matches_float64_and_so_does_the_existing_path(P, N, A):
-    from radiation_ppo_amd import _lib
-    lib = _lib.load()
-    m = _master(P, A)
-    t, seqs = m["t"], m["seqs"]
-    a2 = m["a2"][:, :N].contiguous()
-    u, alive = t.u[:N].cuda().contiguous(), S.alive_for(t, N).cuda()
-    assert int(alive[N - 1]) == 0 and (N == 1 or (int(alive[0]) == 1 and 0 < int(alive.sum()) < N))
-    got = _head(lib, seqs, t.flat, a2, u, alive, A, N)
-    refs = m["refs"] if N == t.N else [S.reference(t.actors[a].actor, a2[a], u[:, a]) for a in range(A)]
-    worst = {k: dict(y1=0.0, logp=0.0, differing=0, unexcused=0, act8=0) for k in ("kernel", "existing")}
-    fails = []
-    for a in range(A):
-        assert S.distinct_actions(m["refs"][a]) >= 3, a                 # a visibly non-uniform policy that still draws several actions
-        if N >= 31:
-            assert S.distinct_actions(refs[a]) >= 3, (N, a)
-        q = S.ratios(refs[a], u[:, a], alive, got["act"][a], got["logp"][a], got["act8"][:, a], y1=got["y1"][a])
-        xa2, y1, act, logp, a8 = _existing_path(lib, m, a, N, u, alive)
-        assert torch.equal(_bits(xa2), _bits(a2[a])), a              # both paths start from the same trunk bits
-        qe = S.ratios(refs[a], u[:, a], alive, act, logp, a8, y1=y1)
-        for name, r in (("kernel", q), ("existing", qe)):
-            for k in r:
-                worst[name][k] = max(worst[name][k], r[k])
-            if not S.passes(r):
-                fails.append((name, a, r))
-    for name in worst:
-        print(f"cnn sized team head P{P} flat {t.flat} N{N} A{A} {name:8s} | "
-              + " ".join(f"{k} {v:.4f}" if isinstance(v, float) else f"{k} {v}" for k, v in worst[name].items()))
-    assert not [f for f in fails if f[0] == "existing"], fails       # the existing path past 1.0 would mean the MODEL is wrong
-    assert not fails, fails
-    assert bool((got["act"] >= 0).all()) and bool((got["act"] <= 7).all())
-    want8 = torch.where(alive.view(N, 1) != 0, got["act"].t(), torch.full_like(got["act"].t(), 8)).to(torch.int8)
-    assert torch.equal(got["act8"], want8)                           # act8[n][a] = alive[n] ? act[a][n] : 8, exactly
-    # the optional outputs NULL: act8 alone, the same rows; a second call: the same bits
-    only8 = _head(lib, seqs, t.flat, a2, u, alive, A, N, outputs=False)
-    assert torch.equal(only8["act8"], got["act8"])
-    again = _head(lib, seqs, t.flat, a2, u, alive, A, N)
-    for k in got:
-        assert torch.equal(_bits(again[k]), _bits(got[k])) if got[k].dtype == torch.float32 else torch.equal(again[k], got[k]), k
-    # the same lanes inside the master call (130 lanes at P = 15 and at P = 73 with 2 agents): equal bits, no dependence on N or the grid
-    big = m["out"]
-    assert torch.equal(_bits(big["y1"][:, :N]), _bits(got["y1"])) and torch.equal(_bits(big["logp"][:, :N]), _bits(got["logp"]))
-    assert torch.equal(big["act"][:, :N], got["act"])
+    """the master call has 130 lanes at P = 15 and at P = 73 with 2 agents"""
+    D.head_matches_float64_and_so_does_the_existing_path(D.SIZED, (P, A), N)
 
 
 # ------------------------------------------------------------------------------------------------ whole runs

@@ -2,13 +2,13 @@
 fixed-order second stage), rs_cnn_sized_team_critic_infer and the collector that issues them (CNNCollector.use_sized_team_round).
 
 First layer, exact: a2 rows that are one-hot at k must give y1 == float32(W1[:, k] + b1) bit for bit on actor and critic rows, at the k
-computed from rs_cnn_sized_team_head_slice_floats() -- in the first, a middle and the last slice the first and last float of every wave
-quarter, the piece boundary 31 / 32, the lane halves' 15 / 16 (7 / 8 of a 16-float tail), the first and last float of a tail, and the
-floats on either side of every slice boundary -- at p = 4 (less than one slice), 5, 15, the first p whose depth is a whole number of
-slices, and 73 (85 264).
+computed from rs_cnn_sized_team_head_slice_floats() (_cnn_sized_team_ref.onehot_ks_sliced) -- in the first, a middle and the last slice
+the first and last float of every wave quarter, the piece boundary 31 / 32, the lane halves' 15 / 16 (7 / 8 of a 16-float tail), the
+first and last float of a tail, and the floats on either side of every slice boundary -- at p = 4 (less than one slice), 5, 15, the
+first p whose depth is a whole number of slices, and 73 (85 264).
 
-Float64: tests/_cnn_sized_team_ref.reference with K1 at the case's depth on the actor rows (y1, log-probability, the draws equal except
-within DRAW_CAP), the same allowance for the one output on the critic rows (test_cnn_team_step_gpu.py's _value_ratio at that K1); p = 15
+Float64: tests/_cnn_team_ref.reference with K1 at the case's depth on the actor rows (y1, log-probability, the draws equal except
+within DRAW_CAP), the same allowance for the one output on the critic rows (_cnn_team_ref.value_ratios at that K1); p = 15
 with A = 3, C in {1, 3}, N in {1, 63, 64, 65, 130} and p = 73 with (N, A) in {(64, 8), (33, 2), (130, 2)}, both critic modes.  The float32
 torch composition on the same inputs is held to the same rule by tests/test_cnn_sized_team_eval_cpu.py.  Every worst ratio is printed;
 profiles/cnn_sized_team_step_float64_ratios.txt keeps a copy.
@@ -16,8 +16,10 @@ profiles/cnn_sized_team_step_float64_ratios.txt keeps a copy.
 Scratch discipline (the scratch is NaN before every call of this file and guarded on both sides: every output finite), the bootstrap
 round, sharding (N = 130 against 65 twice), the critic team trunk against rs_cnn_sized_infer(agent = -1) per critic, and the collector on
 31 x 31 maps: team round on against off, every stored row against the modules, graph against eager, two half collectors against one,
-the fall-back conditions, and one walls-off train_PPO('cnn') epoch."""
-import ctypes as C
+the fall-back conditions, and one walls-off train_PPO('cnn') epoch.
+
+The guarded calls (the scratch among them), the master and the bodies this file has in common with tests/test_cnn_team_step_gpu.py are
+tests/_cnn_team_drive.py's, run here with SIZED; what is written out below is this family's own."""
 import os
 import sys
 
@@ -26,25 +28,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
 import _cnn_sized_team_ref as S  # noqa: E402
+import _cnn_team_drive as D  # noqa: E402
 import _cnn_team_ref as T  # noqa: E402
-import _f64_ref as R  # noqa: E402
+from _cnn_team_drive import SIZED as F, bits as _bits, is_sentinel as _is_sentinel  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -12345.678
-SEED = 1234
-GUARD = 4096                                                # floats of NaN on both sides of the scratch
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32).cpu()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def _lib_():
@@ -52,94 +40,18 @@ def _lib_():
     return _lib, _lib.load()
 
 
-def _params(seqs):
-    from radiation_ppo_amd import _lib
-    return (_lib.RsCnnHeadParams * len(seqs))(*[_lib.RsCnnHeadParams(_p(s[6].weight), _p(s[6].bias), _p(s[8].weight), _p(s[8].bias),
-                                                                      _p(s[10].weight), _p(s[10].bias)) for s in seqs])
-
-
-def _conv_params(seqs):
-    from radiation_ppo_amd import _lib
-    return (_lib.RsCnnConvParams * len(seqs))(*[_lib.RsCnnConvParams(_p(s[0].weight), _p(s[0].bias), _p(s[3].weight), _p(s[3].bias)) for s in seqs])
-
-
 def _side(P):
     return S.SIDE.get(P, 2 * P + 1)
 
 
-def _critics(n, seed, M):
-    """n critic networks for M x M maps with biases that matter and visibly different values"""
-    from radiation_ppo_amd.maps import CNNCritic
-    with torch.random.fork_rng(devices=[]):
-        torch.manual_seed(seed)
-        mods = [CNNCritic(map_dim=(M, M)) for _ in range(n)]
-    with torch.no_grad():
-        for m in mods:
-            m.critic[0].bias.uniform_(-0.05, 0.15)
-            m.critic[3].bias.uniform_(-0.1, 0.1)
-            for i in (6, 8, 10):
-                for p in m.critic[i].parameters():
-                    p.mul_(T.SCALE)
-    return mods
-
-
-def _is_sentinel(t):
-    return torch.equal(_bits(t), _bits(torch.full_like(t, SENTINEL)))
-
-
-def _call(lib, actors, critics, flat, a2a, a2c, u, N, A, mask=None, boot=False, rows_of_scratch=None):
-    """rs_cnn_sized_team_step_head into sentinel-filled, guarded buffers through a NaN-filled, guarded scratch of exactly the size the
-    size function gives for the launched rows: dict(rc, act [A, N], f [A, 3, N], act8 [N, A], y1 [A + C, N, 32])"""
-    nc = len(critics)
-    act = torch.full((A * N + 2,), -1, dtype=torch.int64, device="cuda")
-    f = torch.full((A * 3 * N + 2,), SENTINEL, device="cuda")
-    act8 = torch.full((N + 2, A), -1, dtype=torch.int8, device="cuda")
-    y1 = torch.full(((A + nc) * N + 2, 32), SENTINEL, device="cuda")
-    need = lib.rs_cnn_sized_team_head_scratch_floats(flat, rows_of_scratch or (nc if boot else A + nc), N)
-    assert need > 0
-    scr = torch.full((need + 2 * GUARD,), float("nan"), device="cuda")
-    if boot:
-        rc = lib.rs_cnn_sized_team_step_head(None, A, _params(critics), nc, flat, None, _p(a2c), None, None, _p(f[1:]), None, _p(mask), _p(y1[1:]),
-                                             _p(scr[GUARD:]), need, N, _stream())
-    else:
-        rc = lib.rs_cnn_sized_team_step_head(_params(actors), A, _params(critics), nc, flat, _p(a2a), _p(a2c), _p(u), _p(act[1:]), _p(f[1:]),
-                                             _p(act8[1:]), _p(mask), _p(y1[1:]), _p(scr[GUARD:]), need, N, _stream())
-    torch.cuda.synchronize()
-    assert int(act[0]) == -1 and int(act[-1]) == -1 and bool((act8[0] == -1).all()) and bool((act8[N + 1] == -1).all())
-    for g in (f[0], f[-1], y1[0], y1[-1]):
-        assert _is_sentinel(g)
-    assert bool(torch.isnan(scr[:GUARD]).all()) and bool(torch.isnan(scr[GUARD + need:]).all())       # nothing written beside the scratch
-    out = dict(rc=rc, act=act[1:A * N + 1].view(A, N), f=f[1:A * 3 * N + 1].view(A, 3, N), act8=act8[1:N + 1],
-               y1=y1[1:(A + nc) * N + 1].view(A + nc, N, 32))
-    assert bool(torch.isfinite(out["f"]).all()) and bool(torch.isfinite(out["y1"]).all())             # no NaN of the scratch reached an output
-    return out
+def _call(actors, critics, flat, a2a, a2c, u, N, A, **kw):
+    return D.step_head(F, actors, critics, flat, a2a, a2c, u, N, A, **kw)
 
 
 # ------------------------------------------------------------------------------------------------ the first layer, exact
 def _whole_p(sl):
     """the first p in 4..128 whose depth 16 p p is a whole number of slices, or None"""
     return next((p for p in range(4, 129) if (16 * p * p) % sl == 0), None)
-
-
-def onehot_ks(flat, sl):
-    """The k of the exact check, from the slice length: in the first, a middle and the last slice, per wave quarter (a quarter of the
-    slice length, cut at the slice's end) its first and last float, 15 / 16, 31 / 32, the last float of its whole pieces, the first and
-    last float of a tail and 7 / 8 inside it; and both sides of every slice boundary."""
-    n_sl, q = -(-flat // sl), sl // 4
-    ks = set()
-    for s in sorted({0, n_sl // 2, n_sl - 1}):
-        L = min(sl, flat - s * sl)
-        for w in range(4):
-            lw = max(0, min(q, L - w * q))
-            np_, tail = lw // 32, lw % 32
-            rel = {0, lw - 1, 15, 16, 31, 32, 32 * np_ - 1}
-            if tail:
-                rel |= {32 * np_, 32 * np_ + 7, 32 * np_ + 8, 32 * np_ + tail - 1}
-            ks |= {s * sl + w * q + k for k in rel if 0 <= k < lw}
-    for s in range(1, n_sl):
-        ks |= {s * sl - 1, s * sl}
-    assert all(0 <= k < flat for k in ks) and {0, flat - 1} <= ks
-    return sorted(ks)
 
 
 def _onehot_depths():
@@ -160,83 +72,24 @@ def test_first_layer_is_exact_on_one_hot_rows(P):
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(50 + P)
         seqs = [CNNActor(map_dim=(M, M)).actor.cuda() for _ in range(A)]
-    crit = [c.critic.cuda() for c in _critics(A, 60 + P, M)]
+    crit = [c.critic.cuda() for c in D.critics(A, 60 + P, M)]
     assert seqs[0][6].weight.shape == (32, flat) and crit[0][6].weight.shape == (32, flat)
-    ks = onehot_ks(flat, sl)
+    ks = S.onehot_ks_sliced(flat, sl)
     if flat > sl:
         assert {sl - 1, sl, sl // 4 - 1, sl // 4, 15, 16, 31, 32} <= set(ks)
-    N = len(ks)
-    a2 = torch.zeros(A, N, flat, device="cuda")
-    a2[:, torch.arange(N), torch.tensor(ks)] = 1.0
-    u = torch.rand(N, A, device="cuda")
-    got = _call(lib, seqs, crit, flat, a2, a2, u, N, A)
+    a2, u = D.onehot_rows(A, flat, ks)
+    got = _call(seqs, crit, flat, a2, a2, u, len(ks), A)
     assert got["rc"] == 0
-    for row, s in enumerate(seqs + crit):
-        with torch.no_grad():
-            want = s[6].weight[:, ks].t().contiguous() + s[6].bias                    # [N, 32], one float32 add each
-        bad = (_bits(got["y1"][row]) != _bits(want)).nonzero()
-        assert bad.numel() == 0, (P, row, [(ks[n], j) for n, j in bad[:6].tolist()])
-        assert float(want.abs().min()) > 0
+    D.check_onehot_y1(got["y1"], seqs + crit, ks, P)
 
 
 # ------------------------------------------------------------------------------------------------ float64
-_MASTER = {}
-
-
-def _team_trunks(lib, _lib, t, seqs, crit):
-    """(a2a [A, N, flat], a2c [C, N, flat]) of the team's master lanes by the two team trunk kernels"""
-    A, nc, N = t.A, len(crit), t.N
-    maps = t.maps.cuda()
-    a2a, a2c = torch.empty(A, N, t.flat, device="cuda"), torch.empty(nc, N, t.flat, device="cuda")
-    _lib.check(lib.rs_cnn_sized_team_infer(_p(maps), _p(t.cells.int().cuda()), _p(t.pcells.int().cuda()), A, N, t.M, _conv_params(seqs), _p(a2a),
-                                           _stream()), "rs_cnn_sized_team_infer")
-    _lib.check(lib.rs_cnn_sized_team_critic_infer(_p(maps), nc, N, t.M, _conv_params(crit), _p(a2c), _stream()), "rs_cnn_sized_team_critic_infer")
-    torch.cuda.synchronize()
-    return a2a, a2c
-
-
-def _master(P, A):
-    """Once per (depth, team size): _cnn_sized_team_ref's actors and maps, A critics, both roles' trunk outputs on the master lanes."""
-    if (P, A) in _MASTER:
-        return _MASTER[P, A]
-    _lib, lib = _lib_()
-    t = S.team(P, A)
-    seqs = [S.clone_seq(ac.actor, "cuda") for ac in t.actors]
-    cpu_critics = _critics(A, 7400 + 10 * P + A, t.M)
-    crit = [S.clone_seq(c.critic, "cuda") for c in cpu_critics]
-    a2a, a2c = _team_trunks(lib, _lib, t, seqs, crit)
-    assert float(a2a.min()) >= 0.0 and float(a2c.min()) >= 0.0 and float(a2c.max()) > 0.0
-    m = dict(t=t, seqs=seqs, crit=crit, cpu_critics=cpu_critics, a2a=a2a, a2c=a2c, u=t.u.cuda())
-    _MASTER[P, A] = m
-    return m
-
-
-def _value_ratio(seq_cpu, a2, got_v, got_y1):
-    """(worst |y1 - ref| / allowance, worst |value - ref| / allowance) under _cnn_sized_team_ref.reference's lines for y1 and for a logit,
-    K1 at a2's depth"""
-    s64 = R.f64(seq_cpu)
-    K1 = S.k1(a2.shape[1])
-    with torch.no_grad():
-        x = a2.detach().double().cpu()
-        W1, b1, W2, W3 = s64[6].weight, s64[6].bias, s64[8].weight, s64[10].weight
-        y1 = x @ W1.t() + b1
-        mag1 = x.abs() @ W1.abs().t() + b1.abs()
-        y1_allow = R.FF_RTOL * y1.abs() + K1 * R.U * mag1 + R.FF_TINY
-        val, mag3, carried = R.cnn_head_f64(s64, y1)
-        through = (mag1 @ W2.abs().t()) @ W3.abs().t()
-        allow = R.FF_RTOL * val.abs() + R.U * (K1 * through + R.HEAD_K2 * carried + R.HEAD_K3 * mag3) + R.FF_TINY
-        gv, gy = got_v.detach().double().cpu().reshape(val.shape), got_y1.detach().double().cpu()
-        assert bool(torch.isfinite(gv).all()) and bool(torch.isfinite(gy).all())
-        return float(((gy - y1).abs() / y1_allow).max()), float(((gv - val).abs() / allow).max())
-
-
 F64_CASES = [(15, N, 3) for N in (1, 63, 64, 65, 130)] + [(73, 64, 8), (73, 33, 2), (73, 130, 2)]
 
 
 @pytest.mark.parametrize("P,N,A", F64_CASES, ids=[f"P{p}-N{n}-A{a}" for p, n, a in F64_CASES])
 def test_step_round_holds_to_float64_in_both_critic_modes(P, N, A):
-    _lib, lib = _lib_()
-    m = _master(P, A)
+    m = D.master(F, (P, A), critics_too=True)
     t = m["t"]
     a2a, a2c, u = m["a2a"][:, :N].contiguous(), m["a2c"][:, :N].contiguous(), m["u"][:N].contiguous()
     alive = torch.ones(N, dtype=torch.uint8)
@@ -245,7 +98,7 @@ def test_step_round_holds_to_float64_in_both_critic_modes(P, N, A):
     worst = dict(y1=0.0, logp=0.0, differing=0, unexcused=0, act8=0, critic_y1=0.0, value=0.0)
     fails, first = [], None
     for nc in (1, A):
-        got = _call(lib, m["seqs"], m["crit"][:nc], t.flat, a2a, a2c[:nc].contiguous(), u, N, A)
+        got = _call(m["seqs"], m["crit"][:nc], t.flat, a2a, a2c[:nc].contiguous(), u, N, A)
         assert got["rc"] == 0
         assert bool((got["act"] >= 0).all()) and bool((got["act"] <= 7).all()) and torch.equal(got["act8"].long(), got["act"].t())
         assert _is_sentinel(got["f"][:, 2])                                  # the step round leaves the bootstrap slot alone
@@ -268,74 +121,46 @@ def test_step_round_holds_to_float64_in_both_critic_modes(P, N, A):
                 assert torch.equal(_bits(got["f"][c, 1]), _bits(crit_ref[c][0])) and torch.equal(_bits(got["y1"][A + c]), _bits(crit_ref[c][1]))
                 continue
             crit_ref[c] = (got["f"][rows[0], 1].clone(), got["y1"][A + c].clone())
-            qy, qv = _value_ratio(m["cpu_critics"][c].critic, a2c[c], got["f"][rows[0], 1], got["y1"][A + c])
+            qy, qv = T.value_ratios(m["cpu_critics"][c].critic, a2c[c], got["f"][rows[0], 1], got["y1"][A + c], S.k1(t.flat))
             worst["critic_y1"], worst["value"] = max(worst["critic_y1"], qy), max(worst["value"], qv)
         if nc == A and A > 1:
             assert not torch.equal(got["f"][0, 1], got["f"][A - 1, 1])       # every critic its own value
-    line = (f"cnn sized team step P{P} flat {t.flat} N{N} A{A} | "
-            + " ".join(f"{k} {v:.4f}" if isinstance(v, float) else f"{k} {v}" for k, v in worst.items()))
+    line = f"cnn sized team step {F.case(t, N)} | " + D.fmt(worst)
     print(line)
     assert not fails, (line, fails)
-    assert worst["critic_y1"] <= 1.0 and worst["value"] <= 1.0, line
+    assert T.value_passes(worst["critic_y1"], worst["value"]), line
     if N >= 63:
         assert all(S.distinct_actions(r) >= 3 for r in refs)                 # visibly non-uniform policies that still draw several actions
 
 
 # ------------------------------------------------------------------------------------------------ scratch discipline, sharding
 def test_bootstrap_round_writes_slot_two_under_the_mask_and_nothing_else():
-    _lib, lib = _lib_()
+    def boot_y1(got, step, on, A):                          # the k-split kernel masks per lane
+        assert _is_sentinel(got["y1"][A:][:, ~on]) and torch.equal(_bits(got["y1"][A:][:, on]), _bits(step["y1"][A:][:, on]))
+
+    def masked_y1(got, on):
+        assert _is_sentinel(got["y1"][:, ~on])
+
     P, A, N = 15, 3, 130
-    m = _master(P, A)
+    m, step = D.bootstrap_round(F, (P, A), boot_y1, masked_y1)
     flat, a2a, a2c, u = m["t"].flat, m["a2a"], m["a2c"], m["u"]
-    step = {nc: _call(lib, m["seqs"], m["crit"][:nc], flat, a2a, a2c[:nc].contiguous(), u, N, A) for nc in (1, A)}
-    mask = torch.zeros(N, dtype=torch.uint8, device="cuda")
-    mask[[64, 70, 127, 128, 129]] = 1                                       # lanes 0..63 all zero: the first tile returns early
-    mask[100] = 7                                                           # any non-zero byte counts
-    on = mask != 0
-    for nc in (1, A):
-        got = _call(lib, None, m["crit"][:nc], flat, None, a2c[:nc].contiguous(), None, N, A, mask=mask, boot=True)
-        assert got["rc"] == 0
-        assert bool((got["act"] == -1).all()) and bool((got["act8"] == -1).all())
-        assert _is_sentinel(got["f"][:, 0]) and _is_sentinel(got["f"][:, 1]) and _is_sentinel(got["y1"][:A])
-        assert _is_sentinel(got["f"][:, 2][:, ~on]) and _is_sentinel(got["y1"][A:][:, ~on])
-        # the masked envs: the step round's value bits (the same critic on the same a2), in slot 2
-        assert torch.equal(_bits(got["f"][:, 2][:, on]), _bits(step[nc]["f"][:, 1][:, on])), nc
-        assert torch.equal(_bits(got["y1"][A:][:, on]), _bits(step[nc]["y1"][A:][:, on]))
-    # a step round under a mask: the masked-out envs write nothing, the others what the unmasked round wrote
-    got = _call(lib, m["seqs"], m["crit"], flat, a2a, a2c, u, N, A, mask=mask)
-    assert got["rc"] == 0
-    assert bool((got["act"][:, ~on] == -1).all()) and bool((got["act8"][~on] == -1).all()) and _is_sentinel(got["f"][:, :, ~on])
-    assert _is_sentinel(got["y1"][:, ~on])
-    assert torch.equal(got["act"][:, on], step[A]["act"][:, on]) and torch.equal(_bits(got["f"][:, :2][:, :, on]), _bits(step[A]["f"][:, :2][:, :, on]))
-    assert torch.equal(got["act8"][on].long(), got["act"][:, on].t())
-    # an empty mask: nothing written, RS_OK
-    got = _call(lib, None, m["crit"], flat, None, a2c, None, N, A, mask=torch.zeros(N, dtype=torch.uint8, device="cuda"), boot=True)
-    assert got["rc"] == 0 and _is_sentinel(got["f"]) and _is_sentinel(got["y1"])
     # refusals that need no launch: a bootstrap round without a mask, a scratch one float short, a depth that is no 16 p p
+    _lib, lib = _lib_()
     scr = torch.empty(lib.rs_cnn_sized_team_head_scratch_floats(flat, 2 * A, N), device="cuda")
     f = step[A]["f"].clone()
-    assert lib.rs_cnn_sized_team_step_head(None, A, _params(m["crit"]), A, flat, None, _p(a2c), None, None, _p(f), None, None, None, _p(scr),
-                                           scr.numel(), N, _stream()) == 1
+    ap, cp = D.head_params(m["seqs"]), D.head_params(m["crit"])
+    assert D.call("rs_cnn_sized_team_step_head", None, A, cp, A, flat, None, a2c, None, None, f, None, None, None, scr, scr.numel(), N) == 1
     for bad_flat, floats in ((flat, scr.numel() - 1), (flat + 16, scr.numel())):
-        assert lib.rs_cnn_sized_team_step_head(_params(m["seqs"]), A, _params(m["crit"]), A, bad_flat, _p(a2a), _p(a2c), _p(u), _p(step[A]["act"]),
-                                               _p(f), _p(step[A]["act8"]), None, None, _p(scr), floats, N, _stream()) == 1
+        assert D.call("rs_cnn_sized_team_step_head", ap, A, cp, A, bad_flat, a2a, a2c, u, step[A]["act"], f, step[A]["act8"], None, None, scr,
+                      floats, N) == 1
     assert torch.equal(_bits(f), _bits(step[A]["f"]))
 
 
 def test_results_do_not_depend_on_how_the_envs_are_sharded():
     """N = 130 in one call against the same lanes as two calls of 65, each through a scratch of its own size: equal bits in every output;
     and a scratch larger than needed changes nothing."""
-    _lib, lib = _lib_()
-    P, A, N = 15, 3, 130
-    m = _master(P, A)
-    flat = m["t"].flat
-    whole = _call(lib, m["seqs"], m["crit"], flat, m["a2a"], m["a2c"], m["u"], N, A)
-    for lo in (0, 65):
-        sl = slice(lo, lo + 65)
-        part = _call(lib, m["seqs"], m["crit"], flat, m["a2a"][:, sl].contiguous(), m["a2c"][:, sl].contiguous(), m["u"][sl].contiguous(), 65, A)
-        assert torch.equal(part["act"], whole["act"][:, sl]) and torch.equal(part["act8"], whole["act8"][sl])
-        assert torch.equal(_bits(part["f"][:, :2]), _bits(whole["f"][:, :2, sl])) and torch.equal(_bits(part["y1"]), _bits(whole["y1"][:, sl]))
-    big = _call(lib, m["seqs"], m["crit"], flat, m["a2a"], m["a2c"], m["u"], N, A, rows_of_scratch=16)
+    m, whole = D.sharding(F, (15, 3))
+    big = _call(m["seqs"], m["crit"], m["t"].flat, m["a2a"], m["a2c"], m["u"], 130, 3, rows_of_scratch=16)
     assert torch.equal(big["act"], whole["act"]) and torch.equal(_bits(big["f"][:, :2]), _bits(whole["f"][:, :2]))
 
 
@@ -360,129 +185,32 @@ def test_critic_team_trunk_cases_take_the_shortcut_and_the_full_path():
 
 @pytest.mark.parametrize("M,N,nc", CRITIC_TRUNK_CASES, ids=[f"M{m}-N{n}-C{c}" for m, n, c in CRITIC_TRUNK_CASES])
 def test_critic_team_trunk_equals_one_trunk_launch_per_critic_bit_for_bit(M, N, nc):
-    _lib, lib = _lib_()
-    crit = [c.critic.cuda() for c in _critics(nc, 100 * N + nc + M, M)]
-    maps = _trunk_maps(M, N).cuda()
-    flat = 16 * (M // 2) ** 2
-    G = 2 * flat
-    buf = torch.full((G + nc * N * flat + G,), SENTINEL, device="cuda")
-    _lib.check(lib.rs_cnn_sized_team_critic_infer(_p(maps), nc, N, M, _conv_params(crit), _p(buf[G:]), _stream()), "rs_cnn_sized_team_critic_infer")
-    torch.cuda.synchronize()
-    assert _is_sentinel(buf[:G]) and _is_sentinel(buf[G + nc * N * flat:])
-    got = buf[G:G + nc * N * flat].view(nc, N, flat)
-    assert not bool((got == SENTINEL).any())                                # every element written
-    for c, s in enumerate(crit):
-        want = torch.full((N, flat), SENTINEL, device="cuda")
-        _lib.check(lib.rs_cnn_sized_infer(_p(maps), None, None, 0, -1, N, M, _p(s[0].weight), _p(s[0].bias), _p(s[3].weight), _p(s[3].bias), _p(want),
-                                          _stream()), "rs_cnn_sized_infer")
-        torch.cuda.synchronize()
-        assert float(want.abs().max()) > 0 and bool(torch.isfinite(want).all())
-        bad = (_bits(got[c]) != _bits(want)).nonzero()
-        assert bad.numel() == 0, (M, N, nc, c, bad[:4].tolist())
-    if nc > 1:
-        assert not torch.equal(got[0], got[nc - 1])                         # distinct critics, distinct outputs
+    crit = [c.critic.cuda() for c in D.critics(nc, 100 * N + nc + M, M)]
+    D.check_team_trunk(F, "critic", crit, _trunk_maps(M, N))
 
 
 # ------------------------------------------------------------------------------------------------ the collector, walls off
 CN, CA, CT, CL = 64, 3, 8, 4                                # 4-step episodes: 31 x 31 maps
-KEYS = ("obs", "act", "rew", "val", "logp", "last_val", "cut", "adv", "ret")
+FLAG = "sized_team_round"
 
 
-def _collector(team, N=CN, base=32, use_graph=False, sized_team_round=None, record=None, ids=None, mixed=False):
-    from radiation_ppo_amd.envs import RadSearchVec
-    from radiation_ppo_amd.maps import CNNCritic, heat_map_geometry
-    from radiation_ppo_amd.ppo_cnn import CNNAgentPPO, CNNCollector
-    torch.manual_seed(8)
-    env = RadSearchVec(N, number_agents=CA, obstruction_count=2, enforce_grid_boundaries=False, seed=SEED, env_id_base=base)
-    kw = dict(map_dim=tuple(heat_map_geometry(env, CL, False)[2]))
-    gc = CNNCritic(**kw).cuda() if team else None
-    opt = lambda: torch.optim.Adam(gc.parameters(), lr=1e-3)
-    agents = {i: CNNAgentPPO(id=i, GlobalCritic=gc if team and not (mixed and i == CA - 1) else None,
-                             GlobalCriticOptimizer=opt() if team and not (mixed and i == CA - 1) else None, **kw)
-              for i in (ids if ids is not None else range(CA))}
-    with torch.no_grad():
-        for ag in agents.values():
-            for p in list(ag.pi.actor[6:].parameters()):
-                p.mul_(3.0)                                   # visibly non-uniform policies
-    col = CNNCollector(env, agents, CT, CL, global_critic_flag=team, use_graph=use_graph)
+def _collector(team, **kw):
+    col, agents = D.collector(team, FLAG, False, CT, CL, **kw)
     assert tuple(col.maps.map_dimensions) == (31, 31)
-    if sized_team_round is not None:
-        col.sized_team_round = sized_team_round
-    if record is not None:                                    # the bootstrap rounds' maps and masks, as the team round receives them
-        inner = col._sized_team_round
-
-        def spy(maps, mask8=None):
-            if mask8 is not None:
-                record.append((int(col._t), maps.clone(), mask8.clone()))
-            return inner(maps, mask8=mask8)
-        col._sized_team_round = spy
     return col, agents
-
-
-def _stored(col):
-    return {**{k: getattr(col.buf, k).clone() for k in KEYS}, "shared": col.shared.clone(), "cells": col.cells.clone(),
-            "pcells": col.pcells.clone(), "complete_len": col.complete_len.clone()}
 
 
 @pytest.mark.parametrize("team", [True, False], ids=["global-critic", "own-critics"])
 def test_collector_sized_team_round_against_the_per_agent_round_and_the_modules(team):
-    boots = []
-    cf, af = _collector(team, record=boots)
-    assert cf.use_sized_team_round and not cf.use_team_round
-    cf.collect()
+    cf, cm = D.collector_round_against_the_per_agent_round_and_the_modules(_collector, FLAG, team, CT, CA)
+    assert not cf.use_team_round and not cm.use_team_round
     assert getattr(cf, "_sz_scratch", None) is not None and cf._sz_a2_cri.shape[0] == (1 if team else CA)
-    cm, _ = _collector(team, sized_team_round=False)
-    assert not cm.use_sized_team_round and not cm.use_team_round and cm.use_heads
-    cm.collect()
     assert getattr(cm, "_sz_scratch", None) is None
-    # ---- the first lock-step, where both collectors see the same state
-    same = cf.buf.act[0] == cm.buf.act[0]
-    assert float(same.float().mean()) > 0.99
-    assert torch.allclose(cf.buf.logp[0][same], cm.buf.logp[0][same], rtol=1e-4, atol=2e-5)
-    assert torch.allclose(cf.buf.val[0], cm.buf.val[0], rtol=1e-4, atol=2e-5)
-    assert torch.equal(cf.buf.obs[0], cm.buf.obs[0]) and torch.equal(cf.shared[0], cm.shared[0])
-    assert torch.equal(cf.cells[0], cm.cells[0]) and torch.equal(cf.pcells[0], cm.pcells[0])
-    # ---- the whole epoch: every stored row against the modules on the stored maps
-    assert int(cf.buf.act.min()) >= 0 and int(cf.buf.act.max()) <= 7 and int(torch.unique(cf.buf.act).numel()) >= 3
-    for t in range(CT):
-        for a, ag in af.items():
-            logits = ag.pi.logits_from_maps(cf.shared[t], cf.cells[t], cf.pcells[t], a)
-            lp = torch.log_softmax(logits, dim=-1).gather(-1, cf.buf.act[t, :, a].unsqueeze(-1)).squeeze(-1)
-            assert torch.allclose(cf.buf.logp[t, :, a], lp, rtol=1e-4, atol=2e-5), (t, a)
-            assert torch.allclose(cf.buf.val[t, :, a], ag.critic.value_from_maps(cf.shared[t]), rtol=1e-4, atol=2e-5), (t, a)
-    if not team:
-        assert not torch.equal(cf.buf.val[:, :, 0], cf.buf.val[:, :, CA - 1])
-    # ---- last_val: non-zero on cut rows only, and there the critic on the bootstrap round's maps
-    nz = cf.buf.last_val != 0
-    assert int(nz.sum()) > 0 and bool((cf.buf.cut[nz.any(dim=2)] == 1).all())
-    assert len(boots) == CT
-    timeouts = 0
-    for t, maps, mask in boots:
-        on = mask != 0
-        assert not bool(nz[t][~on].any()), t
-        if t < CT - 1:
-            timeouts += int(on.sum())                                   # before the epoch's end only time-outs are bootstrapped
-        for a, ag in af.items():
-            v = ag.critic.value_from_maps(maps)
-            assert torch.allclose(cf.buf.last_val[t, :, a][on], v[on], rtol=1e-4, atol=2e-5), (t, a)
-    assert timeouts > 0 and bool((boots[-1][2] != 0).all())
 
 
 @pytest.mark.parametrize("team", [True, False], ids=["global-critic", "own-critics"])
 def test_collector_sized_team_round_graph_equals_eager_and_two_halves_equal_the_whole(team):
-    runs = {}
-    for name, kw in (("eager", dict()), ("graph", dict(use_graph=True)), ("lo", dict(N=CN // 2, base=32)), ("hi", dict(N=CN // 2, base=32 + CN // 2))):
-        col, _ = _collector(team, **kw)
-        assert col.use_sized_team_round
-        col.collect()
-        assert (col._graph is not None) == (name == "graph") and col.env.error_flags() == 0
-        runs[name] = _stored(col)
-    for k in runs["eager"]:
-        assert torch.equal(runs["graph"][k], runs["eager"][k]), k
-        halves = torch.cat([runs["lo"][k], runs["hi"][k]], dim=0 if k == "complete_len" else 1)
-        if k in ("adv", "ret"):
-            continue                                                    # (GAE over the rows checked here)
-        assert torch.equal(halves, runs["eager"][k]), k
+    D.collector_graph_equals_eager_and_two_halves_equal_the_whole(_collector, FLAG, team, CN)
 
 
 def test_collector_falls_back_to_the_per_agent_round():
@@ -493,7 +221,7 @@ def test_collector_falls_back_to_the_per_agent_round():
         assert int(b.act.min()) >= 0 and int(b.act.max()) <= 7
         for k in ("logp", "val", "last_val", "rew"):
             assert bool(torch.isfinite(getattr(b, k)[:, :, cols]).all()), k
-    col, _ = _collector(True, N=8, sized_team_round=False)
+    col, _ = _collector(True, N=8, on=False)
     assert col.use_heads and not col.use_sized_team_round and not col.use_team_round
     finite(col, [0, 1, 2])
     col, _ = _collector(True, N=8)
@@ -511,25 +239,9 @@ def test_collector_falls_back_to_the_per_agent_round():
 
 
 def test_train_ppo_cnn_runs_a_walls_off_epoch_with_the_sized_team_round_on():
-    import numpy as np
-    from radiation_ppo_amd.envs import RadSearchVec
-    from radiation_ppo_amd.train import train_PPO
-    A = 2
-    env = RadSearchVec(16, number_agents=A, obstruction_count=1, enforce_grid_boundaries=False, seed=6)
-    sim = train_PPO(env=env, logger_kwargs={}, ppo_kwargs=dict(steps_per_epoch=16, steps_per_episode=8, number_of_agents=A, train_pi_iters=2,
-                                                               train_v_iters=2),
-                    seed=6, number_of_agents=A, actor_critic_architecture="cnn", global_critic_flag=True, steps_per_epoch=16,
-                    steps_per_episode=8, total_epochs=1)
-    sim.train()
-    col = sim.collector
+    col = D.train_ppo_cnn_one_epoch(walls=False).collector
     assert tuple(col.maps.map_dimensions) == (35, 35) and col.use_sized_team_round and not col.use_team_round
-    flat = 16 * 17 * 17
+    A, flat = 2, 16 * 17 * 17
     assert col._sz_a2_act.shape == (A, 16, flat) and col._sz_a2_cri.shape == (1, 16, flat)                # the sized team round ran
-    from radiation_ppo_amd import _lib
-    assert col._sz_scratch.numel() == _lib.load().rs_cnn_sized_team_head_scratch_floats(flat, A + 1, 16) > 0 and getattr(col, "_cv_act", None) is not None
-    for i in range(A):
-        rows = sim.loggers[i].rows
-        assert len(rows) == 1 and np.isfinite(rows[0]["loss_policy"]), i
-    assert np.isfinite(sim.loggers[0].rows[0]["loss_critic"])         # only agent 0 updates the global critic (ppo.py:858)
-    buf = col.buf
-    assert bool(torch.isfinite(buf.logp).all()) and bool(torch.isfinite(buf.val).all()) and int(buf.act.max()) <= 7
+    _lib, lib = _lib_()
+    assert col._sz_scratch.numel() == lib.rs_cnn_sized_team_head_scratch_floats(flat, A + 1, 16) > 0 and getattr(col, "_cv_act", None) is not None

@@ -10,8 +10,10 @@ the trunk kernel, at N = 1, 31, 32, 33, 63, 64, 65, 130 (the 32-image MFMA tile,
 (64, 8) for the full team; the existing path (rs_cnn_trunk_infer + BLAS linear + rs_cnn_head) goes through the same rule in the same
 test.  Every worst ratio is printed; profiles/cnn_team_head_float64_ratios.txt keeps a copy.
 
+Both bodies are tests/_cnn_team_drive.py's (check_team_trunk, head_matches_float64_and_so_does_the_existing_path), run here with
+FAMILY27; the any-side twin is tests/test_cnn_sized_team_eval_gpu.py.
+
 Whole runs: every lane of a fused run replayed through the oracle, fused against composed, the early stop, the arguments, the driver."""
-import ctypes as C
 import os
 import sys
 
@@ -20,38 +22,11 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _cnn_team_drive as D  # noqa: E402
 import _cnn_team_ref as T  # noqa: E402
 import _eval_runs as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -12345.678
-FLAT = 2704
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32).cpu()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _prepare(lib, seqs):
-    """every actor's convolution weights in K9's layout: wt [A, scratch]"""
-    from radiation_ppo_amd import _lib
-    wt = torch.empty(len(seqs), lib.rs_cnn_trunk_scratch_floats(6), dtype=torch.float32, device="cuda")
-    for a, s in enumerate(seqs):
-        _lib.check(lib.rs_cnn_trunk_prepare(6, s[0].weight.data_ptr(), s[0].bias.data_ptr(), s[3].weight.data_ptr(), s[3].bias.data_ptr(),
-                                            wt[a].data_ptr(), _stream()), "rs_cnn_trunk_prepare")
-    return wt
-
-
-def _team_trunk(lib, maps, cells32, pcells32, wt, A, N, out):
-    from radiation_ppo_amd import _lib
-    _lib.check(lib.rs_cnn_team_trunk_infer(maps.data_ptr(), cells32.data_ptr(), pcells32.data_ptr(), A, N, wt.data_ptr(), out.data_ptr(),
-                                           _stream()), "rs_cnn_team_trunk_infer")
-    torch.cuda.synchronize()
-
 
 # ------------------------------------------------------------------------------------------------ the team trunk
 TRUNK_CASES = [(N, A) for N in (1, 2, 3, 4, 64, 65, 193) for A in (1, 3, 8)] + [(4099, 3)]
@@ -59,153 +34,19 @@ TRUNK_CASES = [(N, A) for N in (1, 2, 3, 4, 64, 65, 193) for A in (1, 3, 8)] + [
 
 @pytest.mark.parametrize("N,A", TRUNK_CASES, ids=[f"N{n}-A{a}" for n, a in TRUNK_CASES])
 def test_team_trunk_equals_one_trunk_launch_per_agent_bit_for_bit(N, A):
-    from radiation_ppo_amd import _lib
-    from radiation_ppo_amd.maps import CNNActor
-    lib = _lib.load()
-    torch.manual_seed(100 * N + A)
-    seqs = [CNNActor().cuda().actor for _ in range(A)]
-    with torch.no_grad():                                  # make biases matter (pool ties on empty regions, ReLU gates)
-        for s in seqs:
-            s[0].bias.uniform_(-0.05, 0.15)
-            s[3].bias.uniform_(-0.1, 0.1)
-    maps, cells, pcells = (t.cuda() for t in T.random_maps(N, A, seed=31 * N + A))
+    seqs = D.actors(A, 27, 100 * N + A)
+    maps, cells, pcells = T.random_maps(N, A, seed=31 * N + A)
     if N > 3:
         assert bool(((cells < 0) & (pcells < 0)).all(dim=1).any())                  # a fresh map is among the lanes
     if N > 5 and A > 1:
         assert bool(((cells[:, 0] == cells[:, A - 1]) & (cells[:, 0] >= 0)).any())  # and two agents on one cell
-    wt = _prepare(lib, seqs)
-    G = 2 * FLAT                                           # guard rows on both sides of [A][N][2704]
-    buf = torch.full((G + A * N * FLAT + G,), SENTINEL, device="cuda")
-    _team_trunk(lib, maps, cells.int().contiguous(), pcells.int().contiguous(), wt, A, N, buf[G:])
-    got = buf[G:G + A * N * FLAT].view(A, N, FLAT)
-    sent = _bits(torch.full((G,), SENTINEL, device="cuda"))
-    assert torch.equal(_bits(buf[:G]), sent) and torch.equal(_bits(buf[G + A * N * FLAT:]), sent), (N, A)
-    assert not bool((got == SENTINEL).any()), (N, A)       # every element written
-    for a in range(A):
-        want = torch.full((N, FLAT), SENTINEL, device="cuda")
-        _lib.check(lib.rs_cnn_trunk_infer(maps.data_ptr(), cells.data_ptr(), pcells.data_ptr(), A, a, N, wt[a].data_ptr(), want.data_ptr(),
-                                          _stream()), "rs_cnn_trunk_infer")
-        torch.cuda.synchronize()
-        assert float(want.abs().max()) > 0 and bool(torch.isfinite(want).all())
-        assert torch.equal(_bits(got[a]), _bits(want)), (N, A, a)
-    if A > 1:
-        assert not torch.equal(got[0], got[A - 1])         # the agents are told apart: their own weights and cell columns
+    D.check_team_trunk(D.FAMILY27, "actor", seqs, maps, cells, pcells)
 
 
 # ------------------------------------------------------------------------------------------------ the head
-_MASTER = {}
-
-
-def _master(A):
-    """Once per team size: the actors on the GPU, a2 [A, MASTER, 2704] from the team trunk on the master maps, and the head's
-    outputs on all MASTER lanes (what a case's lanes must equal bit for bit: grid independence)."""
-    if A in _MASTER:
-        return _MASTER[A]
-    from radiation_ppo_amd import _lib
-    lib = _lib.load()
-    t = T.team(A)
-    seqs = [T.clone_seq(ac.actor, "cuda") for ac in t.actors]
-    wt = _prepare(lib, seqs)
-    a2 = torch.empty(A, T.MASTER, FLAT, device="cuda")
-    _team_trunk(lib, t.maps.cuda(), t.cells.int().cuda(), t.pcells.int().cuda(), wt, A, T.MASTER, a2)
-    assert float(a2.min()) >= 0.0 and float((a2 == 0).float().mean()) > 0.2        # non-negative and sparse, as in a run
-    m = dict(t=t, seqs=seqs, wt=wt, a2=a2)
-    m["out"] = _head(lib, seqs, a2, t.u.cuda(), T.alive_for(t, T.MASTER).cuda(), A, T.MASTER)
-    _MASTER[A] = m
-    return m
-
-
-def _head_params(seqs):
-    from radiation_ppo_amd import _lib
-    p = lambda t: t.data_ptr()
-    return (_lib.RsCnnHeadParams * len(seqs))(*[_lib.RsCnnHeadParams(p(s[6].weight), p(s[6].bias), p(s[8].weight), p(s[8].bias), p(s[10].weight),
-                                                                      p(s[10].bias)) for s in seqs])
-
-
-def _head(lib, seqs, a2, u, alive, A, N, outputs=True):
-    """rs_cnn_team_eval_head into sentinel-guarded buffers: dict(act8 [N, A], act [A, N], logp [A, N], y1 [A, N, 32]); outputs=False:
-    the three optional outputs NULL."""
-    from radiation_ppo_amd import _lib
-    act8 = torch.full((N + 2, A), -1, dtype=torch.int8, device="cuda")
-    act = torch.full((A * N + 2,), -1, dtype=torch.int64, device="cuda")
-    logp = torch.full((A * N + 2,), SENTINEL, device="cuda")
-    y1 = torch.full((A * N + 2, 32), SENTINEL, device="cuda")
-    o = (act[1:].data_ptr(), logp[1:].data_ptr(), y1[1:].data_ptr()) if outputs else (None, None, None)
-    _lib.check(lib.rs_cnn_team_eval_head(_head_params(seqs), A, a2.data_ptr(), u.data_ptr(), alive.data_ptr(), act8[1:].data_ptr(), *o, N,
-                                         _stream()), "rs_cnn_team_eval_head")
-    torch.cuda.synchronize()
-    assert bool((act8[0] == -1).all()) and bool((act8[N + 1] == -1).all())          # the guards on both sides
-    assert int(act[0]) == -1 and int(act[-1]) == -1
-    for t in (logp[0], logp[-1], y1[0], y1[-1]):
-        assert torch.equal(_bits(t), _bits(torch.full_like(t, SENTINEL)))
-    if not outputs:
-        assert bool((act == -1).all()) and torch.equal(_bits(logp), _bits(torch.full_like(logp, SENTINEL)))
-    return dict(act8=act8[1:N + 1], act=act[1:A * N + 1].view(A, N), logp=logp[1:A * N + 1].view(A, N), y1=y1[1:A * N + 1].view(A, N, 32))
-
-
-def _existing_path(lib, m, a, N, u, alive):
-    """The collector's composition for agent a on the case's lanes: rs_cnn_trunk_infer + BLAS linear + rs_cnn_head + the idle rule."""
-    from radiation_ppo_amd import _lib
-    t, s = m["t"], m["seqs"][a]
-    A = t.A
-    a2 = torch.empty(N, FLAT, device="cuda")
-    maps, cells, pcells = t.maps[:N].cuda().contiguous(), t.cells[:N].cuda().contiguous(), t.pcells[:N].cuda().contiguous()
-    _lib.check(lib.rs_cnn_trunk_infer(maps.data_ptr(), cells.data_ptr(), pcells.data_ptr(), A, a, N, m["wt"][a].data_ptr(), a2.data_ptr(),
-                                      _stream()), "rs_cnn_trunk_infer")
-    with torch.no_grad():
-        y1 = torch.nn.functional.linear(a2, s[6].weight, s[6].bias)
-    act = torch.empty(N, dtype=torch.int64, device="cuda")
-    logp = torch.empty(N, device="cuda")
-    _lib.check(lib.rs_cnn_head(y1.data_ptr(), s[8].weight.data_ptr(), s[8].bias.data_ptr(), s[10].weight.data_ptr(), s[10].bias.data_ptr(), 8,
-                               u.data_ptr() + 4 * a, A, act.data_ptr(), logp.data_ptr(), None, 1, None, 1, 0, None, N, _stream()), "rs_cnn_head")
-    torch.cuda.synchronize()
-    return a2, y1, act, logp, torch.where(alive != 0, act, torch.full_like(act, 8)).to(torch.int8)
-
-
 @pytest.mark.parametrize("N,A", T.CASES, ids=[f"N{n}-A{a}" for n, a in T.CASES])
 def test_team_head_matches_float64_and_so_does_the_existing_path(N, A):
-    from radiation_ppo_amd import _lib
-    lib = _lib.load()
-    m = _master(A)
-    t, seqs = m["t"], m["seqs"]
-    a2 = m["a2"][:, :N].contiguous()
-    u, alive = t.u[:N].cuda().contiguous(), T.alive_for(t, N).cuda()
-    assert int(alive[N - 1]) == 0 and (N == 1 or (int(alive[0]) == 1 and 0 < int(alive.sum()) < N))
-    got = _head(lib, seqs, a2, u, alive, A, N)
-    refs = [T.reference(t.actors[a].actor, a2[a], u[:, a]) for a in range(A)]
-    master_refs = [T.reference(t.actors[a].actor, m["a2"][a], t.u[:, a]) for a in range(A)]
-    worst = {k: dict(y1=0.0, logp=0.0, differing=0, unexcused=0, act8=0) for k in ("kernel", "existing")}
-    fails = []
-    for a in range(A):
-        assert T.distinct_actions(master_refs[a]) >= 3, a           # a visibly non-uniform policy that still draws several actions
-        if N >= 31:
-            assert T.distinct_actions(refs[a]) >= 3, (N, a)
-        q = T.ratios(refs[a], u[:, a], alive, got["act"][a], got["logp"][a], got["act8"][:, a], y1=got["y1"][a])
-        xa2, y1, act, logp, a8 = _existing_path(lib, m, a, N, u, alive)
-        assert torch.equal(_bits(xa2), _bits(a2[a])), a              # both paths start from the same trunk bits
-        qe = T.ratios(refs[a], u[:, a], alive, act, logp, a8, y1=y1)
-        for name, r in (("kernel", q), ("existing", qe)):
-            for k in r:
-                worst[name][k] = max(worst[name][k], r[k])
-            if not T.passes(r):
-                fails.append((name, a, r))
-    for name in worst:
-        print(f"cnn team head N{N} A{A} {name:8s} | " + " ".join(f"{k} {v:.4f}" if isinstance(v, float) else f"{k} {v}" for k, v in worst[name].items()))
-    assert not [f for f in fails if f[0] == "existing"], fails       # the existing path past 1.0 would mean the MODEL is wrong
-    assert not fails, fails
-    assert bool((got["act"] >= 0).all()) and bool((got["act"] <= 7).all())
-    want8 = torch.where(alive.view(N, 1) != 0, got["act"].t(), torch.full_like(got["act"].t(), 8)).to(torch.int8)
-    assert torch.equal(got["act8"], want8)                           # act8[n][a] = alive[n] ? act[a][n] : 8, exactly
-    # the optional outputs NULL: act8 alone, the same rows; a second call: the same bits
-    only8 = _head(lib, seqs, a2, u, alive, A, N, outputs=False)
-    assert torch.equal(only8["act8"], got["act8"])
-    again = _head(lib, seqs, a2, u, alive, A, N)
-    for k in got:
-        assert torch.equal(_bits(again[k]), _bits(got[k])) if got[k].dtype == torch.float32 else torch.equal(again[k], got[k]), k
-    # the same lanes inside a larger N: equal bits (no dependence on N or the grid)
-    big = m["out"]
-    assert torch.equal(_bits(big["y1"][:, :N]), _bits(got["y1"])) and torch.equal(_bits(big["logp"][:, :N]), _bits(got["logp"]))
-    assert torch.equal(big["act"][:, :N], got["act"])
+    D.head_matches_float64_and_so_does_the_existing_path(D.FAMILY27, A, N)
 
 
 # ------------------------------------------------------------------------------------------------ whole runs

@@ -1105,6 +1105,44 @@ int rs_ridfim_eval_step(rs_handle* h, const rs_bpf_params* p, const rs_bpf_state
  * RS_ERR_INVALID_ARG, before anything is launched: a NULL handle, num_particles < 2. */
 int rs_bpf_draws(rs_handle* h, int32_t num_particles, double* prior_u, double* normals, double* resample_u, rs_stream_t stream);
 
+/* rs_bpf_fim: the particles' 3 x 3 Fisher information matrix, FIC.particle_FIM (core.py:686-694; the same expression in
+ * test_policy.py:119-126, 146-153, 204-211), for every pair of a lane with alive[n] != 0, one launch, one workgroup per pair:
+ *   F[i][j] = sum_p w_p ((g_i g_j) s) c_j          with I4, d, den, g = (g0, g_x, g_y) and s as in rs_ridfim_eval_step above,
+ * evaluated at pos[n][a] (NULL: the agent's present position, the handle's) with the env's own background rate.  c is the column
+ * scale of J @ scale, so F is not symmetric.
+ *   prior == 0: the state's particles and weights, c = (1e10, 1, 1).  trace(F) is J_fish of rs_ridfim_eval_step at that position.
+ *   prior != 0: the initial bound (test_policy.py:127-135 with uni_probs of :363-365): the prior's particles, regenerated from the
+ *     draws rs_bpf_track(first = 1) consumes at the env's present step (the same device function; nothing is read from xp or w),
+ *     weights 1 / NP, c = (1e10 / (I_hi - I_lo), 1 / (c_hi - c_lo), 1 / (c_hi - c_lo)) from the params' prior box.
+ * Sums are taken lane by lane, wave by wave in rs_bpf_track's fixed order.  A particle exactly at the position gives inf / nan entries,
+ * as numpy does.  None of a finished lane's outputs is written.
+ * One difference from the reference, on purpose: its `FIM` and 'rid-fim' `init_est` branches index a 2-vector detector position with
+ * [1:], which broadcasts y over both axes (test_policy.py:121, 197, 206); here the position is the detector's (x, y), as the `act`
+ * branches and 'bpf-a2c''s `init_est` have it.
+ *   alive [N]; pos [N][A][2] or NULL; F [N][A][3][3]; trace [N][A] or NULL: F[0][0] + F[1][1] + F[2][2]
+ * RS_ERR_INVALID_ARG, before anything is launched: what rs_bpf_track refuses (its obs aside), a NULL F. */
+int rs_bpf_fim(rs_handle* h, const rs_bpf_params* p, const rs_bpf_state* s, const uint8_t* alive, const double* pos, int32_t prior, double* F,
+               double* trace, rs_stream_t stream);
+
+/* rs_bpf_a2c_eval_step: the policy round of 'bpf-a2c' (test_policy.py:136-154) -- the trained recurrent actor fed the particle filter's
+ * location estimate in place of the PFGRU's -- for every agent of every lane in one launch (csrc/rs_rnn_policy.hip; the grid and the
+ * weights of rs_rnn_team_eval_step, default widths only: GRU 24, heads 32 / 32).  On a lane with alive[n] != 0, in order:
+ *   x = obs[n][a][0..10] with x[0] = clip((float)(((double)obs0 - mean) / std), -8, 8)     rs_welford_standardize's expression, then
+ *                                                                                          the clip of test_policy.py:400, 422
+ *   loc = (float)(est[n][a][1..2] / area_max)         est: the filter state's xpHatMean; area_max: the env's search_area[2][1] (:141, 392)
+ *   rs_rnn_team_eval_step's arithmetic, operation by operation: GRU, policy head, the draw #{j < 7 : cdf_j <= u}; h updated in place
+ *   sim_pos[n][a] = (double)position + ACTION[act]    the controller's own table (:18-27: +-100 and +-71), not the env's step, and no
+ *                                                     blocking test (sim_step, :241); position: the handle's
+ * A finished lane gets act8 = 8 and nothing else of it is written; a wave without a live lane leaves at once.
+ *   weights [num_agents] pointers to RS_RNN_POLICY_WEIGHT_FLOATS floats; obs [N][A][11]; mean, std [N][A]; est [N][A][3];
+ *   hid [A][N][24]; u [N][A]; alive [N]; act8 [N][A]; sim_pos [N][A][2]; x_out [N][A][11] and loc_out [N][A][2] or NULL (for tests
+ *   and the composed runner)
+ * RS_ERR_INVALID_ARG, before anything is launched: a NULL handle or required pointer, a NULL entry among the first num_agents weights,
+ * num_agents outside 1..RS_MAX_AGENTS or not the handle's. */
+int rs_bpf_a2c_eval_step(rs_handle* h, const float* const* weights, int32_t num_agents, const float* obs, const double* mean, const double* std,
+                         const double* est, double area_max, float* hid, const float* u, const uint8_t* alive, int8_t* act8, double* sim_pos,
+                         float* x_out, float* loc_out, rs_stream_t stream);
+
 /* ---- The env's look-ahead and the gradient-search baseline on top of it (radiation_ppo_amd/evaluate.py:
  * run_test_environments_gradient_search; csrc/rs_lookahead.hpp, csrc/rs_lookahead.hip).
  *

@@ -2,9 +2,11 @@
 algos/test_environment/eval/test_policy.py:184-231, 573-574; ParticleFilter, FIC and ssp in eval/core.py:528-620, 655-764, 767-799)
 for every (env, agent) pair of a RadSearchVec at once: one filter over (intensity, x, y) per pair, nothing shared between agents.
 
-`BootstrapParticleFilter` owns the state tensors (float64) and runs the HIP kernels of csrc/rs_bpf.hip -- `track` (rs_bpf_track) and
-`act` (rs_ridfim_eval_step).  `track_composed` and `act_composed` are the same two rounds composed from rs_bpf_draws, rs_peek and
-float64 torch ops on the same state: the A/B form of the evaluation runner, not a fallback -- without the library nothing here runs."""
+`BootstrapParticleFilter` owns the state tensors (float64) and runs the HIP kernels of csrc/rs_bpf.hip -- `track` (rs_bpf_track),
+`act` (rs_ridfim_eval_step) and `fim` (rs_bpf_fim: the particles' 3 x 3 Fisher information matrix, which 'bpf-a2c' scores its moves by
+and the Fisher analysis records).  `track_composed`, `act_composed` and `fim_composed` are the same rounds composed from rs_bpf_draws,
+rs_peek and float64 torch ops on the same state: the A/B form of the evaluation runners, not a fallback -- without the library nothing
+here runs.  `pcrb` is the posterior Cramer-Rao bound's recursion on the recorded matrices (test_policy.py:368-371, 435), on the host."""
 import ctypes as C
 from types import SimpleNamespace
 
@@ -98,6 +100,24 @@ class BootstrapParticleFilter:
                                                 None if J is None else J.data_ptr(), None if J_fish is None else J_fish.data_ptr(),
                                                 self.vec._stream()), "rs_ridfim_eval_step")
         return act8
+
+    def fim(self, alive: torch.Tensor, pos: torch.Tensor = None, prior: bool = False, F: torch.Tensor = None,
+            trace: torch.Tensor = None) -> torch.Tensor:
+        """FIC.particle_FIM (core.py:686-694; rs_bpf_fim): the particles' Fisher information matrix F [N, A, 3, 3] float64 at pos
+        [N, A, 2] float64 (None: every agent's present position), F[i][j] = sum_p w_p g_i g_j s c_j with the column scale
+        c = (1e10, 1, 1).  prior: the initial bound (test_policy.py:127-135) -- the prior's particles, regenerated from the draws
+        `track(first=True)` consumes at the env's present step, weights 1 / NP, c = (1e10 / (I_hi - I_lo), 1 / (c_hi - c_lo),
+        1 / (c_hi - c_lo)).  trace [N, A], where given, receives the diagonal's sum.  Rows of finished lanes (alive[n] == 0) are not
+        written; without an F a zeroed one is made.
+        One difference from the reference, on purpose: its `FIM` and 'rid-fim' `init_est` branches index a 2-vector detector position
+        with [1:], which broadcasts y over both axes (test_policy.py:121, 197, 206); here the position is the detector's (x, y), as
+        the `act` branches and 'bpf-a2c''s `init_est` have it."""
+        if F is None:
+            F = torch.zeros(self.N, self.A, 3, 3, dtype=torch.float64, device=self.vec.device)
+        _lib.check(self.lib.rs_bpf_fim(self.vec._h, self._p, self._s, alive.data_ptr(), None if pos is None else pos.data_ptr(),
+                                       1 if prior else 0, F.data_ptr(), None if trace is None else trace.data_ptr(), self.vec._stream()),
+                   "rs_bpf_fim")
+        return F
 
     def draws(self):
         """(prior_u [N, A, 3, NP], normals [N, A, 3, NP], resample_u [N, A, NP - 1]): what `track` would consume at the env's step"""
@@ -250,3 +270,61 @@ class BootstrapParticleFilter:
         if J_fish is not None:
             J_fish.copy_(Jf.view(N, A, 8))
         return act8
+
+    def fim_composed(self, alive, pos=None, prior=False, F=None, trace=None):
+        """`fim` in float64 torch ops; the prior's particles come from `draws()`"""
+        N, A, NP, P = self.N, self.A, self.NP, self.params
+        dev = self.vec.device
+        det, bkg = self._det_bkg()
+        if pos is not None:
+            det = pos
+        if prior:
+            u = self.draws()[0]
+            lo = torch.tensor([P.intensity[0], P.coord[0], P.coord[0]], dtype=torch.float64, device=dev).view(1, 1, 3, 1)
+            hi = torch.tensor([P.intensity[1], P.coord[1], P.coord[1]], dtype=torch.float64, device=dev).view(1, 1, 3, 1)
+            xp, w = lo + (hi - lo) * u, torch.full((N, A, NP), 1.0 / NP, dtype=torch.float64, device=dev)
+            c = [1e10 / (P.intensity[1] - P.intensity[0]), 1.0 / (P.coord[1] - P.coord[0]), 1.0 / (P.coord[1] - P.coord[0])]
+        else:
+            xp, w, c = self.xp, self.w, [1e10, 1.0, 1.0]
+        c = torch.tensor(c, dtype=torch.float64, device=dev).view(1, 1, 3, 1)
+        xp, w, det, bkg = xp.view(N * A, 3, NP), w.view(N * A, NP), det.reshape(N * A, 2), bkg.reshape(-1)
+        Fm = torch.empty(N * A, 3, 3, dtype=torch.float64, device=dev)
+        rows_per = max(1, int(2e7 // (9 * NP)))
+        for b0 in range(0, N * A, rows_per):
+            sl = slice(b0, b0 + rows_per)
+            I4 = xp[sl, 0] * 1e4
+            ex, ey = det[sl, 0:1] - xp[sl, 1], det[sl, 1:2] - xp[sl, 2]
+            den = ex * ex + ey * ey
+            f = I4 / (den * den)
+            g = torch.stack([1.0 / den, (2.0 * ex) * f, (2.0 * ey) * f], dim=1)         # [b, 3, NP]
+            s = 1.0 / (I4 / den + bkg[sl, None])
+            Fm[sl] = ((((g.unsqueeze(2) * g.unsqueeze(1)) * s[:, None, None]) * c) * w[sl, None, None]).sum(dim=-1)
+        Fm = Fm.view(N, A, 3, 3)
+        live = (alive != 0).view(N, 1)
+        if F is None:
+            F = torch.zeros_like(Fm)
+        F.copy_(torch.where(live.view(N, 1, 1, 1), Fm, F))
+        if trace is not None:
+            trace.copy_(torch.where(live, (Fm[..., 0, 0] + Fm[..., 1, 1]) + Fm[..., 2, 2], trace))
+        return F
+
+
+def pcrb(F0, R, noise_params=(15.0, 1.0, 1.0)):
+    """The posterior Cramer-Rao bound's recursion as the reference writes it (test_policy.py:368-371, 435), on the host in numpy, batched
+    over the leading axes:  D = inv(diag(sigma^2)) with sigma = (noise_params[1], noise_params[0], noise_params[0]),  B_0 = F0,
+    B_t = D + R_t - np.square(D) @ inv(B_{t-1} + D)  -- np.square is elementwise, as in the reference.
+    F0 [..., 3, 3]: the initial bound (`fim(prior=True)`); R [T, ..., 3, 3]: the matrix at the detector after steps 1..T (`fim`).
+    Returns B [T + 1, ..., 3, 3]; from the first step at which a lane's R_t or B_{t-1} is not finite (a finished lane's rows are nan) its
+    B_t is nan."""
+    import numpy as np
+    F0, R = np.asarray(F0, dtype=np.float64), np.asarray(R, dtype=np.float64)
+    sigma = np.array([noise_params[1], noise_params[0], noise_params[0]], dtype=np.float64)
+    D = np.linalg.inv(np.diag(np.square(sigma)))
+    B = np.full((R.shape[0] + 1,) + F0.shape, np.nan)
+    B[0] = F0
+    for t in range(1, B.shape[0]):
+        M = B[t - 1] + D
+        ok = np.isfinite(M).all(axis=(-2, -1)) & np.isfinite(R[t - 1]).all(axis=(-2, -1))
+        if ok.any():
+            B[t][ok] = D + R[t - 1][ok] - np.square(D) @ np.linalg.inv(M[ok])
+    return B

@@ -1,7 +1,8 @@
 // rs_bpf.hip -- the bootstrap particle filter (rs_bpf_track: ParticleFilter.track, algos/test_environment/eval/core.py:554-591, with
 // the SSP resampler ssp, :767-799) and the RID-FIM controller's policy round (rs_ridfim_eval_step: FIC.optim_action with L = 1,
-// :703-764) for every (env, agent) pair, and the test-facing rs_bpf_draws.  One workgroup of RS_BPF_THREADS lanes per pair
-// (rs_bpf.hpp); the candidate positions of the eight moves are rs_peek's lane function (rs_lookahead.hpp).  Neither kernel writes env
+// :703-764) for every (env, agent) pair, the particles' 3 x 3 Fisher information matrix (rs_bpf_fim: FIC.particle_FIM, :686-694, and
+// the initial bound of test_policy.py:127-135) and the test-facing rs_bpf_draws.  One workgroup of RS_BPF_THREADS lanes per pair
+// (rs_bpf.hpp); the candidate positions of the eight moves are rs_peek's lane function (rs_lookahead.hpp).  No kernel writes env
 // state.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -375,6 +376,62 @@ __global__ void __launch_bounds__(RS_BPF_THREADS) rs_bpf_draws_kernel(RsParams P
     }
 }
 
+// FIC.particle_FIM (core.py:686-694) of one pair at (detx, dety): F[i][j] = sum_p w_p ((g_i g_j) s) c_j, the column scale c = J @ scale.
+// PRIOR: the particles are the prior's, regenerated from the draws rs_bpf_track(first = 1) consumes at the env's present step, with
+// weights 1 / NP (test_policy.py:127-135); nothing is read from the state.  A particle exactly at the position gives inf / nan, as numpy.
+template <bool PRIOR>
+__global__ void __launch_bounds__(RS_BPF_THREADS) rs_bpf_fim_kernel(RsParams P, BpfArgs B, const uint8_t* __restrict__ alive,
+                                                                     const double* __restrict__ pos, double c0, double c1, double c2,
+                                                                     double* __restrict__ F, double* __restrict__ trace) {
+    __shared__ double red[RS_BPF_WAVES];
+    const long long pair = blockIdx.x;
+    const int n = (int)(pair / P.A), a = (int)(pair - (long long)n * P.A);
+    if (alive[n] == 0) return;                               // the whole workgroup: none of a finished lane's outputs is written
+    const int NP = B.NP, tid = threadIdx.x;
+    const double* xI = B.xp + (size_t)pair * 3 * NP;
+    const double* xx = xI + NP;
+    const double* xy = xx + NP;
+    const double* w = B.w + (size_t)pair * NP;
+    const size_t ia = (size_t)a * P.N + n;
+    const double detx = pos ? pos[2 * pair] : (double)P.ax[ia], dety = pos ? pos[2 * pair + 1] : (double)P.ay[ia];
+    const double bkg = (double)P.bkg[n], w0 = 1.0 / (double)NP;
+    const RsBpfKey K = rs_bpf_key(P, n, a);
+    double acc[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) acc[q] = 0.0;
+    for (int p = tid; p < NP; p += RS_BPF_THREADS) {
+        double I, x, y, wv;
+        if (PRIOR) {
+            double uI, ux, uy;
+            rs_bpf_prior_u(K, (uint32_t)p, uI, ux, uy);
+            I = B.i_lo + (B.i_hi - B.i_lo) * uI;
+            x = B.c_lo + (B.c_hi - B.c_lo) * ux;
+            y = B.c_lo + (B.c_hi - B.c_lo) * uy;
+            wv = w0;
+        } else {
+            I = xI[p]; x = xx[p]; y = xy[p]; wv = w[p];
+        }
+        const double I4 = I * 1e4;
+        const double ex = detx - x, ey = dety - y;
+        const double den = ex * ex + ey * ey;
+        const double f = I4 / (den * den);
+        const double g[3] = {1.0 / den, (2.0 * ex) * f, (2.0 * ey) * f};
+        const double s = 1.0 / (I4 / den + bkg);
+        const double c[3] = {c0, c1, c2};
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[3 * i + j] += (((g[i] * g[j]) * s) * c[j]) * wv;
+    }
+#pragma unroll
+    for (int q = 0; q < 9; ++q) acc[q] = rs_bpf_block_sum(acc[q], red);
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) F[(size_t)pair * 9 + q] = acc[q];
+        if (trace) trace[pair] = (acc[0] + acc[4]) + acc[8];
+    }
+}
+
 // the refusals of both entries and the kernels' argument block; false: refuse
 bool bpf_args(const rs_handle* h, const rs_bpf_params* p, const rs_bpf_state* s, BpfArgs& B) {
     if (!h || !p || !s) return false;
@@ -450,6 +507,20 @@ int rs_bpf_draws(rs_handle* h, int32_t num_particles, double* prior_u, double* n
     const long long pairs = (long long)h->P.N * h->P.A;
     hipLaunchKernelGGL(rs_bpf_draws_kernel, dim3((unsigned)pairs), dim3(RS_BPF_THREADS), 0, static_cast<hipStream_t>(stream), h->P,
                        (int)num_particles, prior_u, normals, resample_u);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_bpf_fim(rs_handle* h, const rs_bpf_params* p, const rs_bpf_state* s, const uint8_t* alive, const double* pos, int32_t prior, double* F,
+               double* trace, rs_stream_t stream) {
+    BpfArgs B;
+    if (!alive || !F || !bpf_args(h, p, s, B)) return RS_ERR_INVALID_ARG;
+    const dim3 grid((unsigned)s->num_pairs);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (prior)                                               // scale @ uni_probs (test_policy.py:362-365) from the params' prior box
+        hipLaunchKernelGGL(rs_bpf_fim_kernel<true>, grid, dim3(RS_BPF_THREADS), 0, st, h->P, B, alive, pos, 1e10 / (B.i_hi - B.i_lo),
+                           1.0 / (B.c_hi - B.c_lo), 1.0 / (B.c_hi - B.c_lo), F, trace);
+    else
+        hipLaunchKernelGGL(rs_bpf_fim_kernel<false>, grid, dim3(RS_BPF_THREADS), 0, st, h->P, B, alive, pos, 1e10, 1.0, 1.0, F, trace);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

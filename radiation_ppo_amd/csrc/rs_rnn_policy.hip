@@ -14,6 +14,7 @@
 
 #include "../../include/radsearch.h"
 #include "rs_draws.hpp"
+#include "rs_handle.hpp"
 #include "rs_sstream.hpp"
 
 namespace {
@@ -236,6 +237,116 @@ __global__ void __launch_bounds__(64) rs_rnn_team_step_kernel(TeamArgs t) {
         if (o < NA - 1 && cdf <= uu) { act = o + 1; }
     }
     if (keep) *arow = (int8_t)act;
+}
+
+// The policy round of 'bpf-a2c' (algos/test_environment/eval/test_policy.py:136-154) for every agent of every lane in one launch: the
+// trained actor fed the bootstrap particle filter's location estimate in place of the PFGRU's.  The grid, the rows and the in-place h
+// of rs_rnn_team_step_kernel; in front of its arithmetic a lane standardises and clips its reading (:400, 422) and scales the filter's
+// estimate by the search area (:141), behind it the detector's position after the drawn move by the controller's own table (:18-27,
+// 241).  K14's arithmetic, operation by operation and in K14's order, in between; a body of its own for the reason given above.  A
+// finished lane gets act8 = 8 and nothing else of it is written.  Everything a lane needs after the products -- its flag, its
+// addresses, its position -- is in vector registers before them.
+struct BpfA2cArgs {
+    const float* w[RS_MAX_AGENTS];
+    const float* obs;      // [N][A][11] the raw observation
+    const double* mean;    // [N][A] the reading's running mean and deviation (rs_welford.hpp)
+    const double* sd;
+    const double* est;     // [N][A][3] the filter's xpHatMean
+    float* h;              // [A][N][24]
+    const float* u;        // [N][A]
+    const uint8_t* alive;  // [N]
+    int8_t* act8;          // [N][A]
+    const int* ax;         // [A][N] the env's detector positions
+    const int* ay;
+    double* sim_pos;       // [N][A][2]
+    float* x_out;          // [N][A][11] or null
+    float* loc_out;        // [N][A][2] or null
+    double area_max;
+    int N, A;
+};
+
+__global__ void __launch_bounds__(64) rs_bpf_a2c_step_kernel(BpfA2cArgs t) {
+    const int e = blockIdx.x * 64 + threadIdx.x, a = blockIdx.y;
+    const bool live = e < t.N && t.alive[e] != 0;
+    if (e < t.N && !live) t.act8[(size_t)e * t.A + a] = (int8_t)8;     // a finished lane idles
+    if (!__any(live)) return;
+    const int ec = e < t.N ? e : t.N - 1;                  // idle lanes shadow a real lane, store nothing
+    const cmem_t W = as_cmem(t.w[a]);
+    const size_t i = (size_t)ec * t.A + a;
+    float* hrow = t.h + ((size_t)a * t.N + ec) * GH;
+    int8_t* arow = t.act8 + i;
+    double* srow = t.sim_pos + i * 2;
+    const float uu = t.u[i];
+    int px = t.ax[(size_t)a * t.N + ec], py = t.ay[(size_t)a * t.N + ec];
+    int keep = live ? 1 : 0;
+    float x[NX], h[GH];
+#pragma unroll
+    for (int k = 0; k < RS_OBS_DIM; ++k) x[k] = t.obs[i * RS_OBS_DIM + k];
+    // rs_welford_standardized's expression, then np.clip(., -8, 8)
+    x[0] = fminf(fmaxf((float)(((double)x[0] - t.mean[i]) / t.sd[i]), -8.0f), 8.0f);
+    x[RS_OBS_DIM] = (float)(t.est[i * 3 + 1] / t.area_max); x[RS_OBS_DIM + 1] = (float)(t.est[i * 3 + 2] / t.area_max);
+    if (keep) {
+        if (t.x_out) {
+#pragma unroll
+            for (int k = 0; k < RS_OBS_DIM; ++k) t.x_out[i * RS_OBS_DIM + k] = x[k];
+        }
+        if (t.loc_out) { t.loc_out[i * 2] = x[RS_OBS_DIM]; t.loc_out[i * 2 + 1] = x[RS_OBS_DIM + 1]; }
+    }
+    asm volatile("" : "+v"(keep), "+v"(arow), "+v"(srow), "+v"(px), "+v"(py));
+#pragma unroll
+    for (int u = 0; u < GH; u += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(hrow + u);
+        h[u] = v.x; h[u + 1] = v.y; h[u + 2] = v.z; h[u + 3] = v.w;
+    }
+    float gi[80], gh[80];
+#pragma unroll
+    for (int o = 0; o < 80; ++o) { gi[o] = W[P_BIH + o]; gh[o] = W[P_BHH + o]; }
+    mv<NX, 80, 72>(W + P_IH, [&](int k) -> float { return x[k]; }, gi);
+    mv<GH, 80, 72>(W + P_HH, [&](int k) -> float { return h[k]; }, gh);
+#pragma unroll
+    for (int j = 0; j < GH; ++j) {
+        const float r = rs_sigmoid(gi[j] + gh[j]);
+        const float z = rs_sigmoid(gi[GH + j] + gh[GH + j]);
+        const float n = rs_tanh(gi[2 * GH + j] + r * gh[2 * GH + j]);
+        h[j] = (1.0f - z) * n + z * h[j];
+    }
+    if (keep) {
+#pragma unroll
+        for (int u = 0; u < GH; u += 4) *reinterpret_cast<float4*>(hrow + u) = make_float4(h[u], h[u + 1], h[u + 2], h[u + 3]);
+    }
+    // ---- policy head, log-softmax, inverse-CDF draw
+    float tt[HD];
+#pragma unroll
+    for (int o = 0; o < HD; ++o) tt[o] = W[P_B1 + o];
+    mv<GH, HD>(W + P_W1, [&](int k) -> float { return h[k]; }, tt);
+#pragma unroll
+    for (int o = 0; o < HD; ++o) tt[o] = rs_tanh(tt[o]);
+    float lg[16];
+#pragma unroll
+    for (int o = 0; o < 16; ++o) lg[o] = W[P_B2 + o];
+    mv<HD, 16>(W + P_W2, [&](int k) -> float { return tt[k]; }, lg);
+    float mx = lg[0];
+#pragma unroll
+    for (int o = 1; o < NA; ++o) mx = fmaxf(mx, lg[o]);
+    float se = 0.0f;
+#pragma unroll
+    for (int o = 0; o < NA; ++o) se += expf(lg[o] - mx);
+    const float lse = logf(se);
+    float cdf = 0.0f;
+    int act = 0;
+#pragma unroll
+    for (int o = 0; o < NA; ++o) {
+        const float lp = (lg[o] - mx) - lse;
+        cdf += expf(lp);
+        if (o < NA - 1 && cdf <= uu) { act = o + 1; }
+    }
+    if (keep) {
+        // ACTION (test_policy.py:18-27): 0 (-100, 0), 1 (-71, 71), 2 (0, 100), 3 (71, 71), 4 (100, 0), 5 (71, -71), 6 (0, -100), 7 (-71, -71)
+        const double dx = act == 0 ? -100.0 : (act == 1 || act == 7) ? -71.0 : (act == 2 || act == 6) ? 0.0 : act == 4 ? 100.0 : 71.0;
+        const double dy = (act == 0 || act == 4) ? 0.0 : (act == 1 || act == 3) ? 71.0 : act == 2 ? 100.0 : act == 6 ? -100.0 : -71.0;
+        *arow = (int8_t)act;
+        srow[0] = (double)px + dx; srow[1] = (double)py + dy;
+    }
 }
 
 // The policy round of a whole team as a collector runs it, step round (u given) or bootstrap round (u null), in one launch: the grid,
@@ -528,6 +639,23 @@ int rs_rnn_team_eval_step(const float* const* weights, int32_t num_agents, const
     }
     t.x = x; t.loc = loc; t.h = h; t.u = u; t.active = active; t.act8 = act8; t.N = num_envs; t.A = num_agents;
     hipLaunchKernelGGL(rs_rnn_team_step_kernel, dim3((num_envs + 63) / 64, num_agents), dim3(64), 0, static_cast<hipStream_t>(stream), t);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
+}
+
+int rs_bpf_a2c_eval_step(rs_handle* h, const float* const* weights, int32_t num_agents, const float* obs, const double* mean, const double* std,
+                         const double* est, double area_max, float* hid, const float* u, const uint8_t* alive, int8_t* act8, double* sim_pos,
+                         float* x_out, float* loc_out, rs_stream_t stream) {
+    if (!h || !weights || !obs || !mean || !std || !est || !hid || !u || !alive || !act8 || !sim_pos) return RS_ERR_INVALID_ARG;
+    if (num_agents < 1 || num_agents > RS_MAX_AGENTS || num_agents != h->P.A) return RS_ERR_INVALID_ARG;
+    BpfA2cArgs t{};
+    for (int a = 0; a < RS_MAX_AGENTS; ++a) {
+        if (a < num_agents && !weights[a]) return RS_ERR_INVALID_ARG;
+        t.w[a] = weights[a < num_agents ? a : 0];                  // the slots behind the team repeat agent 0 (never read)
+    }
+    t.obs = obs; t.mean = mean; t.sd = std; t.est = est; t.h = hid; t.u = u; t.alive = alive; t.act8 = act8;
+    t.ax = h->P.ax; t.ay = h->P.ay; t.sim_pos = sim_pos; t.x_out = x_out; t.loc_out = loc_out; t.area_max = area_max;
+    t.N = h->P.N; t.A = num_agents;
+    hipLaunchKernelGGL(rs_bpf_a2c_step_kernel, dim3((t.N + 63) / 64, num_agents), dim3(64), 0, static_cast<hipStream_t>(stream), t);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_ERR_HIP;
 }
 

@@ -18,7 +18,9 @@ HIP (csrc/rs_eval.hip, csrc/rs_rnn_policy.hip) and composed; `run_test_environme
 `run_test_environments` sends a recurrent agent there --, `run_test_environments_gradient_search` the reference's non-learned
 gradient-search controller over the env's look-ahead (csrc/rs_lookahead.hip), a fourth front to `_run_lane_per_run_team` --,
 `run_test_environments_rid_fim` the reference's bootstrap particle filter with the RID-FIM controller (csrc/rs_bpf.hip,
-radiation_ppo_amd/bpf.py), a fifth --,
+radiation_ppo_amd/bpf.py), a fifth --, `run_test_environments_bpf_a2c` the reference's 'bpf-a2c', the trained recurrent actor fed that
+filter's location estimate (csrc/rs_rnn_policy.hip: rs_bpf_a2c_eval_step), a sixth; both take `fisher` for the posterior Cramer-Rao
+bound (rs_bpf_fim, bpf.pcrb) --,
 `summarize` the result statistics
 (evaluate.py:645-880), `evaluate_PPO` the driver with the reference's eval_kwargs (:581-643).
 """
@@ -143,16 +145,22 @@ def recurrent_team_start(agents, N, seed, dev, impl):
     ONE PredictorBank of A owners around the agents' own PFGRUs with its particle sets drawn, and every agent's GRU state from the hash
     of ITS row of the bank's lane keys (every agent has its own `hiddens` entry).  The composed and the fused runners start from this one
     definition, so their initial states cannot drift apart.  Returns (bank, hid [A, N, hid])."""
-    from .pfgru import PredictorBank, hash_uniform
+    from .pfgru import PredictorBank
     A = len(agents)
     ac0 = agents[0].agent
     bank = PredictorBank(N, A, hidden_size=ac0.rec, seed=seed, carry_hidden=True, device=dev, impl=impl)
     for a in range(A):
         bank.cells[a] = agents[a].agent.model
     bank.reset()
-    unit = torch.arange(ac0.hid, dtype=torch.int64, device=dev).view(1, -1)
-    hid = torch.stack([agents[a].agent.gru_h0(hash_uniform((bank._base[a] * 1000003 + 5).view(-1, 1) * 1048583 + unit)) for a in range(A)])
-    return bank, hid.contiguous()
+    return bank, _gru_team_h0(agents, bank._base, dev)
+
+
+def _gru_team_h0(agents, base, dev):
+    """hid [A, N, hid]: every agent's GRU state from the hash of ITS row of the lane keys `base` [A, N] (pfgru.lane_base)."""
+    from .pfgru import hash_uniform
+    unit = torch.arange(agents[0].agent.hid, dtype=torch.int64, device=dev).view(1, -1)
+    hid = torch.stack([agents[a].agent.gru_h0(hash_uniform((base[a] * 1000003 + 5).view(-1, 1) * 1048583 + unit)) for a in range(len(agents))])
+    return hid.contiguous()
 
 
 def recurrent_start(ac, N, seed, dev, impl):
@@ -798,40 +806,165 @@ def run_test_environments_gradient_search(env_sets: Dict[str, tuple], number_of_
                                   return_actions, fused, welford=False, falloff=falloff)
 
 
-def _rid_fim_rounds(run, fused, bpf_kwargs, loc_err):
-    """The RID-FIM lock-step's two rounds over one BootstrapParticleFilter per (lane, agent) (radiation_ppo_amd/bpf.py).  before():
-    ParticleFilter.track on the current reading -- the first call of a run draws the prior and sets the latch --, then, where loc_err
-    (a dict) is given, the squared distance of agent 0's estimate from the source is added to the lane's sum.  policy_round:
-    FIC.optim_action.  fused: rs_bpf_track and rs_ridfim_eval_step; composed: rs_bpf_draws, rs_peek and float64 torch ops."""
-    from .bpf import BootstrapParticleFilter
-    bpf = BootstrapParticleFilter(run.vec, **bpf_kwargs)
+def _filter_before(run, bpf, fused, rec):
+    """before() of the two particle-filter runners, and the pass's records in the dict `rec` (on entry: the flags "estimates" and
+    "fisher").  before() is ParticleFilter.track on the current reading -- the first call of a run draws the prior and sets the latch
+    --; with "fisher" one Fisher-matrix launch into row it of rec["fim"] [L, N, A, 3, 3] (nan where a lane had finished): the initial
+    bound from the prior's particles at lock-step 0, the matrix at the agent's position afterwards (test_policy.py:403, 434); with
+    "estimates" the squared distance of agent 0's estimate from the source is added to the lane's sum.  rec["it"] counts the calls."""
     obs, alive, alive8 = run.obs, run.alive, run.alive8
-    track, act = (bpf.track, bpf.act) if fused else (bpf.track_composed, bpf.act_composed)
-    calls = [0]
-    if loc_err is not None:
+    track, fim = (bpf.track, bpf.fim) if fused else (bpf.track_composed, bpf.fim_composed)
+    f64 = dict(dtype=torch.float64, device=run.dev)
+    rec["it"] = 0
+    if rec.get("estimates"):
         src = torch.stack([run.vec.state("src_x").view(-1), run.vec.state("src_y").view(-1)], dim=-1).double()
-        loc_err.update(sq=torch.zeros(run.N, dtype=torch.float64, device=run.dev), n=torch.zeros(run.N, dtype=torch.float64, device=run.dev),
-                       last=torch.zeros(run.N, dtype=torch.float64, device=run.dev))
+        rec.update(sq=torch.zeros(run.N, **f64), n=torch.zeros(run.N, **f64), last=torch.zeros(run.N, **f64))
+    if rec.get("fisher"):
+        rec["fim"] = torch.full((run.L, run.N, run.A, 3, 3), float("nan"), **f64)
 
     def before():
-        track(obs, alive8, calls[0] == 0)
-        calls[0] += 1
-        if loc_err is not None:
+        it = rec["it"]
+        track(obs, alive8, it == 0)
+        rec["it"] = it + 1
+        if rec.get("fisher"):
+            fim(alive8, prior=it == 0, F=rec["fim"][it])
+        if rec.get("estimates"):
             d2 = ((bpf.estimate[:, 0, 1:] - src) ** 2).sum(dim=-1)
-            loc_err["sq"] += torch.where(alive, d2, torch.zeros_like(d2))
-            loc_err["n"] += alive.double()
-            loc_err["last"].copy_(torch.where(alive, d2.sqrt(), loc_err["last"]))
+            rec["sq"] += torch.where(alive, d2, torch.zeros_like(d2))
+            rec["n"] += alive.double()
+            rec["last"].copy_(torch.where(alive, d2.sqrt(), rec["last"]))
+    return before
+
+
+def _rid_fim_rounds(run, fused, bpf_kwargs, rec):
+    """The RID-FIM lock-step's two rounds over one BootstrapParticleFilter per (lane, agent) (radiation_ppo_amd/bpf.py).  before():
+    _filter_before.  policy_round: FIC.optim_action.  fused: rs_bpf_track and rs_ridfim_eval_step; composed: rs_bpf_draws, rs_peek and
+    float64 torch ops."""
+    from .bpf import BootstrapParticleFilter
+    bpf = BootstrapParticleFilter(run.vec, **bpf_kwargs)
+    obs, alive8 = run.obs, run.alive8
+    act = bpf.act if fused else bpf.act_composed
 
     def policy_round(a8):
         act(obs, alive8, a8)
     run.bpf = bpf
-    return before, policy_round
+    return _filter_before(run, bpf, fused, rec), policy_round
+
+
+# the controller's own table of moves (algos/test_environment/eval/test_policy.py:18-27), which sim_step (:241) adds to the detector's
+# position: not the env's step -- the diagonals are 71 cm here --, and no blocking test
+BPF_A2C_ACTION = ((-100.0, 0.0), (-71.0, 71.0), (0.0, 100.0), (71.0, 71.0), (100.0, 0.0), (71.0, -71.0), (0.0, -100.0), (-71.0, -71.0))
+
+
+def _bpf_a2c_rounds(run, fused, agents, bpf_kwargs, rec, env_id_base):
+    """The BPF-A2C lock-step's two rounds (test_policy.py:109-156): before() is _filter_before; policy_round feeds every agent's
+    recurrent actor its standardised, clipped observation and the filter's location estimate over the search area's side, draws the
+    action, and takes the step's score J_tot: the trace of the particles' Fisher matrix at the detector's position after that move by
+    the controller's own table (row it of rec["scores"] [L, N, A] where the caller keeps them).
+    fused: rs_bpf_a2c_eval_step, then rs_bpf_fim.  composed: the standardisation, the clip and the scaling in torch, rs_rnn_team_eval_step
+    (rs_rnn_sized_team_step at other widths than the default), the torch idle rule, the table in torch and fim_composed.
+    GRU states: what recurrent_team_start draws, from the lanes' own keys (env_id_base + lane), fresh for every run; no PFGRU bank."""
+    from .bpf import BootstrapParticleFilter
+    from .pfgru import lane_base
+    lib, vec, obs, stat, N, A, u, alive, alive8, st, dev = run.lib, run.vec, run.obs, run.stat, run.N, run.A, run.u, run.alive, run.alive8, run.st, run.dev
+    p = lambda t: t.data_ptr()
+    bpf = BootstrapParticleFilter(vec, **bpf_kwargs)
+    acs = [agents[a].agent for a in range(A)]
+    hid = _gru_team_h0(agents, lane_base(N, A, run.seed, env_id_base, dev), dev)
+    wts = [agents[a].policy_weights() for a in range(A)]          # kept alive for the run: the kernels read them by address
+    wp = (C.c_void_p * A)(*[p(w) for w in wts])
+    area_max = float(vec.cfg.bbox[3] - vec.cfg.observation_area[1])               # search_area[2][1] (test_policy.py:392)
+    f64 = dict(dtype=torch.float64, device=dev)
+    sim_pos, F = torch.zeros(N, A, 2, **f64), torch.zeros(N, A, 3, 3, **f64)
+    if rec.get("want_scores"):
+        rec["scores"] = torch.full((run.L, N, A), float("nan"), **f64)
+    score = torch.zeros(N, A, **f64)
+    row = lambda: rec["scores"][rec["it"] - 1] if "scores" in rec else score      # before() has counted this lock-step already
+    if fused:
+        def policy_round(a8):
+            _lib.check(lib.rs_bpf_a2c_eval_step(vec._h, wp, A, p(obs), p(stat.mean), p(stat.std), p(bpf.estimate), area_max, p(hid), p(u),
+                                                p(alive8), p(a8), p(sim_pos), None, None, st), "rs_bpf_a2c_eval_step")
+            bpf.fim(alive8, pos=sim_pos, F=F, trace=row())
+    else:
+        default = all(ac.fused_policy for ac in acs)
+        x, loc = torch.empty_like(obs), torch.empty(N, A, 2, dtype=torch.float32, device=dev)
+        k8 = torch.full((N, A), 8, dtype=torch.int8, device=dev)
+        table = torch.tensor(BPF_A2C_ACTION, **f64)
+
+        def policy_round(a8):
+            x.copy_(obs)
+            x[..., 0] = ((obs[..., 0].double() - stat.mean) / stat.std).float().clamp(-8.0, 8.0)     # test_policy.py:400, 422
+            loc.copy_((bpf.estimate[..., 1:] / area_max).float())
+            if default:
+                _lib.check(lib.rs_rnn_team_eval_step(wp, A, p(x), p(loc), p(hid), p(u), p(alive8), p(k8), N, st), "rs_rnn_team_eval_step")
+            else:
+                _lib.check(lib.rs_rnn_sized_team_step(wp, A, acs[0].hid, acs[0].pol[0], acs[0].val[0], p(x), p(loc), p(hid), p(u), None, None,
+                                                      p(k8), p(alive8), N, st), "rs_rnn_sized_team_step")
+            a8.copy_(torch.where(alive.view(N, 1), k8, torch.full_like(k8, 8)))                      # finished episodes idle
+            pos = torch.stack([vec.state("x").t(), vec.state("y").t()], dim=-1).double()
+            sim_pos.copy_(torch.where(alive.view(N, 1, 1), pos + table[a8.long().clamp(0, 7)], sim_pos))
+            bpf.fim_composed(alive8, pos=sim_pos, F=F, trace=row())
+    run.bpf, run.hid, run.sim_pos = bpf, hid, sim_pos
+    return _filter_before(run, bpf, fused, rec), policy_round
+
+
+def _filter_passes(rounds, agents, who, env_sets, montecarlo_runs, steps_per_episode, team_mode, obstruction_count, enforce_grid_boundaries,
+                   seed, device, return_actions, falloff, fused, welford, lanes_per_pass, return_estimates, fisher, return_scores, bpf_kwargs):
+    """What the two particle-filter runners (`who`: the caller's name, for messages) share around _run_lane_per_run_team: the refusals,
+    the split of the saved environments into passes of at most lanes_per_pass lanes -- whole environments; every lane keeps the Philox
+    key of its place in the whole set, so the split does not change a result -- and the results put together.  rounds(run, fused, rec,
+    env_id_base) returns the pass's (before, policy_round)."""
+    A, R = len(agents), int(montecarlo_runs)
+    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
+        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}")
+    if torch.device(device).type != "cuda":
+        raise ValueError(f"{who} needs a cuda device")
+    NP = int(bpf_kwargs.get("nParticles", 6000))
+    if NP < 2:
+        raise ValueError("nParticles must be at least 2")
+    if lanes_per_pass is not None and lanes_per_pass < R:
+        raise ValueError("lanes_per_pass must hold one environment's runs at least (montecarlo_runs lanes): a pass runs whole environments")
+    from .bpf import BootstrapParticleFilter, pcrb
+    if lanes_per_pass is None:
+        free = torch.cuda.mem_get_info(torch.device(device))[0]
+        lanes_per_pass = max(1, int(free // 3 // (BootstrapParticleFilter.bytes_per_pair(NP) * A)))
+    keys = sorted(env_sets, key=lambda k: int(k.split("_")[1]))
+    per = max(1, int(lanes_per_pass) // R)                        # the free-memory default may be below R: one environment is the minimum
+    results, logs, extra = [], [], {}
+    for e0 in range(0, len(keys), per):
+        part = {f"env_{i}": env_sets[k] for i, k in enumerate(keys[e0:e0 + per])}
+        rec = dict(estimates=return_estimates, fisher=fisher, want_scores=return_scores)
+        out = _run_lane_per_run_team(lambda run, f: rounds(run, f, rec, e0 * R), agents, part, R, steps_per_episode, team_mode,
+                                     obstruction_count, enforce_grid_boundaries, seed, device, return_actions, fused, welford=welford,
+                                     falloff=falloff, env_id_base=e0 * R)
+        for res, k in zip(out[0], keys[e0:e0 + per]):
+            res.id = int(k.split("_")[1])
+        results += out[0]
+        if return_actions:
+            logs.append(out[2])
+        if return_estimates:
+            extra.setdefault("rmse", []).append((rec["sq"] / rec["n"].clamp(min=1.0)).sqrt().cpu().numpy())
+            extra.setdefault("final", []).append(rec["last"].cpu().numpy())
+        if fisher:                                                # the bound's recursion, on the host, on the recorded matrices
+            m = rec["fim"].cpu().numpy()
+            extra.setdefault("bounds", []).append(pcrb(m[0], m[1:], bpf_kwargs.get("noise_params", (15.0, 1.0, 1.0))).transpose(1, 2, 0, 3, 4))
+        if return_scores:
+            extra.setdefault("scores", []).append(rec["scores"].cpu().numpy())
+    ret = [results, summarize(results)]
+    if return_actions:
+        L = max(l.shape[0] for l in logs)
+        logs = [np.concatenate([l, np.full((L - l.shape[0],) + l.shape[1:], 8, dtype=np.int8)]) for l in logs]
+        ret.append(np.concatenate(logs, axis=1))
+    if extra:
+        ret.append({k: np.concatenate(v, axis=1 if k == "scores" else 0) for k, v in extra.items()})
+    return tuple(ret)
 
 
 def run_test_environments_rid_fim(env_sets: Dict[str, tuple], number_of_agents: int = 1, montecarlo_runs: int = 100, steps_per_episode: int = 120,
                                   team_mode: str = "individual", obstruction_count: int = 0, enforce_grid_boundaries: bool = True,
                                   seed: int = 0, device: str = "cuda:0", return_actions: bool = False, falloff: str = "reference",
-                                  fused: bool = True, lanes_per_pass: int = None, return_estimates: bool = False, **bpf_kwargs):
+                                  fused: bool = True, lanes_per_pass: int = None, return_estimates: bool = False, fisher: bool = False,
+                                  **bpf_kwargs):
     """The reference's information-driven baseline ('rid-fim' in algos/test_environment/eval/test_policy.py:184-231; FIC and
     ParticleFilter, eval/core.py:528-620, 655-764) on saved test environments: every agent runs a bootstrap particle filter over
     (intensity, x, y) on its own readings and moves where the Renyi divergence of the predicted readings -- after the latch has
@@ -859,46 +992,70 @@ def run_test_environments_rid_fim(env_sets: Dict[str, tuple], number_of_agents: 
     Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps, N, A] int8 action log (rows of 8 where a lane
     had finished; passes that stopped early are padded with 8); with return_estimates also a dict of per-lane float64 arrays:
     "rmse", the root of the mean squared distance of agent 0's estimates from the source over the lane's steps (the reference's
-    LocEstErr, test_policy.py:444, without its initial prior-mean entry), and "final", the distance of the last estimate."""
-    A, R = int(number_of_agents), int(montecarlo_runs)
+    LocEstErr, test_policy.py:444, without its initial prior-mean entry), and "final", the distance of the last estimate.
+    fisher (the reference's --fisher, test_policy.py:361-371, 403-405, 432-436): every track is followed by one rs_bpf_fim launch -- the
+    initial bound from the prior's particles at lock-step 0, the matrix at the agent's position afterwards -- and that dict (returned
+    with fisher alone too) holds "bounds" [N, A, L, 3, 3] float64: the posterior Cramer-Rao bound's recursion (bpf.pcrb) on the
+    recorded matrices, nan from a lane's end on.  The position is the detector's (x, y), not the reference's broadcast y (bpf.fim)."""
+    A = int(number_of_agents)
     if not 1 <= A <= _lib.RS_MAX_AGENTS:
         raise ValueError(f"number_of_agents must be in 1..{_lib.RS_MAX_AGENTS}")
+    return _filter_passes(lambda run, f, rec, base: _rid_fim_rounds(run, f, bpf_kwargs, rec), {i: None for i in range(A)},
+                          "run_test_environments_rid_fim", env_sets, montecarlo_runs, steps_per_episode, team_mode, obstruction_count,
+                          enforce_grid_boundaries, seed, device, return_actions, falloff, fused, False, lanes_per_pass, return_estimates,
+                          fisher, False, bpf_kwargs)
+
+
+def run_test_environments_bpf_a2c(agents: Dict[int, Any], env_sets: Dict[str, tuple], montecarlo_runs: int = 100, steps_per_episode: int = 120,
+                                  team_mode: str = "individual", obstruction_count: int = 0, enforce_grid_boundaries: bool = True,
+                                  seed: int = 0, device: str = "cuda:0", return_actions: bool = False, falloff: str = "reference",
+                                  fused=None, lanes_per_pass: int = None, fisher: bool = False, return_scores: bool = False,
+                                  return_estimates: bool = False, **bpf_kwargs):
+    """The reference's 'bpf-a2c' controller (algos/test_environment/eval/test_policy.py:109-156, 573-574) on saved test environments:
+    the trained recurrent actor of RAD-A2C fed the bootstrap particle filter's location estimate in place of its PFGRU's -- the one
+    comparison of the RAD-A2C paper that needs both.  agents: {id: RNNAgentPPO}, ids 0..A-1 with A in 1..8, all of the same widths;
+    every agent has its own network, GRU state, filter and statistics buffer, nothing is shared.  A lock-step is rs_action_uniforms,
+    the filter's track on the current reading, the policy round (the reading standardised and clipped to +-8, the estimate over the
+    search area's side, GRU, policy head, draw; then the step's score J_tot, the trace of the particles' Fisher matrix at the position
+    the controller's own table of moves predicts), rs_step and the bookkeeping, on _run_lane_per_run_team with the running
+    statistics: one lane per (saved environment, Monte-Carlo run), every run with a fresh filter and a fresh GRU state (`hidden = None`,
+    test_policy.py:490) drawn as recurrent_team_start draws it; the agents' PFGRUs are not used.  bpf_kwargs go to
+    BootstrapParticleFilter (the reference's values by default); the passes and lanes_per_pass are run_test_environments_rid_fim's.
+
+    fused=True: rs_bpf_track, rs_bpf_a2c_eval_step and rs_bpf_fim, one launch each for every agent of every lane; default widths only
+    (GRU 24, heads 32 / 32: the reference's ac_kwargs, :569-570), ValueError at others.  fused=False: the same lock-step composed from
+    track_composed, the standardisation, clip and scaling in torch, rs_rnn_team_eval_step (rs_rnn_sized_team_step at the other
+    widths), fim_composed and the torch idle rule with the torch bookkeeping: the A/B form.  fused=None: fused at the default widths.
+
+    As for 'rid-fim', the filter's measurement model is the inverse-square law I 1e4 / R^2 + bkg (core.py:594-596), while the env's
+    reference falloff is I / r: under falloff="reference" -- the default -- the filter is mis-specified, as it is in the reference, and
+    the actor is fed an estimate that does not localise; falloff="inverse_square" is the env the filter models.
+
+    Returns (List[MonteCarloResults], summary); with return_actions also the [lock-steps, N, A] int8 action log; with fisher,
+    return_scores or return_estimates also a dict of float64 arrays: "bounds" [N, A, L, 3, 3] (fisher: the posterior Cramer-Rao bound,
+    as run_test_environments_rid_fim returns it), "scores" [L, N, A] (J_tot of every step; nan where a lane had finished), "rmse" and
+    "final" [N] (agent 0's localisation error, as for 'rid-fim')."""
+    A = len(agents)
+    if sorted(agents) != list(range(A)) or not 1 <= A <= _lib.RS_MAX_AGENTS:
+        raise ValueError(f"agents must carry the ids 0..A-1 with A in 1..{_lib.RS_MAX_AGENTS}")
     if torch.device(device).type != "cuda":
-        raise ValueError("run_test_environments_rid_fim needs a cuda device")
-    NP = int(bpf_kwargs.get("nParticles", 6000))
-    if NP < 2:
-        raise ValueError("nParticles must be at least 2")
-    if lanes_per_pass is not None and lanes_per_pass < R:
-        raise ValueError("lanes_per_pass must hold one environment's runs at least (montecarlo_runs lanes): a pass runs whole environments")
-    from .bpf import BootstrapParticleFilter
-    if lanes_per_pass is None:
-        free = torch.cuda.mem_get_info(torch.device(device))[0]
-        lanes_per_pass = max(1, int(free // 3 // (BootstrapParticleFilter.bytes_per_pair(NP) * A)))
-    keys = sorted(env_sets, key=lambda k: int(k.split("_")[1]))
-    per = max(1, int(lanes_per_pass) // R)                        # the free-memory default may be below R: one environment is the minimum
-    results, logs, est = [], [], {"rmse": [], "final": []}
-    for e0 in range(0, len(keys), per):
-        part = {f"env_{i}": env_sets[k] for i, k in enumerate(keys[e0:e0 + per])}
-        loc = {} if return_estimates else None
-        out = _run_lane_per_run_team(lambda run, f: _rid_fim_rounds(run, f, bpf_kwargs, loc), {i: None for i in range(A)}, part, R,
-                                     steps_per_episode, team_mode, obstruction_count, enforce_grid_boundaries, seed, device, return_actions,
-                                     fused, welford=False, falloff=falloff, env_id_base=e0 * R)
-        for res, k in zip(out[0], keys[e0:e0 + per]):
-            res.id = int(k.split("_")[1])
-        results += out[0]
-        if return_actions:
-            logs.append(out[2])
-        if return_estimates:
-            est["rmse"].append((loc["sq"] / loc["n"].clamp(min=1.0)).sqrt().cpu().numpy())
-            est["final"].append(loc["last"].cpu().numpy())
-    ret = [results, summarize(results)]
-    if return_actions:
-        L = max(l.shape[0] for l in logs)
-        logs = [np.concatenate([l, np.full((L - l.shape[0],) + l.shape[1:], 8, dtype=np.int8)]) for l in logs]
-        ret.append(np.concatenate(logs, axis=1))
-    if return_estimates:
-        ret.append({k: np.concatenate(v) for k, v in est.items()})
-    return tuple(ret)
+        raise ValueError("run_test_environments_bpf_a2c needs a cuda device")
+    acs = [getattr(agents[a], "agent", None) for a in range(A)]
+    if not all(hasattr(ac, "gru_cell") and hasattr(agents[a], "policy_weights") for a, ac in enumerate(acs)):
+        raise ValueError("run_test_environments_bpf_a2c evaluates recurrent (RAD-A2C) agents")
+    if len({(ac.hid, tuple(ac.pol), tuple(ac.val)) for ac in acs}) != 1:
+        raise ValueError("the agents of a team must have the same GRU and head widths: the state tensor holds one width")
+    default = all(ac.fused_policy for ac in acs)
+    if not default and not all(ac.sized_policy for ac in acs):
+        raise ValueError("the policy kernels serve a GRU of 1..64 units with single-layer heads of 2..64 units")
+    if fused is None:
+        fused = default
+    if fused and not default:
+        raise ValueError("the fused BPF-A2C lock-step is built for the default widths (GRU 24, heads 32 / 32); fused=False composes the others")
+    return _filter_passes(lambda run, f, rec, base: _bpf_a2c_rounds(run, f, agents, bpf_kwargs, rec, base), agents,
+                          "run_test_environments_bpf_a2c", env_sets, montecarlo_runs, steps_per_episode, team_mode, obstruction_count,
+                          enforce_grid_boundaries, seed, device, return_actions, falloff, fused, True, lanes_per_pass, return_estimates,
+                          fisher, return_scores, bpf_kwargs)
 
 
 def _collect_results(keys, E, R, ep_len, ep_ret, success, inten, bkg) -> List[MonteCarloResults]:
@@ -978,7 +1135,9 @@ class evaluate_PPO:
     (directory holding `<id>_agent*/actor.pt, critic.pt[, predictor.pt]` or `<id>_agent*/pyt_save/model.pt`),
     actor_critic_architecture ('cnn' | 'rnn' | 'ff' / 'mlp' | 'gs', the gradient-search baseline, which reads no model_path and takes
     `q`, default 1.0 | 'rid-fim', the particle-filter baseline, which reads no model_path either and takes BootstrapParticleFilter's
-    parameters), number_of_agents, steps_per_episode, enforce_boundaries, team_mode, seed.
+    parameters | 'bpf-a2c', the recurrent actor on the particle filter's estimate: agents loaded as for 'rnn', the filter's parameters as
+    for 'rid-fim', and `fisher` (the posterior Cramer-Rao bounds, kept in `extras["bounds"]`)), number_of_agents, steps_per_episode,
+    enforce_boundaries, team_mode, seed.
     The set is read with the safe reader (radiation_ppo_amd.testsets); all episodes x runs advance in lock-step on the device."""
     eval_kwargs: Dict[str, Any]
 
@@ -1012,6 +1171,12 @@ class evaluate_PPO:
             f = os.path.join(agent_dir(i), "pyt_save", "model.pt")
             ag.load(f if os.path.exists(f) else os.path.join(agent_dir(i), "model.pt"))
             return ag
+
+        def rnn_agent(i):                                               # pyt_save/model.pt (epoch_logger.py:216-284)
+            from .rada2c import RNNAgentPPO
+            ag = RNNAgentPPO(id=i, device=dev)
+            ag.load(agent_dir(i))
+            return ag
         if arch == "cnn":
             from .maps import CNNCritic
             from .pfgru import PFGRUCell
@@ -1041,12 +1206,6 @@ class evaluate_PPO:
                 runner = run_test_environments_cnn
             self.results, self.summary = runner(agents, sets, team_mode=kw.get("team_mode", "individual"), **common)
         elif arch == "rnn":
-            from .rada2c import RNNAgentPPO
-
-            def rnn_agent(i):                                           # pyt_save/model.pt (epoch_logger.py:216-284)
-                ag = RNNAgentPPO(id=i, device=dev)
-                ag.load(agent_dir(i))
-                return ag
             carry = bool(kw.get("carry_hidden_across_runs", True))
             if A >= 2:
                 # a recurrent team: one RNNModelActorCritic per agent on its own rows (evaluate.py:305-318)
@@ -1065,6 +1224,14 @@ class evaluate_PPO:
             bpf = {k: kw[k] for k in ("nParticles", "noise_params", "thresh", "intensity", "coord", "alpha", "fim_thresh", "interval") if k in kw}
             self.results, self.summary = run_test_environments_rid_fim(sets, number_of_agents=A, team_mode=kw.get("team_mode", "individual"),
                                                                        falloff=kw.get("falloff", "reference"), **common, **bpf)
+        elif arch == "bpf-a2c":
+            # the trained recurrent actor on the particle filter's estimate (eval/test_policy.py:109-156): agents as for 'rnn', the
+            # filter's parameters as for 'rid-fim'; with `fisher` the posterior Cramer-Rao bounds are kept in self.extras["bounds"]
+            bpf = {k: kw[k] for k in ("nParticles", "noise_params", "thresh", "intensity", "coord", "alpha", "fim_thresh", "interval") if k in kw}
+            out = run_test_environments_bpf_a2c({i: rnn_agent(i) for i in range(A)}, sets, team_mode=kw.get("team_mode", "individual"),
+                                                falloff=kw.get("falloff", "reference"), fisher=bool(kw.get("fisher", False)), **common, **bpf)
+            self.results, self.summary = out[:2]
+            self.extras = out[2] if len(out) > 2 else {}
         elif A >= 2:
             # a feed-forward team: every agent's own network on its own rows (evaluate.py:305-331)
             team_mode = kw.get("team_mode", "individual")

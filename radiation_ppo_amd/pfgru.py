@@ -78,6 +78,14 @@ def draw_key(base: torch.Tensor, counter) -> torch.Tensor:
     return (base * 1000003) ^ (_s64(counter * mix) if isinstance(counter, int) else counter * _s64(mix))
 
 
+def lane_base(num_envs: int, number_agents: int, seed: int, env_id_base: int, device) -> torch.Tensor:
+    """[A, N] int64: the identities of every (owner, env) draw stream.  Key layout: seed | global env id | owner; (episode, step, kind)
+    and (particle, unit) are mixed in per call."""
+    env = torch.arange(num_envs, dtype=torch.int64, device=device) + int(env_id_base)
+    own = torch.arange(number_agents, dtype=torch.int64, device=device)
+    return hash_uniform((env.view(1, -1) * 64 + own.view(-1, 1)) ^ _s64(int(seed) * 0x2545F4914F6CDD1D)).mul(2.0 ** 52).long()
+
+
 def lane_offsets(P: int, H: int, device) -> torch.Tensor:
     """[P, H] int64: particle * 4096 + unit, what a draw's key adds for its lane (csrc/rs_draws.hpp: rs_draw_lane, + unit)."""
     return (torch.arange(P, dtype=torch.int64, device=device).view(P, 1) * 4096
@@ -278,10 +286,7 @@ class PredictorBank:
         assert self.sized or impl != "hip" or hidden_size == 24
         P, H = self.cells[0].num_particles, hidden_size
         self.P, self.H = P, H
-        env = torch.arange(num_envs, dtype=torch.int64, device=self.dev) + int(env_id_base)
-        own = torch.arange(number_agents, dtype=torch.int64, device=self.dev)
-        # key layout: seed | global env id | owner, then (episode, step, kind) and (particle, unit) are mixed in per call
-        self._base = hash_uniform((env.view(1, -1) * 64 + own.view(-1, 1)) ^ _s64(int(seed) * 0x2545F4914F6CDD1D)).mul(2.0 ** 52).long()   # [A, N]
+        self._base = lane_base(num_envs, number_agents, seed, env_id_base, self.dev)                                                           # [A, N]
         self._pu = lane_offsets(P, H, self.dev)                                                                                                # [P, H]
         # the kernels keep the particle sets quad-major ([A, N, H / 4, P, 4], include/radsearch.h); `h` is the logical [A, N, P, H] view of it
         self._hq = torch.zeros(number_agents, num_envs, H // 4, P, 4, dtype=torch.float32, device=self.dev) if impl == "hip" else None
